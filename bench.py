@@ -26,6 +26,10 @@ Extra objects on the JSON line:
                     bytes of a list they never read --, and per kernel instantiation
   cpu_baseline      the CPU oracle (numpy + C restatement, OpenMP on all host cores) timed on ONE step of the bench's own
                     scene ("same inputs"; ~1 minute at 1M particles; --cpu-side bounds it), rank 0, N = 1
+  outputs_dumped    with ``--dump-outputs DIR`` (one GPU): what the last timed step returned to its caller -- the particles'
+                    new positions and velocities -- written after the timed steps as DIR/pos.npy and DIR/vel.npy (float32).
+                    The inputs are seeded, so two builds run with the same arguments can be compared output for output.
+                    Beyond 64 MB in all, the same fixed, seeded sample of particles is kept from every array (``rows``).
 """
 import argparse
 import json
@@ -98,6 +102,32 @@ def cpu_baseline(side, weights, cfg, same=False):
                        f"and network; {dt:.1f} s, {ref.pairs} neighbour pairs")
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """``arrays``: name -> per-particle array the timed path returned (torch tensor or numpy, equal first dimensions).  Writes
+    <out_dir>/<name>.npy in float32; if they exceed ``limit`` bytes together, the rows of
+    sorted(default_rng(0).choice(n, k, replace=False)) are kept from each (the largest k that fits).  -> what was written."""
+    arrays = {k: np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+              for k, v in arrays.items()}
+    n = {a.shape[0] for a in arrays.values()}
+    assert len(n) == 1, "per-particle arrays of different lengths"
+    n = n.pop()
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    header_bytes = 256 * len(arrays)  # room for the .npy headers (128 bytes for these shapes)
+    rows = n
+    if n * row_bytes + header_bytes > limit:
+        rows = max((limit - header_bytes) // row_bytes, 0)
+        keep = np.sort(np.random.default_rng(0).choice(n, rows, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return dict(dir=out_dir, arrays={k: list(a.shape) for k, a in arrays.items()}, dtype="float32", rows=int(rows), of_rows=int(n),
+                sample=None if rows == n else f"rows sorted(numpy.random.default_rng(0).choice({n}, {rows}, replace=False))")
+
+
 def scene_snapshot(pos, vel, lo, hi):
     """What state the scene is in (outside the timed region): fluid particles outside the boundary shell's bounding box, the
     largest speed.  The 5 m column of config 5 is far outside what the network was trained on: from step ~10 on particles leak
@@ -150,7 +180,17 @@ def parse_args(argv=None):
                          "@1/2/4/8 GPUs' read literally)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / reduction logic only, on the gloo backend without a GPU (CPU test)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="one GPU: after the timed steps, write what the last timed step computed (positions and velocities) as "
+                         "DIR/pos.npy and DIR/vel.npy, float32, at most 64 MB in all (a fixed, seeded sample of particles beyond)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs is a single-GPU option")
+    return args
 
 
 def block_grid(world):
@@ -288,6 +328,7 @@ def small_config_main(args):
         repeated = sim.repeated_steps - rep0
         allocs = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0
         assert torch.isfinite(state[0]).all()
+        dumped = dump_outputs(args.dump_outputs, dict(pos=state[0], vel=state[1])) if args.dump_outputs else None
         # ---- untimed: one step's synchronising reads and kernel dispatches
         torch.cuda.set_sync_debug_mode("warn")
         with warnings.catch_warnings(record=True) as ws:
@@ -368,6 +409,8 @@ def small_config_main(args):
         line["cpu_baseline"] = dict(value=n * k / dt, unit="particle-steps/s", cores=len(os.sched_getaffinity(0)), kind="port",
                                     sample=f"{k} consecutive step(s) of the CPU oracle (oracle/model_ref.py: numpy + OpenMP C restatement "
                                            f"of the Open3D CPU algorithms; not TensorFlow/Open3D) on the same scene from its initial state, {dt:.1f} s")
+    if dumped:
+        line["outputs_dumped"] = dumped
     if args.layers_json:
         json.dump([dict(kind=k, ms=ms, **m) for k, m, ms in recs], open(args.layers_json, "w"))
     print(json.dumps(line), flush=True)
@@ -397,6 +440,8 @@ def main():
     # DMCF_BENCH_SHARDED=1 under a launcher with ONE process: the sharded driver + RCCL collectives at world size 1 (the
     # only way to exercise that path on a 1-GPU box; its ghost sets are empty)
     sharded = world > 1 or (os.environ.get("DMCF_BENCH_SHARDED") == "1" and in_launcher)
+    if sharded and args.dump_outputs is not None:
+        raise SystemExit("--dump-outputs is a single-GPU option (the sharded driver holds the particles in shards)")
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
 
     if args.dry_run:
@@ -526,6 +571,8 @@ def main():
     if settled_scene:
         state = settled_out
     assert torch.isfinite(state["pos"] if isinstance(state, dict) else state[0]).all()
+    if args.dump_outputs:
+        extra["outputs_dumped"] = dump_outputs(args.dump_outputs, dict(zip(("pos", "vel"), _pv(state))))
     from dmcf_amd.utils.convolutions import neighbor_hints
     snap1 = scene_snapshot(*_pv(state), shell_lo, shell_hi)
     allocs = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0

@@ -638,13 +638,16 @@ def test_fps_multiscale_2d(dev):
     assert [len(i) for i in ref.fps_idx[1:]] == [len(model.all_pos) // 2, len(model.all_pos) // 4]
 
 
-def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the fields the driver reads (small workload so the test stays quick)."""
+def test_bench_line_contract(tmp_path):
+    """bench.py prints ONE JSON line with the fields the driver reads (small workload so the test stays quick) and, with
+    --dump-outputs, writes the positions and velocities of its last timed step."""
     import json
     import subprocess
     import sys
+    from tools import scenes
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--side", "24", "--steps", "2", "--warmup", "1",
-                          "--cpu-side", "8"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cpu-side", "8", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600,
+                         cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -669,6 +672,11 @@ def test_bench_line_contract():
     assert all(0 < v["frac_flops"] < 1 for v in g["by_kernel"].values() if "frac_mfma_f32" not in v)
     assert 0 < g["neighbour_list"]["frac_flops"] < 1
     assert "frs_query" not in d["kernel_ms_per_step"]
+    assert d["outputs_dumped"]["rows"] == d["outputs_dumped"]["of_rows"] == 24 ** 3 and d["outputs_dumped"]["sample"] is None
+    for name in ("pos", "vel"):
+        a = np.load(tmp_path / "out" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (24 ** 3, 3) and np.isfinite(a).all(), name
+    assert not np.array_equal(np.load(tmp_path / "out" / "pos.npy"), scenes.box_scene(24)["pos"])  # stepped, not the input
 
 
 def test_full_size_step_against_the_oracle(dev):

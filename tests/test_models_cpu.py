@@ -7,16 +7,21 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REF = "/root/reference"
 
 
-def test_config_dicts_match_reference_yaml():
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present (GPU box)")
+def test_config_dicts_match_reference_yaml(tmp_path):
+    """tests/golden/reference_configs.json holds the ``model`` sections of the reference's configs/<name>.yml
+    (make_reader_fixtures.py); each is written back as YAML and read through Config.load_from_file."""
+    import yaml
     from dmcf_amd.utils.config import Config
     from tools import configs
+    with open(os.path.join(GOLDEN, "reference_configs.json")) as f:
+        sections = json.load(f)
+    assert sorted(sections) == sorted(configs.BY_NAME)
     for name, d in configs.BY_NAME.items():
-        cfg = Config.load_from_file(os.path.join(REF, "configs", name + ".yml"))
+        path = tmp_path / (name.replace("/", "_") + ".yml")
+        path.write_text(yaml.safe_dump({"model": sections[name]}))
+        cfg = Config.load_from_file(str(path))
         for k, v in d.items():
             assert cfg.model[k] == v, (name, k)
 
@@ -47,11 +52,14 @@ def test_architecture_matches_checkpoint_index(name, n_convs):
     assert tc.load_into_model(model, w, device="cpu") == len([k for k in shapes if k.endswith("/kernel")])
 
 
-def test_tf_checkpoint_reader_on_reference_blob():
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present (GPU box)")
+def test_tf_checkpoint_reader_on_reference_blob(tmp_path):
+    """The reference's checkpoints/Liquid3d/ckpt, restored from tests/golden/liquid3d_ckpt.npz (make_reader_fixtures.py:
+    the index and data files byte for byte, the Adam slots the reader skips zeroed)."""
     from dmcf_amd.utils import tf_checkpoint as tc
-    w = tc.load_checkpoint(os.path.join(REF, "checkpoints/Liquid3d/ckpt"))
+    blob = np.load(os.path.join(GOLDEN, "liquid3d_ckpt.npz"))
+    (tmp_path / "ckpt.index").write_bytes(blob["index"].tobytes())
+    (tmp_path / "ckpt.data-00000-of-00001").write_bytes(blob["data"].tobytes())
+    w = tc.load_checkpoint(str(tmp_path / "ckpt"))
     model_vars = {k: v for k, v in w.items() if k.startswith("model/")}
     assert sum(v.size for v in model_vars.values()) == 275084
     assert all(np.isfinite(v).all() for v in model_vars.values())

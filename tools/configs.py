@@ -1,6 +1,6 @@
 """Model sections of the reference's shipped configurations, restated as Python dicts so that tests and
-bench.py run where /root/reference does not exist (the GPU box).  tests/test_models_cpu.py checks them
-against the YAML files whenever the reference tree is present.  Source: configs/<name>.yml, section ``model``
+bench.py run without the reference tree.  tests/test_models_cpu.py checks them against the YAML files'
+model sections stored in tests/golden/reference_configs.json.  Source: configs/<name>.yml, section ``model``
 (keys that only matter for training -- loss, rest_dens, window_dens, dens_* = False, ckpt_path -- omitted)."""
 
 LIQUID3D = dict(  # configs/Liquid3d.yml:7-31
