@@ -109,7 +109,9 @@ class CconvScatterArgs(ctypes.Structure):
 SYMBOLS = [
     "dmcf_version", "dmcf_error_string", "dmcf_last_hip_error",
     "dmcf_frs_workspace_bytes", "dmcf_frs_build", "dmcf_frs_count", "dmcf_frs_write", "dmcf_frs_search_padded", "dmcf_frs_window_sum",
+    "dmcf_radius_search_count", "dmcf_radius_search_write",
     "dmcf_cconv_workspace_bytes", "dmcf_cconv_forward", "dmcf_cconv_kernel_name",
+    "dmcf_cconv_forward_extents", "dmcf_cconv_extents_kernel_name",
     "dmcf_cconv_scatter_plan_bytes", "dmcf_cconv_scatter_plan", "dmcf_cconv_scatter_workspace_bytes", "dmcf_cconv_scatter_forward",
     "dmcf_lattice_conv_workspace_bytes", "dmcf_lattice_conv_forward",
     "dmcf_lattice_conv_batch_workspace_bytes", "dmcf_lattice_conv_forward_batch",
@@ -160,12 +162,22 @@ def lib():
     L.dmcf_frs_window_sum.restype = c.c_int
     L.dmcf_frs_window_sum.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_int, c.c_void_p, c.c_size_t,
                                       c.c_void_p, c.c_void_p]
+    L.dmcf_radius_search_count.restype = c.c_int
+    L.dmcf_radius_search_count.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float, c.c_int, c.c_void_p, c.c_size_t,
+                                           c.c_void_p, c.c_void_p]
+    L.dmcf_radius_search_write.restype = c.c_int
+    L.dmcf_radius_search_write.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float, c.c_int, c.c_void_p, c.c_size_t,
+                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
     L.dmcf_cconv_workspace_bytes.restype = c.c_size_t
     L.dmcf_cconv_workspace_bytes.argtypes = [c.POINTER(CconvArgs)]
     L.dmcf_cconv_forward.restype = c.c_int
     L.dmcf_cconv_forward.argtypes = [c.POINTER(CconvArgs), c.c_void_p, c.c_size_t, c.c_void_p]
     L.dmcf_cconv_kernel_name.restype = c.c_int
     L.dmcf_cconv_kernel_name.argtypes = [c.POINTER(CconvArgs), c.c_char_p, c.c_size_t]
+    L.dmcf_cconv_forward_extents.restype = c.c_int
+    L.dmcf_cconv_forward_extents.argtypes = [c.POINTER(CconvArgs), c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_cconv_extents_kernel_name.restype = c.c_int
+    L.dmcf_cconv_extents_kernel_name.argtypes = [c.POINTER(CconvArgs), c.c_char_p, c.c_size_t]
     L.dmcf_cconv_scatter_plan_bytes.restype = c.c_size_t
     L.dmcf_cconv_scatter_plan_bytes.argtypes = [c.c_int64]
     L.dmcf_cconv_scatter_plan.restype = c.c_int

@@ -38,6 +38,8 @@ struct CconvParams {
     int KT;        // matrix-core splat only: number of 16-cell tiles (ceil(K/16))
     float* partial;  // matrix-core splat, small launches: [nchunks][n_out][cout] partial sums, one channel chunk per workgroup row
     int csplit;      // ... 1: blockIdx.y = the workgroup's chunk (cconv_mfma.hip, kSplitMaxOut)
+    // (no field for the individual extents of dmcf_cconv_forward_extents: cconv_ext_kernel takes them as a second argument.
+    // A field here -- 8 bytes more of every kernel's by-value argument -- changes the code of the generic cconv_kernel.)
 };
 
 // ---- per-pair math (float restatement of Open3D's CoordinateTransformation.h, see oracle/dmcf_oracle.c).
@@ -94,23 +96,24 @@ __device__ __forceinline__ void cyl_to_cube(float& x, float& y) {
     y = tiny ? 0.0f : ny;
 }
 
+// inv_extent: 1 / the filter extent of the pair's output row (p.inv_extent, or the row's own with individual extents)
 template <bool GENERIC>
-__device__ __forceinline__ void filter_coords(float& x, float& y, float& z, const CconvParams& p) {
+__device__ __forceinline__ void filter_coords(float& x, float& y, float& z, const CconvParams& p, float inv_extent) {
     if (!GENERIC || p.mapping == DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING) {
-        const float s = 2.0f * p.inv_extent;
+        const float s = 2.0f * inv_extent;
         x *= s; y *= s; z *= s;
         sphere_to_cyl(x, y, z);
         cyl_to_cube(x, y);
         x *= 0.5f; y *= 0.5f; z *= 0.5f;
     } else if (p.mapping == DMCF_MAP_BALL_TO_CUBE_RADIAL) {
-        const float s = 2.0f * p.inv_extent;
+        const float s = 2.0f * inv_extent;
         x *= s; y *= s; z *= s;
         const float radius = fast_sqrt(x * x + y * y + z * z);
         const float abs_max = fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z)));
         const float k = abs_max < 1e-8f ? 0.0f : 0.5f * radius * fast_rcp(abs_max);
         x *= k; y *= k; z *= k;
     } else {
-        x *= p.inv_extent; y *= p.inv_extent; z *= p.inv_extent;
+        x *= inv_extent; y *= inv_extent; z *= inv_extent;
     }
     if (!GENERIC || (p.flags & DMCF_FLAG_ALIGN_CORNERS)) {
         x = (x + 0.5f) * (float)(p.sx - 1);
@@ -124,6 +127,11 @@ __device__ __forceinline__ void filter_coords(float& x, float& y, float& z, cons
         if (p.sy % 2 == 0) y -= 0.5f;
         if (p.sz % 2 == 0) z -= 0.5f;
     }
+}
+
+template <bool GENERIC>
+__device__ __forceinline__ void filter_coords(float& x, float& y, float& z, const CconvParams& p) {
+    filter_coords<GENERIC>(x, y, z, p, p.inv_extent);
 }
 
 // Squared length of a pair's relative position x_in - x_out, bit for bit what the search returns for the pair (frs.hip:

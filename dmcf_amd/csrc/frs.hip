@@ -1,7 +1,8 @@
 // Fixed-radius neighbour search for gfx950: cell-sorted uniform grid + one wavefront per query.
 //
 // Replaces ml3d.layers.FixedRadiusSearch (reference call sites utils/convolutions.py:207-210,354-358,
-// utils/tools/losses.py:296-298).  The Open3D structure behind that layer (spatial hash with ~64
+// utils/tools/losses.py:296-298) and, with a radius per query, ml3d.layers.RadiusSearch (:212-216, 366-370; frs_query_radii).
+// The Open3D structure behind that layer (spatial hash with ~64
 // points per bin, 8 corner bins per query) is NOT what is built here; only its result contract is
 // kept (see include/dmcf_hip.h).  MI355X-first choices:
 //   * cell edge ~= radius/3 (then radius/2; radius-sized or coarser cells when the grid would be too sparse or too big) and
@@ -676,6 +677,32 @@ __global__ __launch_bounds__(256) void frs_query(const float* __restrict__ queri
     }
 }
 
+// Radius search (dmcf_radius_search_count / _write): the same wave-per-query scan with the radius of the query, on the grid
+// built for max_radius.  The scan range and the chord trimming follow r_i; the cells stay sized for max_radius, so a small
+// radius still visits whole cells of that size.  A radius outside [0, max_radius] (NaN included) gives
+// an empty row.  No open3d visibility flags here: the validation rejects them, so the scan never needs its fixup.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void frs_query_radii(const float* __restrict__ queries, int64_t m, const FrsHeader* __restrict__ h,
+                                                       const uint32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
+                                                       const float* __restrict__ radii, float max_radius, int flags,
+                                                       int32_t* __restrict__ counts, const int64_t* __restrict__ row_splits,
+                                                       int32_t* __restrict__ nbr_index, float* __restrict__ nbr_dist, int64_t capacity) {
+    __shared__ uint32_t marks[4][kWin * kWave + kWave];
+    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (qi >= m) return;  // whole wave leaves
+    if (WRITE && row_splits[qi + 1] > capacity) return;  // (as frs_query: the caller sees the overflow in row_splits[m])
+    const float radius = radii[qi];
+    int32_t cnt = 0;
+    if (radius >= 0.0f && radius <= max_radius) {  // (wave uniform: one query per wave)
+        const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
+        float unused = 0.0f;
+        bool redo = false;
+        cnt = frs_scan<WRITE ? 1 : 0, false>(qx, qy, qz, h, cell_start, sorted, radius, flags, WRITE ? row_splits[qi] : 0, nbr_index,
+                                             nbr_dist, 0, 0.0f, unused, marks[threadIdx.x >> 6], 0x7fffffff, redo);
+    }
+    if (!WRITE && lane_id() == 0) counts[qi] = cnt;
+}
+
 // Single pass into padded rows (see dmcf_frs_search_padded): row qi starts at qi * stride.
 __global__ __launch_bounds__(256) void frs_query_padded(const float* __restrict__ queries, int64_t m,
                                                         const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
@@ -884,6 +911,42 @@ int dmcf_frs_write(const float* queries, int64_t m, int64_t n, float radius, int
         hipLaunchKernelGGL((frs_fix<1>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags,
                            (const uint8_t*)qflags, (int32_t*)nullptr, row_splits, (int64_t)0, neighbors_index, neighbors_distance,
                            pair_capacity, 0, (float*)nullptr);
+    return check_launch();
+}
+
+int dmcf_radius_search_count(const float* queries, int64_t m, int64_t n, const float* radii, float max_radius, int flags,
+                             void* workspace, size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
+    if (m < 0 || n < 0 || !workspace || !(max_radius > 0.0f) || !row_splits || (m > 0 && (!queries || !radii))) return DMCF_EINVAL;
+    const FrsLayout L = frs_layout(n, m);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    char* ws = (char*)workspace;
+    int32_t* counts = (int32_t*)(ws + L.off_counts);
+    if (m > 0) {
+        const unsigned g = (unsigned)((m + 3) / 4);
+        hipLaunchKernelGGL((frs_query_radii<false>), dim3(g), dim3(256), 0, stream, queries, m, (const FrsHeader*)(ws + L.off_header),
+                           (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radii, max_radius, flags, counts,
+                           (const int64_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int64_t)0);
+    }
+    return scan_counts_to_row_splits(counts, row_splits, m, ws + L.off_scan, L.scan_bytes, stream);
+}
+
+int dmcf_radius_search_write(const float* queries, int64_t m, int64_t n, const float* radii, float max_radius, int flags,
+                             const void* workspace, size_t workspace_bytes, const int64_t* row_splits, int32_t* neighbors_index,
+                             float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
+    if (m < 0 || n < 0 || !workspace || !(max_radius > 0.0f) || !row_splits || (m > 0 && (!queries || !radii))) return DMCF_EINVAL;
+    if (m == 0) return DMCF_OK;
+    if (!neighbors_index || pair_capacity < 0) return DMCF_EINVAL;
+    const FrsLayout L = frs_layout(n, m);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    const char* ws = (const char*)workspace;
+    const unsigned g = (unsigned)((m + 3) / 4);
+    hipLaunchKernelGGL((frs_query_radii<true>), dim3(g), dim3(256), 0, stream, queries, m, (const FrsHeader*)(ws + L.off_header),
+                       (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radii, max_radius, flags,
+                       (int32_t*)nullptr, row_splits, neighbors_index, neighbors_distance, pair_capacity);
     return check_launch();
 }
 

@@ -5,6 +5,7 @@ Same names, argument meaning and error behaviour as the Open3D operators the ref
 
   ml3d.layers.FixedRadiusSearch    utils/convolutions.py:207-210 (ctor), :354-358 (call),
                                    utils/tools/losses.py:296-298 (tuple-unpacked)
+  ml3d.layers.RadiusSearch         utils/convolutions.py:212-216 (ctor), :366-370, :1006-1010 (call)
   ml3d.ops.continuous_conv         utils/convolutions.py:414-431, :454
   ml3d.ops.reduce_subarrays_sum    models/pbf_model.py:450-453
 
@@ -464,6 +465,97 @@ class FixedRadiusSearch:
         return twin
 
 
+def radius_search(points, queries, radii, ignore_query_point=False, return_distances=True, normalize_distances=True):
+    """A radius per query (dmcf_radius_search_count / _write) -> NeighborSearchResult(neighbors_index int32 [P],
+    neighbors_row_splits int64 [m+1], neighbors_distance float32 [P] (empty if not return_distances)).
+
+    Row i holds the points within ``radii[i]`` of query i (the set of include/dmcf_hip.h; always the distance set, whatever
+    DMCF_FRS_SET says: the open3d emulations are of FixedRadiusSearch's hash walk).  ``normalize_distances``: d^2 / r_i^2 --
+    the L2 form of Open3D's normalize_distances, restated, not pinned against the library; 0 in a row
+    of radius 0.  One host read checks the radii and forms max_radius, the grid is built at max_radius, a second reads P."""
+    L = _lib.lib()
+    points = _dev_f32(points, "points", 3)
+    queries = _dev_f32(queries, "queries", 3)
+    radii = _dev_f32(radii, "radii")
+    n, m = points.shape[0], queries.shape[0]
+    if radii.dim() != 1 or radii.shape[0] != m:
+        raise ValueError(f"radii must have shape [{m}] (one per query), got {tuple(radii.shape)}")
+    dev = points.device
+    row_splits = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    if m == 0:
+        return NeighborSearchResult(torch.empty(0, dtype=torch.int32, device=dev), row_splits,
+                                    torch.empty(0, dtype=torch.float32, device=dev), total=0)
+    bad, max_radius = torch.stack([(~torch.isfinite(radii) | (radii < 0)).any().float(), radii.max()]).tolist()
+    if bad:
+        raise ValueError("radii must be finite and non-negative")
+    max_radius = float(np.float32(max_radius)) if max_radius > 0 else 1.0  # (all zero: any grid serves, the rows are coincident points)
+    table = build_spatial_hash_table(points, max_radius, n_queries=m)
+    ws = table.workspace
+    nbytes = L.dmcf_frs_workspace_bytes(n, m)
+    flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_radius_search_count(_ptr(queries), m, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
+                                          _stream()), "dmcf_radius_search_count")
+    total = int(row_splits[-1].item())  # the one host round trip of the two-phase search, as in fixed_radius_search
+    capacity = pair_capacity(total) if total else 0
+    index = torch.empty(capacity, dtype=torch.int32, device=dev)
+    dist = torch.empty(capacity if return_distances else 0, dtype=torch.float32, device=dev)
+    if capacity > 0:
+        _lib.check(L.dmcf_radius_search_write(_ptr(queries), m, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
+                                              _ptr(index), _ptr(dist) if return_distances else None, capacity, _stream()),
+                   "dmcf_radius_search_write")
+    if timer is not None:
+        timer.end("radius_search", dict(n_points=n, n_queries=m, pairs=total, distances=bool(return_distances)), t0)
+    if return_distances and normalize_distances and total > 0:
+        r2 = radii * radii  # (float32, as the kernel's r_i * r_i)
+        per_pair = torch.repeat_interleave(r2, torch.diff(row_splits), output_size=total)
+        d = dist[:total]
+        d.div_(per_pair).masked_fill_(per_pair == 0, 0.0)
+    return NeighborSearchResult(index, row_splits, dist, total=total)
+
+
+class RadiusSearch:
+    """Mirror of ``ml3d.layers.RadiusSearch`` (ctor utils/convolutions.py:212-216; call :366-370, :1006-1010)."""
+
+    def __init__(self, metric="L2", ignore_query_point=False, return_distances=False, normalize_distances=False,
+                 index_dtype=torch.int32, **kwargs):
+        if metric != "L2":
+            raise NotImplementedError(f"metric {metric!r}: only 'L2' is implemented on the HIP path")
+        if index_dtype != torch.int32:
+            raise NotImplementedError("index_dtype must be int32 (Open3D 0.15.2 returns int32 indices)")
+        self.metric = metric
+        self.ignore_query_point = ignore_query_point
+        self.return_distances = return_distances
+        self.normalize_distances = normalize_distances
+
+    def __call__(self, points, queries, radii, points_row_splits=None, queries_row_splits=None):
+        if points_row_splits is not None or queries_row_splits is not None:
+            raise NotImplementedError("batched row_splits are not used by DMCF (batch items are looped, "
+                                      "pipelines/simulator.py:68-70)")
+        return radius_search(points, queries, radii, self.ignore_query_point, self.return_distances, self.normalize_distances)
+
+    call = __call__
+
+    def index_only(self):
+        """The same search without the distance output (for callers that re-form d^2 from the positions)."""
+        twin = getattr(self, "_index_only", None)
+        if twin is None:
+            twin = self._index_only = RadiusSearch(self.metric, self.ignore_query_point, False, False)
+        return twin
+
+
+def per_point_extents(extent, n_out):
+    """None for a scalar extent (a number, or a tensor of one element); else the extents as a float32 [n_out] tensor -- from
+    shape [n_out] or [n_out, 1].  Anisotropic extents ([n, 3]) raise NotImplementedError, any other shape ValueError."""
+    if not isinstance(extent, torch.Tensor) or extent.numel() == 1:
+        return None
+    if extent.dim() == 2 and extent.shape[1] == 3:
+        raise NotImplementedError("anisotropic extents [n, 3] are not implemented")
+    if tuple(extent.shape) not in ((n_out,), (n_out, 1)):
+        raise ValueError(f"per-point extents must have shape [{n_out}] or [{n_out}, 1], got {tuple(extent.shape)}")
+    return extent.reshape(n_out)
+
+
 def _empty(t):
     return t is None or (isinstance(t, torch.Tensor) and t.numel() == 0)
 
@@ -696,9 +788,18 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
     """One call of dmcf_cconv_forward.  ``row_length_hint``: 0 unknown / 1 tens / 2 hundreds of neighbours per row -- what the
     caller knows about the LAYER from its configuration (include/dmcf_hip.h).  ``skip_self``: DMCF_FLAG_SKIP_SELF (the list holds the query points, the layer ignores them; only the direct kernel).  ``name_only``: no launch, returns the name of the kernel these arguments dispatch to.  ``filter_tile_mask``: see ``block_diagonal_tile_mask`` (0 = no hint).  ``neighbors_row_count``: int32 [n_out] for padded lists (PaddedNeighborList).  ``window``: None | 'explicit' (neighbors_value = importance) |
     'poly6' | 'cubic' | 'linear' | 'peak' | 'cubic_grad' (neighbors_value = squared distances).
+    ``extent``: a scalar, or one extent per output row -- a tensor of shape [n_out] or [n_out, 1] (dmcf_cconv_forward_extents:
+    row i maps its pairs with extents[i] and evaluates a distance window on d^2 / (extents[i] / 2)^2).  Per-point extents must
+    be finite and positive (ValueError otherwise: one host read); that call always packs the filter (``packed_cache`` unused).
     """
     L = _lib.lib()
     n_out, cout = out_positions.shape[0], filters.shape[4]
+    ext = per_point_extents(extent, n_out)
+    if ext is not None:
+        ext = _dev_f32(ext, "extents")
+        if n_out > 0 and not bool((torch.isfinite(ext) & (ext > 0)).all()):
+            raise ValueError("per-point extents must be finite and positive")
+        extent = 1.0  # (args->extent is ignored by dmcf_cconv_forward_extents; the workspace query wants a positive one)
     if out is None:
         if accumulate:
             raise ValueError("accumulate=True needs an out tensor")
@@ -718,13 +819,14 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
                           neighbors_row_splits, neighbors_value, window, window_fac, inp_importance, align_corners,
                           coordinate_mapping, interpolation, normalize, symmetric, sym_axis, bias, out, accumulate,
                           neighbors_row_count, filter_tile_mask, skip_self, row_length_hint)
+    kernel_name = L.dmcf_cconv_kernel_name if ext is None else L.dmcf_cconv_extents_kernel_name
     if name_only:
         name = ctypes.create_string_buffer(96)
-        _lib.check(L.dmcf_cconv_kernel_name(ctypes.byref(a), name, 96), "dmcf_cconv_kernel_name")
+        _lib.check(kernel_name(ctypes.byref(a), name, 96), "dmcf_cconv_kernel_name")
         return name.value.decode()
     nbytes = L.dmcf_cconv_workspace_bytes(ctypes.byref(a))
     ws = None
-    if packed_cache is not None:
+    if packed_cache is not None and ext is None:
         # ``packed_cache``: a dict the calling LAYER owns.  It keeps the workspace of the layer's last call; while the filter
         # tensor (storage, version), its interpretation and the kernel the dispatch picks are the same, the packed filter in it
         # is still valid and is not formed again (DMCF_FLAG_FILTER_PACKED: one launch less per layer and step)
@@ -747,13 +849,16 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
     if ws is None:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=filters.device)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_cconv_forward(ctypes.byref(a), _ptr(ws), nbytes, _stream()), "dmcf_cconv_forward")
+    if ext is None:
+        _lib.check(L.dmcf_cconv_forward(ctypes.byref(a), _ptr(ws), nbytes, _stream()), "dmcf_cconv_forward")
+    else:
+        _lib.check(L.dmcf_cconv_forward_extents(ctypes.byref(a), _ptr(ext), _ptr(ws), nbytes, _stream()), "dmcf_cconv_forward_extents")
     if timer is not None:
         kdims = [int(d) for d in filters.shape[:3]]
         if symmetric:
             kdims[int(sym_axis)] *= 2
         name = ctypes.create_string_buffer(96)
-        L.dmcf_cconv_kernel_name(ctypes.byref(a), name, 96)
+        kernel_name(ctypes.byref(a), name, 96)
         timer.end("cconv", dict(pairs=n_pairs_ref if n_pairs_ref is not None else int(a.n_pairs), n_out=n_out, cin=int(filters.shape[3]), cout=cout,
                                 K=kdims[0] * kdims[1] * kdims[2], symmetric=bool(symmetric), kernel=name.value.decode(),
                                 pair_values=bool(a.neighbors_value), accumulate=bool(accumulate)), t0)
@@ -867,17 +972,17 @@ def continuous_conv(filters, out_positions, extents, offset, inp_positions, inp_
                     max_temp_mem_MB=64, **_ignored):
     """Mirror of ``ml3d.ops.continuous_conv`` with the keyword set of utils/convolutions.py:414-431.
 
-    ``extents`` must hold a single value (DMCF always passes a scalar extent, :352-353,:390-392);
+    ``extents``: a single value (every shipped DMCF config, :352-353,:390-392) or individual extents of shape [n_out] or
+    [n_out, 1] (the RadiusSearch branch, :366-370 and :397-399); anisotropic extents ([n_out, 3], [1, 3]) are not implemented.
     ``offset`` must be zero (:200-201).  An empty tensor means "absent" for the importance inputs (:335,:376).
     """
     ext = extents if isinstance(extents, torch.Tensor) else torch.as_tensor(extents)
-    if ext.numel() != 1:
-        raise NotImplementedError("per-point extents (RadiusSearch path, utils/convolutions.py:366-370) "
-                                  "are not used by DMCF and not implemented")
+    if ext.dim() == 2 and ext.shape[1] == 3:
+        raise NotImplementedError("anisotropic extents ([n, 3] / [1, 3]) are not used by DMCF and not implemented")
     if offset is not None and bool(torch.as_tensor(offset).ne(0).any()):
         raise NotImplementedError("non-zero offset is not used by DMCF and not implemented")
     window = None if _empty(neighbors_importance) else "explicit"
-    return cconv_forward(filters, out_positions, float(ext), inp_positions, inp_features, neighbors_index,
+    return cconv_forward(filters, out_positions, float(ext) if ext.numel() == 1 else ext, inp_positions, inp_features, neighbors_index,
                          neighbors_row_splits, neighbors_value=neighbors_importance, window=window,
                          inp_importance=inp_importance, align_corners=align_corners,
                          coordinate_mapping=coordinate_mapping, interpolation=interpolation, normalize=normalize)

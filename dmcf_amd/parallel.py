@@ -817,6 +817,10 @@ class ShardedSimulator:
         """model.conv_hook: conv(feats, inp_pos -> out_pos) with the input rows extended by the ghosts within extent / 2.
         ``widest_extent``: the largest extent any layer reading the SAME ``feats`` uses -- the ghost rows then travel once,
         at that width, and the narrower sets are subsets of those rows (GhostPlan.extend_from)."""
+        if isinstance(extent, torch.Tensor) and extent.numel() != 1:
+            # (the ghost plans are keyed on one radius per point set; per-point extents would need the widest of them)
+            raise NotImplementedError("per-point extents (rank 1) are not implemented in the sharded step: run the model "
+                                      "on one rank")
         inp = self._set_name(inp_pos)
         plan = self._plan(inp, 0.5 * float(extent))
         n_own = feats.shape[0]

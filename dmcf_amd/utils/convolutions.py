@@ -423,6 +423,13 @@ def _init_tensor(name, shape, device):
 _ACTIVATIONS = {None: None, "linear": None, "relu": torch.relu, "tanh": torch.tanh}
 
 
+def _rank1_extents(extents, out_positions):
+    """Do these extents take the per-point branch (convolutions.py:366-370, 1006-1010)?  Rank 1 with more than one value, or
+    with one per output point; a one-element vector for several outputs stays the scalar it always was here."""
+    return (isinstance(extents, torch.Tensor) and extents.dim() == 1
+            and (extents.numel() > 1 or extents.numel() == out_positions.shape[0]))
+
+
 class PlainAttributes:
     """Mix-in for the modules of this package: attributes that are neither parameters, buffers nor sub-modules go straight to the
     instance dictionary.  torch.nn.Module.__setattr__ walks its registries and type checks for every assignment -- a layer sets
@@ -486,6 +493,10 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         self.fixed_radius_search = ops.FixedRadiusSearch(
             metric=self.radius_search_metric, ignore_query_point=self.radius_search_ignore_query_points,
             return_distances=self.window_function is not None)
+        # convolutions.py:212-216 (extents of rank 1)
+        self.radius_search = ops.RadiusSearch(
+            metric=self.radius_search_metric, ignore_query_point=self.radius_search_ignore_query_points,
+            return_distances=self.window_function is not None, normalize_distances=self.window_function is not None)
         self.use_dense_layer_for_center = use_dense_layer_for_center
         self.dense = None
         self.in_channels = None
@@ -565,10 +576,12 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                                   fixed_radius_search_hash_table, user_neighbors_index, user_neighbors_row_splits,
                                   user_neighbors_importance))
             return acc if extra_bias is None else acc.add_(extra_bias)
+        if _rank1_extents(extents, out_positions):
+            return self._forward_extents(inp_features, inp_positions, out_positions, extents, inp_importance, user_neighbors_index,
+                                         user_neighbors_row_splits, user_neighbors_importance, acc, extra_bias)
         if isinstance(extents, torch.Tensor):
             if extents.dim() > 0 and extents.numel() != 1:
-                raise NotImplementedError("per-point extents (RadiusSearch, convolutions.py:366-370) are never "
-                                          "used by DMCF and not implemented")
+                raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:352-372)")
             extent = float(extents)
         else:
             extent = float(np.float32(extents))
@@ -670,14 +683,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         d["_pairs_last"] = self.nns if (n_pairs_ref is None and getattr(self, "nns", None) is not None and user_neighbors_index is None) \
             else (n_pairs_ref if n_pairs_ref is not None else neighbors_index.shape[0])
 
-        kernel = self.kernel
-        symmetric = self.symmetric
-        if self.circular:
-            kernel = self._expanded_kernel()
-            symmetric = False  # the mask already made it antisymmetric; second pass still applies below
-            if self.symmetric:
-                raise NotImplementedError("circular + symmetric kernels (filters must be 3 in the reference; "
-                                          "no shipped config uses circular: True)")
+        kernel, symmetric = self._conv_kernel()
         # The reference keeps the operands of the last call for inspection (convolutions.py:398-413).  Inside a rollout
         # step (neighbor_cache scope) that would pin every layer's neighbour list (GBs each) and activations into the
         # next step: there only the small entries are kept.
@@ -691,9 +697,6 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             "coordinate_mapping": self.coordinate_mapping, "interpolation": self.interpolation,
             "normalize": self.normalize,
         }
-        if symmetric and self.normalize:
-            raise NotImplementedError("symmetric=True with normalize=True (DMCF always uses normalize=False, "
-                                      "models/pbf_model.py:203)")
         fuse_bias = self.use_bias and not self.use_dense_layer_for_center
         out_features = ops.cconv_forward(
             kernel, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
@@ -718,6 +721,73 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                 # list's buffers back after the number of consumers it saw in the previous step)
                 _CACHE.with_query_points(self.fixed_radius_search, inp_positions, out_positions,
                                          float(np.float32(0.5) * np.float32(extent)))
+        d["_conv_output"] = None if in_step else out_features
+        return self._finish(out_features, inp_features, extra_bias if self.use_dense_layer_for_center else None)
+
+    def _conv_kernel(self):
+        """(filter tensor, fused ASCC?) of a call: the circular expansion (convolutions.py:395-409) or the stored kernel."""
+        kernel, symmetric = self.kernel, self.symmetric
+        if self.circular:
+            kernel = self._expanded_kernel()
+            symmetric = False  # the mask already made it antisymmetric; second pass still applies below
+            if self.symmetric:
+                raise NotImplementedError("circular + symmetric kernels (filters must be 3 in the reference; "
+                                          "no shipped config uses circular: True)")
+        if symmetric and self.normalize:
+            raise NotImplementedError("symmetric=True with normalize=True (DMCF always uses normalize=False, "
+                                      "models/pbf_model.py:203)")
+        return kernel, symmetric
+
+    def _forward_extents(self, inp_features, inp_positions, out_positions, extents, inp_importance, user_neighbors_index,
+                         user_neighbors_row_splits, user_neighbors_importance, acc, extra_bias):
+        """The branch for extents of rank 1 (convolutions.py:366-370, then :397-399): a radius per output point (RadiusSearch),
+        every row convolved at its own extent (ops.cconv_forward -> dmcf_cconv_forward_extents; with SYMMETRIC each pair at its
+        output row's extent, which does not conserve momentum).  Never the lattice / scatter forms or the step's neighbour
+        cache: all of them key on one radius."""
+        d = self.__dict__
+        n_out = out_positions.shape[0]
+        if extents.shape[0] != n_out:
+            raise ValueError(f"extents of rank 1 must hold one value per output point ({n_out}), got {extents.shape[0]}")
+        window, window_fac, neighbors_value = None, 1.0, None
+        if user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
+            neighbors_index, neighbors_row_splits = user_neighbors_index, user_neighbors_row_splits
+            if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
+                window, neighbors_value = "explicit", user_neighbors_importance
+        else:
+            radii = 0.5 * extents  # :367
+            named = isinstance(self.window_function, WindowFunction)
+            # (a named window is evaluated in the kernel on d^2 re-formed from the positions: no distances needed)
+            search = self.radius_search.index_only() if named else self.radius_search
+            d["nns"] = search(inp_positions, out_positions, radii)
+            neighbors_index, neighbors_row_splits, dist = self.nns
+            if self.window_function is not None:
+                # The reference's rank-1 branch never binds neighbors_distance_normalized (:366-379: only the rank-0 branch
+                # does), so with a window TensorFlow raises there.  Implemented is the evident intent: the window on the
+                # RadiusSearch distances normalised per query, d^2 / r_i^2 (its normalize_distances=True, :212-216).
+                if named:
+                    window, window_fac = self.window_function.name, self.window_function.fac  # q = d^2 / r_i^2 in the kernel
+                else:
+                    window, neighbors_value = "explicit", self.window_function(dist).to(torch.float32)
+        d["_n_out_last"] = n_out
+        d["_pairs_last"] = neighbors_index.shape[0]
+        kernel, symmetric = self._conv_kernel()
+        in_step = _CACHE.depth > 0
+        d["_conv_values"] = {
+            "filters": kernel, "out_positions": out_positions, "extents": extents.reshape(n_out, 1), "offset": self.offset,
+            "inp_positions": inp_positions, "inp_features": None if in_step else inp_features,
+            "inp_importance": inp_importance,
+            "neighbors_index": None if in_step else neighbors_index, "neighbors_row_splits": neighbors_row_splits,
+            "neighbors_importance": None if in_step else neighbors_value, "align_corners": self.align_corners,
+            "coordinate_mapping": self.coordinate_mapping, "interpolation": self.interpolation,
+            "normalize": self.normalize,
+        }
+        fuse_bias = self.use_bias and not self.use_dense_layer_for_center
+        out_features = ops.cconv_forward(
+            kernel, out_positions, extents, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
+            neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
+            align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
+            interpolation=self.interpolation, normalize=self.normalize, symmetric=symmetric, sym_axis=self.sym_axis,
+            bias=self._epilogue_bias(fuse_bias, extra_bias), out=acc, accumulate=acc is not None)
         d["_conv_output"] = None if in_step else out_features
         return self._finish(out_features, inp_features, extra_bias if self.use_dense_layer_for_center else None)
 
@@ -821,6 +891,8 @@ class PointSampling(PlainAttributes, torch.nn.Module):
         self.window_function = window_function
         self.fixed_radius_search = ops.FixedRadiusSearch(metric="L2", ignore_query_point=False,
                                                          return_distances=window_function is not None)
+        self.radius_search = ops.RadiusSearch(metric="L2", ignore_query_point=False, return_distances=window_function is not None,
+                                              normalize_distances=window_function is not None)
         self.kernel = None
         self.nns = None
         self.layer_name = name
@@ -834,14 +906,28 @@ class PointSampling(PlainAttributes, torch.nn.Module):
                 user_neighbors_importance=None):
         if self.kernel is None or self.kernel.shape[-1] != inp_features.shape[-1] or self.kernel.device != inp_features.device:
             self.build(inp_features.shape[-1], inp_features.device)
-        if isinstance(extents, torch.Tensor) and extents.dim() > 0 and extents.numel() != 1:
-            raise NotImplementedError("per-point extents (RadiusSearch, convolutions.py:1006-1010) are not implemented")
-        extent = float(np.float32(float(extents)))
+        per_point = _rank1_extents(extents, out_positions)
+        if not per_point and isinstance(extents, torch.Tensor) and extents.dim() > 0 and extents.numel() != 1:
+            raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:1006-1012)")
+        if per_point and extents.shape[0] != out_positions.shape[0]:
+            raise ValueError(f"extents of rank 1 must hold one value per output point ({out_positions.shape[0]}), "
+                             f"got {extents.shape[0]}")
+        extent = extents if per_point else float(np.float32(float(extents)))
         window, window_fac, neighbors_value, n_pairs_ref, row_count = None, 1.0, None, None, None
         if user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :984-993
             neighbors_index, neighbors_row_splits = user_neighbors_index, user_neighbors_row_splits
             if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
                 window, neighbors_value = "explicit", user_neighbors_importance
+        elif per_point:  # :1006-1010, the reference's defect and its reading as in ContinuousConv._forward_extents
+            named = isinstance(self.window_function, WindowFunction)
+            search = self.radius_search.index_only() if named else self.radius_search
+            self.nns = search(inp_positions, out_positions, 0.5 * extents)
+            neighbors_index, neighbors_row_splits, dist = self.nns
+            if self.window_function is not None:
+                if named:
+                    window, window_fac = self.window_function.name, self.window_function.fac
+                else:
+                    window, neighbors_value = "explicit", self.window_function(dist).to(torch.float32)
         else:
             radius = float(np.float32(0.5) * np.float32(extent))  # :997
             if fixed_radius_search_hash_table is not None:

@@ -13,6 +13,9 @@
  *     utils/convolutions.py:359-379                               dmcf_cconv_forward
  *   ml3d.ops.continuous_conv (utils/convolutions.py:414-431)     dmcf_cconv_forward
  *   ASCC: mirror :410-412 + second continuous_conv :433-458      dmcf_cconv_forward(DMCF_FLAG_SYMMETRIC)
+ *   ml3d.layers.RadiusSearch (utils/convolutions.py:212-216,     dmcf_frs_build / dmcf_radius_search_count /
+ *     366-370, 1006-1010: extents of rank 1)                      dmcf_radius_search_write
+ *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents
  *   o3dml.ops.reduce_subarrays_sum (models/pbf_model.py:450-453) dmcf_reduce_subarrays_sum
  *   tf.keras.layers.Dense (models/hrnet.py:49,93-99;             dmcf_dense_forward
  *     models/pbf_model.py:134-152)
@@ -129,6 +132,29 @@ int dmcf_frs_window_sum(const float* queries, int64_t n_queries, int64_t n_point
                         const void* workspace, size_t workspace_bytes, float* out, dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Radius search: one radius per query.  Replaces ml3d.layers.RadiusSearch(metric='L2', ignore_query_point,
+ * return_distances, normalize_distances)(points, queries, radii)  (utils/convolutions.py:212-216, 366-370 and
+ * 1006-1010: the layers' branch for extents of rank 1, radii = 0.5 * extents).
+ * Result contract: for every query i the SET
+ *   { j : ((dx*dx + dy*dy) + dz*dz) <= r_i*r_i },  r_i = radii[i]     float32, un-fused, inclusive,
+ * minus points whose coordinates equal the query's when DMCF_FRS_IGNORE_QUERY_POINT is set.  Rows come out in the order of
+ * dmcf_frs_write (ascending grid cell, then ascending point index); neighbors_distance holds SQUARED distances (the
+ * library's normalize_distances -- d^2 / r_i^2 for L2 -- is the caller's job).  pair_capacity: as for dmcf_frs_write.
+ * A radius that is negative, NaN or larger than max_radius gives an empty row.
+ * Uses the workspace of dmcf_frs_build(points, n_points, max_radius): max_radius MUST be the radius of that build, the
+ * grid's cells are sized for it and every query scans cells of that size (a query of radius r visits ~(r + cell)^3 of them).
+ * flags: DMCF_FRS_IGNORE_QUERY_POINT only.  The DMCF_FRS_OPEN3D_* flags are DMCF_EINVAL: they emulate the hash walk of
+ * FixedRadiusSearch, and Open3D's RadiusSearch is a different structure (a KD-tree).
+ * ---------------------------------------------------------------------------------------------- */
+int dmcf_radius_search_count(const float* queries, int64_t n_queries, int64_t n_points, const float* radii,
+                             float max_radius, int flags, void* workspace, size_t workspace_bytes,
+                             int64_t* row_splits, dmcf_stream_t stream);
+int dmcf_radius_search_write(const float* queries, int64_t n_queries, int64_t n_points, const float* radii,
+                             float max_radius, int flags, const void* workspace, size_t workspace_bytes,
+                             const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance,
+                             int64_t pair_capacity, dmcf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Continuous convolution (CConv) and its antisymmetric variant (ASCC).
  * Replaces ml3d.ops.continuous_conv(filters, out_positions, extents[1,1], offset=0, inp_positions,
  * inp_features, inp_importance, neighbors_index, neighbors_row_splits, neighbors_importance,
@@ -234,6 +260,24 @@ int dmcf_cconv_forward(const dmcf_cconv_args* args, void* workspace, size_t work
  * layer -- filter shape, channel counts, flags -- never at the neighbour list), as rocprofv3 prints it without the
  * namespace, e.g. "cconv_z3_kernel<1, true>".  bench.py groups its per-launch HIP-event timings by it. */
 int dmcf_cconv_kernel_name(const dmcf_cconv_args* args, char* name, size_t name_bytes);
+
+/* CConv with INDIVIDUAL extents: ml3d.ops.continuous_conv with extents of shape [n_out, 1] (utils/convolutions.py:397-399
+ * after the rank-1 branch :366-370).  Output row i uses its own filter extent e_i = out_extents[i] (device, [n_out]):
+ * Lambda maps x_j - x_i with 1 / e_i, and a distance window is evaluated on d^2 / (e_i / 2)^2.  args->extent is ignored.
+ * Everything else is dmcf_cconv_forward's contract: every mapping / interpolation, ALIGN_CORNERS, NORMALIZE, ACCUMULATE,
+ * windows (neighbors_value == NULL included), bias, padded lists (neighbors_row_count).
+ *   SYMMETRIC  each pair is evaluated at the extent of its OUTPUT row: the two-pass form :433-458 with extents_rank2 =
+ *              [n_out, 1].  Pair (i, j) and pair (j, i) then see different extents, so the layer no longer conserves
+ *              momentum (models/sym_net.py:42-53 relies on equal extents).
+ *   An extent that is not positive and finite gives a zero row (plus the bias).
+ *   out_extents == NULL with n_out > 0: DMCF_EINVAL.  DMCF_FLAG_SKIP_SELF: DMCF_EUNSUPPORTED.  DMCF_FLAG_FILTER_PACKED is
+ *   ignored (the call always packs the filter).
+ * One generic kernel serves every call ("cconv_ext_kernel<CC>"); workspace: dmcf_cconv_workspace_bytes(args), which asks for
+ * a positive args->extent (any value: the size does not depend on it). */
+int dmcf_cconv_forward_extents(const dmcf_cconv_args* args, const float* out_extents, void* workspace,
+                               size_t workspace_bytes, dmcf_stream_t stream);
+/* the name of the kernel dmcf_cconv_forward_extents launches for these arguments (see dmcf_cconv_kernel_name) */
+int dmcf_cconv_extents_kernel_name(const dmcf_cconv_args* args, char* name, size_t name_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * ml3d.ops.continuous_conv (utils/convolutions.py:414-431) FROM particles ONTO a coarse grid_pos lattice with few output
