@@ -45,6 +45,22 @@ class CconvArgs(ctypes.Structure):
     ]
 
 
+class CconvBackwardArgs(ctypes.Structure):
+    """struct dmcf_cconv_backward_args (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_int32),
+        ("grad_out", ctypes.c_void_p),
+        ("inv_index", ctypes.c_void_p),
+        ("inv_pair", ctypes.c_void_p),
+        ("inv_row_splits", ctypes.c_void_p),
+        ("inv_n_rows", ctypes.c_int64),
+        ("inv_n_pairs", ctypes.c_int64),
+        ("grad_filters", ctypes.c_void_p),
+        ("grad_inp_features", ctypes.c_void_p),
+    ]
+
+
 class LatticeConvArgs(ctypes.Structure):
     """struct dmcf_lattice_conv_args (include/dmcf_hip.h)."""
     _fields_ = [
@@ -112,6 +128,8 @@ SYMBOLS = [
     "dmcf_radius_search_count", "dmcf_radius_search_write",
     "dmcf_cconv_workspace_bytes", "dmcf_cconv_forward", "dmcf_cconv_kernel_name",
     "dmcf_cconv_forward_extents", "dmcf_cconv_extents_kernel_name",
+    "dmcf_invert_neighbors_list_workspace_bytes", "dmcf_invert_neighbors_list",
+    "dmcf_cconv_backward_workspace_bytes", "dmcf_cconv_backward", "dmcf_cconv_backward_kernel_names",
     "dmcf_cconv_scatter_plan_bytes", "dmcf_cconv_scatter_plan", "dmcf_cconv_scatter_workspace_bytes", "dmcf_cconv_scatter_forward",
     "dmcf_lattice_conv_workspace_bytes", "dmcf_lattice_conv_forward",
     "dmcf_lattice_conv_batch_workspace_bytes", "dmcf_lattice_conv_forward_batch",
@@ -178,6 +196,17 @@ def lib():
     L.dmcf_cconv_forward_extents.argtypes = [c.POINTER(CconvArgs), c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
     L.dmcf_cconv_extents_kernel_name.restype = c.c_int
     L.dmcf_cconv_extents_kernel_name.argtypes = [c.POINTER(CconvArgs), c.c_char_p, c.c_size_t]
+    L.dmcf_invert_neighbors_list_workspace_bytes.restype = c.c_size_t
+    L.dmcf_invert_neighbors_list_workspace_bytes.argtypes = [c.c_int64]
+    L.dmcf_invert_neighbors_list.restype = c.c_int
+    L.dmcf_invert_neighbors_list.argtypes = [c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p,
+                                             c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_cconv_backward_workspace_bytes.restype = c.c_size_t
+    L.dmcf_cconv_backward_workspace_bytes.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs)]
+    L.dmcf_cconv_backward.restype = c.c_int
+    L.dmcf_cconv_backward.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_cconv_backward_kernel_names.restype = c.c_int
+    L.dmcf_cconv_backward_kernel_names.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_char_p, c.c_size_t]
     L.dmcf_cconv_scatter_plan_bytes.restype = c.c_size_t
     L.dmcf_cconv_scatter_plan_bytes.argtypes = [c.c_int64]
     L.dmcf_cconv_scatter_plan.restype = c.c_int

@@ -27,22 +27,38 @@ class Dense(PlainAttributes, torch.nn.Module):
         if self.use_bias:
             self.bias = torch.nn.Parameter(torch.zeros(self.units, device=device), requires_grad=False)
 
-    @torch.no_grad()
+    def recording(self, x):
+        """Does this call record autograd history (grad mode on, and the input or a weight requires grad)?"""
+        return torch.is_grad_enabled() and (x.requires_grad or any(w is not None and w.requires_grad for w in (self.kernel, self.bias)))
+
     def forward(self, x):
         if self.kernel is None:
-            self.build(x.shape[-1], x.device)
+            with torch.no_grad():
+                self.build(x.shape[-1], x.device)
+        if self.recording(x):  # torch's GEMM, differentiable
+            return torch.addmm(self.bias, x, self.kernel) if self.bias is not None else x @ self.kernel
+        return self._forward_infer(x)
+
+    @torch.no_grad()
+    def _forward_infer(self, x):
         if ops.dense_supported(x, self.kernel):
             return ops.dense_forward(x, self.kernel, self.bias)
         if self.bias is not None:
             return torch.addmm(self.bias, x, self.kernel)
         return x @ self.kernel
 
-    @torch.no_grad()
     def product(self, x, residual=None):
         """``x @ kernel`` (+ ``residual``, inside the GEMM: its C operand) WITHOUT the bias -- the start of a layer's sum
         (models/hrnet.py); the bias rides on the first convolution that accumulates into the result."""
         if self.kernel is None:
-            self.build(x.shape[-1], x.device)
+            with torch.no_grad():
+                self.build(x.shape[-1], x.device)
+        if self.recording(x):
+            return x @ self.kernel if residual is None else residual + x @ self.kernel
+        return self._product_infer(x, residual)
+
+    @torch.no_grad()
+    def _product_infer(self, x, residual=None):
         if ops.dense_supported(x, self.kernel):
             return ops.dense_forward(x, self.kernel, None, residual)
         if residual is not None:
@@ -82,11 +98,19 @@ class BaseModel(PlainAttributes, torch.nn.Module):
     def forward(self, prev, data, training=True, **kwargs):
         raise NotImplementedError
 
+    def recording(self):
+        """Does a call now record autograd history (grad mode on and some weight requires grad)?  Weights are built with
+        requires_grad=False; ``model.requires_grad_(True)`` enables training.  While recording, the models take their unfused,
+        out-of-place forms (the fused epilogues and paired launches have no backward)."""
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
     def loss(self, results, data):
-        raise NotImplementedError("training is out of scope of the MI355X hot path (SURVEY.md section 2 row 16)")
+        raise NotImplementedError(f"{type(self).__name__} defines no loss")
 
     def get_optimizer(self, cfg_pipeline):
-        raise NotImplementedError("training is out of scope of the MI355X hot path (SURVEY.md section 2 row 16)")
+        """models/pbf_model.py:508-517 of the reference: Adam (epsilon 1e-6) with a piecewise-constant learning rate."""
+        from ..utils.tools.losses import get_optimizer
+        return get_optimizer(self.parameters(), cfg_pipeline)
 
     def transform(self, data, training=True, **kwargs):
         return data

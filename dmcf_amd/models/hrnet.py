@@ -65,6 +65,7 @@ class HRNet(PBFNet):
         filter_extent = [float(np.float32(r) * np.float32(2)) for r in self.particle_radii]
         ans_convs = [[feats]]
         ext = None
+        recording = self.recording()  # autograd records: no epilogue fusion, no paired launches (they have no backward)
         stash = {}       # (layer, inp_scale) -> output of a scale-0 conv of that layer computed one layer early (cross_pairs)
         relu_next = {}   # inp_scale -> relu of the next layer's input at that scale, when already formed
         for layer in range(len(self.convs)):
@@ -79,7 +80,7 @@ class HRNet(PBFNet):
                 # convolutions pick them up one by one
                 self.ghost_prefetch([(relu_in[i], pos[i], max(filter_extent[max(i, s)] for s in range(n_scales)))
                                      for i in range(len(relu_in))])
-            cross = self._cross_layer_pairs(layer, dens)
+            cross = set() if recording else self._cross_layer_pairs(layer, dens)
             # output scales >= 1 first when a scale-0 conv of this layer is paired with one of the next layer (which reads this
             # layer's output at that scale): the sums do not depend on the order
             order = list(range(1, n_scales)) + [0] if cross else list(range(n_scales))
@@ -98,7 +99,7 @@ class HRNet(PBFNet):
                 # :115-118): the Dense of the layer's own scale starts it -- with the residual as the GEMM's C operand --, every
                 # convolution adds its result in its epilogue (DMCF_FLAG_ACCUMULATE), the Dense bias rides on the first of
                 # them.  The same terms in a different order of additions (the parity bar of the outputs is 1e-5).
-                fuse = self.add_merge and _FUSE_EPILOGUE
+                fuse = self.add_merge and _FUSE_EPILOGUE and not recording  # (recording: the out-of-place sums below)
                 acc, pending_bias = None, None
                 if fuse and layer < len(self.denses) and scale < n_inp:
                     own = self.denses[layer][scale][0][scale]

@@ -21,7 +21,7 @@ import torch
 from .. import ops
 from ..utils import convolutions as _convs
 from ..utils.convolutions import ContinuousConv, PointSampling
-from ..utils.tools.losses import (compute_density, compute_pressure, compute_transformed_dx, get_dilated_pos,
+from ..utils.tools.losses import (get_loss, compute_density, compute_pressure, compute_transformed_dx, get_dilated_pos,
                                   get_window_func)
 from .base_model import BaseModel, Dense
 
@@ -88,6 +88,13 @@ class PBFNet(BaseModel):
         self.grav = grav
         self.part_scale = part_scale
         self.num_fluid_neighbors = 1
+        # loss setup (pbf_model.py:123-130); a loss this package does not implement raises when it is evaluated
+        self.loss_fn = {}
+        for l, v in (loss or {}).items():
+            v = dict(v)
+            if v.get("typ") == "dense" and "radius" not in v:
+                v["radius"] = dens_radius[0]
+            self.loss_fn[l] = get_loss(**v)
 
         self._all_convs = []  # (name, conv) in creation order == checkpoint key order (pbf_model.py:223)
         self.fluid_convs = self.get_cconv(name="fluid_obs", filters=channels, activation=None,
@@ -310,7 +317,8 @@ class PBFNet(BaseModel):
         a, b = self.fluid_convs, self.obs_convs
         # (nothing here may depend on how many particles there are: in a sharded step every rank must take the same branch,
         # the ghost plans behind the two forms are different collectives)
-        if os.environ.get("DMCF_FUSE_INPUT_CONVS", "1") == "0" or _convs._CACHE.depth == 0 or not fluid_feats.is_cuda:
+        if (os.environ.get("DMCF_FUSE_INPUT_CONVS", "1") == "0" or _convs._CACHE.depth == 0 or not fluid_feats.is_cuda
+                or self.recording()):  # (while autograd records: the two layers one after the other)
             return None
         if ops.search_set() != "distance":
             # an emulation of open3d's hash walk: what a query sees depends on the TABLE of the point set searched (n / 64
@@ -390,6 +398,17 @@ class PBFNet(BaseModel):
                 return ops.reduce_subarrays_sum((idx < n).to(torch.float32), rs)[:n]
         self._fluid_counts = count
         return out[:, :co].contiguous(), out[:, co:].contiguous()
+
+    def loss_keys(self):
+        return self.loss_fn.keys()
+
+    def loss(self, results, data):
+        """pbf_model.py:494-506: every configured loss of one step.  ``results`` = the step's [pos2, vel2]; ``data`` = (input
+        data of the step, target positions, target positions of the previous frame, pre_steps)."""
+        pred, target = results[0], data[1]
+        return {n: l(target, pred, num_fluid_neighbors=self.num_fluid_neighbors, input=data[0], target_prev=data[2],
+                     pre_steps=data[3], pos_correction=self.pos_correction)
+                for n, l in self.loss_fn.items()}
 
     def postprocess(self, prev, data, training=True, vel_corr=None, **kwargs):
         pos, vel, acc = data[:3]

@@ -785,6 +785,42 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
                   normalize=False, symmetric=False, sym_axis=2, bias=None, out=None, accumulate=False,
                   n_pairs_ref=None, neighbors_row_count=None, filter_tile_mask=0, skip_self=False, name_only=False,
                   row_length_hint=0, packed_cache=None):
+    """One call of dmcf_cconv_forward (see ``_cconv_forward_impl`` for the arguments).
+
+    When autograd records (``torch.is_grad_enabled()``) and ``filters`` or ``inp_features`` requires grad, the call goes
+    through ``CconvFunction``: the same forward kernel, and a backward through dmcf_cconv_backward.  ``bias`` is then
+    differentiable too (torch adds it after the kernel).  ``out=`` / ``accumulate=True`` raise ValueError there, per-point
+    extents NotImplementedError.  Otherwise the call is exactly the inference path."""
+    if not name_only and torch.is_grad_enabled() and (
+            (isinstance(filters, torch.Tensor) and filters.requires_grad) or
+            (isinstance(inp_features, torch.Tensor) and inp_features.requires_grad) or
+            (isinstance(bias, torch.Tensor) and bias.requires_grad)):
+        if out is not None or accumulate:
+            raise ValueError("out= / accumulate=True cannot be recorded by autograd: use the returned tensor")
+        if per_point_extents(extent, out_positions.shape[0]) is not None:
+            raise NotImplementedError("the backward pass of CConv with per-point extents is not implemented")
+        kw = dict(out_positions=out_positions, extent=float(extent), inp_positions=inp_positions, neighbors_index=neighbors_index,
+                  neighbors_row_splits=neighbors_row_splits, neighbors_value=neighbors_value, window=window, window_fac=window_fac,
+                  inp_importance=inp_importance, align_corners=align_corners, coordinate_mapping=coordinate_mapping,
+                  interpolation=interpolation, normalize=normalize, symmetric=symmetric, sym_axis=sym_axis,
+                  neighbors_row_count=neighbors_row_count, filter_tile_mask=filter_tile_mask, skip_self=skip_self,
+                  row_length_hint=row_length_hint, n_pairs_ref=n_pairs_ref, packed_cache=packed_cache)
+        res = CconvFunction.apply(filters, inp_features, kw)
+        if bias is not None:
+            res = res + bias
+        return res
+    return _cconv_forward_impl(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
+                               neighbors_value, window, window_fac, inp_importance, align_corners, coordinate_mapping,
+                               interpolation, normalize, symmetric, sym_axis, bias, out, accumulate, n_pairs_ref,
+                               neighbors_row_count, filter_tile_mask, skip_self, name_only, row_length_hint, packed_cache)
+
+
+def _cconv_forward_impl(filters, out_positions, extent, inp_positions, inp_features, neighbors_index,
+                        neighbors_row_splits, neighbors_value=None, window=None, window_fac=1.0, inp_importance=None,
+                        align_corners=True, coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear",
+                        normalize=False, symmetric=False, sym_axis=2, bias=None, out=None, accumulate=False,
+                        n_pairs_ref=None, neighbors_row_count=None, filter_tile_mask=0, skip_self=False, name_only=False,
+                        row_length_hint=0, packed_cache=None):
     """One call of dmcf_cconv_forward.  ``row_length_hint``: 0 unknown / 1 tens / 2 hundreds of neighbours per row -- what the
     caller knows about the LAYER from its configuration (include/dmcf_hip.h).  ``skip_self``: DMCF_FLAG_SKIP_SELF (the list holds the query points, the layer ignores them; only the direct kernel).  ``name_only``: no launch, returns the name of the kernel these arguments dispatch to.  ``filter_tile_mask``: see ``block_diagonal_tile_mask`` (0 = no hint).  ``neighbors_row_count``: int32 [n_out] for padded lists (PaddedNeighborList).  ``window``: None | 'explicit' (neighbors_value = importance) |
     'poly6' | 'cubic' | 'linear' | 'peak' | 'cubic_grad' (neighbors_value = squared distances).
@@ -863,6 +899,144 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
                                 K=kdims[0] * kdims[1] * kdims[2], symmetric=bool(symmetric), kernel=name.value.decode(),
                                 pair_values=bool(a.neighbors_value), accumulate=bool(accumulate)), t0)
     return out
+
+
+InvertedNeighbors = collections.namedtuple("InvertedNeighbors",
+                                           ["neighbors_index", "neighbors_row_splits", "neighbors_attributes", "pair_index"])
+
+
+def invert_neighbors_list(num_points, inp_neighbors_index, inp_neighbors_row_splits, inp_neighbors_attributes=None,
+                          neighbors_row_count=None):
+    """Mirror of ``ml3d.ops.invert_neighbors_list`` (dmcf_invert_neighbors_list): for each of the ``num_points`` input points
+    the forward pairs that reference it.  Returns ``InvertedNeighbors(neighbors_index, neighbors_row_splits,
+    neighbors_attributes, pair_index)``: row j of the result is ``[row_splits[j], row_splits[j+1])``, holding the OUTPUT row of
+    each pair and (``pair_index``) the pair's position in the forward list, in ascending pair order.  The arrays keep the
+    length of the forward list; entries past ``row_splits[-1]`` (pairs of rows reaching past the list, or of padded slots) are
+    -1.  ``inp_neighbors_attributes``: None / empty or a float32 [P] tensor, returned permuted the same way.
+    ``neighbors_row_count``: int32 [n_out] for padded lists."""
+    L = _lib.lib()
+    index = inp_neighbors_index
+    rs = inp_neighbors_row_splits
+    if index.dtype != torch.int32 or rs.dtype != torch.int64:
+        raise TypeError("inp_neighbors_index must be int32 and inp_neighbors_row_splits int64")
+    if not index.is_cuda or not rs.is_cuda:
+        raise _lib.DmcfError("invert_neighbors_list runs on the GPU only (no CPU fallback)")
+    index, rs = index.contiguous(), rs.contiguous()
+    n_inp, n_out, P = int(num_points), rs.shape[0] - 1, index.shape[0]
+    dev = index.device
+    attrs = None if _empty(inp_neighbors_attributes) else _dev_f32(inp_neighbors_attributes, "inp_neighbors_attributes")
+    if attrs is not None and attrs.shape != (P,):
+        raise ValueError("inp_neighbors_attributes must be a float32 [P] tensor")
+    if neighbors_row_count is not None:
+        if neighbors_row_count.dtype != torch.int32 or neighbors_row_count.shape[0] != n_out:
+            raise TypeError("neighbors_row_count must be int32 [n_out]")
+        neighbors_row_count = neighbors_row_count.contiguous()
+    inv_index = torch.empty(P, dtype=torch.int32, device=dev)
+    inv_pair = torch.empty(P, dtype=torch.int32, device=dev)
+    inv_rs = torch.empty(n_inp + 1, dtype=torch.int64, device=dev)
+    inv_attr = torch.empty(P, dtype=torch.float32, device=dev) if attrs is not None else torch.empty(0, dtype=torch.float32, device=dev)
+    nbytes = int(L.dmcf_invert_neighbors_list_workspace_bytes(P))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_invert_neighbors_list(n_inp, _ptr(index), _ptr(rs), _ptr(neighbors_row_count), n_out, P, _ptr(attrs),
+                                            _ptr(inv_index), _ptr(inv_rs), _ptr(inv_pair), _ptr(inv_attr) if attrs is not None else None,
+                                            _ptr(ws), nbytes, _stream()), "dmcf_invert_neighbors_list")
+    if timer is not None:
+        timer.end("invert", dict(pairs=P, n_inp=n_inp), t0)
+    return InvertedNeighbors(inv_index, inv_rs, inv_attr, inv_pair)
+
+
+def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits, grad_out,
+                   neighbors_value=None, window=None, window_fac=1.0, inp_importance=None, align_corners=True,
+                   coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", normalize=False, symmetric=False,
+                   sym_axis=2, neighbors_row_count=None, skip_self=False, need_filters=True, need_features=True, inverted=None,
+                   grad_filters=None, grad_inp_features=None, accumulate=False, **_ignored):
+    """dmcf_cconv_backward: ``(grad_filters, grad_inp_features)`` of the CConv ``cconv_forward`` computes with these
+    arguments, for ``grad_out`` = dL/d out [n_out, Cout].  Either can be skipped (``need_filters`` / ``need_features``
+    False: None is returned for it).  ``inverted``: an ``invert_neighbors_list`` result of the same list (formed here when
+    the input-feature gradient is wanted and none is given).  ``grad_filters`` / ``grad_inp_features``: output tensors to
+    write, or with ``accumulate=True`` to add into.  With ``symmetric`` the filter gradient is that of the stored half
+    kernel."""
+    L = _lib.lib()
+    n_out, n_inp = out_positions.shape[0], inp_positions.shape[0]
+    cin = filters.shape[3]
+    dev = filters.device
+    grad_out = _dev_f32(grad_out, "grad_out", filters.shape[4])
+    if grad_out.shape[0] != n_out:
+        raise ValueError("grad_out must be [n_out, Cout]")
+    if need_filters and grad_filters is None:
+        grad_filters = (torch.zeros if accumulate else torch.empty)(tuple(filters.shape), dtype=torch.float32, device=dev)
+    if need_features and grad_inp_features is None:
+        grad_inp_features = (torch.zeros if accumulate else torch.empty)((n_inp, cin), dtype=torch.float32, device=dev)
+    for t, shape, name in ((grad_filters if need_filters else None, tuple(filters.shape), "grad_filters"),
+                           (grad_inp_features if need_features else None, (n_inp, cin), "grad_inp_features")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"{name} must be a contiguous float32 device tensor of shape {shape}")
+    if not need_filters and not need_features:
+        return None, None
+    a, keep = _cconv_args(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
+                          neighbors_value, window, window_fac, inp_importance, align_corners, coordinate_mapping, interpolation,
+                          normalize, symmetric, sym_axis, None, None, False, neighbors_row_count, 0, skip_self, 0)
+    b = _lib.CconvBackwardArgs()
+    b.struct_size = ctypes.sizeof(_lib.CconvBackwardArgs)
+    b.flags = 1 if accumulate else 0
+    b.grad_out = grad_out.data_ptr()
+    if need_features:
+        if inverted is None:
+            inverted = invert_neighbors_list(n_inp, neighbors_index, neighbors_row_splits, None, neighbors_row_count)
+        b.inv_index = inverted.neighbors_index.data_ptr()
+        b.inv_pair = inverted.pair_index.data_ptr()
+        b.inv_row_splits = inverted.neighbors_row_splits.data_ptr()
+        b.inv_n_rows = inverted.neighbors_row_splits.shape[0] - 1
+        b.inv_n_pairs = inverted.neighbors_index.shape[0]
+        b.grad_inp_features = grad_inp_features.data_ptr()
+    if need_filters:
+        b.grad_filters = grad_filters.data_ptr()
+    nbytes = int(L.dmcf_cconv_backward_workspace_bytes(ctypes.byref(a), ctypes.byref(b)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_cconv_backward(ctypes.byref(a), ctypes.byref(b), _ptr(ws), nbytes, _stream()), "dmcf_cconv_backward")
+    if timer is not None:
+        timer.end("cconv_backward", dict(n_out=n_out, cin=int(cin), cout=int(filters.shape[4]), filters=bool(need_filters),
+                                         features=bool(need_features), kernel=cconv_backward_kernel_names(a, b)), t0)
+    del keep
+    return (grad_filters if need_filters else None), (grad_inp_features if need_features else None)
+
+
+def cconv_backward_kernel_names(a, b):
+    """';'-separated names of the kernels dmcf_cconv_backward launches for these (ctypes) arguments."""
+    name = ctypes.create_string_buffer(256)
+    _lib.check(_lib.lib().dmcf_cconv_backward_kernel_names(ctypes.byref(a), ctypes.byref(b), name, 256),
+               "dmcf_cconv_backward_kernel_names")
+    return name.value.decode()
+
+
+class CconvFunction(torch.autograd.Function):
+    """Autograd node of ``cconv_forward``: the forward is whatever kernel the dispatch picks today (bias excluded: torch adds
+    it); the backward is dmcf_cconv_backward, with the neighbour list inverted once per backward when the input features want
+    a gradient.  Positions, extents and importances get no gradient (as in Open3D)."""
+
+    @staticmethod
+    def forward(ctx, filters, inp_features, kw):
+        ctx.kw = kw
+        ctx.save_for_backward(filters, inp_features)
+        f = dict(kw)
+        return _cconv_forward_impl(filters, f.pop("out_positions"), f.pop("extent"), f.pop("inp_positions"), inp_features,
+                                   f.pop("neighbors_index"), f.pop("neighbors_row_splits"), **f)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        filters, inp_features = ctx.saved_tensors
+        need_w = ctx.needs_input_grad[0]
+        need_f = ctx.needs_input_grad[1] and inp_features is not None
+        if not need_w and not need_f:
+            return None, None, None
+        kw = dict(ctx.kw)
+        gw, gf = cconv_backward(filters.detach(), kw.pop("out_positions"), kw.pop("extent"), kw.pop("inp_positions"),
+                                None if inp_features is None else inp_features.detach(), kw.pop("neighbors_index"),
+                                kw.pop("neighbors_row_splits"), grad_out.contiguous(), need_filters=need_w, need_features=need_f,
+                                **kw)
+        return gw, gf, None
 
 
 class ScatterPlan:

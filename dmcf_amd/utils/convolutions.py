@@ -7,8 +7,9 @@ What differs is underneath: the radius search, the window function, the CConv it
 ASCC body (mirror + two continuous_conv calls + batched matmul, :410-412,:433-458) are one HIP
 search + one HIP kernel launch each (dmcf_amd/ops.py -> libdmcf_hip.so).
 
-Inference only: the layer does not record autograd history (training is out of scope, SURVEY.md
-section 2 row 16).
+Weights are built with ``requires_grad=False``: inference records no autograd history.  After
+``layer.requires_grad_(True)`` (or with input features that require grad) a call records it and takes
+the neighbour-list form, whose backward is dmcf_cconv_backward (``ContinuousConv._forward_train``).
 """
 import math
 import os
@@ -558,12 +559,101 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             kernel = kernel * mask.unsqueeze(-2)
         return kernel
 
-    @torch.no_grad()
     def forward(self, inp_features, inp_positions, out_positions, extents, inp_importance=None,
                 fixed_radius_search_hash_table=None, user_neighbors_index=None, user_neighbors_row_splits=None,
                 user_neighbors_importance=None):
         if self.kernel is None:
-            self.build(inp_features.shape[-1], inp_features.device)
+            with torch.no_grad():
+                self.build(inp_features.shape[-1], inp_features.device)
+        if self.recording(inp_features):
+            return self._forward_train(inp_features, inp_positions, out_positions, extents, inp_importance,
+                                       fixed_radius_search_hash_table, user_neighbors_index, user_neighbors_row_splits,
+                                       user_neighbors_importance)
+        return self._forward_infer(inp_features, inp_positions, out_positions, extents, inp_importance,
+                                   fixed_radius_search_hash_table, user_neighbors_index, user_neighbors_row_splits,
+                                   user_neighbors_importance)
+
+    def recording(self, inp_features=None):
+        """Does a call now record autograd history: grad mode on and a weight (``requires_grad_(True)``) or the input features
+        requiring grad.  Weights are built with requires_grad=False, so inference never records."""
+        if not torch.is_grad_enabled():
+            return False
+        if isinstance(inp_features, torch.Tensor) and inp_features.requires_grad:
+            return True
+        return any(w is not None and w.requires_grad for w in (self.kernel, self.bias, self.dense))
+
+    def _forward_train(self, inp_features, inp_positions, out_positions, extents, inp_importance, hash_table,
+                       user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance):
+        """The layer while autograd records: always the neighbour-list form through ops.cconv_forward's autograd node
+        (dmcf_cconv_backward).  The lattice and scatter forms, the stray-row path, the step's list cache and the epilogue fusions
+        (accumulate_into / extra_bias, fused bias) are not taken: their kernels have no backward.  Bias, the dense centre term,
+        the activation and the circular expansion are torch ops.  A pending accumulate_into / extra_bias request is honoured out
+        of place: the result is ``accumulate_into + layer(x) + extra_bias`` (accumulate_into itself is not written)."""
+        d = self.__dict__
+        acc, extra_bias = self.accumulate_into, self.extra_bias
+        d["accumulate_into"] = d["extra_bias"] = None
+        if _rank1_extents(extents, out_positions):
+            raise NotImplementedError("ContinuousConv with per-point extents (rank 1) has no backward pass: the training path "
+                                      "supports a scalar extent only")
+        if isinstance(extents, torch.Tensor):
+            if extents.dim() > 0 and extents.numel() != 1:
+                raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:352-372)")
+            extent = float(extents)
+        else:
+            extent = float(np.float32(extents))
+        window, window_fac, neighbors_value = None, 1.0, None
+        row_count = None
+        if user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
+            neighbors_index, neighbors_row_splits = user_neighbors_index, user_neighbors_row_splits
+            if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
+                window, neighbors_value = "explicit", user_neighbors_importance
+        else:
+            radius = float(np.float32(0.5) * np.float32(extent))  # :353
+            with torch.no_grad():
+                # (an exact search of its own, outside the step's list cache: the backward needs the list after the step)
+                if hash_table is not None:
+                    d["nns"] = self.fixed_radius_search(inp_positions, out_positions, radius, hash_table=hash_table)
+                else:
+                    d["nns"] = self.fixed_radius_search(inp_positions, out_positions, radius)
+                neighbors_index, neighbors_row_splits, raw_dist = self.nns.raw()
+                row_count = getattr(self.nns, "row_count", None)
+                if self.window_function is not None:  # :359-379
+                    if isinstance(self.window_function, WindowFunction):
+                        window, window_fac = self.window_function.name, self.window_function.fac
+                        neighbors_value = raw_dist
+                    else:
+                        q = self.nns.neighbors_distance / (np.float32(radius) * np.float32(radius))
+                        neighbors_index = self.nns.neighbors_index
+                        if row_count is not None:
+                            neighbors_row_splits, row_count = self.nns.csr_row_splits, None
+                        window, neighbors_value = "explicit", self.window_function(q).to(torch.float32)
+        d["_n_out_last"] = out_positions.shape[0]
+        d["_pairs_last"] = neighbors_index.shape[0]
+        kernel, symmetric = self._conv_kernel()
+        d["_conv_values"] = None
+        out_features = ops.cconv_forward(
+            kernel, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
+            neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
+            align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
+            interpolation=self.interpolation, normalize=self.normalize, symmetric=symmetric, sym_axis=self.sym_axis,
+            neighbors_row_count=row_count, row_length_hint=self.row_length_hint,
+            packed_cache=self._packed if (kernel is self.kernel and os.environ.get("DMCF_CACHE_PACKED_FILTERS", "1") != "0")
+            else None)
+        if self.use_bias and not self.use_dense_layer_for_center:
+            out_features = out_features + self.bias
+        d["_conv_output"] = None
+        # (where the inference path puts the extra bias: inside the activation, unless the call also accumulates)
+        out_features = self._finish(out_features, inp_features, extra_bias if acc is None else None)
+        if acc is not None:
+            out_features = acc + out_features
+            if extra_bias is not None:
+                out_features = out_features + extra_bias
+        return out_features
+
+    @torch.no_grad()
+    def _forward_infer(self, inp_features, inp_positions, out_positions, extents, inp_importance=None,
+                       fixed_radius_search_hash_table=None, user_neighbors_index=None, user_neighbors_row_splits=None,
+                       user_neighbors_importance=None):
         # one-shot requests of the caller (models/hrnet.py): add the result to this tensor in the kernel's epilogue
         # (DMCF_FLAG_ACCUMULATE) instead of returning a new one, and add this vector to the layer's bias
         acc, extra_bias = self.accumulate_into, self.extra_bias

@@ -9,8 +9,11 @@
   compute_pressure  losses.py:367-377  Tait-style pressure from the density
   density_loss      losses.py:380-398  validation metric of pipelines/simulator.py:227-243
 
-The training losses (losses.py:47-110, 400-414: Chamfer / EMD / get_loss) need the reference's custom CUDA ops
-and stay out of scope.
+  get_loss          losses.py:47-110   the training losses mse / weighted_mse / vel / weighted_vel / momentum
+  get_optimizer     models/pbf_model.py:508-517  Adam (eps 1e-6), piecewise-constant learning rate
+
+The density, Chamfer, EMD and histogram losses (losses.py:380-414, the last three on the reference's custom CUDA ops) are
+not implemented: get_loss returns a function that raises NotImplementedError for them.
 """
 import numpy as np
 import torch
@@ -215,3 +218,78 @@ def density_loss(gt, pred, gt_in=None, pred_in=None, radius=0.005, eps=0.01, win
     if use_max:
         return torch.abs(pred_dens.max() - rest_dens) / rest_dens
     return torch.relu(pred_dens - rest_dens - eps).mean()
+
+
+def _pre_factor(kwargs, kw, like):
+    # tf.exp(-pre_scale * float(pre_steps)) (losses.py:51-52)
+    steps = kw.get("pre_steps")
+    steps = 0.0 if steps is None else steps
+    return torch.exp(-float(kwargs.get("pre_scale", 0.0)) * torch.as_tensor(steps, dtype=torch.float32, device=like.device))
+
+
+def get_loss(typ, fac=1.0, **kwargs):
+    """losses.py:47-110: the loss function of one entry of a config's ``loss`` section, called as ``f(target, pred, **kw)``
+    with the keywords of PBFNet.loss (num_fluid_neighbors, input, target_prev, pre_steps, pos_correction)."""
+    gamma = kwargs.get("gamma", 0.5)
+    if typ == "mse":
+        def f(target, pred, **kw):
+            diff = (torch.sum((target - pred) ** 2, dim=-1) + 1e-9) ** gamma
+            return fac * torch.mean(_pre_factor(kwargs, kw, pred) * diff)
+        return f
+    if typ == "weighted_mse":
+        def f(target, pred, **kw):
+            importance = torch.exp(-kwargs.get("neighbor_scale", 1.0) * torch.as_tensor(kw.get("num_fluid_neighbors"),
+                                                                                     dtype=torch.float32, device=pred.device))
+            diff = (torch.sum((target - pred) ** 2, dim=-1) + 1e-9) ** gamma
+            return fac * torch.mean(_pre_factor(kwargs, kw, pred) * importance * diff)
+        return f
+    if typ == "vel":
+        def f(target, pred, **kw):
+            inp, prev = kw.get("input")[0], kw.get("target_prev")
+            diff = (torch.sum(((target - prev) - (pred - inp)) ** 2, dim=-1) + 1e-9) ** gamma
+            return fac * torch.mean(diff)
+        return f
+    if typ == "weighted_vel":
+        def f(target, pred, **kw):
+            inp, prev = kw.get("input")[0], kw.get("target_prev")
+            importance = torch.exp(-kwargs.get("neighbor_scale", 1.0) * torch.as_tensor(kw.get("num_fluid_neighbors"),
+                                                                                     dtype=torch.float32, device=pred.device))
+            diff = (torch.sum(((target - prev) - (pred - inp)) ** 2, dim=-1) + 1e-9) ** gamma
+            return fac * torch.mean(importance * diff)
+        return f
+    if typ == "momentum":
+        def f(target, pred, **kw):
+            return fac * torch.mean(kw.get("pos_correction"))
+        return f
+    if typ in ("dense", "chamfer", "emd", "hist"):
+        def f(*args, **kw):
+            raise NotImplementedError(f"the {typ!r} training loss is not implemented")
+        return f
+    raise NotImplementedError(typ)
+
+
+class PiecewiseConstant:
+    """tf.keras.optimizers.schedules.PiecewiseConstantDecay(boundaries, values): values[0] for step <= boundaries[0],
+    values[k] for boundaries[k-1] < step <= boundaries[k], values[-1] after the last boundary."""
+
+    def __init__(self, boundaries, values):
+        if len(values) != len(boundaries) + 1:
+            raise ValueError("lr_values must have one entry more than lr_boundaries")
+        self.boundaries = [int(b) for b in boundaries]
+        self.values = [float(v) for v in values]
+
+    def __call__(self, step):
+        for b, v in zip(self.boundaries, self.values):
+            if step <= b:
+                return v
+        return self.values[-1]
+
+
+def get_optimizer(params, cfg):
+    """models/pbf_model.py:508-517: Adam with epsilon 1e-6 and the piecewise-constant learning rate of ``cfg['lr_boundaries']``
+    / ``cfg['lr_values']``, as (optimizer, scheduler): call ``scheduler.step()`` after every ``optimizer.step()`` -- the
+    learning rate of optimiser step k (counted from 0, as Keras' iterations) is PiecewiseConstant(...)(k)."""
+    sched = PiecewiseConstant(cfg["lr_boundaries"], cfg["lr_values"])
+    opt = torch.optim.Adam(params, lr=sched.values[0], eps=1e-6)
+    lam = torch.optim.lr_scheduler.LambdaLR(opt, lambda step: sched(step) / sched.values[0])
+    return opt, lam

@@ -280,6 +280,63 @@ int dmcf_cconv_forward_extents(const dmcf_cconv_args* args, const float* out_ext
 int dmcf_cconv_extents_kernel_name(const dmcf_cconv_args* args, char* name, size_t name_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Backward pass of dmcf_cconv_forward (training).  Replaces the gradients Open3D 0.15.2 registers for
+ * ml3d.ops.continuous_conv: continuous_conv_backprop_filter (d filters) and invert_neighbors_list + continuous_conv_transpose
+ * (d inp_features).  Positions, extents and importances get no gradient, as there.
+ *
+ * dmcf_invert_neighbors_list replaces ml3d.ops.invert_neighbors_list(num_points = n_inp, inp_neighbors_index,
+ * inp_neighbors_row_splits, inp_neighbors_attributes): for every input point j the forward pairs that reference it.
+ *   inv_row_splits [n_inp + 1]: row j = entries [inv_row_splits[j], inv_row_splits[j+1]); inv_row_splits[n_inp] = the pairs
+ *                               of the list (rows reaching past n_pairs, as in dmcf_cconv_forward, and indices outside
+ *                               [0, n_inp) are not pairs).  Inside a row: ascending forward pair index (deterministic).
+ *   inv_index [n_pairs]         the output row i of each entry (-1 past inv_row_splits[n_inp])
+ *   inv_pair  [n_pairs]         the forward pair index p of each entry (-1 past the end); required
+ *   inv_values [n_pairs]        optional: values[p] permuted the same way (the attributes; NULL = not wanted)
+ * neighbors_row_count: optional [n_out], padded lists as in dmcf_cconv_args.  A stable radix sort (rocPRIM) keyed by j.
+ * ---------------------------------------------------------------------------------------------- */
+size_t dmcf_invert_neighbors_list_workspace_bytes(int64_t n_pairs);
+int dmcf_invert_neighbors_list(int64_t n_inp, const int32_t* neighbors_index, const int64_t* neighbors_row_splits,
+                               const int32_t* neighbors_row_count, int64_t n_out, int64_t n_pairs, const float* values,
+                               int32_t* inv_index, int64_t* inv_row_splits, int32_t* inv_pair, float* inv_values,
+                               void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+
+/* dmcf_cconv_backward(fwd, bwd): with the forward's arguments `fwd` (out, bias and DMCF_FLAG_ACCUMULATE / FILTER_PACKED are
+ * ignored) and G = bwd->grad_out = dL/d out [n_out, Cout]:
+ *     grad_inp_features[j,:] = sum_{p -> j} (a_p / psi_i) sum_c w_c(p) W_c G[i,:]          (continuous_conv_transpose)
+ *     grad_filters[c]        = sum_p (a_p / psi_i) w_c(p) f_j (x) G[i]                      (continuous_conv_backprop_filter)
+ * a_p the pair weight times s_j, psi_i the forward's normaliser (1 without NORMALIZE or where it is 0).  With SYMMETRIC (ASCC)
+ * the pair features are f_j + f_i, grad_inp_features gets the centre term sum_p (a_p / psi_i) sum_c w_c(p) g_c G[i,:] as well,
+ * and grad_filters is the gradient of the stored HALF kernel (the full kernel's gradient folded back:
+ * dHalf = dFull[upper] - flip_zyx(dFull[lower])); n_inp != n_out (the sharded layout) is DMCF_EUNSUPPORTED.
+ * Every option of dmcf_cconv_forward is supported: mappings, interpolations, ALIGN_CORNERS, windows (neighbors_value == NULL
+ * included), NORMALIZE, inp_importance, SYMMETRIC, SKIP_SELF, padded lists.  Per-point extents are not.
+ * The geometry of each pair is formed as in the generic forward kernel; only the order of the sums differs.  No float
+ * atomics: two identical calls give identical bits.  K * Cin and K * Cout above 16384 (K the full kernel's cells):
+ * DMCF_EUNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------- */
+#define DMCF_BWD_ACCUMULATE 1 /* grad_* += result instead of grad_* = result (a weight shared by several calls) */
+typedef struct dmcf_cconv_backward_args {
+    uint32_t struct_size;           /* sizeof(dmcf_cconv_backward_args) of the caller; smaller: DMCF_EINVAL */
+    int32_t flags;                  /* DMCF_BWD_* */
+    const float* grad_out;          /* [n_out, Cout] */
+    const int32_t* inv_index;       /* dmcf_invert_neighbors_list of the forward list (needed for grad_inp_features only) */
+    const int32_t* inv_pair;
+    const int64_t* inv_row_splits;  /* [inv_n_rows + 1] */
+    int64_t inv_n_rows;             /* must equal fwd->n_inp */
+    int64_t inv_n_pairs;            /* entries inv_index / inv_pair hold */
+    float* grad_filters;            /* shape of fwd->filters, or NULL = not wanted */
+    float* grad_inp_features;       /* [n_inp, Cin], or NULL = not wanted */
+} dmcf_cconv_backward_args;
+
+size_t dmcf_cconv_backward_workspace_bytes(const dmcf_cconv_args* fwd, const dmcf_cconv_backward_args* bwd);
+int dmcf_cconv_backward(const dmcf_cconv_args* fwd, const dmcf_cconv_backward_args* bwd, void* workspace,
+                        size_t workspace_bytes, dmcf_stream_t stream);
+/* Diagnostics: the device kernels dmcf_cconv_backward launches for these arguments, in launch order, separated by ';'
+ * (names as rocprofv3 prints them without the namespace, e.g. "cconv_bwd_input") */
+int dmcf_cconv_backward_kernel_names(const dmcf_cconv_args* fwd, const dmcf_cconv_backward_args* bwd, char* names,
+                                     size_t name_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * ml3d.ops.continuous_conv (utils/convolutions.py:414-431) FROM particles ONTO a coarse grid_pos lattice with few output
  * channels -- the layers models/hrnet.py:83-93 builds for (input scale 0, output scale >= 1) with layer_channels[..][scale] of
  * 4 or 8 (configs/Liquid3d.yml:11: [[16], [8], [4]] / [[32], [16], [8]]).  Same operator, other order of evaluation ("filter

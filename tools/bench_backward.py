@@ -1,0 +1,129 @@
+"""Training-step cost on the 1M-particle Liquid3d box (bench.py's scene, config 5): DESIGN.md section 2, "Backward pass".
+
+  python tools/bench_backward.py [--side 100] [--steps 3] [--out bench_backward.json]
+
+Reports
+  * train_step: forward with autograd recording + weighted_mse loss + backward + Adam, ms (median of --steps after one
+    warm-up) and torch.cuda.max_memory_allocated;
+  * layers: per CConv / ASCC call of one training step, from HIP events around each launch (ops.timer): the forward kernel,
+    the neighbour-list inversion and the backward (both gradients);
+  * split: for a 24-channel 4x4x4 layer on the box's own list at the second scale's radius (hundreds of neighbours per
+    row, like the two 24-channel layers of the network), the forward, the inversion, the input-feature gradient alone and
+    the filter gradient alone."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from dmcf_amd import models, ops  # noqa: E402
+from dmcf_amd.utils import tf_checkpoint as tc  # noqa: E402
+from tools import configs, scenes  # noqa: E402
+
+
+def timed(fn, n=5):
+    fn()
+    ts = []
+    for _ in range(n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return dict(ms_median=float(np.median(ts)), ms_min=float(np.min(ts)), ms_max=float(np.max(ts)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--side", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_backward needs a GPU")
+    dev = torch.device("cuda:0")
+    cfg = dict(configs.LIQUID3D)
+    cfg["loss"] = {"weighted_mse": dict(typ="weighted_mse", fac=128.0, gamma=0.5, neighbor_scale=0.025, pre_scale=0.025)}
+    model = getattr(models, cfg["name"])(**cfg)
+    tc.load_into_model(model, dict(np.load(os.path.join(ROOT, "tests", "golden", "liquid3d_weights.npz"))), device=dev)
+    data = scenes.model_inputs(scenes.box_scene(args.side), device=dev)
+    with torch.no_grad():
+        model(data)
+    model.requires_grad_(True)
+    opt, sched = model.get_optimizer({"lr_boundaries": [1000], "lr_values": [1e-4, 1e-5]})
+    target = data[0] + model.timestep * data[1]
+
+    def train_step():
+        pos2, vel2 = model(data)
+        loss = model.loss([pos2, vel2], ([data[0]], target, data[0], 0))["weighted_mse"]
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        sched.step()
+
+    result = dict(points=int(data[0].shape[0] + data[4].shape[0]), fluid=int(data[0].shape[0]))
+    train_step()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    result["train_step"] = timed(train_step, args.steps)
+    result["train_step"]["max_memory_allocated_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+    print(json.dumps({"train_step": result["train_step"]}), flush=True)
+    with torch.no_grad():
+        result["inference_step"] = timed(lambda: model(data), args.steps)
+    print(json.dumps({"inference_step": result["inference_step"]}), flush=True)
+
+    # per-call breakdown of one training step
+    ops.timer = ops.LaunchTimer()
+    train_step()
+    torch.cuda.synchronize()
+    recs = ops.timer.results()
+    ops.timer = None
+    layers = [dict(kind=k, ms=ms, **m) for k, m, ms in recs]
+    result["layers"] = layers
+    tot = {}
+    for r in layers:
+        tot[r["kind"]] = tot.get(r["kind"], 0.0) + r["ms"]
+    result["layer_totals_ms"] = tot
+    print(json.dumps({"layer_totals_ms": tot}), flush=True)
+
+    # the two gradients of one wide-radius 24-channel layer, separately
+    pos = torch.cat([data[0], data[4]]).contiguous()
+    n = pos.shape[0]
+    radius = float(np.float32(cfg["particle_radii"][1]))
+    nns = ops.fixed_radius_search(pos, pos, radius, return_distances=False)
+    idx, rs = nns.neighbors_index, nns.neighbors_row_splits
+    pairs = int(rs[-1])
+    split = dict(pairs=pairs, radius=radius)
+    for cin, cout in ((24, 16), (24, 32)):
+        rng = np.random.default_rng(0)
+        F = torch.from_numpy(rng.normal(size=(n, cin)).astype(np.float32)).to(dev)
+        W = torch.from_numpy(rng.uniform(-0.1, 0.1, size=(4, 4, 4, cin, cout)).astype(np.float32)).to(dev)
+        G = torch.from_numpy(rng.normal(size=(n, cout)).astype(np.float32)).to(dev)
+        kw = dict(window="poly6", row_length_hint=2)
+        out = torch.empty(n, cout, device=dev)
+        inv = ops.invert_neighbors_list(n, idx, rs)
+        gw = torch.empty_like(W)
+        gf = torch.empty_like(F)
+        row = dict(kernel=ops.cconv_forward(W, pos, 2 * radius, pos, F, idx, rs, name_only=True, **kw))
+        row["forward"] = timed(lambda: ops.cconv_forward(W, pos, 2 * radius, pos, F, idx, rs, out=out, **kw))
+        row["invert"] = timed(lambda: ops.invert_neighbors_list(n, idx, rs))
+        row["grad_inp_features"] = timed(lambda: ops.cconv_backward(W, pos, 2 * radius, pos, F, idx, rs, G, window="poly6",
+                                                                    need_filters=False, inverted=inv, grad_inp_features=gf))
+        row["grad_filters"] = timed(lambda: ops.cconv_backward(W, pos, 2 * radius, pos, F, idx, rs, G, window="poly6",
+                                                               need_features=False, grad_filters=gw))
+        split[f"{cin}->{cout}"] = row
+        print(json.dumps({f"split {cin}->{cout}": row}), flush=True)
+    result["split"] = split
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
