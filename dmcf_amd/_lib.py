@@ -137,6 +137,8 @@ SYMBOLS = [
     "dmcf_fps_workspace_bytes", "dmcf_farthest_point_sample", "dmcf_gather_point",
     "dmcf_grid_pos_workspace_bytes", "dmcf_grid_pos_bounds", "dmcf_grid_pos_count", "dmcf_grid_pos_write",
     "dmcf_ghost_workspace_bytes", "dmcf_ghost_count", "dmcf_ghost_write",
+    "dmcf_nn_distance_workspace_bytes", "dmcf_nn_distance", "dmcf_approx_match_workspace_bytes", "dmcf_approx_match",
+    "dmcf_match_cost_workspace_bytes", "dmcf_match_cost", "dmcf_emd_workspace_bytes", "dmcf_emd",
 ]
 
 
@@ -259,6 +261,21 @@ def lib():
     L.dmcf_grid_pos_write.restype = c.c_int
     L.dmcf_grid_pos_write.argtypes = [c.c_void_p, c.c_int64, f3, c.c_int, c.c_int, c.c_float, c.c_void_p, c.c_size_t,
                                       c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p]
+    for q in ("dmcf_nn_distance_workspace_bytes", "dmcf_approx_match_workspace_bytes", "dmcf_match_cost_workspace_bytes",
+              "dmcf_emd_workspace_bytes"):
+        getattr(L, q).restype = c.c_size_t
+        getattr(L, q).argtypes = [c.c_int64, c.c_int64, c.c_int64]
+    L.dmcf_nn_distance.restype = c.c_int
+    L.dmcf_nn_distance.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
+                                   c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    i32p = c.POINTER(c.c_int32)
+    for f in ("dmcf_approx_match", "dmcf_emd"):
+        getattr(L, f).restype = c.c_int
+        getattr(L, f).argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, i32p, i32p, c.c_void_p, c.c_void_p,
+                                  c.c_size_t, c.c_void_p]
+    L.dmcf_match_cost.restype = c.c_int
+    L.dmcf_match_cost.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
+                                  c.c_size_t, c.c_void_p]
     _lib = L
     return L
 

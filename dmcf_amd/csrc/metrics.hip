@@ -1,0 +1,429 @@
+// Validation metrics (pipelines/simulator.py:167-285 of the reference): the nearest-neighbour distances of the Chamfer
+// metric (utils/tools/nn_distance.*, utils/evaluation_helper.py:25-28) and the approximate-match EMD
+// (utils/tools/tf_approxmatch.*, utils/tools/losses.py:401-409).
+//
+// Both are all-pairs work.  Every pass here is one row-parallel reduction over the whole other set, spread over the
+// device as a grid of (row blocks) x (column splits): a workgroup holds 256 rows, one per lane, and walks one contiguous
+// chunk of the other set through LDS in tiles of 256 points.  Each (split, row) writes its partial into the workspace;
+// a second launch combines the partials of a row in split order.  Nothing is accumulated with atomics, and the split
+// plan depends on the sizes alone (not on the device), so two identical calls give identical bits.
+//
+// Approximate match (behaviour of tf_approxmatch, restated): per batch item with counts n_i (xyz1) and m_i (xyz2),
+//   remainL[k] = multiL, remainR[l] = multiR  (n_i >= m_i: 1 and n_i / m_i; else m_i / n_i and 1, integer division)
+//   for level in -4^7, -4^6, ..., -4^-1, 0:
+//     A  ratioL[k] = remainL[k] / (1e-9 + sum_l e_kl remainR[l])                          e_kl = __expf(level d2_kl)
+//     B  s_l = remainR[l] sum_k e_kl ratioL[k];  ratioR[l] = min(remainR[l] / (s_l + 1e-9), 1) remainR[l];
+//        remainR[l] = max(0, remainR[l] - s_l)
+//     C  w_kl = e_kl ratioL[k] ratioR[l];  match[l, k] += w_kl;  remainL[k] = max(0, remainL[k] - sum_l w_kl)
+// and cost = sum_{l,k} match[l, k] sqrt(d2_kl).  The fused entry point (dmcf_emd) adds w_kl sqrt(d2_kl) into a per-row
+// partial in pass C instead of forming match.  Batch items run one after another (each with a grid sized to its counts),
+// reusing the same workspace.
+#include <math.h>
+
+#include "common.h"
+
+namespace dmcf {
+
+constexpr int kMtThreads = 256;         // rows per workgroup, one per lane
+constexpr int kMtTile = 256;            // points of the other set per LDS tile
+constexpr int64_t kMtTargetBlocks = 2048;  // split the columns until rows x splits reaches this many workgroups
+constexpr int kMtMaxGridYZ = 65535;
+
+struct MtPlan {
+    int64_t row_blocks, nsplit, chunk;
+};
+
+// columns split into nsplit chunks of whole tiles; depends on (rows, cols, batch) only
+inline MtPlan mt_plan(int64_t rows, int64_t cols, int64_t batch = 1) {
+    MtPlan p;
+    p.row_blocks = (rows + kMtThreads - 1) / kMtThreads;
+    const int64_t tiles = cols > 0 ? (cols + kMtTile - 1) / kMtTile : 1;
+    const int64_t want = (kMtTargetBlocks + p.row_blocks * batch - 1) / (p.row_blocks * batch);
+    int64_t ns = want < tiles ? want : tiles;
+    if (ns < 1) ns = 1;
+    const int64_t per = (tiles + ns - 1) / ns;
+    p.nsplit = (tiles + per - 1) / per;
+    p.chunk = per * kMtTile;
+    return p;
+}
+
+// upper bound of nsplit * rows over every rows <= rows_max, cols <= cols_max (batch 1): the workspace of the passes
+inline int64_t mt_partial_bound(int64_t rows_max, int64_t cols_max) {
+    const int64_t tiles = cols_max > 0 ? (cols_max + kMtTile - 1) / kMtTile : 1;
+    const int64_t a = tiles * rows_max;
+    const int64_t b = kMtTargetBlocks * kMtThreads + rows_max + kMtThreads;
+    return a < b ? a : b;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// nearest neighbour: per (batch, row) the smallest squared distance into the chunk and its lowest index
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMtThreads) void nn_partial_kernel(const float* __restrict__ q, int64_t nq,
+                                                                const float* __restrict__ r, int64_t nr, int64_t chunk,
+                                                                float* __restrict__ pd, int32_t* __restrict__ pi) {
+    __shared__ float4 tile[kMtTile];
+    const int64_t b = blockIdx.z, s = blockIdx.y, nb = gridDim.z;
+    const int64_t row = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
+    q += b * nq * 3;
+    r += b * nr * 3;
+    float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+    if (row < nq) {
+        qx = q[3 * row];
+        qy = q[3 * row + 1];
+        qz = q[3 * row + 2];
+    }
+    const int64_t c0 = s * chunk, c1 = c0 + chunk < nr ? c0 + chunk : nr;
+    float best = INFINITY;
+    int32_t bi = (int32_t)c0;
+    for (int64_t t0 = c0; t0 < c1; t0 += kMtTile) {
+        const int cnt = (int)(c1 - t0 < kMtTile ? c1 - t0 : kMtTile);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const int64_t c = t0 + threadIdx.x;
+            tile[threadIdx.x] = make_float4(r[3 * c], r[3 * c + 1], r[3 * c + 2], 0.0f);
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int j = 0; j < cnt; ++j) {
+            const float4 p = tile[j];
+            const float d = dist2_unfused(qx, qy, qz, p.x, p.y, p.z);
+            if (d < best) {  // strict: the lowest index of equal distances stays
+                best = d;
+                bi = (int32_t)(t0 + j);
+            }
+        }
+    }
+    if (row < nq) {
+        pd[(s * nb + b) * nq + row] = best;
+        pi[(s * nb + b) * nq + row] = bi;
+    }
+}
+
+__global__ __launch_bounds__(kMtThreads) void nn_combine_kernel(const float* __restrict__ pd, const int32_t* __restrict__ pi,
+                                                                int64_t total, int64_t nsplit, float* __restrict__ dist,
+                                                                int32_t* __restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
+    if (i >= total) return;
+    float best = pd[i];
+    int32_t bi = pi[i];
+    for (int64_t s = 1; s < nsplit; ++s) {  // splits in column order: strict < keeps the lowest index
+        const float d = pd[s * total + i];
+        if (d < best) {
+            best = d;
+            bi = pi[s * total + i];
+        }
+    }
+    dist[i] = best;
+    if (idx != nullptr) idx[i] = bi;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// approximate match: one kernel for the three all-pairs passes and the cost of a given match
+// ------------------------------------------------------------------------------------------------------------------
+enum MtMode {
+    kMtSumWeighted = 0,  // part[row] = sum_c e_rc cw[c]                          (passes A and B)
+    kMtMatch = 1,        // w = e_rc cw[c] rw[row]; match[c, row] += w; part = sum w   (pass C, dense)
+    kMtFused = 2,        // w as above; part = sum w; part2 = sum w sqrt(d2)           (pass C, fused EMD)
+    kMtCost = 3,         // part = sum_c match[c, row] sqrt(d2_rc)                     (dmcf_match_cost)
+};
+
+template <int MODE>
+__global__ __launch_bounds__(kMtThreads) void am_pass_kernel(const float* __restrict__ rp, int64_t nrow, int64_t rp_bs,
+                                                             const float* __restrict__ cp, int64_t ncol, int64_t cp_bs,
+                                                             int64_t chunk, float level, const float* __restrict__ cw,
+                                                             const float* __restrict__ rw, float* __restrict__ match,
+                                                             int64_t ld, int64_t match_bs, float* __restrict__ part,
+                                                             float* __restrict__ part2) {
+    __shared__ float4 tile[kMtTile];
+    const int64_t b = blockIdx.z, s = blockIdx.y, nb = gridDim.z;
+    const int64_t row = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
+    const bool live = row < nrow;
+    rp += b * rp_bs;
+    cp += b * cp_bs;
+    float x = 0.0f, y = 0.0f, z = 0.0f, rs = 0.0f;
+    if (live) {
+        x = rp[3 * row];
+        y = rp[3 * row + 1];
+        z = rp[3 * row + 2];
+        if (MODE == kMtMatch || MODE == kMtFused) rs = rw[row];
+    }
+    float* mrow = nullptr;
+    if (MODE == kMtMatch || MODE == kMtCost) mrow = match + b * match_bs + row;
+    const int64_t c0 = s * chunk, c1 = c0 + chunk < ncol ? c0 + chunk : ncol;
+    float sum = 0.0f, sum2 = 0.0f;
+    for (int64_t t0 = c0; t0 < c1; t0 += kMtTile) {
+        const int cnt = (int)(c1 - t0 < kMtTile ? c1 - t0 : kMtTile);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const int64_t c = t0 + threadIdx.x;
+            tile[threadIdx.x] = make_float4(cp[3 * c], cp[3 * c + 1], cp[3 * c + 2], MODE == kMtCost ? 0.0f : cw[c]);
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < cnt; ++j) {
+            const float4 p = tile[j];
+            const float dx = x - p.x, dy = y - p.y, dz = z - p.z;
+            const float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+            if (MODE == kMtCost) {
+                const float mv = live ? mrow[(t0 + j) * ld] : 0.0f;
+                sum = fmaf(mv, __builtin_amdgcn_sqrtf(d2), sum);
+            } else {
+                const float e = __expf(level * d2) * p.w;
+                if (MODE == kMtSumWeighted) {
+                    sum += e;
+                } else {
+                    const float w = e * rs;
+                    sum += w;
+                    if (MODE == kMtMatch) {
+                        if (live) mrow[(t0 + j) * ld] += w;
+                    } else {
+                        sum2 = fmaf(w, __builtin_amdgcn_sqrtf(d2), sum2);
+                    }
+                }
+            }
+        }
+    }
+    if (live) {
+        part[(s * nb + b) * nrow + row] = sum;
+        if (MODE == kMtFused) part2[(s * nb + b) * nrow + row] = sum2;
+    }
+}
+
+__global__ __launch_bounds__(kMtThreads) void am_init_kernel(float* __restrict__ remainL, float* __restrict__ costL, int64_t n,
+                                                             float multiL, float* __restrict__ remainR, int64_t m, float multiR) {
+    const int64_t i = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
+    if (i < n) {
+        remainL[i] = multiL;
+        costL[i] = 0.0f;
+    }
+    if (i < m) remainR[i] = multiR;
+}
+
+// pass A: ratioL[k] = remainL[k] / (1e-9 + sum)
+__global__ __launch_bounds__(kMtThreads) void am_finish_a_kernel(const float* __restrict__ part, int64_t n, int64_t nsplit,
+                                                                 const float* __restrict__ remainL, float* __restrict__ ratioL) {
+    const int64_t k = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
+    if (k >= n) return;
+    float s = 1e-9f;
+    for (int64_t j = 0; j < nsplit; ++j) s += part[j * n + k];
+    ratioL[k] = remainL[k] / s;
+}
+
+// pass B: s_l = remainR[l] sum; ratioR[l] = min(remainR[l] / (s_l + 1e-9), 1) remainR[l]; remainR[l] = max(0, remainR[l] - s_l)
+__global__ __launch_bounds__(kMtThreads) void am_finish_b_kernel(const float* __restrict__ part, int64_t m, int64_t nsplit,
+                                                                 float* __restrict__ remainR, float* __restrict__ ratioR) {
+    const int64_t l = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
+    if (l >= m) return;
+    float s = 0.0f;
+    for (int64_t j = 0; j < nsplit; ++j) s += part[j * m + l];
+    const float rr = remainR[l];
+    s *= rr;
+    ratioR[l] = fminf(rr / (s + 1e-9f), 1.0f) * rr;
+    remainR[l] = fmaxf(0.0f, rr - s);
+}
+
+// pass C: remainL[k] = max(0, remainL[k] - sum w); fused: costL[k] += sum w sqrt(d2)
+__global__ __launch_bounds__(kMtThreads) void am_finish_c_kernel(const float* __restrict__ part, const float* __restrict__ part2,
+                                                                 int64_t n, int64_t nsplit, float* __restrict__ remainL,
+                                                                 float* __restrict__ costL) {
+    const int64_t k = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
+    if (k >= n) return;
+    float s = 0.0f, c = 0.0f;
+    for (int64_t j = 0; j < nsplit; ++j) s += part[j * n + k];
+    remainL[k] = fmaxf(0.0f, remainL[k] - s);
+    if (part2 != nullptr) {
+        for (int64_t j = 0; j < nsplit; ++j) c += part2[j * n + k];
+        costL[k] += c;
+    }
+}
+
+// out[b] = sum_{s, k} part[(s * nb + b) * n + k], one workgroup per batch item, fixed order (strided per lane, then a tree)
+__global__ __launch_bounds__(kMtThreads) void am_total_kernel(const float* __restrict__ part, int64_t n, int64_t nsplit,
+                                                              float* __restrict__ out) {
+    __shared__ float red[kMtThreads];
+    const int64_t b = blockIdx.x, nb = gridDim.x;
+    float s = 0.0f;
+    for (int64_t j = 0; j < nsplit; ++j)
+        for (int64_t k = threadIdx.x; k < n; k += kMtThreads) s += part[(j * nb + b) * n + k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kMtThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[b] = red[0];
+}
+
+inline unsigned grid1(int64_t n) { return (unsigned)((n + kMtThreads - 1) / kMtThreads); }
+
+// workspace of dmcf_approx_match / dmcf_emd, carved from the caller's block
+struct AmWork {
+    float *remainL, *ratioL, *costL, *remainR, *ratioR, *part, *part2;
+};
+
+inline size_t am_carve(int64_t n, int64_t m, char* base, AmWork* w) {
+    const int64_t pn = mt_partial_bound(n, m), pm = mt_partial_bound(m, n);
+    const int64_t sizes[7] = {n, n, n, m, m, pn > pm ? pn : pm, pn};
+    float** dst[7] = {&w->remainL, &w->ratioL, &w->costL, &w->remainR, &w->ratioR, &w->part, &w->part2};
+    size_t off = 0;
+    for (int i = 0; i < 7; ++i) {
+        if (base != nullptr) *dst[i] = (float*)(base + off);
+        off += align_up((size_t)(sizes[i] > 0 ? sizes[i] : 1) * sizeof(float), 256);
+    }
+    return off;
+}
+
+bool valid_counts(const int32_t* counts, int64_t b, int64_t limit) {
+    if (counts == nullptr) return true;
+    for (int64_t i = 0; i < b; ++i)
+        if (counts[i] < 0 || counts[i] > limit) return false;
+    return true;
+}
+
+// one batch item of the approximate match: match (dense, already zeroed) or costL (fused) and the final total into *cost
+int approx_match_item(const float* xyz1, const float* xyz2, int64_t ni, int64_t mi, float* match, int64_t ld, float* cost,
+                      const AmWork& w, hipStream_t st) {
+    const float multiL = ni >= mi ? 1.0f : (float)(mi / ni);
+    const float multiR = ni >= mi ? (float)(ni / mi) : 1.0f;
+    const int64_t nm = ni > mi ? ni : mi;
+    am_init_kernel<<<grid1(nm), kMtThreads, 0, st>>>(w.remainL, w.costL, ni, multiL, w.remainR, mi, multiR);
+    const MtPlan pa = mt_plan(ni, mi), pb = mt_plan(mi, ni);
+    const dim3 ga((unsigned)pa.row_blocks, (unsigned)pa.nsplit, 1), gb((unsigned)pb.row_blocks, (unsigned)pb.nsplit, 1);
+    for (int j = 7; j >= -2; --j) {
+        const float level = j == -2 ? 0.0f : -powf(4.0f, (float)j);
+        am_pass_kernel<kMtSumWeighted><<<ga, kMtThreads, 0, st>>>(xyz1, ni, 0, xyz2, mi, 0, pa.chunk, level, w.remainR, nullptr,
+                                                                  nullptr, 0, 0, w.part, nullptr);
+        am_finish_a_kernel<<<grid1(ni), kMtThreads, 0, st>>>(w.part, ni, pa.nsplit, w.remainL, w.ratioL);
+        am_pass_kernel<kMtSumWeighted><<<gb, kMtThreads, 0, st>>>(xyz2, mi, 0, xyz1, ni, 0, pb.chunk, level, w.ratioL, nullptr,
+                                                                  nullptr, 0, 0, w.part, nullptr);
+        am_finish_b_kernel<<<grid1(mi), kMtThreads, 0, st>>>(w.part, mi, pb.nsplit, w.remainR, w.ratioR);
+        if (match != nullptr)
+            am_pass_kernel<kMtMatch><<<ga, kMtThreads, 0, st>>>(xyz1, ni, 0, xyz2, mi, 0, pa.chunk, level, w.ratioR, w.ratioL,
+                                                                match, ld, 0, w.part, nullptr);
+        else
+            am_pass_kernel<kMtFused><<<ga, kMtThreads, 0, st>>>(xyz1, ni, 0, xyz2, mi, 0, pa.chunk, level, w.ratioR, w.ratioL,
+                                                                nullptr, 0, 0, w.part, w.part2);
+        am_finish_c_kernel<<<grid1(ni), kMtThreads, 0, st>>>(w.part, match != nullptr ? nullptr : w.part2, ni, pa.nsplit,
+                                                             w.remainL, w.costL);
+    }
+    if (cost != nullptr) am_total_kernel<<<1, kMtThreads, 0, st>>>(w.costL, ni, 1, cost);
+    return check_launch();
+}
+
+int approx_match_common(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,
+                        const int32_t* count2, float* match, float* cost, void* workspace, size_t workspace_bytes,
+                        dmcf_stream_t stream) {
+    if (b < 0 || n < 0 || m < 0 || n >= INT32_MAX || m >= INT32_MAX) return DMCF_EINVAL;
+    if (!valid_counts(count1, b, n) || !valid_counts(count2, b, m)) return DMCF_EINVAL;
+    if (b == 0) return DMCF_OK;
+    if (xyz1 == nullptr || xyz2 == nullptr || (match == nullptr && cost == nullptr) || workspace == nullptr) return DMCF_EINVAL;
+    AmWork w;
+    if (workspace_bytes < am_carve(n, m, nullptr, &w)) return DMCF_EWORKSPACE;
+    am_carve(n, m, (char*)workspace, &w);
+    hipStream_t st = (hipStream_t)stream;
+    if (match != nullptr && n > 0 && m > 0) {
+        if (hipMemsetAsync(match, 0, (size_t)b * n * m * sizeof(float), st) != hipSuccess) return check_launch();
+    }
+    for (int64_t i = 0; i < b; ++i) {
+        const int64_t ni = count1 != nullptr ? count1[i] : n, mi = count2 != nullptr ? count2[i] : m;
+        if (ni == 0 || mi == 0) {  // nothing to match: zero match rows (already), zero cost
+            if (cost != nullptr && hipMemsetAsync(cost + i, 0, sizeof(float), st) != hipSuccess) return check_launch();
+            continue;
+        }
+        const int rc = approx_match_item(xyz1 + i * n * 3, xyz2 + i * m * 3, ni, mi, match != nullptr ? match + i * n * m : nullptr,
+                                         n, match != nullptr ? nullptr : cost + i, w, st);
+        if (rc != DMCF_OK) return rc;
+    }
+    return check_launch();
+}
+
+}  // namespace dmcf
+
+using namespace dmcf;
+
+extern "C" {
+
+size_t dmcf_nn_distance_workspace_bytes(int64_t b, int64_t n, int64_t m) {
+    if (b <= 0 || n <= 0 || m <= 0) return 0;
+    const MtPlan p1 = mt_plan(n, m, b), p2 = mt_plan(m, n, b);
+    return align_up((size_t)(p1.nsplit * b * n) * 8, 256) + align_up((size_t)(p2.nsplit * b * m) * 8, 256);
+}
+
+int dmcf_nn_distance(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, float* dist1, int32_t* idx1,
+                     float* dist2, int32_t* idx2, void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    if (b < 0 || n < 0 || m < 0 || b > kMtMaxGridYZ || n >= INT32_MAX || m >= INT32_MAX) return DMCF_EINVAL;
+    if ((dist1 == nullptr) != (idx1 == nullptr) || (dist2 == nullptr) != (idx2 == nullptr)) return DMCF_EINVAL;
+    if (dist1 == nullptr && dist2 == nullptr) return DMCF_EINVAL;
+    if (b == 0) return DMCF_OK;
+    if (n == 0 || m == 0) return DMCF_EINVAL;  // a point without a set to search has no nearest neighbour
+    if (xyz1 == nullptr || xyz2 == nullptr || workspace == nullptr) return DMCF_EINVAL;
+    if (workspace_bytes < dmcf_nn_distance_workspace_bytes(b, n, m)) return DMCF_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    for (int dir = 0; dir < 2; ++dir) {
+        const float* q = dir == 0 ? xyz1 : xyz2;
+        const float* r = dir == 0 ? xyz2 : xyz1;
+        const int64_t nq = dir == 0 ? n : m, nr = dir == 0 ? m : n;
+        float* dist = dir == 0 ? dist1 : dist2;
+        int32_t* idx = dir == 0 ? idx1 : idx2;
+        const MtPlan p = mt_plan(nq, nr, b);
+        const size_t bytes = align_up((size_t)(p.nsplit * b * nq) * 8, 256);
+        if (dist != nullptr) {
+            float* pd = (float*)ws;
+            int32_t* pi = (int32_t*)(pd + p.nsplit * b * nq);
+            nn_partial_kernel<<<dim3((unsigned)p.row_blocks, (unsigned)p.nsplit, (unsigned)b), kMtThreads, 0, st>>>(q, nq, r, nr,
+                                                                                                                   p.chunk, pd, pi);
+            nn_combine_kernel<<<grid1(b * nq), kMtThreads, 0, st>>>(pd, pi, b * nq, p.nsplit, dist, idx);
+        }
+        ws += bytes;
+    }
+    return check_launch();
+}
+
+size_t dmcf_approx_match_workspace_bytes(int64_t b, int64_t n, int64_t m) {
+    if (b < 0 || n < 0 || m < 0) return 0;
+    AmWork w;
+    return am_carve(n, m, nullptr, &w);
+}
+
+int dmcf_approx_match(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,
+                      const int32_t* count2, float* match, void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    if (match == nullptr) return DMCF_EINVAL;
+    return approx_match_common(xyz1, xyz2, b, n, m, count1, count2, match, nullptr, workspace, workspace_bytes, stream);
+}
+
+size_t dmcf_emd_workspace_bytes(int64_t b, int64_t n, int64_t m) { return dmcf_approx_match_workspace_bytes(b, n, m); }
+
+int dmcf_emd(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1, const int32_t* count2,
+             float* cost, void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    if (cost == nullptr) return DMCF_EINVAL;
+    return approx_match_common(xyz1, xyz2, b, n, m, count1, count2, nullptr, cost, workspace, workspace_bytes, stream);
+}
+
+size_t dmcf_match_cost_workspace_bytes(int64_t b, int64_t n, int64_t m) {
+    if (b <= 0 || n <= 0 || m <= 0) return 0;
+    const MtPlan p = mt_plan(n, m, b);
+    return align_up((size_t)(p.nsplit * b * n) * sizeof(float), 256);
+}
+
+int dmcf_match_cost(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const float* match, float* cost,
+                    void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    if (b < 0 || n < 0 || m < 0 || b > kMtMaxGridYZ || n >= INT32_MAX || m >= INT32_MAX) return DMCF_EINVAL;
+    if (b == 0) return DMCF_OK;
+    if (cost == nullptr) return DMCF_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0 || m == 0) {
+        if (hipMemsetAsync(cost, 0, (size_t)b * sizeof(float), st) != hipSuccess) return check_launch();
+        return DMCF_OK;
+    }
+    if (xyz1 == nullptr || xyz2 == nullptr || match == nullptr || workspace == nullptr) return DMCF_EINVAL;
+    if (workspace_bytes < dmcf_match_cost_workspace_bytes(b, n, m)) return DMCF_EWORKSPACE;
+    const MtPlan p = mt_plan(n, m, b);
+    float* part = (float*)workspace;
+    am_pass_kernel<kMtCost><<<dim3((unsigned)p.row_blocks, (unsigned)p.nsplit, (unsigned)b), kMtThreads, 0, st>>>(
+        xyz1, n, n * 3, xyz2, m, m * 3, p.chunk, 0.0f, nullptr, nullptr, const_cast<float*>(match), n, n * m, part, nullptr);
+    am_total_kernel<<<(unsigned)b, kMtThreads, 0, st>>>(part, n, p.nsplit, cost);
+    return check_launch();
+}
+
+}  // extern "C"

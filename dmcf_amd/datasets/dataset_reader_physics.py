@@ -167,20 +167,23 @@ def align_vector(v0, v1):
     return (np.eye(3, dtype=np.float32) + vx + vx @ vx * ((1 - c) / (s * s))).astype(np.float32)
 
 
-def get_rollout(dataset, stride=1, time_start=0, time_end=None, cnt=None, translate=None, scale=None, grav_eqvar=None,
-                **kwargs):
+def get_rollout(dataset, stride=1, time_start=0, time_end=None, random_start=1, cnt=None, translate=None, scale=None,
+                grav_eqvar=None, **kwargs):
     """:410-456 with PhysicsSimDataFlow(window=0) unrolled: one dict per scene with the selected frames stacked --
     ``pos / vel / grav [T,N,3]``, ``m / viscosity [T,N]``, ``frame_id / scene_id [T]``, ``box / box_normals [T,M,3]``
     (the static boundary of frame 0 repeated, :333-341) -- after the input transform of :276-293.  Scenes whose
-    particle count changes over time cannot be stacked (as in the reference)."""
+    particle count changes over time cannot be stacked (as in the reference).  ``random_start > 1`` (:428-435): one
+    offset per scene from ``np.random.randint(random_start * stride)`` shifts both ends of the frame window (the validation
+    split's configs use it; run_pipeline seeds numpy with 42)."""
     out = []
     for si in range(len(dataset)):
         if cnt is not None and len(out) >= cnt:
             break
+        off = np.random.randint(random_start * stride) if random_start > 1 else 0
         frames = dataset[si]
         sel = [f for f in frames
-               if int(f["frame_id"]) >= time_start * stride and int(f["frame_id"]) % stride == 0
-               and (time_end is None or int(f["frame_id"]) < time_end * stride)]
+               if int(f["frame_id"]) >= time_start * stride + off and int(f["frame_id"]) % stride == 0
+               and (time_end is None or int(f["frame_id"]) < time_end * stride + off)]
         if not sel:
             continue
         merge = {}

@@ -1435,3 +1435,137 @@ def gather_point(inp, idx):
     out = torch.empty((ii.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
     _lib.check(L.dmcf_gather_point(_ptr(x), _ptr(ii), ii.shape[0], x.shape[1], _ptr(out), _stream()), "dmcf_gather_point")
     return out.unsqueeze(0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# validation metrics (pipelines/simulator.py:167-285): nn_distance (Chamfer), approx_match / match_cost / emd (EMD)
+# ---------------------------------------------------------------------------------------------------------------------
+def _point_batch(t, name):
+    """[b, n, 2|3] or [n, 2|3] float32 GPU tensor -> contiguous [b, n, 3] (2-D scenes padded with z = 0), batched flag."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor")
+    if not t.is_cuda:
+        raise _lib.DmcfError(f"{name} is on {t.device}: the DMCF hot path runs on the GPU only (no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    batched = t.dim() == 3
+    if t.dim() not in (2, 3) or t.shape[-1] not in (2, 3):
+        raise ValueError(f"{name} must have shape [b, n, 3], [b, n, 2], [n, 3] or [n, 2], got {tuple(t.shape)}")
+    if not batched:
+        t = t.unsqueeze(0)
+    if t.shape[-1] == 2:
+        t = torch.nn.functional.pad(t, (0, 1))
+    return t.contiguous(), batched
+
+
+def _pair_batch(xyz1, xyz2):
+    a, b1 = _point_batch(xyz1, "xyz1")
+    b, b2 = _point_batch(xyz2, "xyz2")
+    if b1 != b2 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"xyz1 {tuple(xyz1.shape)} and xyz2 {tuple(xyz2.shape)} must have the same batch size")
+    if a.device != b.device:
+        raise ValueError("xyz1 and xyz2 must be on the same device")
+    return a, b, b1
+
+
+def _host_counts(c, b, limit, name):
+    """None | int | sequence | array | tensor of b point counts -> None or a host int32 array (dmcf_approx_match reads it on
+    the host, before anything is enqueued)."""
+    if c is None:
+        return None
+    if isinstance(c, torch.Tensor):
+        c = c.detach().cpu().numpy()
+    arr = np.asarray(c, dtype=np.int64).reshape(-1)
+    if arr.size == 1 and b != 1:
+        arr = np.full(b, int(arr[0]), dtype=np.int64)
+    if arr.size != b:
+        raise ValueError(f"{name} must hold one count per batch item ({b}), got {arr.size}")
+    if (arr < 0).any() or (arr > limit).any():
+        raise ValueError(f"{name} must lie in [0, {limit}], got {arr.tolist()}")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def _counts_ptr(arr):
+    return None if arr is None else arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def nn_distance(xyz1, xyz2):
+    """Mirror of ``utils/tools/nn_distance.py: nn_distance(xyz1, xyz2)`` -> ``(dist1, idx1, dist2, idx2)``: for each point of
+    xyz1 [b, n, 3] the squared distance to its nearest point of xyz2 [b, m, 3] and that point's int32 index ([b, n]), and the
+    same from xyz2 to xyz1 ([b, m]).  Equal distances go to the lowest index (dmcf_nn_distance)."""
+    L = _lib.lib()
+    a, b, batched = _pair_batch(xyz1, xyz2)
+    nb, n, m = a.shape[0], a.shape[1], b.shape[1]
+    if nb > 0 and (n == 0 or m == 0):
+        raise ValueError("nn_distance needs two non-empty point sets")
+    dev = a.device
+    d1 = torch.empty((nb, n), dtype=torch.float32, device=dev)
+    i1 = torch.empty((nb, n), dtype=torch.int32, device=dev)
+    d2 = torch.empty((nb, m), dtype=torch.float32, device=dev)
+    i2 = torch.empty((nb, m), dtype=torch.int32, device=dev)
+    if nb > 0:
+        nbytes = int(L.dmcf_nn_distance_workspace_bytes(nb, n, m))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dmcf_nn_distance(_ptr(a), _ptr(b), nb, n, m, _ptr(d1), _ptr(i1), _ptr(d2), _ptr(i2), _ptr(ws), nbytes,
+                                      _stream()), "dmcf_nn_distance")
+    out = (d1, i1, d2, i2)
+    return out if batched else tuple(x[0] for x in out)
+
+
+def dense_match_fits(b, n, m, device=None):
+    """True when a dense [b, m, n] float32 match fits in the free device memory (with a quarter to spare)."""
+    need = 4 * int(b) * int(n) * int(m)
+    free = torch.cuda.mem_get_info(device)[0]
+    return need <= 0.75 * free
+
+
+def approx_match(xyz1, xyz2, n=None, m=None):
+    """Mirror of ``utils/tools/tf_approxmatch.py: approx_match(xyz1, xyz2, n, m)`` -> match [b, m, n] (dmcf_approx_match).
+    ``n`` / ``m``: per-batch point counts (None: all points); rows and columns past a count are 0.  Refuses, before anything
+    runs, a dense matrix that would not fit on the device: use :func:`emd` for the cost alone."""
+    L = _lib.lib()
+    a, b, batched = _pair_batch(xyz1, xyz2)
+    nb, nn_, mm = a.shape[0], a.shape[1], b.shape[1]
+    c1, c2 = _host_counts(n, nb, nn_, "n"), _host_counts(m, nb, mm, "m")
+    if not dense_match_fits(nb, nn_, mm, a.device):
+        raise MemoryError(f"approx_match: the dense match [{nb}, {mm}, {nn_}] needs {4 * nb * nn_ * mm / 2 ** 30:.1f} GiB, more "
+                          "than the device has free; ops.emd computes the matching cost without forming it")
+    match = torch.empty((nb, mm, nn_), dtype=torch.float32, device=a.device)
+    nbytes = int(L.dmcf_approx_match_workspace_bytes(nb, nn_, mm))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
+    _lib.check(L.dmcf_approx_match(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(match), _ptr(ws), nbytes,
+                                   _stream()), "dmcf_approx_match")
+    return match if batched else match[0]
+
+
+def match_cost(xyz1, xyz2, match):
+    """Mirror of ``utils/tools/tf_approxmatch.py: match_cost(xyz1, xyz2, match)`` -> cost [b] =
+    sum_{l,k} match[l, k] |xyz2[l] - xyz1[k]| (dmcf_match_cost)."""
+    L = _lib.lib()
+    a, b, batched = _pair_batch(xyz1, xyz2)
+    nb, n, m = a.shape[0], a.shape[1], b.shape[1]
+    mt = _dev_f32(match, "match")
+    if not batched:
+        mt = mt.unsqueeze(0)
+    if tuple(mt.shape) != (nb, m, n):
+        raise ValueError(f"match must have shape {(nb, m, n) if batched else (m, n)}, got {tuple(match.shape)}")
+    cost = torch.empty(nb, dtype=torch.float32, device=a.device)
+    nbytes = int(L.dmcf_match_cost_workspace_bytes(nb, n, m))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
+    _lib.check(L.dmcf_match_cost(_ptr(a), _ptr(b), nb, n, m, _ptr(mt), _ptr(cost), _ptr(ws), nbytes, _stream()), "dmcf_match_cost")
+    return cost if batched else cost[0]
+
+
+def emd(xyz1, xyz2, n=None, m=None):
+    """``match_cost(xyz1, xyz2, approx_match(xyz1, xyz2, n, m))`` without forming the match (dmcf_emd): cost [b] in O(n + m)
+    memory.  Same arguments as :func:`approx_match`."""
+    L = _lib.lib()
+    a, b, batched = _pair_batch(xyz1, xyz2)
+    nb, nn_, mm = a.shape[0], a.shape[1], b.shape[1]
+    c1, c2 = _host_counts(n, nb, nn_, "n"), _host_counts(m, nb, mm, "m")
+    cost = torch.empty(nb, dtype=torch.float32, device=a.device)
+    nbytes = int(L.dmcf_emd_workspace_bytes(nb, nn_, mm))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
+    _lib.check(L.dmcf_emd(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(ws), nbytes, _stream()),
+               "dmcf_emd")
+    return cost if batched else cost[0]

@@ -5,12 +5,15 @@
 the result is fed back verbatim; ``run_rollout(inputs, timesteps)`` (:73-109) loops it.  The reference has
 no ``step()``; it is provided as an alias because BASELINE.json names that surface.
 
-Training / validation / HDF5 writing are out of scope of the hot path.  The number of particles may change
-between steps (run_sample.py:173-177 adds inflow), so nothing here assumes a fixed N.
+``run_test`` (:111-165) writes the rollouts of the test split; ``run_valid`` (:167-285) rolls out the validation split and
+computes the reference's metrics (MSE, Chamfer both ways, density errors, approximate-match EMD, velocity-histogram KL, the
+one-step MSE) with the nearest-neighbour and EMD kernels of dmcf_amd/csrc/metrics.hip.  Training is out of scope.  The
+number of particles may change between steps (run_sample.py:173-177 adds inflow), so nothing here assumes a fixed N.
 """
 import logging
 import os
 import time
+from datetime import datetime
 
 import numpy as np
 import torch
@@ -237,6 +240,99 @@ class Simulator:
                 if stale.endswith((".hdf5", ".npz")) and os.path.join(out_dir, stale) != path:
                     os.remove(os.path.join(out_dir, stale))
             paths.append(path)
-        if cfg.get("test_compute_metric", False):
-            raise NotImplementedError("test_compute_metric (run_valid: Chamfer / EMD metrics) is out of scope of the hot path")
+        if cfg.get("test_compute_metric", False):  # simulator.py:164-165
+            self.run_valid(epoch)
         return paths
+
+    def _data_generator(self, split):
+        """``cfg.data_generator`` merged with its ``split`` section (``**cfg.data_generator, **cfg.data_generator.<split>``)."""
+        gen = dict(self.cfg.get("data_generator") or {})
+        kw = dict(gen.get(split) or {})
+        for k in ("train", "valid", "test"):
+            gen.pop(k, None)
+        return gen, kw
+
+    @torch.no_grad()
+    def run_valid(self, epoch=None):
+        """simulator.py:167-285: roll out every scene of the validation split (``get_rollout(dataset.valid,
+        **data_generator, **data_generator.valid)``), then every ``eval_stride`` frames t >= 1 compare the prediction with
+        the target: ``mse_val``, ``chamfer_val``, ``mse_single_val`` (one step from the target's frame t - 1) and, unless the
+        split is "train", ``dens_val``, ``max_dens_val``, ``chamfer_val_2``, ``emd``, ``vel_diff_val``, ``vel_diff_val_2``.
+        Logs the per-scene means and the overall means (with their sum ``loss``) to ``<logs_dir>/log_valid_<time>.txt``;
+        returns the overall dict, also kept as ``self.valid_loss``."""
+        from ..datasets import get_rollout
+        from ..utils.evaluation_helper import chamfer_distance, compare_dist, distance, merge_dicts
+        from ..utils.tools.losses import density_loss, emd_loss, get_window_func
+        cfg, model = self.cfg, self.model
+        os.makedirs(cfg.logs_dir, exist_ok=True)
+        timestamp = datetime.now().strftime("%Y-%m-%d_%H:%M:%S")
+        log_file_path = os.path.join(cfg.logs_dir, "log_valid_" + timestamp + ".txt")
+        log.info("Logging in file : {}".format(log_file_path))
+        handler = logging.FileHandler(log_file_path)
+        level = log.level
+        if not log.isEnabledFor(logging.INFO):
+            log.setLevel(logging.INFO)
+        log.addHandler(handler)
+        try:
+            gen, valid_kw = self._data_generator("valid")
+            valid_data = get_rollout(self.dataset.valid, **gen, **valid_kw)
+            if epoch is None:
+                epoch = self.load_ckpt(model.cfg.get("ckpt_path"))
+            log.info("Started validation")
+            results = self.run_rollout(valid_data, valid_data[0]["pos"].shape[0])
+            eval_stride = valid_kw.get("eval_stride", 1)
+            dev = lambda a: self._to_device(a)  # noqa: E731
+            losses = []
+            for i in range(len(valid_data)):
+                data = valid_data[i]
+                target_pos, target_vel = data["pos"], data["vel"]
+                box = data["box"][0]
+                box_d = dev(box)
+                loss_seq = []
+                for t in range(1, target_pos.shape[0]):
+                    pos, vel = results[i][t][:2]
+                    if t % eval_stride != 0:
+                        continue
+                    loss = {}
+                    if box.shape[0] > 0:
+                        pos = torch.clamp(pos, dev(np.min(box, axis=0)), dev(np.max(box, axis=0)))
+                    tgt = dev(target_pos[t])
+                    loss["mse_val"] = float(np.mean(distance(target_pos[t], pos)))
+                    loss["chamfer_val"] = float(np.mean(chamfer_distance(tgt, pos).astype(np.float32)))
+                    if cfg.get("split") != "train":
+                        # the reference's argument order, kept as it is: dens_val's target densities are taken over
+                        # gt_in = pos + box (the PREDICTION's particles) and its prediction's over target + box;
+                        # max_dens_val passes the prediction as gt and the target as pred
+                        pos_in, tgt_in = torch.cat([pos, box_d]), torch.cat([tgt, box_d])
+                        loss["dens_val"] = float(density_loss(tgt, pos, pos_in, tgt_in, win=get_window_func("poly6")).mean())
+                        loss["max_dens_val"] = float(density_loss(pos, tgt, pos_in, tgt_in, radius=model.particle_radii[0],
+                                                                  win=get_window_func(model.window_dens), use_max=True))
+                        loss["chamfer_val_2"] = float(np.mean(chamfer_distance(pos, tgt).astype(np.float32)))
+                        loss["emd"] = float(np.mean(emd_loss(tgt.unsqueeze(0), pos.unsqueeze(0)).cpu().numpy().astype(np.float32)))
+                        loss["vel_diff_val"] = compare_dist(target_vel[t], vel)
+                        loss["vel_diff_val_2"] = compare_dist(vel, target_vel[t])
+                    # mse for a single step only: one model step from the target's previous frame
+                    pos_sub = self.run_inference([[dev(target_pos[t - 1]), dev(target_vel[t - 1])] + list(results[i][t][2:])])[0][0]
+                    loss["mse_single_val"] = float(np.mean(distance(target_pos[t], pos_sub)))
+                    losses.append(loss)
+                    loss_seq.append(loss)
+                loss_m = merge_dicts(loss_seq, lambda x, y: x + y / len(loss_seq))
+                desc = "%d -" % i
+                for k, v in loss_m.items():
+                    desc += " %s: %.05f" % (k, v)
+                log.info(desc)
+            loss = merge_dicts(losses, lambda x, y: x + y / len(losses))
+            sum_loss = 0
+            desc = "validation of epoch %d -" % epoch
+            for k, v in loss.items():
+                desc += " %s: %.05f" % (k, v)
+                sum_loss += v
+            desc += " > loss: %.05f" % sum_loss
+            loss["loss"] = sum_loss
+            log.info(desc)
+        finally:
+            log.removeHandler(handler)
+            handler.close()
+            log.setLevel(level)
+        self.valid_loss = loss
+        return loss

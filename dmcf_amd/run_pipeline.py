@@ -1,11 +1,13 @@
-"""The reference's ``run_pipeline.py`` for the test split on the MI355X path: YAML config -> model -> checkpoint ->
-``get_rollout`` -> ``Simulator.run_rollout`` -> ``write_results`` (run_pipeline.py:80-154, pipelines/simulator.py:111-165).
+"""The reference's ``run_pipeline.py`` on the MI355X path: YAML config -> model -> checkpoint -> ``get_rollout`` ->
+``Simulator.run_rollout`` (run_pipeline.py:80-154, pipelines/simulator.py:111-285).
 
     python -m dmcf_amd.run_pipeline -c configs/Liquid3d.yml --split test --dataset_path <dir with *.msgpack.zst> \\
         --ckpt_path checkpoints/Liquid3d/ckpt --output_dir output [--model.timestep 0.02 ...]
 
-Same flags as the reference; ``--section.key value`` overrides go through Config.merge_cfg_file.  ``--split train`` /
-``valid`` raise: training and the validation metrics are outside the per-step hot path.
+Same flags as the reference; ``--section.key value`` overrides go through Config.merge_cfg_file.  ``--split test`` writes
+the rollouts (``Simulator.run_test``); ``--split valid`` rolls out the validation split and computes its metrics
+(``Simulator.run_valid``: MSE, Chamfer, density, EMD, velocity histograms).  ``--split train`` raises: the training loop is
+not implemented.
 """
 import argparse
 import random
@@ -20,7 +22,7 @@ def parse_args(argv=None):
     parser.add_argument("--dataset_path", help="path to the dataset")
     parser.add_argument("--ckpt_path", help="path to the checkpoint")
     parser.add_argument("--device", help="device to run the pipeline", default="gpu")
-    parser.add_argument("--split", help="train or test", default="train")
+    parser.add_argument("--split", help="train, valid or test", default="train")
     parser.add_argument("--regen", default=False, action="store_true")
     parser.add_argument("--restart", default=False, action="store_true")
     parser.add_argument("--main_log_dir", help="the dir to save logs and models")
@@ -53,11 +55,14 @@ def main(argv=None, data=None):
     random.seed(42)
     np.random.seed(42)
     args, extra = parse_args(argv)
-    if args.split != "test":
-        raise NotImplementedError(f"--split {args.split}: only the test split (rollout + write_results) is on the hot path")
+    if args.split not in ("test", "valid"):
+        raise NotImplementedError(f"--split {args.split}: the training loop is not implemented (test and valid are)")
     pipeline = build(args, extra, data)
+    if args.split == "valid":  # run_pipeline.py:151-152
+        return pipeline.run_valid()
     return pipeline.run_test()
 
 
 if __name__ == "__main__":
-    print("\n".join(main(sys.argv[1:])))
+    res = main(sys.argv[1:])
+    print("\n".join(res) if isinstance(res, list) else "\n".join("%s: %.05f" % kv for kv in res.items()))

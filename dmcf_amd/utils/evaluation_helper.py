@@ -1,0 +1,76 @@
+"""Validation metrics of ``Simulator.run_valid`` -- mirror of the reference's ``utils/evaluation_helper.py`` (same names and
+arguments):
+
+  distance          :14-16  per-point Euclidean distance (host numpy)
+  chamfer_distance  :25-28  for each point of ``gt`` the distance to its nearest point of ``pred``; on the GPU through
+                            ops.nn_distance (dmcf_nn_distance) instead of a host cKDTree
+  compare_dist      :43-75  KL divergence of two histograms (one bin per ``bin_size`` points, 1e-5 prior); host numpy,
+                            vectorised, the same value as the reference's per-point loop
+  merge_dicts       :78-85
+
+``optimal_assignment_distance`` and ``compute_stats`` are not used by run_valid and are not rebuilt.
+"""
+import numpy as np
+import torch
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def distance(x, y):
+    """:14-16: ``|x - y|`` along the last axis."""
+    return np.linalg.norm(_host(x) - _host(y), axis=-1)
+
+
+def chamfer_distance(pred, gt):
+    """:25-28: for each point of ``gt`` [n, 3] the Euclidean distance to its nearest point of ``pred`` [m, 3], as a float32
+    numpy array [n].  Numpy arrays or device tensors; the nearest neighbours come from ops.nn_distance on the GPU (float32
+    squared distances, then the square root), where the reference queries a cKDTree in float64."""
+    from .. import ops
+    dev = next((t.device for t in (pred, gt) if isinstance(t, torch.Tensor) and t.is_cuda), torch.device("cuda"))
+
+    def to_dev(x):
+        if isinstance(x, torch.Tensor):
+            return x.detach().to(dev, dtype=torch.float32)
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+
+    d_gt, _, _, _ = ops.nn_distance(to_dev(gt), to_dev(pred))
+    return torch.sqrt(d_gt).cpu().numpy()
+
+
+def compare_dist(x, y, bin_size=25):
+    """:43-75: histogram both point sets (e.g. velocities) [cnt, dim] on the same grid -- bin_cnt = cnt // bin_size bins in all,
+    int(bin_cnt ** (1 / dim)) per axis between the 5th and 95th percentiles of both, clipped at the edges, every bin starting at
+    1e-5 -- and return the KL divergence KL(x || y) of the two normalised histograms (scipy.stats.entropy(bins_x, bins_y))."""
+    x, y = _host(x), _host(y)
+    assert x.shape == y.shape
+    cnt = x.shape[0]
+    dim = x.shape[-1]
+    bin_cnt = cnt // bin_size
+    bin_cnt_per_dim = int(bin_cnt ** (1 / dim))
+    both = np.concatenate((x, y), axis=0)
+    min_v = np.percentile(both, 5, axis=0)
+    max_v = np.percentile(both, 95, axis=0)
+    bin_w = (max_v - min_v + 1e-6) / bin_cnt_per_dim
+    shape = (bin_cnt_per_dim + 1,) * dim
+
+    def hist(v):
+        idx = np.clip(((v - min_v) / bin_w).astype("int32"), 0, bin_cnt_per_dim)
+        flat = np.ravel_multi_index(tuple(idx.T), shape) if len(idx) else np.zeros(0, dtype=np.int64)
+        return np.bincount(flat, minlength=int(np.prod(shape))).astype(np.float64) + 1e-5
+
+    px, py = hist(x), hist(y)
+    px, py = px / px.sum(), py / py.sum()
+    return float(np.sum(px * np.log(px / py)))
+
+
+def merge_dicts(dicts, op, start_val=0):
+    """:78-85: fold the values of equal keys with ``op``, starting from ``start_val``."""
+    output = {}
+    for d in dicts:
+        for k, v in d.items():
+            if k not in output:
+                output[k] = start_val
+            output[k] = op(output[k], v)
+    return output

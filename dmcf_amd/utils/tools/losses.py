@@ -8,12 +8,14 @@
   compute_density   losses.py:285-306  windowed neighbour sum (fused into the search scan: ops.window_sum)
   compute_pressure  losses.py:367-377  Tait-style pressure from the density
   density_loss      losses.py:380-398  validation metric of pipelines/simulator.py:227-243
+  emd_loss          losses.py:401-409  approximate-match EMD per batch item (validation metric; ops.emd, no gradient)
 
   get_loss          losses.py:47-110   the training losses mse / weighted_mse / vel / weighted_vel / momentum
   get_optimizer     models/pbf_model.py:508-517  Adam (eps 1e-6), piecewise-constant learning rate
 
 The density, Chamfer, EMD and histogram losses (losses.py:380-414, the last three on the reference's custom CUDA ops) are
-not implemented: get_loss returns a function that raises NotImplementedError for them.
+not implemented as training losses: get_loss returns a function that raises NotImplementedError for them (they would
+need the gradients of nn_distance / match_cost).  emd_loss and utils/evaluation_helper.py serve validation only.
 """
 import numpy as np
 import torch
@@ -218,6 +220,21 @@ def density_loss(gt, pred, gt_in=None, pred_in=None, radius=0.005, eps=0.01, win
     if use_max:
         return torch.abs(pred_dens.max() - rest_dens) / rest_dens
     return torch.relu(pred_dens - rest_dens - eps).mean()
+
+
+def emd_loss(y_true, y_pred, n=None, m=None):
+    """losses.py:401-409: ``match_cost(approx_match(y_true, y_pred, n, m)) / max(n, m)`` per batch item, [b].  ``y_true``
+    [b, n, 3], ``y_pred`` [b, m, 3] (2-D: z = 0); ``n`` / ``m`` per-batch point counts (None: all points).  Runs the fused
+    kernel (ops.emd), which never forms the [b, m, n] match.  No gradient."""
+    from ... import ops
+    b = y_true.shape[0]
+    nn_ = ops._host_counts(n, b, y_true.shape[1], "n")
+    mm = ops._host_counts(m, b, y_pred.shape[1], "m")
+    cost = ops.emd(y_true, y_pred, nn_, mm)
+    nv = np.full(b, y_true.shape[1]) if nn_ is None else nn_
+    mv = np.full(b, y_pred.shape[1]) if mm is None else mm
+    denom = torch.from_numpy(np.maximum(nv, mv).astype(np.float32)).to(cost.device)
+    return cost / denom
 
 
 def _pre_factor(kwargs, kw, like):

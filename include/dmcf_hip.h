@@ -548,6 +548,42 @@ int dmcf_farthest_point_sample(const float* points, int64_t n_points, int64_t n_
 int dmcf_gather_point(const float* inp, const int32_t* index, int64_t n_index, int channels, float* out,
                       dmcf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Validation metrics (pipelines/simulator.py:167-285, run_valid): the reference's custom CUDA ops
+ * utils/tools/nn_distance.py:nn_distance (Chamfer, utils/evaluation_helper.py:25-28) and
+ * utils/tools/tf_approxmatch.py:approx_match / match_cost (EMD, utils/tools/losses.py:401-409).
+ * Point sets are float32 [b, n, 3] / [b, m, 3] (2-D scenes: z = 0).  Every pass is a row-parallel reduction over the other
+ * set, spread over the whole device (rows x column splits), with per-split partials combined in a fixed order: no float
+ * atomics, and the split plan depends on the sizes only, so two identical calls give identical bits.  b = 0: DMCF_OK,
+ * nothing enqueued.  The workspace is the caller's; its size comes from the matching *_workspace_bytes query.
+ * ---------------------------------------------------------------------------------------------- */
+/* nn_distance(xyz1, xyz2) (nn_distance.py:40-53): dist1 [b, n] = squared distance from each point of xyz1 to its nearest
+ * point of xyz2, idx1 [b, n] its index; dist2 / idx2 [b, m] the same from xyz2 to xyz1.  Equal distances: the lowest index.
+ * A direction is skipped when both its pointers are NULL (one NULL of a pair, or both directions skipped: DMCF_EINVAL).
+ * Squared distances in float32 as (dx*dx + dy*dy) + dz*dz without fused multiply-adds.  n or m == 0 with b > 0, or
+ * b > 65535: DMCF_EINVAL. */
+size_t dmcf_nn_distance_workspace_bytes(int64_t b, int64_t n, int64_t m);
+int dmcf_nn_distance(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, float* dist1, int32_t* idx1,
+                     float* dist2, int32_t* idx2, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* approx_match(xyz1, xyz2, n, m) (tf_approxmatch.py:40-54): match [b, m, n] of the approximate EMD assignment (the algorithm
+ * is restated in dmcf_amd/csrc/metrics.hip: ten levels of three all-pairs passes, __expf weights, the reference's 1e-9 terms,
+ * clamps and integer division).  count1 / count2: HOST arrays of b int32 point counts (n_i <= n, m_i <= m; NULL = all
+ * n / m), validated before anything is enqueued; rows and columns past a count are 0 and play no part.  The workspace is
+ * O(n + m) and is reused by the batch items, which run one after another. */
+size_t dmcf_approx_match_workspace_bytes(int64_t b, int64_t n, int64_t m);
+int dmcf_approx_match(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,
+                      const int32_t* count2, float* match, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* match_cost(xyz1, xyz2, match) (tf_approxmatch.py:60-69): cost [b] = sum_{l,k} match[l, k] * |xyz2[l] - xyz1[k]|. */
+size_t dmcf_match_cost_workspace_bytes(int64_t b, int64_t n, int64_t m);
+int dmcf_match_cost(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const float* match, float* cost,
+                    void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* match_cost(approx_match(...)) fused (the cost of emd_loss, losses.py:401-409): pass C adds w_kl * |d_kl| into per-row
+ * partials instead of forming match, so memory stays O(n + m) (a dense match at n = m = 1e5 would be 40 GB).  Same
+ * arguments as dmcf_approx_match; cost [b]. */
+size_t dmcf_emd_workspace_bytes(int64_t b, int64_t n, int64_t m);
+int dmcf_emd(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1, const int32_t* count2,
+             float* cost, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
