@@ -61,6 +61,54 @@ class CconvBackwardArgs(ctypes.Structure):
     ]
 
 
+class NeighborDenseArgs(ctypes.Structure):
+    """struct dmcf_neighbor_dense_args (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_int32),
+        ("x", ctypes.c_void_p),
+        ("n_in", ctypes.c_int64),
+        ("cin", ctypes.c_int32),
+        ("cout", ctypes.c_int32),
+        ("kernel", ctypes.c_void_p),
+        ("bias", ctypes.c_void_p),
+        ("residual", ctypes.c_void_p),
+        ("mask", ctypes.c_void_p),
+        ("neighbors_index", ctypes.c_void_p),
+        ("neighbors_row_splits", ctypes.c_void_p),
+        ("neighbors_row_count", ctypes.c_void_p),
+        ("n_out", ctypes.c_int64),
+        ("n_pairs", ctypes.c_int64),
+        ("host_row_splits", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("record_s", ctypes.c_void_p),
+        ("record_count", ctypes.c_void_p),
+    ]
+
+
+class NeighborDenseBackwardArgs(ctypes.Structure):
+    """struct dmcf_neighbor_dense_backward_args (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_int32),
+        ("x", ctypes.c_void_p),
+        ("n_in", ctypes.c_int64),
+        ("cin", ctypes.c_int32),
+        ("cout", ctypes.c_int32),
+        ("kernel", ctypes.c_void_p),
+        ("grad_out", ctypes.c_void_p),
+        ("n_out", ctypes.c_int64),
+        ("s", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+        ("inv_index", ctypes.c_void_p),
+        ("inv_row_splits", ctypes.c_void_p),
+        ("inv_n_pairs", ctypes.c_int64),
+        ("grad_x", ctypes.c_void_p),
+        ("grad_kernel", ctypes.c_void_p),
+        ("grad_bias", ctypes.c_void_p),
+    ]
+
+
 class LatticeConvArgs(ctypes.Structure):
     """struct dmcf_lattice_conv_args (include/dmcf_hip.h)."""
     _fields_ = [
@@ -139,6 +187,8 @@ SYMBOLS = [
     "dmcf_ghost_workspace_bytes", "dmcf_ghost_count", "dmcf_ghost_write",
     "dmcf_nn_distance_workspace_bytes", "dmcf_nn_distance", "dmcf_approx_match_workspace_bytes", "dmcf_approx_match",
     "dmcf_match_cost_workspace_bytes", "dmcf_match_cost", "dmcf_emd_workspace_bytes", "dmcf_emd",
+    "dmcf_neighbor_dense_forward", "dmcf_neighbor_dense_backward_workspace_bytes", "dmcf_neighbor_dense_backward",
+    "dmcf_neighbor_dense_kernel_names",
 ]
 
 
@@ -276,6 +326,15 @@ def lib():
     L.dmcf_match_cost.restype = c.c_int
     L.dmcf_match_cost.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
                                   c.c_size_t, c.c_void_p]
+    L.dmcf_neighbor_dense_forward.restype = c.c_int
+    L.dmcf_neighbor_dense_forward.argtypes = [c.POINTER(NeighborDenseArgs), c.c_void_p]
+    L.dmcf_neighbor_dense_backward_workspace_bytes.restype = c.c_size_t
+    L.dmcf_neighbor_dense_backward_workspace_bytes.argtypes = [c.POINTER(NeighborDenseBackwardArgs)]
+    L.dmcf_neighbor_dense_backward.restype = c.c_int
+    L.dmcf_neighbor_dense_backward.argtypes = [c.POINTER(NeighborDenseBackwardArgs), c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_neighbor_dense_kernel_names.restype = c.c_int
+    L.dmcf_neighbor_dense_kernel_names.argtypes = [c.POINTER(NeighborDenseArgs), c.POINTER(NeighborDenseBackwardArgs), c.c_char_p,
+                                                   c.c_size_t]
     _lib = L
     return L
 

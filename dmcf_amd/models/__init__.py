@@ -4,5 +4,6 @@ from .pbf_model import PBFNet
 from .hrnet import HRNet
 from .sym_net import SymNet
 from .cconv import CConv
+from .pointnet import PointNet
 
-__all__ = ["BaseModel", "Dense", "PBFNet", "HRNet", "SymNet", "CConv"]
+__all__ = ["BaseModel", "Dense", "PBFNet", "HRNet", "SymNet", "CConv", "PointNet"]

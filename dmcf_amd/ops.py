@@ -1039,6 +1039,214 @@ class CconvFunction(torch.autograd.Function):
         return gw, gf, None
 
 
+ND_RELU, ND_W_TRANSPOSED = 1, 2
+
+
+class SharedInverse:
+    """The inversion of one neighbour list, formed on first use and then shared: every PointNet layer of a step walks the
+    same list, so its backward inverts it once per step, not once per layer.  ``n_points``: the range of the indices (the
+    list's input rows); a layer with fewer input rows (PointNet's layer 0: fluid only) reads the first rows of it."""
+
+    def __init__(self, n_points, neighbors_index, neighbors_row_splits, neighbors_row_count=None):
+        self.n_points = int(n_points)
+        self.args = (neighbors_index, neighbors_row_splits, neighbors_row_count)
+        self._inv = None
+
+    def get(self):
+        if self._inv is None:
+            index, rs, count = self.args
+            self._inv = invert_neighbors_list(self.n_points, index, rs, None, count)
+        return self._inv
+
+
+def _nd_operands(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, residual, neighbors_row_count):
+    kernel = _dev_f32(kernel, "kernel")
+    if kernel.dim() != 2:
+        raise ValueError("kernel must be [Cin, Cout]")
+    cin, cout = kernel.shape
+    x = _dev_f32(x, "x", cin)
+    n_in = x.shape[0] if n_in is None else int(n_in)
+    if not 0 <= n_in <= x.shape[0]:
+        raise ValueError(f"n_in = {n_in} for {x.shape[0]} rows of x")
+    if not isinstance(neighbors_index, torch.Tensor) or not isinstance(neighbors_row_splits, torch.Tensor):
+        raise TypeError("neighbors_index and neighbors_row_splits must be torch tensors")
+    if not neighbors_index.is_cuda or not neighbors_row_splits.is_cuda:
+        raise _lib.DmcfError("the neighbour list is on the CPU: the DMCF hot path runs on the GPU only (no CPU fallback)")
+    if neighbors_index.dtype != torch.int32 or neighbors_row_splits.dtype != torch.int64:
+        raise TypeError("neighbors_index must be int32 and neighbors_row_splits int64")
+    if neighbors_row_count is not None:
+        if neighbors_row_count.dtype != torch.int32 or neighbors_row_count.dim() != 1:
+            raise TypeError("neighbors_row_count must be int32 [n_out]")
+        n_out = neighbors_row_count.shape[0]
+        if neighbors_row_splits.shape[0] < n_out:
+            raise ValueError("padded lists need a row begin per row")
+        neighbors_row_count = neighbors_row_count.contiguous()
+    else:
+        n_out = neighbors_row_splits.shape[0] - 1
+        if n_out < 0:
+            raise ValueError("neighbors_row_splits must have n_out+1 entries")
+    if bias is not None:
+        bias = _dev_f32(bias, "bias")
+        if tuple(bias.shape) != (cout,):
+            raise ValueError("bias must be [Cout]")
+    if residual is not None:
+        residual = _dev_f32(residual, "residual", cout)
+        if residual.shape[0] != n_out:
+            raise ValueError("residual must be [n_out, Cout]")
+    return (x, kernel, bias, neighbors_index.contiguous(), neighbors_row_splits.contiguous(), n_in, residual, neighbors_row_count,
+            n_out, cin, cout)
+
+
+def _nd_forward(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, relu, residual, neighbors_row_count, record=False):
+    """dmcf_neighbor_dense_forward; returns out (and with ``record`` the aggregate S [n_out, Cin] and counts c [n_out])."""
+    L = _lib.lib()
+    (x, kernel, bias, index, rs, n_in, residual, count, n_out, cin, cout) = _nd_operands(
+        x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, residual, neighbors_row_count)
+    dev = x.device
+    out = torch.empty(n_out, cout, dtype=torch.float32, device=dev)
+    a = _lib.NeighborDenseArgs()
+    a.struct_size = ctypes.sizeof(_lib.NeighborDenseArgs)
+    a.flags = ND_RELU if relu else 0
+    a.x, a.n_in, a.cin, a.cout = x.data_ptr(), n_in, cin, cout
+    a.kernel = kernel.data_ptr()
+    a.bias = None if bias is None else bias.data_ptr()
+    a.residual = None if residual is None else residual.data_ptr()
+    a.neighbors_index, a.neighbors_row_splits = index.data_ptr(), rs.data_ptr()
+    a.neighbors_row_count = None if count is None else count.data_ptr()
+    a.n_out, a.n_pairs = n_out, index.shape[0]
+    a.out = out.data_ptr()
+    s = c = None
+    if record:
+        s = torch.empty(n_out, cin, dtype=torch.float32, device=dev)
+        c = torch.empty(n_out, dtype=torch.float32, device=dev)
+        a.record_s, a.record_count = s.data_ptr(), c.data_ptr()
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_neighbor_dense_forward(ctypes.byref(a), _stream()), "dmcf_neighbor_dense_forward")
+    if timer is not None:
+        timer.end("neighbor_dense", dict(n_out=n_out, cin=int(cin), cout=int(cout), pairs=int(index.shape[0]),
+                                         kernel=neighbor_dense_kernel_names(a, None)), t0)
+    return (out, s, c) if record else out
+
+
+def neighbor_dense_kernel_names(fwd, bwd):
+    """';'-separated names of the kernels dmcf_neighbor_dense_forward (``fwd``) and / or _backward (``bwd``) launch for these
+    (ctypes) arguments."""
+    name = ctypes.create_string_buffer(256)
+    _lib.check(_lib.lib().dmcf_neighbor_dense_kernel_names(None if fwd is None else ctypes.byref(fwd),
+                                                           None if bwd is None else ctypes.byref(bwd), name, 256),
+               "dmcf_neighbor_dense_kernel_names")
+    return name.value.decode()
+
+
+def neighbor_dense_backward(x, kernel, grad_out, s, count, n_in=None, relu=True, inverted=None, neighbors_index=None,
+                            neighbors_row_splits=None, neighbors_row_count=None, need_x=True, need_kernel=True, need_bias=True):
+    """dmcf_neighbor_dense_backward: ``(grad_x, grad_kernel, grad_bias)`` of :func:`neighbor_dense` for ``grad_out`` = dL/d out,
+    from the forward's recorded aggregate ``s`` and counts ``count``.  ``inverted``: an ``invert_neighbors_list`` result of the
+    forward list over at least ``n_in`` input rows, or a :class:`SharedInverse`; formed from ``neighbors_index`` /
+    ``neighbors_row_splits`` when None and the input gradient is wanted.  grad_x has x's rows; rows past ``n_in`` get 0."""
+    L = _lib.lib()
+    kernel = _dev_f32(kernel, "kernel")
+    cin, cout = kernel.shape
+    x = _dev_f32(x, "x", cin)
+    n_in = x.shape[0] if n_in is None else int(n_in)
+    grad_out = _dev_f32(grad_out, "grad_out", cout)
+    n_out = grad_out.shape[0]
+    dev = x.device
+    b = _lib.NeighborDenseBackwardArgs()
+    b.struct_size = ctypes.sizeof(_lib.NeighborDenseBackwardArgs)
+    b.flags = ND_RELU if relu else 0
+    b.x, b.n_in, b.cin, b.cout = x.data_ptr(), n_in, cin, cout
+    b.kernel = kernel.data_ptr()
+    b.grad_out, b.n_out = grad_out.data_ptr(), n_out
+    gx = gw = gb = None
+    keep = []
+    if need_x:
+        if inverted is None:
+            inverted = invert_neighbors_list(n_in, neighbors_index, neighbors_row_splits, None, neighbors_row_count)
+        elif isinstance(inverted, SharedInverse):
+            if inverted.n_points < n_in:
+                raise ValueError("the shared inversion covers fewer input rows than the layer has")
+            inverted = inverted.get()
+        if inverted.neighbors_row_splits.shape[0] < n_in + 1:
+            raise ValueError("the inverted list covers fewer input rows than the layer has")
+        gx = torch.zeros(x.shape[0], cin, dtype=torch.float32, device=dev) if n_in < x.shape[0] else \
+            torch.empty(n_in, cin, dtype=torch.float32, device=dev)
+        b.inv_index = inverted.neighbors_index.data_ptr()
+        b.inv_row_splits = inverted.neighbors_row_splits.data_ptr()
+        b.inv_n_pairs = inverted.neighbors_index.shape[0]
+        b.grad_x = gx.data_ptr()
+        keep.append(inverted)
+    if need_kernel or need_bias:
+        s = _dev_f32(s, "s", cin)
+        count = _dev_f32(count, "count")
+        if s.shape[0] != n_out or tuple(count.shape) != (n_out,):
+            raise ValueError("s must be [n_out, Cin] and count [n_out]")
+        b.s, b.count = s.data_ptr(), count.data_ptr()
+        if need_kernel:
+            gw = torch.empty(cin, cout, dtype=torch.float32, device=dev)
+            b.grad_kernel = gw.data_ptr()
+        if need_bias:
+            gb = torch.empty(cout, dtype=torch.float32, device=dev)
+            b.grad_bias = gb.data_ptr()
+    if gx is None and gw is None and gb is None:
+        return None, None, None
+    nbytes = int(L.dmcf_neighbor_dense_backward_workspace_bytes(ctypes.byref(b)))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_neighbor_dense_backward(ctypes.byref(b), _ptr(ws), nbytes, _stream()), "dmcf_neighbor_dense_backward")
+    if timer is not None:
+        timer.end("neighbor_dense_backward", dict(n_out=n_out, cin=int(cin), cout=int(cout),
+                                                  kernel=neighbor_dense_kernel_names(None, b)), t0)
+    del keep
+    return gx, gw, gb
+
+
+class NeighborDenseFunction(torch.autograd.Function):
+    """Autograd node of :func:`neighbor_dense`: the same forward kernel, recording S and c; the backward is
+    dmcf_neighbor_dense_backward (the list inverted on first need, or shared through ``kw['inverted']``).  The residual's
+    gradient is grad_out itself."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, residual, kw):
+        out, s, c = _nd_forward(x, kernel, bias, kw["neighbors_index"], kw["neighbors_row_splits"], kw["n_in"], kw["relu"],
+                                residual, kw["neighbors_row_count"], record=True)
+        ctx.kw = kw
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, kernel, s, c)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, kernel, s, c = ctx.saved_tensors
+        kw = ctx.kw
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        gx, gw, gb = neighbor_dense_backward(x.detach(), kernel.detach(), grad_out.contiguous(), s, c, n_in=kw["n_in"],
+                                             relu=kw["relu"], inverted=kw["inverted"], neighbors_index=kw["neighbors_index"],
+                                             neighbors_row_splits=kw["neighbors_row_splits"],
+                                             neighbors_row_count=kw["neighbors_row_count"], need_x=need_x, need_kernel=need_w,
+                                             need_bias=need_b and ctx.has_bias)
+        return gx, gw, gb, (grad_out if need_r else None), None
+
+
+def neighbor_dense(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in=None, relu=True, residual=None,
+                   neighbors_row_count=None, inverted=None):
+    """PointNet's layer (models/pointnet.py:137-145 of the reference) in one launch (dmcf_neighbor_dense_forward):
+    ``out[r] = sum_{p in row r} (act(x[idx[p]]) @ kernel + bias)`` (+ ``residual[r]``), act = relu or the identity.
+
+    ``n_in``: the rows of ``x`` the indices may address (default: all of them).  A pair whose index is outside [0, n_in)
+    contributes nothing, neither features nor bias -- what TensorFlow's GPU gather does for the reference's layer 0, which
+    gathers fluid-only rows with indices over fluid and boundary points.  ``neighbors_row_count``: int32 [n_out] for padded
+    lists.  When autograd records and an operand requires grad the call goes through :class:`NeighborDenseFunction`
+    (``inverted``: an optional :class:`SharedInverse` of the list for the input gradient); otherwise it is the inference
+    path: the same kernel, the same bits, no ``grad_fn``."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, kernel, bias, residual)):
+        kw = dict(neighbors_index=neighbors_index, neighbors_row_splits=neighbors_row_splits, n_in=n_in, relu=bool(relu),
+                  neighbors_row_count=neighbors_row_count, inverted=inverted)
+        return NeighborDenseFunction.apply(x, kernel, bias, residual, kw)
+    with torch.no_grad():
+        return _nd_forward(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, relu, residual, neighbors_row_count)
+
+
 class ScatterPlan:
     """dmcf_cconv_scatter_plan's output (include/dmcf_hip.h): the input points counting-sorted by the block of ``block_cells``^3
     lattice cells they lie in.  Depends on the two point sets, the lattice spacing and the radius only -- one plan serves every

@@ -735,6 +735,8 @@ class ShardedSimulator:
         self._mdecomp = copy.copy(decomp)
         self._mdecomp.__dict__.pop("_bounds_cache", None)
         self._mdecomp.__dict__.pop("_boxes_cache", None)
+        if not getattr(m, "sharded_step_supported", True):
+            raise NotImplementedError(f"{type(m).__name__} in the sharded path")
         if m.dens_feats or m.pres_feats or m.dens_norm or m.use_pre_adv or m.use_feats:
             raise NotImplementedError("dens_feats / pres_feats / dens_norm / use_pre_adv / use_feats in the sharded path")
         if not m.use_bnds and type(m).__name__ == "SymNet":

@@ -141,7 +141,10 @@ def model_weight_items(model):
     PBFNet-family model.  TensorFlow names a variable by the shortest attribute path to it, so a conv that
     is also a direct attribute is stored under that name (``model/fluid_convs``, ``model/obs_convs``,
     ``model/sym_convs/<i>``, ``model/adv_convs/<i>``) and all others under ``model/_all_convs/<i>/1``
-    (observed in checkpoints/*/ckpt.index)."""
+    (observed in checkpoints/*/ckpt.index).  A model with a ``checkpoint_items()`` method (PointNet) lists its own."""
+    own = getattr(model, "checkpoint_items", None)
+    if own is not None:
+        return own()
     alias = {id(model.fluid_convs): "model/fluid_convs", id(model.obs_convs): "model/obs_convs"}
     for i, conv in enumerate(getattr(model, "sym_convs", [])):
         alias[id(conv)] = f"model/sym_convs/{i}"

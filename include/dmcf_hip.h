@@ -584,6 +584,79 @@ size_t dmcf_emd_workspace_bytes(int64_t b, int64_t n, int64_t m);
 int dmcf_emd(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1, const int32_t* count2,
              float* cost, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PointNet's layer (models/pointnet.py:137-145): tf.keras.layers.Dense, tf.gather by neighbors_index and the ragged
+ * tf.reduce_sum over the row splits, with the relu before the Dense and the residual after it.  Per output row r:
+ *     out_r = (sum_{p in row r, 0 <= idx[p] < n_in} act(x_{idx[p]})) W + c_r b (+ residual_r)       (+ mask, below)
+ * c_r the number of those pairs; act = relu (DMCF_ND_RELU) or the identity; the bias is summed once per neighbour, as the
+ * reference's Dense-then-gather does.  A neighbour index outside [0, n_in) contributes nothing, neither features nor bias:
+ * what TensorFlow's GPU gather returns for out-of-range rows (zeros) and what its gradient does with them (drops them).
+ * One launch: gather, relu, contraction on the matrix cores (v_mfma_f32_16x16x4_f32), bias and residual.  Row sums are
+ * formed in pair order and no float atomics are used: two identical calls give identical bits.
+ * Rows reaching outside [0, n_pairs) are empty.  Cin, Cout <= 128 (DMCF_EUNSUPPORTED beyond).  Sizes, pointers and, when
+ * host_row_splits is given, the row splits are validated on the host before anything is enqueued (DMCF_EINVAL).
+ * ---------------------------------------------------------------------------------------------- */
+#define DMCF_ND_RELU 1          /* act = relu (forward); the backward masks the input gradient with x > 0 */
+#define DMCF_ND_W_TRANSPOSED 2  /* kernel is stored [Cout, Cin] (the backward's input gradient uses W^T) */
+typedef struct dmcf_neighbor_dense_args {
+    uint32_t struct_size;                 /* sizeof(dmcf_neighbor_dense_args) of the caller; smaller: DMCF_EINVAL */
+    int32_t flags;                        /* DMCF_ND_* */
+    const float* x;                       /* [n_in, cin]; may be NULL when n_in == 0 */
+    int64_t n_in;
+    int32_t cin;
+    int32_t cout;
+    const float* kernel;                  /* [cin, cout] ([cout, cin] with DMCF_ND_W_TRANSPOSED) */
+    const float* bias;                    /* [cout] or NULL */
+    const float* residual;                /* [n_out, cout] or NULL */
+    const float* mask;                    /* [n_out, cout] or NULL: out = 0 where mask <= 0 (the backward's relu) */
+    const int32_t* neighbors_index;       /* [n_pairs] */
+    const int64_t* neighbors_row_splits;  /* [n_out + 1] CSR, or [n_out] row begins with neighbors_row_count */
+    const int32_t* neighbors_row_count;   /* optional [n_out]: padded lists (dmcf_frs_search_padded); NULL = CSR */
+    int64_t n_out;
+    int64_t n_pairs;                      /* entries neighbors_index holds */
+    const int64_t* host_row_splits;       /* optional HOST copy of neighbors_row_splits: checked (CSR: starts at 0, monotone,
+                                             ends at n_pairs; padded: begins inside [0, n_pairs]) */
+    float* out;                           /* [n_out, cout]; may not alias x or mask */
+    float* record_s;                      /* optional [n_out, cin]: the aggregate S (the backward's operand) */
+    float* record_count;                  /* [n_out] c_r, given together with record_s */
+} dmcf_neighbor_dense_args;
+
+int dmcf_neighbor_dense_forward(const dmcf_neighbor_dense_args* args, dmcf_stream_t stream);
+
+/* Backward of dmcf_neighbor_dense_forward for G = grad_out = dL/d out [n_out, cout]:
+ *     grad_x_j    = act'(x_j) (sum_{r : j in row r} G_r) W^T   (nd_gather_mfma on the inverted list, W^T, mask x > 0)
+ *     grad_kernel = S^T G,   grad_bias = sum_r c_r G_r         (per-slab partials on the matrix cores, summed in slab order)
+ * with S and c as dmcf_neighbor_dense_forward recorded them.  inv_*: dmcf_invert_neighbors_list(n_in, ...) of the forward
+ * list (out-of-range indices are dropped there).  Each output is optional (NULL = not wanted).  The residual's gradient is
+ * G itself (the caller's).  No float atomics: two identical calls give identical bits. */
+typedef struct dmcf_neighbor_dense_backward_args {
+    uint32_t struct_size;                 /* sizeof(dmcf_neighbor_dense_backward_args) of the caller; smaller: DMCF_EINVAL */
+    int32_t flags;                        /* DMCF_ND_RELU: the forward applied relu */
+    const float* x;                       /* [n_in, cin] the forward's input (read for the relu mask only) */
+    int64_t n_in;
+    int32_t cin;
+    int32_t cout;
+    const float* kernel;                  /* [cin, cout] */
+    const float* grad_out;                /* [n_out, cout] */
+    int64_t n_out;
+    const float* s;                       /* [n_out, cin] record_s of the forward */
+    const float* count;                   /* [n_out] record_count of the forward */
+    const int32_t* inv_index;             /* [inv_n_pairs] */
+    const int64_t* inv_row_splits;        /* [n_in + 1] */
+    int64_t inv_n_pairs;
+    float* grad_x;                        /* [n_in, cin] or NULL */
+    float* grad_kernel;                   /* [cin, cout] or NULL */
+    float* grad_bias;                     /* [cout] or NULL */
+} dmcf_neighbor_dense_backward_args;
+
+size_t dmcf_neighbor_dense_backward_workspace_bytes(const dmcf_neighbor_dense_backward_args* args);
+int dmcf_neighbor_dense_backward(const dmcf_neighbor_dense_backward_args* args, void* workspace, size_t workspace_bytes,
+                                 dmcf_stream_t stream);
+/* Diagnostics: the device kernels the forward (fwd) and / or the backward (bwd) launch for these arguments, in launch
+ * order, separated by ';' (names as rocprofv3 prints them, e.g. "nd_gather_mfma<2>"); either argument may be NULL */
+int dmcf_neighbor_dense_kernel_names(const dmcf_neighbor_dense_args* fwd, const dmcf_neighbor_dense_backward_args* bwd,
+                                     char* names, size_t name_bytes);
+
 #ifdef __cplusplus
 }
 #endif

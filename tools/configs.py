@@ -42,5 +42,11 @@ CCONV2D = dict(  # configs/other/cconv.yml:7-21
     ignore_query_points=True, use_bnds=False, particle_radii=[0.025], timestep=0.0025, grav=-9.81,
     out_scale=[6.25e-06, 6.25e-06, 0.0])
 
+# configs/other/pointnet.yml:7-20.  Not in BY_NAME (whose keys are those of tests/golden/reference_configs.json): checked
+# against tests/golden/reference_pointnet_config.json (tools/make_pointnet_config_fixture.py) by tests/test_pointnet_abi.py
+POINTNET2D = dict(
+    name="PointNet", layer_channels=[64, 128, 128, 128, 3], particle_radii=[0.01], timestep=0.0025, grav=-9.81,
+    out_scale=[6.25e-06, 6.25e-06, 0.0], use_bnds=True)
+
 BY_NAME = {"Liquid3d": LIQUID3D, "WaterRamps": WATERRAMPS, "WBC-SPH": WBC_SPH, "column/hrnet": COLUMN_HRNET,
            "other/cconv": CCONV2D}
