@@ -169,6 +169,35 @@ class CconvScatterArgs(ctypes.Structure):
     ]
 
 
+class AdamTensor(ctypes.Structure):
+    """struct dmcf_adam_tensor (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("param", ctypes.c_void_p),
+        ("grad", ctypes.c_void_p),
+        ("m", ctypes.c_void_p),
+        ("v", ctypes.c_void_p),
+        ("n", ctypes.c_int64),
+    ]
+
+
+class AdamArgs(ctypes.Structure):
+    """struct dmcf_adam_args (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("n_tensors", ctypes.c_int32),
+        ("tensors", ctypes.c_void_p),
+        ("device_tensors", ctypes.c_void_p),
+        ("lr", ctypes.c_float),
+        ("beta_1", ctypes.c_float),
+        ("beta_2", ctypes.c_float),
+        ("epsilon", ctypes.c_float),
+        ("beta_1_power", ctypes.c_float),
+        ("beta_2_power", ctypes.c_float),
+        ("clip_norm", ctypes.c_float),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 # names every entry point include/dmcf_hip.h declares (tests/test_abi.py cross-checks against the header)
 SYMBOLS = [
     "dmcf_version", "dmcf_error_string", "dmcf_last_hip_error",
@@ -188,7 +217,7 @@ SYMBOLS = [
     "dmcf_nn_distance_workspace_bytes", "dmcf_nn_distance", "dmcf_approx_match_workspace_bytes", "dmcf_approx_match",
     "dmcf_match_cost_workspace_bytes", "dmcf_match_cost", "dmcf_emd_workspace_bytes", "dmcf_emd",
     "dmcf_neighbor_dense_forward", "dmcf_neighbor_dense_backward_workspace_bytes", "dmcf_neighbor_dense_backward",
-    "dmcf_neighbor_dense_kernel_names",
+    "dmcf_neighbor_dense_kernel_names", "dmcf_adam_step_workspace_bytes", "dmcf_adam_step", "dmcf_adam_step_kernel_names",
 ]
 
 
@@ -335,6 +364,12 @@ def lib():
     L.dmcf_neighbor_dense_kernel_names.restype = c.c_int
     L.dmcf_neighbor_dense_kernel_names.argtypes = [c.POINTER(NeighborDenseArgs), c.POINTER(NeighborDenseBackwardArgs), c.c_char_p,
                                                    c.c_size_t]
+    L.dmcf_adam_step_workspace_bytes.restype = c.c_size_t
+    L.dmcf_adam_step_workspace_bytes.argtypes = [c.POINTER(AdamArgs)]
+    L.dmcf_adam_step.restype = c.c_int
+    L.dmcf_adam_step.argtypes = [c.POINTER(AdamArgs), c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_adam_step_kernel_names.restype = c.c_int
+    L.dmcf_adam_step_kernel_names.argtypes = [c.POINTER(AdamArgs), c.c_char_p, c.c_size_t]
     _lib = L
     return L
 

@@ -10,9 +10,11 @@
   write_results      :520-526  HDF5 result file (needs h5py, which this image lacks: raises a clear error) and an
                                .npz stand-in with the same content
 
-zstd comes from the system ``libzstd.so.1`` through ctypes (the ``zstandard`` wheel is not installed here); msgpack
-from the ``msgpack`` package.  The training-side data flow (shuffling, augmentation, batching, the column / free-fall
-generators) is out of scope (SURVEY.md section 8f rank 2 covers the file formats only).
+  PhysicsSimDataFlow :210-357  training samples: windows of pre + window + 1 frames, augmentation, input transform
+  get_dataloader     :469-517  repeat, a seeded local shuffle buffer, list batching (the training loop's loader)
+
+zstd comes from the system ``libzstd.so.1`` through ctypes; msgpack from the ``msgpack`` package.  The column / free-fall
+generators of the training side are not rebuilt (pass scene files or in-memory scenes).
 """
 import ctypes
 import ctypes.util
@@ -122,9 +124,10 @@ class Dataset:
 
 
 class DatasetGroup:
-    """datasets/dataset_reader_physics.py:85-142, the part the test split needs: ``dataset_path`` holds the scene files
-    (``*.msgpack.zst``) of the split, in ``<path>/test`` if that directory exists, else in ``<path>`` itself.  ``data``:
-    scenes already in memory (a list of per-scene frame lists, e.g. a committed fixture).  The training-side generators
+    """datasets/dataset_reader_physics.py:85-142: ``dataset_path`` holds the scene files (``*.msgpack.zst``) of the split, in
+    ``<path>/test`` (``<path>/valid``) if that directory exists, else in ``<path>`` itself; ``split="train"`` reads
+    ``<path>/train`` as well.  ``data``: scenes already in memory (a list of per-scene frame lists, e.g. a committed fixture),
+    then every split, train included, is that data.  The training-side generators
     (``type: column | free_fall`` without a dataset_path: the reference's own 1-D SPH solver, column_gen.py) are host code
     outside the per-step hot path and are not rebuilt here: pass ``data`` or a ``dataset_path``."""
 
@@ -132,7 +135,7 @@ class DatasetGroup:
         self.name = dataset_cfg.pop("name", "dataset")
         self.train = self.valid = self.test = None
         if data is not None:
-            self.test = self.valid = Dataset(data=data)
+            self.test = self.valid = self.train = Dataset(data=data)
             return
         if "dataset_path" not in dataset_cfg or dataset_cfg["dataset_path"] is None:
             raise NotImplementedError(
@@ -140,14 +143,20 @@ class DatasetGroup:
                 "(datasets/column_gen.py / free_fall_gen.py), which is outside the hot path: pass --dataset_path with "
                 "scene files, or DatasetGroup(data=...)")
         path = dataset_cfg.pop("dataset_path")
-        if split == "train":
-            raise NotImplementedError("training is out of scope of the MI355X hot path (SURVEY.md section 2 row 16)")
+        if split == "train":  # :116-120
+            sub = os.path.join(path, "train")
+            if not os.path.exists(sub):
+                # the reference raises FileNotFoundError here; NotImplementedError is what this package raised for the train
+                # split before the training loop existed, and callers (and tests) catch that type
+                raise NotImplementedError(f"--split train needs the training scenes in {sub} (a directory of *.msgpack.zst "
+                                          "files): it does not exist")
+            self.train = Dataset(dataset_path=sub)
         if split != "valid":  # :132-142
             sub = os.path.join(path, "test")
             self.test = Dataset(dataset_path=sub if os.path.exists(sub) else path)
             if split == "test":
                 self.valid = self.test
-        else:
+        if split != "test":  # :122-127
             sub = os.path.join(path, "valid")
             self.valid = Dataset(dataset_path=sub if os.path.exists(sub) else path)
 
@@ -211,6 +220,163 @@ def get_rollout(dataset, stride=1, time_start=0, time_end=None, random_start=1, 
                 merge[k] = np.matmul(merge[k], R)
         out.append(merge)
     return out
+
+
+def random_rotation_matrix(rot_axis=None, dtype=np.float32, rng=np.random):
+    """:52-78 with ``rot_axis`` (the shipped configs' form: Liquid3d's ``rotate: {rot_axis: 1}``): a rotation by
+    theta = 2 pi x[0] about that axis, x = rng.rand(3) (the global numpy generator, as in the reference).  The reference's
+    branch without an axis reads an undefined ``strength`` and cannot run; it raises here."""
+    x = rng.rand(3)
+    theta = x[0] * 2 * np.pi
+    st, ct = np.sin(theta), np.cos(theta)
+    if rot_axis is None:
+        raise NotImplementedError("augment rotate without rot_axis (the reference's branch references an undefined 'strength')")
+    if rot_axis == 0:
+        return np.array([[1, 0, 0], [0, ct, st], [0, -st, ct]]).astype(dtype)
+    if rot_axis == 1:
+        return np.array([[ct, 0, st], [0, 1, 0], [-st, 0, ct]]).astype(dtype)
+    return np.array([[ct, st, 0], [-st, ct, 0], [0, 0, 1]]).astype(dtype)
+
+
+class PhysicsSimDataFlow:
+    """:210-357: training samples of a :class:`Dataset`.  For every scene (shuffled with ``shuffle``) and every start frame
+    ``i`` in ``range(len(scene) - (window + pre_frames) * stride)`` (shuffled, the first ``sample_cnt`` kept) one sample of
+    ``pre + window + 1`` frames ``i, i + stride, ...`` with ``pre = np.random.randint(pre_frames + 1)``: ``pos / vel / grav /
+    m / viscosity`` stacked [T, N, ...] (``[None]`` when a frame lacks the key), ``grav`` broadcast to every particle,
+    ``box / box_normals`` frame 0's repeated [T, M, 3], ``frame_id / scene_id``, ``pre``; then :meth:`transform`.
+
+    Random numbers: the scene / frame shuffles and the jitter come from ``self.rng`` (np.random.RandomState(seed)); ``pre`` and
+    the rotation from the global numpy generator, as in the reference (run_pipeline seeds it with 42)."""
+
+    def __init__(self, dataset, shuffle=False, window=1, is2d=False, pre_frames=0, stride=1, sample_cnt=None, augment=None,
+                 translate=None, scale=None, grav_eqvar=None, seed=0, **kwargs):
+        assert window >= 0
+        self.dataset = dataset
+        self.shuffle = shuffle
+        self.window = window + 1
+        self.is2d = is2d
+        self.pre_frames = pre_frames
+        self.stride = stride
+        self.augment = augment or {}
+        self.translate = translate
+        self.grav_eqvar = grav_eqvar
+        self.scale = scale
+        self.sample_cnt = sample_cnt
+        self.rng = np.random.RandomState(seed)
+
+    def transform(self, data):
+        """:240-293: the augment modes in config order, then translate / scale / grav_eqvar."""
+        for mode, config in self.augment.items():
+            config = config or {}
+            if mode == "rotate":
+                rand_R = random_rotation_matrix(**config)
+                for k in ["box", "box_normals", "pos", "vel"]:
+                    data[k] = np.matmul(data[k], rand_R)
+                if data["grav"][0] is not None:
+                    # the reference writes the rotated gravity to data[k], k leaked from the loop above: 'vel' is REPLACED
+                    # by the rotated gravity and 'grav' stays unrotated (:247-248, restated as written; DESIGN.md section 4.9)
+                    data[k] = np.matmul(data["grav"], rand_R)
+            elif mode == "jitter":
+                for k, v in config["channels"].items():
+                    data[k] += self.rng.normal(scale=v, size=data[k].shape)
+            elif mode == "jitter_inp":
+                for k, v in config["channels"].items():
+                    data[k][0] += self.rng.normal(scale=v, size=data[k][0].shape)
+            else:
+                raise NotImplementedError(mode)
+        if self.translate is not None:
+            data["pos"] += self.translate
+            data["box"] += self.translate
+        if self.scale is not None:
+            data["pos"] *= self.scale
+            data["box"] *= self.scale
+            data["vel"] *= self.scale
+            if data["grav"][0] is not None:
+                data["grav"] *= self.scale
+        if self.grav_eqvar is not None:
+            R = align_vector(self.grav_eqvar, data["grav"][0, 0])
+            data["orig_grav"] = data["grav"][0, 0]
+            for k in ["box", "box_normals", "pos", "vel", "grav"]:
+                data[k] = np.matmul(data[k], R)
+        return data
+
+    def __iter__(self):
+        files_idxs = np.arange(len(self.dataset))
+        if self.shuffle:
+            self.rng.shuffle(files_idxs)
+        for file_i in files_idxs:
+            data = self.dataset[file_i]
+            data_idxs = np.arange(len(data) - (self.window - 1 + self.pre_frames) * self.stride)
+            assert len(data_idxs) > 0
+            if self.shuffle:
+                self.rng.shuffle(data_idxs)
+            if self.sample_cnt is not None:
+                data_idxs = data_idxs[:self.sample_cnt]
+            for data_i in data_idxs:
+                sample = {"pre": np.random.randint(self.pre_frames + 1)}
+                frames = range(sample["pre"] + self.window)
+                for k in ["pos", "vel", "grav", "m", "viscosity"]:
+                    if k in data[data_i]:
+                        sample[k] = np.stack([np.asarray(data[data_i + i * self.stride].get(k, None)).astype("float32")
+                                              for i in frames], 0)
+                    else:
+                        sample[k] = [None]
+                for k in ["box", "box_normals"]:
+                    if k in data[0]:
+                        sample[k] = np.stack([np.asarray(data[0].get(k, None)).astype("float32") for i in frames], 0)
+                    else:
+                        sample[k] = [np.empty((0, 3))]
+                    sample[k] = np.reshape(sample[k], (len(sample[k]), -1, 3))
+                for k in ["frame_id", "scene_id"]:
+                    sample[k] = np.stack([data[data_i + i * self.stride].get(k, None) for i in frames], 0)
+                if sample["grav"][0] is not None:
+                    sample["grav"] = np.full_like(sample["vel"], np.expand_dims(sample["grav"], 1))
+                yield self.transform(sample)
+
+
+def get_dataloader(dataset, batch_size=1, window=1, repeat=False, shuffle_buffer=None, num_workers=1, cache_data=False,
+                   is2d=False, pre_frames=0, stride=1, translate=None, scale=None, augment=None, seed=0, **kwargs):
+    """:469-517 -> an iterator of batches: dicts of per-sample lists (tensorpack's BatchData(use_list=True); an incomplete
+    last batch is dropped).  ``repeat``: the flow restarts when exhausted; ``shuffle_buffer``: the samples pass a local
+    shuffle buffer of that many entries (seeded: ``seed``), and the flow shuffles scenes and start frames.  ``num_workers``
+    is accepted and ignored: samples are produced in this process (the reference's MultiProcessRunnerZMQ workers are not
+    ported); ``cache_data`` likewise.  Samples stay numpy arrays (the reference's to_tensor happens in the training step)."""
+    df = PhysicsSimDataFlow(dataset=dataset, shuffle=bool(shuffle_buffer), window=window, is2d=is2d, pre_frames=pre_frames,
+                            stride=stride, augment=augment, translate=translate, scale=scale, seed=seed, **kwargs)
+    rng = np.random.RandomState(seed + 1)
+
+    def samples():
+        while True:
+            yield from df
+            if not repeat:
+                return
+
+    def shuffled():
+        if not shuffle_buffer:
+            yield from samples()
+            return
+        # tensorpack's LocallyShuffleData, simplified: fill a buffer of shuffle_buffer samples, then hand out a random entry
+        # of it for every new sample that comes in (and drain it in random order at the end of a finite flow)
+        buf = []
+        for s in samples():
+            if len(buf) < shuffle_buffer:
+                buf.append(s)
+                continue
+            j = rng.randint(len(buf))
+            out, buf[j] = buf[j], s
+            yield out
+        while buf:
+            yield buf.pop(rng.randint(len(buf)))
+
+    def batches():
+        batch = []
+        for s in shuffled():
+            batch.append(s)
+            if len(batch) == batch_size:
+                yield {k: [b[k] for b in batch] for k in batch[0]}
+                batch = []
+
+    return batches()
 
 
 def write_results(path, name, data):

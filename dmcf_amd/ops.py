@@ -1777,3 +1777,61 @@ def emd(xyz1, xyz2, n=None, m=None):
     _lib.check(L.dmcf_emd(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(ws), nbytes, _stream()),
                "dmcf_emd")
     return cost if batched else cost[0]
+
+
+def _adam_args(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, beta_2_power, clip_norm):
+    """-> (dmcf_adam_args, host table, [params, grads, ms, vs]) for :func:`adam_step` (device_tensors not yet set)."""
+    if not (len(params) == len(grads) == len(ms) == len(vs)):
+        raise ValueError("params, grads, m and v must have one entry each per tensor")
+    recs = (_lib.AdamTensor * max(len(params), 1))()
+    for i, (p, g, m, v) in enumerate(zip(params, grads, ms, vs)):
+        for t, name in ((p, "param"), (g, "grad"), (m, "m"), (v, "v")):
+            _dev_f32(t, name)
+            if not t.is_contiguous():
+                raise ValueError(f"{name} of tensor {i} must be contiguous")
+            if t.numel() != p.numel():
+                raise ValueError(f"tensor {i}: param, grad, m and v must have the same number of elements")
+        recs[i].param, recs[i].grad, recs[i].m, recs[i].v = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+        recs[i].n = p.numel()
+    a = _lib.AdamArgs()
+    a.struct_size = ctypes.sizeof(_lib.AdamArgs)
+    a.n_tensors = len(params)
+    a.tensors = ctypes.cast(recs, ctypes.c_void_p).value
+    a.lr, a.beta_1, a.beta_2, a.epsilon = float(lr), float(beta_1), float(beta_2), float(epsilon)
+    a.beta_1_power, a.beta_2_power = float(beta_1_power), float(beta_2_power)
+    a.clip_norm = float(clip_norm) if clip_norm is not None else -1.0
+    return a, recs
+
+
+def adam_step_kernel_names(params, grads, ms, vs, clip_norm=None):
+    """';'-separated names of the kernels dmcf_adam_step launches for these tensors (rocprofv3's kernel names)."""
+    a, recs = _adam_args(params, grads, ms, vs, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, clip_norm)
+    a.device_tensors = 1 if len(params) else None  # (validated for presence only: nothing is read)
+    name = ctypes.create_string_buffer(64)
+    _lib.check(_lib.lib().dmcf_adam_step_kernel_names(ctypes.byref(a), name, 64), "dmcf_adam_step_kernel_names")
+    return name.value.decode()
+
+
+def adam_step(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, beta_2_power, clip_norm=None):
+    """dmcf_adam_step: one Adam update of every (param, grad, m, v) in place, in the order of operations of TensorFlow's
+    ApplyAdam (``alpha = lr sqrt(1 - beta_2_power) / (1 - beta_1_power)``, ``param -= alpha m / (epsilon + sqrt(v))``), each
+    gradient clipped per tensor to ``clip_norm`` first when that is > 0 (tf.clip_by_norm).  Lists of contiguous float32 device
+    tensors; the scalars are Keras' coefficients for the iteration (utils/tools/losses.KerasAdam computes them).  One launch
+    (two with clipping); the descriptor table goes to the device in one copy."""
+    L = _lib.lib()
+    a, recs = _adam_args(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, beta_2_power, clip_norm)
+    if not params:
+        return
+    dev = params[0].device
+    raw = torch.frombuffer(bytearray(ctypes.string_at(recs, ctypes.sizeof(_lib.AdamTensor) * len(params))), dtype=torch.uint8)
+    table = raw.to(dev, non_blocking=False)
+    a.device_tensors = table.data_ptr()
+    nbytes = int(L.dmcf_adam_step_workspace_bytes(ctypes.byref(a)))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_adam_step(ctypes.byref(a), _ptr(ws), nbytes, _stream()), "dmcf_adam_step")
+    if timer is not None:
+        timer.end("adam_step", dict(tensors=len(params), kernel=adam_step_kernel_names(params, grads, ms, vs, clip_norm)), t0)
+    # (the table and the workspace are freed into torch's caching allocator, which keeps them from reuse until the stream has
+    # passed this point)
+    del table, ws

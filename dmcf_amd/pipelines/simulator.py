@@ -7,8 +7,12 @@ no ``step()``; it is provided as an alias because BASELINE.js
 
 ``run_test`` (:111-165) writes the rollouts of the test split; ``run_valid`` (:167-285) rolls out the validation split and
 computes the reference's metrics (MSE, Chamfer both ways, density errors, approximate-match EMD, velocity-histogram KL, the
-one-step MSE) with the nearest-neighbour and EMD kernels of dmcf_amd/csrc/metrics.hip.  Training is out of scope.  The
-number of particles may change between steps (run_sample.py:173-177 adds inflow), so nothing here assumes a fixed N.
+one-step MSE) with the nearest-neighbour and EMD kernels of dmcf_amd/csrc/metrics.hip.  ``run_train`` (:287-518) is the
+training loop: ``train_step`` (the reference's ``train(data, time_w, it, max_err, max_dens_err)``) warms every sample up
+on the inference path, records the time-weighted window, back-propagates and applies utils/tools/losses.KerasAdam
+(dmcf_adam_step); the outer loop follows the window / warm-up / iteration schedules, writes checkpoints with their Adam
+state (utils/tf_checkpoint.CheckpointManager) and validates and tests after every epoch.  The number of particles may
+change between steps (run_sample.py:173-177 adds inflow), so nothing here assumes a fixed N.
 """
 import logging
 import os
@@ -117,6 +121,12 @@ class Simulator:
                         str(kwargs.get("version", ""))])
         self.cfg.logs_dir = os.path.join(main_log_dir, tag)
         self.cfg.out_dir = os.path.join(kwargs.get("output_dir", "./output"), tag)
+        if split == "train" and kwargs.get("restart"):  # base_pipeline.py:54-65 (the train split only here)
+            import shutil
+            for d in (self.cfg.logs_dir, self.cfg.out_dir):
+                if os.path.exists(d):
+                    shutil.rmtree(d)
+        self.optimizer = None
 
     def _to_device(self, x):
         if x is None:
@@ -336,3 +346,273 @@ class Simulator:
             log.setLevel(level)
         self.valid_loss = loss
         return loss
+
+
+    def train_loader(self, schedule):
+        """get_dataloader(dataset.train, batch_size, pre_frames, window, **data_generator, **data_generator.train)
+        (simulator.py:297-305 and the rebuilds of :438-458)."""
+        from ..datasets import get_dataloader
+        gen, kw = self._data_generator("train")
+        kw.pop("seed", None)
+        self._loader_seed = getattr(self, "_loader_seed", -1) + 1
+        return get_dataloader(self.dataset.train, batch_size=self.cfg.batch_size, pre_frames=schedule.pre_frames,
+                              window=schedule.window, seed=int(self.cfg.get("seed", 0)) + 7919 * self._loader_seed, **gen, **kw)
+
+    def make_optimizer(self):
+        """KerasAdam over every built weight of the model (checkpoint order), from ``cfg.optimizer`` and ``grad_clip_norm``."""
+        from ..utils import tf_checkpoint as tc
+        from ..utils.tools.losses import KerasAdam
+        self._variables = tc.model_variables(self.model)
+        params = [getattr(mod, attr) for _, mod, attr in self._variables]
+        named = {id(p) for p in params}
+        params += [p for p in self.model.parameters() if id(p) not in named]  # (weights without a checkpoint name: none today)
+        self.optimizer = KerasAdam.from_config(params, self.cfg.optimizer, clip_norm=self.cfg.get("grad_clip_norm", -1))
+        return self.optimizer
+
+    def restore_train_state(self, ckpt_path=None):
+        """base_pipeline.py:155-187 for training: an explicit ``ckpt_path`` restores the weights, the Adam slots, ``iter`` and
+        ``save_counter`` and the run starts at epoch 0; otherwise the newest ``ckpt-<n>`` of ``<logs_dir>/checkpoint`` restores
+        the same and the run continues at epoch ``(n - 1) save_ckpt_freq + 1``.  Call after the weights are built;
+        builds the optimizer.  Returns the start epoch."""
+        from ..utils import tf_checkpoint as tc
+        self.manager = tc.CheckpointManager(os.path.join(self.cfg.logs_dir, "checkpoint"), max_to_keep=100)
+        self.save_counter, self.object_graph, epoch = 0, None, 0
+        prefix = ckpt_path or self.manager.latest_checkpoint
+        if prefix:
+            weights, slots, opt, graph = tc.read_train_state(prefix)
+            tc.load_into_model(self.model, weights, device=self.device)
+            self.object_graph = graph
+            # tf.train.Checkpoint.restore restores save_counter from any checkpoint, an explicit one included, and the manager
+            # numbers its next checkpoint save_counter + 1: a run fine-tuned from a checkpoint with save_counter 51 writes
+            # ckpt-52 first (DESIGN.md section 4.9)
+            self.save_counter = int(opt.get("save_counter", 0))
+            if not ckpt_path:
+                epoch = tc.checkpoint_epoch(prefix, int(self.cfg.get("save_ckpt_freq", 1) or 1))
+            log.info("Restored from %s", prefix)
+        else:
+            log.info("Initializing from scratch.")
+        opt_ = self.make_optimizer()
+        if prefix:
+            opt_.iterations = int(opt.get("iter", 0))
+            for k in ("beta_1", "beta_2", "decay"):
+                if k in opt:
+                    setattr(opt_, k, float(opt[k]))
+            for key, mod, attr in self._variables:
+                if key in slots and "m" in slots[key] and "v" in slots[key]:
+                    opt_.set_slots(getattr(mod, attr), slots[key]["m"], slots[key]["v"])
+        return epoch
+
+    def save_ckpt(self, epoch):
+        """CheckpointManager.save (base_pipeline.py:189-191): ``ckpt-<save_counter + 1>``."""
+        self.save_counter += 1
+        path = self.manager.save(self.model, self.optimizer, self.save_counter, self.object_graph)
+        log.info("Saved checkpoint at: %s", path)
+        return path
+
+    def _sample_tensors(self, data, bi):
+        dev = self._to_device
+        grav = data["grav"][bi]
+        return dict(pos=data["pos"][bi], grav0=dev(grav[0]) if grav[0] is not None else None, box0=dev(data["box"][bi][0]),
+                    boxn0=dev(data["box_normals"][bi][0]))
+
+    def warm_up(self, data, max_err=None, max_dens_err=None):
+        """simulator.py:325-368 on the inference path (no gradients): per sample up to ``pre`` model steps from frame 0, with
+        the ``max_err`` / ``max_dens_err`` early exits.  Restated as written: the state after p + 1 steps is compared with
+        frame p, and a warm-up that runs all k steps hands on pre = k - 1, the last loop index, with the state of frame k
+        (DESIGN.md section 4.9).  -> (in_pos, in_vel, pre) lists."""
+        from ..utils.tools.losses import density_loss, get_window_func
+        model = self.model
+        in_pos, in_vel, pres = [], [], []
+        with torch.no_grad():
+            for bi in range(len(data["pos"])):
+                s = self._sample_tensors(data, bi)
+                pr_pos, pr_vel = self._to_device(data["pos"][bi][0]), self._to_device(data["vel"][bi][0])
+                p = 0
+                prev_err, prev_dens_err = 0.0, 0.0
+                for p in range(int(data["pre"][bi])):
+                    pos, vel = model([pr_pos, pr_vel, s["grav0"], None, s["box0"], s["boxn0"]], training=False)
+                    frame = self._to_device(s["pos"][p])
+                    if max_err is not None:
+                        err = float(torch.max(torch.sum(torch.abs(pos - frame), dim=-1)))
+                        if p > 0 and err > prev_err and err > max_err:
+                            break
+                        prev_err = err
+                    if max_dens_err is not None:
+                        # the reference's argument order: the prediction as gt, the frame as pred
+                        err = float(density_loss(pos, frame, torch.cat([pos, s["box0"]]), torch.cat([frame, s["box0"]]),
+                                                 radius=model.particle_radii[0], win=get_window_func(model.window_dens),
+                                                 use_max=True))
+                        if p > 0 and err > prev_dens_err and err > max_dens_err:
+                            break
+                        prev_dens_err = err
+                    pr_pos, pr_vel = pos, vel
+                pres.append(p)
+                in_pos.append(pr_pos)
+                in_vel.append(pr_vel)
+        return in_pos, in_vel, pres
+
+    def window_loss(self, data, time_w, in_pos, in_vel, pres, it=0):
+        """simulator.py:370-403 on the recording path: per sample, ``len(time_w)`` model steps from the warmed-up state with
+        gradients through all of them; the step-t losses against target frame t + pre + 1 (previous frame t + pre), weighted
+        by time_w[t]; summed over the samples and divided by sum(time_w) * batch; plus ``w_decay`` sum w^2.  -> the loss
+        vector (one entry per model.loss_keys())."""
+        from ..utils.evaluation_helper import merge_dicts
+        model = self.model
+        if it > 1:
+            # simulator.py:386-391 calls model(inputs, vel, training=True): Keras rejects the second positional argument next
+            # to training=..., so the reference cannot run it either (every shipped config has iterations: [0])
+            raise NotImplementedError("iterations > 1 (the reference's inner iteration loop cannot run)")
+        model.requires_grad_(True)
+        rows = []
+        tw = torch.as_tensor(np.asarray(time_w, dtype=np.float32), device=self.device)
+        for bi in range(len(data["pos"])):
+            s = self._sample_tensors(data, bi)
+            pos, vel, pre = in_pos[bi], in_vel[bi], int(pres[bi])
+            for t in range(len(time_w)):
+                inputs = [pos, vel, s["grav0"], None, s["box0"], s["boxn0"]]
+                pos, vel = model(inputs, training=True)
+                target = s["pos"]
+                ls = [model.loss([pos, vel], [inputs, self._to_device(target[t + pre + 1]), self._to_device(target[t + pre]), pre])]
+                ls = merge_dicts(ls, lambda x, y: x + y / len(ls))
+                rows.append(torch.stack([torch.as_tensor(v, device=self.device).reshape(()) for v in ls.values()]) * tw[t])
+        loss_sum = torch.stack(rows).sum(0) / (tw.sum() * len(data["pos"]))
+        w_decay = self.cfg.get("w_decay", 0) or 0
+        if w_decay > 0:
+            # a scalar added to every entry of the loss vector (simulator.py:407-410: w_decay * reduce_sum of the per-weight sums)
+            loss_sum = loss_sum + w_decay * torch.stack([torch.sum(w ** 2) for w in self.optimizer.params]).sum()
+        return loss_sum
+
+    def train_step(self, data, time_w, it=0, max_err=None, max_dens_err=None):
+        """The reference's ``train(data, time_w, it, max_err, max_dens_err)`` (simulator.py:318-414): warm-up, the recorded
+        window, backward, KerasAdam.  ``data``: one batch of get_dataloader.  The model's weights must be built (run_train
+        makes one inference call first): the optimizer takes the weights that exist when it is made.  -> (loss vector as numpy, pre list).  Times the
+        phases into ``self.train_timing`` (warm_up, forward, backward, optimizer; seconds, device-synchronised)."""
+        if self.optimizer is None:
+            self.make_optimizer()
+        if getattr(self.model, "shard", None) is not None:
+            raise NotImplementedError("training in the sharded step")
+        sync = lambda: torch.cuda.synchronize(self.device)  # noqa: E731
+        t0 = time.perf_counter()
+        in_pos, in_vel, pres = self.warm_up(data, max_err, max_dens_err)
+        sync()
+        t1 = time.perf_counter()
+        self.optimizer.zero_grad()
+        loss_sum = self.window_loss(data, time_w, in_pos, in_vel, pres, it)
+        sync()
+        t2 = time.perf_counter()
+        loss_sum.sum().backward()  # (tape.gradient of a vector: the gradient of its sum)
+        sync()
+        t3 = time.perf_counter()
+        self.optimizer.step()
+        sync()
+        t4 = time.perf_counter()
+        self.train_timing = dict(warm_up=t1 - t0, forward=t2 - t1, backward=t3 - t2, optimizer=t4 - t3)
+        return loss_sum.detach().cpu().numpy(), pres
+
+    def run_train(self):
+        """simulator.py:287-518: the training loop.  Logs ``training - <key>: ... > loss: ...`` per iteration to
+        ``<logs_dir>/log_train_<time>.txt`` (no TensorBoard); checkpoint every ``save_ckpt_freq`` epochs, run_valid and
+        run_test after every epoch.  Returns the last iteration's loss dict."""
+        cfg, model = self.cfg, self.model
+        os.makedirs(cfg.logs_dir, exist_ok=True)
+        timestamp = datetime.now().strftime("%Y-%m-%d_%H:%M:%S")
+        handler = logging.FileHandler(os.path.join(cfg.logs_dir, "log_train_" + timestamp + ".txt"))
+        level = log.level
+        if not log.isEnabledFor(logging.INFO):
+            log.setLevel(logging.INFO)
+        log.addHandler(handler)
+        try:
+            schedule = TrainSchedule(cfg)
+            loader = self.train_loader(schedule)
+            first = next(loader)
+            # build the lazily created weights before the optimizer takes them ("dummy init", simulator.py:94)
+            with torch.no_grad():
+                s = self._sample_tensors(first, 0)
+                model([self._to_device(first["pos"][0][0]), self._to_device(first["vel"][0][0]), s["grav0"], None, s["box0"],
+                       s["boxn0"]], training=False)
+            start_ep = self.restore_train_state(model.cfg.get("ckpt_path"))
+            pending = [first]
+            log.info("Started training")
+            loss = {}
+            for epoch in range(start_ep, cfg.max_epoch + 1):
+                log.info(f"=== EPOCH {epoch:d}/{cfg.max_epoch:d} ===")
+                for i in range(cfg.iter):
+                    step = epoch * cfg.iter + i
+                    if schedule.advance(step):
+                        loader, pending = self.train_loader(schedule), []
+                    t0 = time.perf_counter()
+                    data = pending.pop() if pending else next(loader)
+                    time_w = schedule.time_weights([d.shape[0] for d in data["pos"]], data["pre"], step)
+                    t_data = time.perf_counter() - t0
+                    loss_l, pre = self.train_step(data, time_w, schedule.iterations, cfg.get("max_err", None),
+                                                  cfg.get("max_dens_err", None))
+                    self.train_timing["data"] = t_data
+                    loss = {}
+                    desc = "training -"
+                    for k, v in zip(model.loss_keys(), loss_l):
+                        desc += " %s: %.05f" % (k, v)
+                        loss[k] = float(v)
+                    loss["loss"] = float(np.sum(loss_l))
+                    desc += " > loss: %.05f" % loss["loss"]
+                    loss["timesteps"] = float(min(np.sum(time_w), np.ceil(np.sum(time_w))))
+                    loss["warmup"] = float(np.mean(data["pre"]))
+                    loss["warmup_diff"] = float(np.mean(np.asarray(data["pre"]) - np.asarray(pre)))
+                    log.info(desc)
+                if epoch % cfg.save_ckpt_freq == 0:
+                    self.save_ckpt(epoch)
+                self.run_valid(epoch)
+                self.run_test(epoch)
+        finally:
+            log.removeHandler(handler)
+            handler.close()
+            log.setLevel(level)
+        self.train_loss = loss
+        return loss
+
+
+class TrainSchedule:
+    """The schedules of the training loop, simulator.py:430-480: ``window_it`` / ``warm_up_it`` / ``it_idx`` advance while
+    ``step`` has reached the next entry of ``window_bnds`` / ``warm_up_bnds`` / ``its_bnds`` (each bounded by the shorter of
+    the two lists); a change of the window or the warm-up rebuilds the loader.  ``time_weights`` is the ``time_w`` blend."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.window_it = self.warm_up_it = self.it_idx = 0
+
+    def advance(self, step):
+        """-> True when the loader must be rebuilt for this step (the window or the warm-up changed)."""
+        cfg, rebuild = self.cfg, False
+        while self.window_it < min(len(cfg.windows), len(cfg.window_bnds)) and step >= cfg.window_bnds[self.window_it]:
+            self.window_it += 1
+            rebuild = True
+        while self.warm_up_it < min(len(cfg.max_warm_up), len(cfg.warm_up_bnds)) and step >= cfg.warm_up_bnds[self.warm_up_it]:
+            self.warm_up_it += 1
+            rebuild = True
+        while self.it_idx < min(len(cfg.iterations), len(cfg.its_bnds)) and step >= cfg.its_bnds[self.it_idx]:
+            self.it_idx += 1
+        return rebuild
+
+    @property
+    def window(self):
+        return self.cfg.windows[self.window_it]
+
+    @property
+    def pre_frames(self):
+        return self.cfg.max_warm_up[self.warm_up_it]
+
+    @property
+    def iterations(self):
+        return self.cfg.iterations[self.it_idx]
+
+    def time_weights(self, lengths, pres, step):
+        """simulator.py:466-478: ones over min(T_b - 1 - pre_b) frames; while a new window blends in (``time_blend`` steps
+        after its bound) its last ``windows[k] - windows[k-1]`` weights ramp from ``a`` down by 1 / diff, clipped to [0, 1]."""
+        cfg = self.cfg
+        time_w = np.ones(int(np.min([t - 1 - p for t, p in zip(lengths, pres)])), dtype=np.float32)
+        if self.window_it > 0:
+            a = (step - cfg.window_bnds[self.window_it - 1] + 1) / cfg.time_blend
+            if a < 1.0 and len(time_w) >= cfg.windows[self.window_it]:
+                diff = cfg.windows[self.window_it] - cfg.windows[self.window_it - 1]
+                time_w[-diff:] = np.clip(a - np.arange(diff) / diff, 0.0, 1.0)
+        return time_w
+

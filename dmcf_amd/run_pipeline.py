@@ -6,8 +6,11 @@
 
 Same flags as the reference; ``--section.key value`` overrides go through Config.merge_cfg_file.  ``--split test`` writes
 the rollouts (``Simulator.run_test``); ``--split valid`` rolls out the validation split and computes its metrics
-(``Simulator.run_valid``: MSE, Chamfer, density, EMD, velocity histograms).  ``--split train`` raises: the training loop is
-not implemented.
+(``Simulator.run_valid``: MSE, Chamfer, density, EMD, velocity histograms); ``--split train`` (the default, as in the
+reference) runs the training loop (``Simulator.run_train``: scenes from ``<dataset_path>/train``, checkpoints with the Adam
+state in ``<logs_dir>/checkpoint``, resumed from the newest one there unless ``--ckpt_path`` is given; ``--restart`` clears
+the run's logs and outputs first).  A config without ``dataset_path`` (the generated column / free-fall datasets) raises
+NotImplementedError in every split.
 """
 import argparse
 import random
@@ -48,6 +51,8 @@ def build(args, extra, data=None):
     cfg_dataset, cfg_pipeline, cfg_model = Config.merge_cfg_file(cfg, args, extra)
     dataset = DatasetGroup(**cfg_dataset, split=args.split, regen=args.regen, data=data)
     model = Model(**cfg_model)
+    if args.restart:
+        cfg_pipeline["restart"] = True
     return Pipeline(model, dataset, **cfg_pipeline)
 
 
@@ -55,9 +60,11 @@ def main(argv=None, data=None):
     random.seed(42)
     np.random.seed(42)
     args, extra = parse_args(argv)
-    if args.split not in ("test", "valid"):
-        raise NotImplementedError(f"--split {args.split}: the training loop is not implemented (test and valid are)")
+    if args.split not in ("train", "test", "valid"):
+        raise NotImplementedError(f"--split {args.split}: train, valid or test")
     pipeline = build(args, extra, data)
+    if args.split == "train":  # run_pipeline.py:147-148
+        return pipeline.run_train()
     if args.split == "valid":  # run_pipeline.py:151-152
         return pipeline.run_valid()
     return pipeline.run_test()

@@ -11,7 +11,8 @@
   emd_loss          losses.py:401-409  approximate-match EMD per batch item (validation metric; ops.emd, no gradient)
 
   get_loss          losses.py:47-110   the training losses mse / weighted_mse / vel / weighted_vel / momentum
-  get_optimizer     models/pbf_model.py:508-517  Adam (eps 1e-6), piecewise-constant learning rate
+  get_optimizer     models/pbf_model.py:508-517  Adam (eps 1e-6), piecewise-constant learning rate (torch.optim.Adam)
+  KerasAdam         the same optimizer with Keras' update rule and state, on dmcf_adam_step: what the training loop uses
 
 The density, Chamfer, EMD and histogram losses (losses.py:380-414, the last three on the reference's custom CUDA ops) are
 not implemented as training losses: get_loss returns a function that raises NotImplementedError for them (they would
@@ -305,8 +306,88 @@ class PiecewiseConstant:
 def get_optimizer(params, cfg):
     """models/pbf_model.py:508-517: Adam with epsilon 1e-6 and the piecewise-constant learning rate of ``cfg['lr_boundaries']``
     / ``cfg['lr_values']``, as (optimizer, scheduler): call ``scheduler.step()`` after every ``optimizer.step()`` -- the
-    learning rate of optimiser step k (counted from 0, as Keras' iterations) is PiecewiseConstant(...)(k)."""
+    learning rate of optimiser step k (counted from 0, as Keras' iterations) is PiecewiseConstant(...)(k).  This is torch's
+    update rule (epsilon added to the bias-corrected sqrt(v)); the training loop (Simulator.run_train) uses :class:`KerasAdam`,
+    the reference's rule and checkpoint state."""
     sched = PiecewiseConstant(cfg["lr_boundaries"], cfg["lr_values"])
     opt = torch.optim.Adam(params, lr=sched.values[0], eps=1e-6)
     lam = torch.optim.lr_scheduler.LambdaLR(opt, lambda step: sched(step) / sched.values[0])
     return opt, lam
+
+
+class KerasAdam:
+    """tf.keras.optimizers.Adam(learning_rate=PiecewiseConstantDecay(lr_boundaries, lr_values), epsilon=1e-6) of
+    models/pbf_model.py:511-517, on the HIP kernel dmcf_adam_step (ops.adam_step).  For optimizer iteration t (``iterations``
+    before the step, counted from 0): lr = the schedule at t (divided by ``1 + decay t`` when ``decay`` > 0, Keras'
+    _decayed_lr), beta_*^(t + 1) in float32, and TensorFlow's ApplyAdam:
+        alpha = lr sqrt(1 - beta_2^(t+1)) / (1 - beta_1^(t+1));  m += (1 - beta_1)(g - m);  v += (1 - beta_2)(g^2 - v)
+        param -= alpha m / (epsilon + sqrt(v))
+    -- epsilon is added to sqrt(v), not to the bias-corrected one as torch.optim.Adam does.  ``clip_norm`` > 0: each gradient
+    is clipped first as tf.clip_by_norm does (the pipeline's ``grad_clip_norm``).
+
+    State, named like a checkpoint's ``optimizer/*`` and ``.OPTIMIZER_SLOT/optimizer/{m,v}`` entries: ``iterations``,
+    ``beta_1``, ``beta_2``, ``decay``, and the slots ``m`` / ``v`` (one per parameter, None until the parameter first has a
+    gradient: as in Keras, a parameter whose gradient is None is neither updated nor given slots)."""
+
+    def __init__(self, params, lr_boundaries=(), lr_values=(1e-3,), beta_1=0.9, beta_2=0.999, epsilon=1e-6, decay=0.0,
+                 clip_norm=None):
+        self.params = list(params)
+        self.schedule = PiecewiseConstant(lr_boundaries, lr_values)
+        self.beta_1, self.beta_2, self.epsilon, self.decay = float(beta_1), float(beta_2), float(epsilon), float(decay)
+        self.clip_norm = clip_norm if clip_norm is not None and clip_norm > 0 else None
+        self.iterations = 0
+        self.m = [None] * len(self.params)
+        self.v = [None] * len(self.params)
+
+    @classmethod
+    def from_config(cls, params, cfg, clip_norm=None):
+        """The pipeline's ``optimizer:`` section (lr_boundaries, lr_values) -> the reference's optimizer."""
+        return cls(params, cfg["lr_boundaries"], cfg["lr_values"], epsilon=1e-6, clip_norm=clip_norm)
+
+    def lr(self, iterations=None):
+        """Learning rate of optimizer iteration ``iterations`` (default: the next step's), float32 like Keras'."""
+        t = self.iterations if iterations is None else int(iterations)
+        lr = np.float32(self.schedule(t))
+        if self.decay > 0:
+            lr = np.float32(lr / (np.float32(1.0) + np.float32(self.decay) * np.float32(t)))
+        return lr
+
+    def coefficients(self, iterations=None):
+        """(lr, beta_1^(t+1), beta_2^(t+1)) in float32 for iteration t (default: the next step's)."""
+        t = self.iterations if iterations is None else int(iterations)
+        step = np.float32(t + 1)
+        return self.lr(t), np.power(np.float32(self.beta_1), step), np.power(np.float32(self.beta_2), step)
+
+    def zero_grad(self):
+        for p in self.params:
+            p.grad = None
+
+    def step(self):
+        """One update of every parameter that has a gradient; ``iterations`` += 1 (also when none has one, as Keras)."""
+        from ... import ops
+        live = [i for i, p in enumerate(self.params) if p.grad is not None]
+        for i in live:
+            if self.m[i] is None:
+                self.m[i] = torch.zeros_like(self.params[i], memory_format=torch.contiguous_format)
+                self.v[i] = torch.zeros_like(self.params[i], memory_format=torch.contiguous_format)
+        lr, b1p, b2p = self.coefficients()
+        if live:
+            with torch.no_grad():
+                ops.adam_step([self.params[i] for i in live], [self.params[i].grad.contiguous() for i in live],
+                              [self.m[i] for i in live], [self.v[i] for i in live], lr, self.beta_1, self.beta_2,
+                              self.epsilon, b1p, b2p, self.clip_norm)
+            # the kernel wrote through raw pointers: advance the parameters' version counters as an in-place torch op would
+            # (ops.cconv_forward's packed-filter cache is keyed on them)
+            for i in live:
+                torch.autograd.graph.increment_version(self.params[i])
+        self.iterations += 1
+
+    def slots_by_param(self):
+        """{id(parameter): {'m': tensor, 'v': tensor}} for the parameters that have slots."""
+        return {id(p): {"m": m, "v": v} for p, m, v in zip(self.params, self.m, self.v) if m is not None}
+
+    def set_slots(self, param, m, v):
+        """Restore the slots of ``param`` (arrays or tensors of its shape)."""
+        i = next(k for k, p in enumerate(self.params) if p is param)
+        as_t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32)).to(param.device).reshape(param.shape).contiguous()  # noqa: E731
+        self.m[i], self.v[i] = as_t(m), as_t(v)

@@ -657,6 +657,46 @@ int dmcf_neighbor_dense_backward(const dmcf_neighbor_dense_backward_args* args, 
 int dmcf_neighbor_dense_kernel_names(const dmcf_neighbor_dense_args* fwd, const dmcf_neighbor_dense_backward_args* bwd,
                                      char* names, size_t name_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * The training loop's optimizer step (ABI 2.11): tf.keras.optimizers.Adam(epsilon=...) of models/pbf_model.py:511-517 over
+ * every trainable tensor of a model in one launch, in the order of operations of TensorFlow's ApplyAdam GPU functor:
+ *     alpha = lr sqrt(1 - beta_2_power) / (1 - beta_1_power)
+ *     m += (1 - beta_1)(g - m);   v += (1 - beta_2)(g g - v);   param -= alpha m / (epsilon + sqrt(v))
+ * Keras' coefficients for optimizer iteration t (counted from 0): lr = the schedule at t, beta_*_power = pow(beta_*, t + 1)
+ * in float32 -- computed by the caller.  clip_norm > 0: every gradient is first clipped per tensor as tf.clip_by_norm does,
+ * g c / max(|g|_2, c) (|g|_2 = 0 when the l2 sum is 0), with the l2 sums reduced in a fixed order (per-block partials in
+ * the workspace, one combine): two launches; one without clipping.  No float atomics: two identical calls give identical
+ * bits.  Gradients are read only; param, m and v are updated in place and may not alias each other or a gradient.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dmcf_adam_tensor {
+    float* param;                          /* [n] */
+    const float* grad;                     /* [n] */
+    float* m;                              /* [n] first-moment slot */
+    float* v;                              /* [n] second-moment slot */
+    int64_t n;                             /* elements; 0: skipped (the pointers may then be NULL) */
+} dmcf_adam_tensor;
+
+typedef struct dmcf_adam_args {
+    uint32_t struct_size;                  /* sizeof(dmcf_adam_args) of the caller; smaller: DMCF_EINVAL */
+    int32_t n_tensors;                     /* 0 .. 65535 */
+    const dmcf_adam_tensor* tensors;       /* HOST array [n_tensors]: validated, and sizes the launch */
+    const dmcf_adam_tensor* device_tensors; /* the same n_tensors records in DEVICE memory: what the kernels read */
+    float lr;
+    float beta_1;
+    float beta_2;
+    float epsilon;
+    float beta_1_power;
+    float beta_2_power;
+    float clip_norm;                       /* <= 0: no clipping */
+    int32_t reserved;                      /* 0 */
+} dmcf_adam_args;
+
+size_t dmcf_adam_step_workspace_bytes(const dmcf_adam_args* args);
+int dmcf_adam_step(const dmcf_adam_args* args, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* Diagnostics: the kernels dmcf_adam_step launches for these arguments, in launch order, separated by ';'
+ * ("adam_sumsq;adam_update" with clipping, "adam_update" without, "" when no tensor holds an element) */
+int dmcf_adam_step_kernel_names(const dmcf_adam_args* args, char* names, size_t name_bytes);
+
 #ifdef __cplusplus
 }
 #endif
