@@ -218,6 +218,7 @@ SYMBOLS = [
     "dmcf_match_cost_workspace_bytes", "dmcf_match_cost", "dmcf_emd_workspace_bytes", "dmcf_emd",
     "dmcf_neighbor_dense_forward", "dmcf_neighbor_dense_backward_workspace_bytes", "dmcf_neighbor_dense_backward",
     "dmcf_neighbor_dense_kernel_names", "dmcf_adam_step_workspace_bytes", "dmcf_adam_step", "dmcf_adam_step_kernel_names",
+    "dmcf_raster_workspace_bytes", "dmcf_raster_count", "dmcf_raster_discs",
 ]
 
 
@@ -370,6 +371,14 @@ def lib():
     L.dmcf_adam_step.argtypes = [c.POINTER(AdamArgs), c.c_void_p, c.c_size_t, c.c_void_p]
     L.dmcf_adam_step_kernel_names.restype = c.c_int
     L.dmcf_adam_step_kernel_names.argtypes = [c.POINTER(AdamArgs), c.c_char_p, c.c_size_t]
+    L.dmcf_raster_workspace_bytes.restype = c.c_size_t
+    L.dmcf_raster_workspace_bytes.argtypes = [c.c_int64, c.c_int64, c.c_int64, c.c_int32, c.c_int32]
+    L.dmcf_raster_count.restype = c.c_int
+    L.dmcf_raster_count.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_int32, c.c_int32, c.c_void_p, c.c_size_t,
+                                    c.c_void_p, c.c_void_p]
+    L.dmcf_raster_discs.restype = c.c_int
+    L.dmcf_raster_discs.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_uint32, c.c_int32, c.c_int32, c.c_void_p,
+                                    c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p]
     _lib = L
     return L
 

@@ -1835,3 +1835,60 @@ def adam_step(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, 
     # (the table and the workspace are freed into torch's caching allocator, which keeps them from reuse until the stream has
     # passed this point)
     del table, ws
+
+
+def raster_discs(xy, radius, color_argb, width, height, out=None):
+    """Draw filled, anti-aliased discs of one colour (dmcf_raster_count / dmcf_raster_discs; the pixel model is in
+    include/dmcf_hip.h) into ``out``, float32 RGB ``[F, H, W, 3]`` in [0, 1], composited in place; ``out=None``: a new white
+    image.  ``xy``: float32 CUDA ``[F, N, 2]`` (frame f's points into frame f) or ``[N, 2]`` (the same points in every frame,
+    binned once) in pixel coordinates; ``radius`` in pixels; ``color_argb`` 0xAARRGGBB.  Returns ``out``.  The two calls
+    bracket one host read of the bin size."""
+    L = _lib.lib()
+    if not isinstance(xy, torch.Tensor):
+        raise TypeError("xy must be a torch tensor")
+    if xy.dim() not in (2, 3) or xy.shape[-1] != 2:
+        raise ValueError(f"xy must have shape [F, N, 2] or [N, 2], got {tuple(xy.shape)}")
+    width, height, color_argb = int(width), int(height), int(color_argb)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"width and height must be positive, got {width} x {height}")
+    if not 0 <= color_argb <= 0xFFFFFFFF:
+        raise ValueError(f"color_argb must be a 32-bit ARGB value, got {color_argb:#x}")
+    xy = _dev_f32(xy, "xy")
+    if out is None:
+        frames = xy.shape[0] if xy.dim() == 3 else 1
+        out = torch.ones((frames, height, width, 3), dtype=torch.float32, device=xy.device)
+    else:
+        _dev_f32(out, "out")
+        if out.device != xy.device:
+            raise ValueError(f"out is on {out.device}, xy on {xy.device}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous (it is written in place)")
+        if out.dim() != 4 or tuple(out.shape[1:]) != (height, width, 3):
+            raise ValueError(f"out must have shape [F, {height}, {width}, 3], got {tuple(out.shape)}")
+    frames = out.shape[0]
+    if xy.dim() == 3 and xy.shape[0] != frames:
+        raise ValueError(f"xy holds {xy.shape[0]} frames, out {frames}")
+    n = xy.shape[-2]
+    stride = n if xy.dim() == 3 else 0
+    radius = float(radius)
+    if n == 0 or frames == 0 or not (np.isfinite(radius) and radius > 0.0) or (color_argb >> 24) == 0:
+        return out  # nothing is drawn (the library would not launch either)
+    nbytes = int(L.dmcf_raster_workspace_bytes(n, frames, stride, width, height))
+    if nbytes == 0:
+        raise ValueError(f"dmcf_raster: unsupported size (n={n}, frames={frames}, {width} x {height})")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=xy.device)
+    total = torch.empty(1, dtype=torch.int64, device=xy.device)
+    _lib.check(L.dmcf_raster_count(_ptr(xy), n, frames, stride, radius, width, height, _ptr(ws), nbytes, _ptr(total), _stream()),
+               "dmcf_raster_count")
+    cap = int(total.item())
+    bins = torch.empty((max(cap, 1), 2), dtype=torch.float32, device=xy.device)
+    _lib.check(L.dmcf_raster_discs(_ptr(xy), n, frames, stride, radius, color_argb, width, height, _ptr(out), _ptr(ws), nbytes,
+                                   _ptr(bins), cap, _stream()), "dmcf_raster_discs")
+    return out
+
+
+def rgba8(image):
+    """float RGB ``[..., 3]`` in [0, 1] -> uint8 RGBA ``[..., 4]``: ``round(255 C)`` (half to even), clamped to [0, 255], alpha
+    255."""
+    q = torch.clamp(torch.round(image * 255.0), 0.0, 255.0).to(torch.uint8)
+    return torch.cat([q, torch.full_like(q[..., :1], 255)], dim=-1)

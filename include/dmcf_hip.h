@@ -697,6 +697,36 @@ int dmcf_adam_step(const dmcf_adam_args* args, void* workspace, size_t workspace
  * ("adam_sumsq;adam_update" with clipping, "adam_update" without, "" when no tensor holds an element) */
 int dmcf_adam_step_kernel_names(const dmcf_adam_args* args, char* names, size_t name_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * Disc rasterizer of the renderer (ABI 2.12; dmcf_amd/utils/draw_sim2d.py, the reference's utils/draw_sim2d.py:11-45, where
+ * skia's canvas.drawCircle draws one anti-aliased circle per particle).  Filled discs of ONE colour and radius r (pixels)
+ * composited over F frames of a float32 RGB image [F, H, W, 3] (values in [0, 1]).  Pixel model:
+ *   - pixel (i, j) (column i, row j) has its centre at (i + 0.5, j + 0.5) in the coordinates of the disc centres;
+ *   - a disc with centre p covers the pixel by  cov = clamp(r + 0.5 - |p - centre|, 0, 1) * min(1, 2 r);
+ *   - per pixel and call  T = prod over the discs of (1 - a cov),  a = alpha / 255 of color_argb (0xAARRGGBB), and
+ *     C <- C T + colour (1 - T)  with colour = (R, G, B) / 255; a pixel no disc covers keeps its bits.
+ * Discs with a centre that is not finite contribute nothing; discs partly or wholly off the canvas are legal.  A radius that
+ * is not finite or <= 0, or alpha 0, draws nothing (no launch).  Since every disc of a call has the same colour, the result
+ * does not depend on the order of the discs beyond rounding; T is formed as exp of the sum of log(1 - a cov) in 2^-32 fixed
+ * point (int64, exactly associative), so two identical calls, and any binning or launch geometry, give identical bits.  No
+ * float atomics.
+ * xy: float32 [F, n, 2] pixel coordinates, frame f's points at xy + 2 f frame_stride; frame_stride = 0: the same n points in
+ * every frame (binned once); otherwise frame_stride >= n.  8-byte aligned.  Limits (DMCF_EINVAL beyond): 1 <= W, H <= 32768,
+ * F <= 65535, n < 2^31.  Two phases, because the size of the tile bins depends on the data:
+ *   dmcf_raster_count  bins the discs into 16 x 16-pixel tiles (per source frame) and writes the number of (disc, tile)
+ *                      entries to *total (one device int64);
+ *   the caller reads *total and allocates bins of 2 * total floats (bin_capacity = total);
+ *   dmcf_raster_discs  fills the bins and draws, with the same xy / n / F / frame_stride / radius / W / H and the workspace
+ *                      the count left behind.  Entries past bin_capacity are dropped (never written out of bounds).
+ * Workspace: dmcf_raster_workspace_bytes(n, F, frame_stride, W, H).
+ * ---------------------------------------------------------------------------------------------- */
+size_t dmcf_raster_workspace_bytes(int64_t n_points, int64_t n_frames, int64_t frame_stride, int32_t width, int32_t height);
+int dmcf_raster_count(const float* xy, int64_t n_points, int64_t n_frames, int64_t frame_stride, float radius, int32_t width,
+                      int32_t height, void* workspace, size_t workspace_bytes, int64_t* total, dmcf_stream_t stream);
+int dmcf_raster_discs(const float* xy, int64_t n_points, int64_t n_frames, int64_t frame_stride, float radius, uint32_t color_argb,
+                      int32_t width, int32_t height, float* image, void* workspace, size_t workspace_bytes, float* bins,
+                      int64_t bin_capacity, dmcf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
