@@ -818,11 +818,12 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         """(filter tensor, fused ASCC?) of a call: the circular expansion (convolutions.py:395-409) or the stored kernel."""
         kernel, symmetric = self.kernel, self.symmetric
         if self.circular:
-            kernel = self._expanded_kernel()
-            symmetric = False  # the mask already made it antisymmetric; second pass still applies below
+            # (refused before the expansion, whose mask broadcasts only when filters == 3)
             if self.symmetric:
                 raise NotImplementedError("circular + symmetric kernels (filters must be 3 in the reference; "
                                           "no shipped config uses circular: True)")
+            kernel = self._expanded_kernel()
+            symmetric = False  # the mask already made it antisymmetric; second pass still applies below
         if symmetric and self.normalize:
             raise NotImplementedError("symmetric=True with normalize=True (DMCF always uses normalize=False, "
                                       "models/pbf_model.py:203)")

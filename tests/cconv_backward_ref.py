@@ -9,6 +9,12 @@ import torch
 
 import oracle
 
+# dmcf_amd/csrc/cconv_bwd.hip: the filter gradient's plan
+BWD_CHUNK_FLOATS = 1 << 28  # kBwdChunkFloats: B chunk [R, K * Cin] of at most 2^28 floats
+BWD_MAX_SLABS = 256         # kBwdMaxSlabs
+BWD_SLAB_ROWS = 256         # kBwdSlabRows: at least this many rows per slab
+BWD_LDS_FLOATS = 16384      # kBwdLdsFloats: K * max(Cin, Cout) limit
+
 INTERP = ("linear", "linear_border", "nearest_neighbor")
 
 
@@ -161,3 +167,140 @@ def grads(pw, filters, feats, grad_out, abs_mode=False, **kw):
         out = conv(pw, Wt, Ft if not abs_mode else Ft, abs_mode=abs_mode, **kw)
         (out * G).sum().backward()
     return Wt.grad.numpy(), Ft.grad.numpy(), out.detach().numpy()
+
+
+def grads_blocked(pw, filters, feats, grad_out, abs_mode=False, normalize=False, symmetric=False, sym_axis=2,
+                  block_floats=1 << 24):
+    """grads() without the dense [n_out * K, Cin] matrix: the same (d filters, d feats) in float64, and with ``abs_mode`` the
+    same sums of absolute terms.  Pairs are taken in blocks of ``block_floats / max(Cin, Cout)``; within a block, per corner t,
+    the pairs are grouped by their filter cell and each cell takes two float64 matmuls:
+        dW_cell += F'^T (x G_i),   dF'  = (x G_i) W_cell^T   (x = w_t a_p / psi_i; F' = f_j, or f_j + f_i for ASCC)
+    Peak memory is a few blocks of doubles (about 1 GB at the default); the full-kernel gradient is folded onto the stored half
+    by the autograd of mirror()."""
+    Wt = torch.as_tensor(np.asarray(filters), dtype=torch.float64)
+    Ft = torch.as_tensor(np.asarray(feats), dtype=torch.float64)
+    G = torch.as_tensor(np.asarray(grad_out), dtype=torch.float64)
+    if abs_mode:
+        Wt, Ft, G = Wt.abs(), Ft.abs(), G.abs()
+    Wfull = mirror(Wt, sym_axis, abs_mode) if symmetric else Wt
+    K, cin, cout = pw.K, Wfull.shape[3], Wfull.shape[4]
+    Wk = Wfull.reshape(K, cin, cout)
+    coef = pw.a
+    if normalize:
+        psi = np.zeros(pw.n_out)
+        np.add.at(psi, pw.i, pw.norm_term)
+        psi = np.where(psi != 0, psi, 1.0)
+        coef = coef / psi[pw.i]
+    dWk = torch.zeros(K, cin, cout, dtype=torch.float64)
+    dF = torch.zeros_like(Ft)
+    n = pw.i.shape[0]
+    step = max(1024, block_floats // max(cin, cout))
+    for b0 in range(0, n, step):
+        b1 = min(n, b0 + step)
+        i = torch.from_numpy(pw.i[b0:b1])
+        j = torch.from_numpy(pw.j[b0:b1])
+        fp = Ft[j] + Ft[i] if symmetric else Ft[j]
+        Gi = G[i]
+        for t in range(8):
+            x = pw.wts[b0:b1, t] * coef[b0:b1]
+            if abs_mode:
+                x = np.abs(x)
+            live = np.nonzero(x)[0]
+            if live.size == 0:
+                continue
+            cells = pw.cells[b0:b1, t][live]
+            order = live[np.argsort(cells, kind="stable")]
+            cs = pw.cells[b0:b1, t][order]
+            starts = np.flatnonzero(np.r_[True, cs[1:] != cs[:-1]])
+            ends = np.r_[starts[1:], cs.size]
+            o = torch.from_numpy(order)
+            Y = torch.from_numpy(x[order])[:, None] * Gi[o]
+            Fo = fp[o]
+            dFo = torch.empty(order.size, cin, dtype=torch.float64)
+            for s, e in zip(starts.tolist(), ends.tolist()):
+                c = int(cs[s])
+                dWk[c] += Fo[s:e].T @ Y[s:e]
+                dFo[s:e] = Y[s:e] @ Wk[c].T
+            dF.index_add_(0, j[o], dFo)
+            if symmetric:
+                dF.index_add_(0, i[o], dFo)
+    dW = dWk.reshape(Wfull.shape)
+    if symmetric:
+        half = Wt.clone().requires_grad_(True)
+        with torch.enable_grad():
+            mirror(half, sym_axis, abs_mode).backward(dW)
+        dW = half.grad
+    return dW.numpy(), dF.numpy()
+
+
+def bwd_plan(n_out, K, cin, cout):
+    """The filter gradient's geometry, as bwd_plan / dmcf_cconv_backward (cconv_bwd.hip) form it: chunk rows R, slab count S and
+    rows per slab of a full chunk, and per chunk (row0, rows, rows per slab, slabs)."""
+    M = K * cin
+    R = min(max(n_out, 1), BWD_CHUNK_FLOATS // M)
+    S = min(-(-R // BWD_SLAB_ROWS), BWD_MAX_SLABS)
+    chunks = []
+    for row0 in range(0, n_out, R):
+        rows = min(R, n_out - row0)
+        rps = -(-rows // S)
+        chunks.append((row0, rows, rps, -(-rows // rps)))
+    return dict(M=M, R=R, S=S, rows_per_slab=-(-R // S), chunks=chunks)
+
+
+def bwd_supported(K, cin, cout):
+    return K * cin <= BWD_LDS_FLOATS and K * cout <= BWD_LDS_FLOATS
+
+
+def bwd_workspace_bytes(n_out, K, cin, cout, symmetric=False, want_features=True, want_filters=True):
+    """dmcf_cconv_backward_workspace_bytes: aligned blocks psi [n_out], the expanded ASCC filter, B chunk [R, M], slabs [S, M,
+    Cout] and the full-kernel gradient [M, Cout] (floats), + 256."""
+    pl = bwd_plan(n_out, K, cin, cout)
+    full = pl["M"] * cout
+    blocks = [max(n_out, 1), full if symmetric and want_features else 0, pl["R"] * pl["M"] if want_filters else 0,
+              pl["S"] * full if want_filters else 0, full if want_filters else 0]
+    return sum(-(-4 * b // 256) * 256 for b in blocks) + 256
+
+
+def float64_cconv(real):
+    """ops.cconv_forward while autograd records, restated in float64 on the CPU (differentiable in filters and features); other
+    calls go to ``real``.  ``monkeypatch.setattr(ops, "cconv_forward", float64_cconv(ops.cconv_forward))``."""
+    def shim(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
+             neighbors_value=None, window=None, window_fac=1.0, inp_importance=None, align_corners=True,
+             coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", normalize=False, symmetric=False,
+             sym_axis=2, bias=None, out=None, accumulate=False, neighbors_row_count=None, skip_self=False, name_only=False,
+             **kw):
+        if name_only or not torch.is_grad_enabled() or not (filters.requires_grad or inp_features.requires_grad):
+            return real(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
+                        neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
+                        align_corners=align_corners, coordinate_mapping=coordinate_mapping, interpolation=interpolation,
+                        normalize=normalize, symmetric=symmetric, sym_axis=sym_axis, bias=bias, out=out, accumulate=accumulate,
+                        neighbors_row_count=neighbors_row_count, skip_self=skip_self, name_only=name_only, **kw)
+        dims = list(filters.shape[:3])
+        if symmetric:
+            dims[sym_axis] *= 2
+        cpu = lambda t: None if t is None else t.detach().cpu().numpy()  # noqa: E731
+        pw = PairWeights(cpu(out_positions), cpu(inp_positions), cpu(neighbors_index), cpu(neighbors_row_splits), extent, dims,
+                         window=window, window_fac=window_fac, nval=cpu(neighbors_value), inp_importance=cpu(inp_importance),
+                         align_corners=align_corners, mapping=coordinate_mapping, interpolation=interpolation,
+                         skip_self=skip_self, row_count=cpu(neighbors_row_count))
+        res = conv(pw, filters.double().cpu(), inp_features.double().cpu(), normalize=normalize, symmetric=symmetric,
+                   sym_axis=sym_axis)
+        res = res.to(filters.device).float()
+        return res if bias is None else res + bias
+    return shim
+
+
+EPS = 2.0 ** -24
+WORST = {}  # worst err / bar per group of the GPU backward tests (printed by their test_report_worst_ratio)
+
+
+def check(name, got, want, bound, kbar):
+    """|got - want| <= kbar * 2^-24 * bound element-wise; records the worst err / bar under ``name``."""
+    got = np.asarray(got, dtype=np.float64)
+    # (an element whose every term is zero must come out zero; a floor of 1e-6 of the largest A covers terms that are an
+    # exact zero on one side and a rounding residue on the other, e.g. a clamped interpolation weight)
+    bar = kbar * EPS * np.maximum(bound, 1e-6 * max(float(np.max(bound)) if bound.size else 0.0, 1e-30))
+    err = np.abs(got - want)
+    ratio = float(np.max(err / bar)) if err.size else 0.0
+    WORST[name] = max(WORST.get(name, 0.0), ratio)
+    assert np.all(err <= bar), f"{name}: worst err/bar {ratio:.3g}"

@@ -151,3 +151,57 @@ def test_ops_surface_errors_before_launch():
         ops.cconv_forward(W, P, 0.2, P, F, idx, rs, out=torch.zeros(10, 5))
     with pytest.raises(NotImplementedError):
         ops.cconv_forward(W, P, torch.full((10,), 0.2), P, F, idx, rs)
+
+
+PLAN_SHAPES = [
+    # (n_out, full dims, Cin, Cout, symmetric)
+    (600, (4, 4, 4), 5, 7, False),         # one chunk
+    (38836, (6, 6, 6), 32, 16, True),      # exactly R = 2^28 / 6912 rows
+    (38837, (6, 6, 6), 32, 16, True),      # R + 1: a second chunk of one row
+    (45000, (6, 6, 6), 32, 16, True),      # the shipped ASCC layer, two chunks
+    (40000, (4, 4, 4), 256, 4, False),     # three chunks of R = 16384
+    (70000, (4, 4, 4), 3, 5, False),       # the slab cap: S = 256, 274 rows per slab
+    (1, (1, 8, 1), 1, 1, False),
+]
+
+
+@pytest.mark.parametrize("n_out,dims,cin,cout,sym", PLAN_SHAPES)
+def test_plan_geometry_matches_workspace(hip_lib, n_out, dims, cin, cout, sym):
+    """cconv_backward_ref.bwd_plan / bwd_workspace_bytes (what the GPU tests rely on to know the path a case takes) against
+    dmcf_cconv_backward_workspace_bytes, for each combination of the wanted gradients."""
+    import cconv_backward_ref as ref
+    K = dims[0] * dims[1] * dims[2]
+    stored = list(dims)
+    if sym:
+        stored[2] //= 2
+    pl = ref.bwd_plan(n_out, K, cin, cout)
+    for want_f in (True, False):
+        for want_w in (True, False):
+            a = _fwd(n_out=n_out, n_inp=n_out, flags=4 if sym else 0, dims=(*stored, cin, cout))
+            b = _bwd(n_inp=n_out, grad_filters=FAKE if want_w else None, grad_inp_features=FAKE if want_f else None)
+            got = hip_lib.dmcf_cconv_backward_workspace_bytes(ctypes.byref(a), ctypes.byref(b))
+            assert got == ref.bwd_workspace_bytes(n_out, K, cin, cout, sym, want_f, want_w), (want_f, want_w)
+    R = ref.BWD_CHUNK_FLOATS // (K * cin)
+    assert pl["R"] == min(n_out, R)
+    if n_out == R:
+        assert len(pl["chunks"]) == 1
+    if n_out == R + 1:
+        assert len(pl["chunks"]) == 2 and pl["chunks"][-1][1] == 1
+    if n_out == 70000:
+        assert pl["S"] == ref.BWD_MAX_SLABS and pl["rows_per_slab"] == 274 and len(pl["chunks"]) == 1
+
+
+@pytest.mark.parametrize("dims,cin,cout,ok", [
+    ((4, 4, 4), 256, 3, True), ((4, 4, 4), 3, 256, True), ((4, 4, 4), 257, 3, False), ((4, 4, 4), 3, 257, False),
+    ((1, 8, 8), 256, 256, True), ((1, 8, 8), 257, 1, False), ((6, 6, 3), 75, 75, True), ((6, 6, 3), 76, 1, False),
+])
+def test_lds_limit(hip_lib, dims, cin, cout, ok):
+    """K * Cin and K * Cout up to 16384 are accepted; one channel more returns DMCF_EUNSUPPORTED (ASCC: K of the full kernel)."""
+    import cconv_backward_ref as ref
+    sym = dims == (6, 6, 3)
+    K = dims[0] * dims[1] * dims[2] * (2 if sym else 1)
+    assert ref.bwd_supported(K, cin, cout) == ok
+    a = _fwd(flags=4 if sym else 0, dims=(*dims, cin, cout))
+    rc = hip_lib.dmcf_cconv_backward(ctypes.byref(a), ctypes.byref(_bwd()), None, 0, None)
+    assert rc == (EINVAL if ok else EUNSUPPORTED)  # (valid arguments stop at the NULL workspace)
+    assert (hip_lib.dmcf_cconv_backward_workspace_bytes(ctypes.byref(a), ctypes.byref(_bwd())) > 256) == ok

@@ -14,8 +14,8 @@ import cconv_backward_ref as ref  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 K_BAR = 256
-EPS = 2.0 ** -24
-WORST = {}
+EPS = ref.EPS
+WORST = ref.WORST  # (shared with tests/test_gpu_cconv_backward_sets.py, whose report prints every group)
 
 
 def _dev():
@@ -31,14 +31,7 @@ def _scene(n, seed, dims=3, scale=1.0):
 
 
 def _check(name, got, want, bound):
-    got = np.asarray(got, dtype=np.float64)
-    # (an element whose every term is zero must come out zero; a floor of 1e-6 of the largest A covers terms that are an
-    # exact zero on one side and a rounding residue on the other, e.g. a clamped interpolation weight)
-    bar = K_BAR * EPS * np.maximum(bound, 1e-6 * max(float(np.max(bound)) if bound.size else 0.0, 1e-30))
-    err = np.abs(got - want)
-    ratio = float(np.max(err / bar)) if err.size else 0.0
-    WORST[name] = max(WORST.get(name, 0.0), ratio)
-    assert np.all(err <= bar), f"{name}: worst err/bar {ratio:.3g}"
+    ref.check(name, got, want, bound, K_BAR)
 
 
 def _run(pos, feat, filt, radius, *, window="poly6", use_dist=False, normalize=False, symmetric=False, sym_axis=2,

@@ -15,34 +15,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _float64_cconv(real):
-    """ops.cconv_forward while autograd records, restated in float64 on the CPU (differentiable in filters and features)."""
-    def shim(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
-             neighbors_value=None, window=None, window_fac=1.0, inp_importance=None, align_corners=True,
-             coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", normalize=False, symmetric=False,
-             sym_axis=2, bias=None, out=None, accumulate=False, neighbors_row_count=None, skip_self=False, name_only=False,
-             **kw):
-        if name_only or not torch.is_grad_enabled() or not (filters.requires_grad or inp_features.requires_grad):
-            return real(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
-                        neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
-                        align_corners=align_corners, coordinate_mapping=coordinate_mapping, interpolation=interpolation,
-                        normalize=normalize, symmetric=symmetric, sym_axis=sym_axis, bias=bias, out=out, accumulate=accumulate,
-                        neighbors_row_count=neighbors_row_count, skip_self=skip_self, name_only=name_only, **kw)
-        dims = list(filters.shape[:3])
-        if symmetric:
-            dims[sym_axis] *= 2
-        cpu = lambda t: None if t is None else t.detach().cpu().numpy()  # noqa: E731
-        pw = ref.PairWeights(cpu(out_positions), cpu(inp_positions), cpu(neighbors_index), cpu(neighbors_row_splits), extent, dims,
-                             window=window, window_fac=window_fac, nval=cpu(neighbors_value), inp_importance=cpu(inp_importance),
-                             align_corners=align_corners, mapping=coordinate_mapping, interpolation=interpolation,
-                             skip_self=skip_self, row_count=cpu(neighbors_row_count))
-        res = ref.conv(pw, filters.double().cpu(), inp_features.double().cpu(), normalize=normalize, symmetric=symmetric,
-                       sym_axis=sym_axis)
-        res = res.to(filters.device).float()
-        return res if bias is None else res + bias
-    return shim
-
-
 def _model(name, weights=None, seed=0):
     from dmcf_amd import models
     from dmcf_amd.utils import tf_checkpoint as tc
@@ -94,7 +66,7 @@ def test_gradients_against_float64_restatement(name, weights, monkeypatch):
     loss.backward()
     got = {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}
     assert got, "no gradients"
-    monkeypatch.setattr(ops, "cconv_forward", _float64_cconv(ops.cconv_forward))
+    monkeypatch.setattr(ops, "cconv_forward", ref.float64_cconv(ops.cconv_forward))
     model.zero_grad()
     loss_ref, _, _ = _loss(model, data)
     loss_ref.backward()
