@@ -4,6 +4,8 @@
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE JSON line on rank 0.
 A "step" is one pass of the hot path (Simulator.run_inference: neighbour searches + 18 CConv/ASCC layers
 of the Liquid3d SymNet with the reference's trained weights + integration) over one scene held in HBM.
+Such a plain run only sets up, warms up, times the K steps, writes --dump-outputs and prints the line; what needs runs of
+its own (the CPU baseline; with --config, the counted and the instrumented steps after the window) is measured with --full.
 
 Workload (BASELINE.json: metric quoted on "1M particles"; config 5 "synthetic 3-D box"): per GPU a cube of
 ``side``^3 = 1,000,000 fluid particles, spacing h = 0.05, jitter U(-0.1h, 0.1h) seed 0, velocities N(0, 0.1^2)
@@ -24,8 +26,9 @@ Extra objects on the JSON line:
   roofline_groups   the same fraction for (a) all neighbour-list kernels together, (b) the lattice-form launches --
                     charged the bytes THEY move (input volume + per-offset matrices + table + outputs), not the pair
                     bytes of a list they never read --, and per kernel instantiation
-  cpu_baseline      the CPU oracle (numpy + C restatement, OpenMP on all host cores) timed on ONE step of the bench's own
-                    scene ("same inputs"; ~1 minute at 1M particles; --cpu-side bounds it), rank 0, N = 1
+  cpu_baseline      with --full: the CPU oracle (numpy + C restatement, OpenMP on all host cores) timed on ONE step of the
+                    bench's own scene ("same inputs"; ~1 minute at 1M particles; --cpu-side bounds it),
+                    rank 0, N = 1
   outputs_dumped    with ``--dump-outputs DIR`` (one GPU): what the last timed step returned to its caller -- the particles'
                     new positions and velocities -- written after the timed steps as DIR/pos.npy and DIR/vel.npy (float32).
                     The inputs are seeded, so two builds run with the same arguments can be compared output for output.
@@ -155,12 +158,16 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)  # the caching allocator reaches its steady state after ~3 steps
     ap.add_argument("--side", type=int, default=100, help="fluid cube edge in particles per GPU (100 -> 1M particles)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline and, with --config, the dispatches, "
+                         "synchronising reads and per-kernel table of extra steps after the timed window")
     ap.add_argument("--cpu-side", type=int, default=None,
-                    help="edge of the CPU-baseline box (default: --side, i.e. ONE step of the CPU oracle on the bench's own scene -- "
-                         "about a minute of the host's cores at 1M particles; smaller = a bounded sample from the same generator; 0 = skip)")
+                    help="with --full: edge of the CPU-baseline box (default: --side, i.e. ONE step of the CPU oracle on the bench's own "
+                         "scene -- about a minute of the host's cores at 1M particles; smaller = a bounded sample from the same "
+                         "generator; 0 = skip)")
     ap.add_argument("--config", default="box", choices=["box", "waterramps", "wbcsph", "liquid3d_dam"],
                     help="box (default) = BASELINE.json config 5, the headline; the others = configs 2 / 3 / 4 on one GPU "
-                         "(tools/long_rollout.py's scenes): the same JSON line with dispatches and synchronising reads per step")
+                         "(tools/long_rollout.py's scenes): the same JSON line, with --full also dispatches and synchronising reads per step")
     ap.add_argument("--scene", default="column", choices=["column", "settled"],
                     help="--config box only.  column (default, the headline): config 5 as specified -- a 5 m column under g, far outside "
                          "the network's training range, which dissolves inside the window.  settled: the same box, particles and "
@@ -169,7 +176,8 @@ def parse_args(argv=None):
                          "particles at rest, gravity scaled to 0 ... 1 %, velocities damped to zero after every step, thicker and "
                          "denser shells: the network alone pushes tens of thousands of particles of this jittered lattice through "
                          "a synthetic wall within 25 steps, DESIGN.md section 5)")
-    ap.add_argument("--layers-json", default=None, help="write the per-launch table here")
+    ap.add_argument("--layers-json", default=None,
+                    help="write the per-launch table here (--config: that of the instrumented steps, so with --full only)")
     ap.add_argument("--reserve-gib", type=float, default=None,
                     help="Simulator(reserve_gib=...) in GiB (default: the product's opt-in 'auto' rule, 40 KiB per particle handed "
                          "to the caching allocator before the first step; 0 = none)")
@@ -190,6 +198,10 @@ def parse_args(argv=None):
         ap.error("--warmup must not be negative")
     if args.dump_outputs is not None and args.gpus != 1:
         ap.error("--dump-outputs is a single-GPU option")
+    if args.cpu_side and not args.full:
+        ap.error("--cpu-side sizes the CPU baseline, which only --full measures")
+    if args.layers_json and args.config != "box" and not args.full:
+        ap.error("--config: --layers-json writes the table of the instrumented steps, which only --full runs")
     return args
 
 
@@ -284,10 +296,10 @@ SMALL_CONFIGS = {
 
 def small_config_main(args):
     """``--config waterramps | wbcsph | liquid3d_dam``: BASELINE.json configs 2 / 3 / 4 on one GPU, the same JSON line.  These
-    steps are paced by dispatch count and host reads, not by any kernel, so the line also carries the GPU kernel dispatches and
-    the synchronising device -> host reads of ONE step (counted on an extra step after the timed window).  The timed window
-    runs as Simulator.run_rollout runs its loop (inside steady_steps) WITHOUT the per-launch events; the per-kernel table comes
-    from a second, untimed pass of the same length."""
+    steps are paced by dispatch count and host reads, not by any kernel, so with --full the line also carries the GPU kernel
+    dispatches and the synchronising device -> host reads of ONE step (counted on an extra step after the timed window).  The
+    timed window runs as Simulator.run_rollout runs its loop (inside steady_steps) WITHOUT the per-launch events; with --full the
+    per-kernel table comes from a second, untimed pass of the same length."""
     import warnings
 
     import torch
@@ -329,72 +341,76 @@ def small_config_main(args):
         allocs = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0
         assert torch.isfinite(state[0]).all()
         dumped = dump_outputs(args.dump_outputs, dict(pos=state[0], vel=state[1])) if args.dump_outputs else None
-        # ---- untimed: one step's synchronising reads and kernel dispatches
-        torch.cuda.set_sync_debug_mode("warn")
-        with warnings.catch_warnings(record=True) as ws:
-            warnings.simplefilter("always")
-            state = sim.step([state])[0]
-        torch.cuda.set_sync_debug_mode("default")
-        sync_sites = {}
-        for wv in ws:
-            k = f"{os.path.basename(wv.filename)}:{wv.lineno}"
-            sync_sites[k] = sync_sites.get(k, 0) + 1
-        dispatches = None
-        try:
-            from torch.profiler import ProfilerActivity, profile
-            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        if args.full:
+            # ---- untimed: one step's synchronising reads and kernel dispatches
+            torch.cuda.set_sync_debug_mode("warn")
+            with warnings.catch_warnings(record=True) as ws:
+                warnings.simplefilter("always")
+                state = sim.step([state])[0]
+            torch.cuda.set_sync_debug_mode("default")
+            sync_sites = {}
+            for wv in ws:
+                k = f"{os.path.basename(wv.filename)}:{wv.lineno}"
+                sync_sites[k] = sync_sites.get(k, 0) + 1
+            dispatches = None
+            try:
+                from torch.profiler import ProfilerActivity, profile
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    state = sim.step([state])[0]
+                    torch.cuda.synchronize(dev)
+                kinds = {}
+                for e in prof.events():
+                    if getattr(e, "device_type", None) is not None and "cuda" in str(e.device_type).lower():
+                        kinds[e.name] = kinds.get(e.name, 0) + 1
+                memops = sum(v for k, v in kinds.items() if k.lower().startswith(("memcpy", "memset")))
+                dispatches = dict(kernels=sum(kinds.values()) - memops, memcpy_memset=memops)
+            except Exception as e:  # (the count is a diagnostic: never fail the line for it)
+                dispatches = dict(error=f"{type(e).__name__}: {e}")
+            # ---- untimed: the same number of steps with HIP events around every library launch -> per-kernel table, per-step times
+            ops.timer = ops.LaunchTimer()
+            marks, step_ms = [], []
+            for _ in range(args.steps):
+                marks.append(len(ops.timer.records))
+                torch.cuda.synchronize(dev)
+                t1 = time.perf_counter()
                 state = sim.step([state])[0]
                 torch.cuda.synchronize(dev)
-            kinds = {}
-            for e in prof.events():
-                if getattr(e, "device_type", None) is not None and "cuda" in str(e.device_type).lower():
-                    kinds[e.name] = kinds.get(e.name, 0) + 1
-            memops = sum(v for k, v in kinds.items() if k.lower().startswith(("memcpy", "memset")))
-            dispatches = dict(kernels=sum(kinds.values()) - memops, memcpy_memset=memops)
-        except Exception as e:  # (the count is a diagnostic: never fail the line for it)
-            dispatches = dict(error=f"{type(e).__name__}: {e}")
-        # ---- untimed: the same number of steps with HIP events around every library launch -> per-kernel table, per-step times
-        ops.timer = ops.LaunchTimer()
-        marks, step_ms = [], []
-        for _ in range(args.steps):
-            marks.append(len(ops.timer.records))
-            torch.cuda.synchronize(dev)
-            t1 = time.perf_counter()
-            state = sim.step([state])[0]
-            torch.cuda.synchronize(dev)
-            step_ms.append(1e3 * (time.perf_counter() - t1))
-            steady.tick()
-        timer, ops.timer = ops.timer, None
-    recs = timer.results()
-    table, dominant = summarise(recs, args.steps)
-    dom = table["by_kernel"].get(dominant, dict(achieved=0.0, frac=0.0, launches=0, avg_launch_ms=0.0, algorithmic_bytes_per_launch=0.0))
-    other = {}
-    for k, m, ms in recs:
-        other[k] = other.get(k, 0.0) + ms
+                step_ms.append(1e3 * (time.perf_counter() - t1))
+                steady.tick()
+            timer, ops.timer = ops.timer, None
     line = {
         "metric": "rollout_particle_steps_per_sec", "value": n * args.steps / elapsed, "unit": "particle-steps/s", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": SMALL_CONFIGS[args.config] + f"; {n} fluid + {int(state[4].shape[0])} boundary particles, one rollout step",
                    "parallelism": "single GPU", "particles_per_gpu": n},
-        "roofline": {"bound": "hbm", "kernel": f"dmcf::{dominant}", "achieved": dom["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": dom["frac"], "traffic": None, "launches": dom["launches"], "avg_launch_ms": dom["avg_launch_ms"],
-                     "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"], "frac_flops": dom.get("frac_flops"),
-                     "note": "from the instrumented pass; a step of this size is bound by dispatches and host reads, not by this kernel"},
-        "roofline_groups": table,
-        "kernel_ms_per_step": {k: v / args.steps for k, v in other.items()},
-        "library_launch_ms_per_step": sum(other.values()) / args.steps,
-        "dispatches_per_step": dispatches,
-        "synchronising_reads_per_step": {"count": len(ws), "sites": sync_sites},
-        "step_ms_instrumented": {"median": float(np.median(step_ms)), "first": float(step_ms[0]), "last": float(step_ms[-1]),
-                                 "note": "second pass, one device synchronise per step and events around every library launch"},
-        "scene_state": {"simulated_steps_before_window": args.warmup, "simulated_steps_at_end": args.warmup + args.steps,
-                        "fluid_outside_shell_at_window_start": snap0[0], "fluid_outside_shell_at_end": snap1[0],
-                        "max_speed_at_window_start": snap0[1], "max_speed_at_end": snap1[1],
-                        "repeated_steps_in_window": repeated, "device_allocations_in_window": int(allocs),
-                        "reserved_gib": torch.cuda.memory_stats(dev)["reserved_bytes.all.current"] / 2 ** 30},
     }
-    if args.cpu_side is None or args.cpu_side > 0:
+    if args.full:
+        recs = timer.results()
+        table, dominant = summarise(recs, args.steps)
+        dom = table["by_kernel"].get(dominant, dict(achieved=0.0, frac=0.0, launches=0, avg_launch_ms=0.0, algorithmic_bytes_per_launch=0.0))
+        other = {}
+        for k, m, ms in recs:
+            other[k] = other.get(k, 0.0) + ms
+        line.update({
+            "roofline": {"bound": "hbm", "kernel": f"dmcf::{dominant}", "achieved": dom["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": dom["frac"], "traffic": None, "launches": dom["launches"], "avg_launch_ms": dom["avg_launch_ms"],
+                         "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"], "frac_flops": dom.get("frac_flops"),
+                         "note": "from the instrumented pass; a step of this size is bound by dispatches and host reads, not by this kernel"},
+            "roofline_groups": table,
+            "kernel_ms_per_step": {k: v / args.steps for k, v in other.items()},
+            "library_launch_ms_per_step": sum(other.values()) / args.steps,
+            "dispatches_per_step": dispatches,
+            "synchronising_reads_per_step": {"count": len(ws), "sites": sync_sites},
+            "step_ms_instrumented": {"median": float(np.median(step_ms)), "first": float(step_ms[0]), "last": float(step_ms[-1]),
+                                     "note": "second pass, one device synchronise per step and events around every library launch"},
+        })
+    line["scene_state"] = {"simulated_steps_before_window": args.warmup, "simulated_steps_at_end": args.warmup + args.steps,
+                           "fluid_outside_shell_at_window_start": snap0[0], "fluid_outside_shell_at_end": snap1[0],
+                           "max_speed_at_window_start": snap0[1], "max_speed_at_end": snap1[1],
+                           "repeated_steps_in_window": repeated, "device_allocations_in_window": int(allocs),
+                           "reserved_gib": torch.cuda.memory_stats(dev)["reserved_bytes.all.current"] / 2 ** 30}
+    if args.full and (args.cpu_side is None or args.cpu_side > 0):
         # the CPU oracle on the same scene from its initial state: whole steps until ~10 s are spent (at most 40)
         import oracle  # noqa: F401
         from oracle.model_ref import ModelRef
@@ -673,7 +689,7 @@ def main():
         }
         line.update(extra)
         cpu_side = args.side if args.cpu_side is None else args.cpu_side
-        if world == 1 and cpu_side > 0:
+        if args.full and world == 1 and cpu_side > 0:
             line["cpu_baseline"] = cpu_baseline(cpu_side, weights, cfg, same=cpu_side == args.side)
         if args.layers_json:
             json.dump([dict(kind=k, ms=ms, **m) for k, m, ms in recs], open(args.layers_json, "w"))

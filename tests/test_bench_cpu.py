@@ -14,6 +14,18 @@ def test_steps_and_dump_arguments():
             bench.parse_args(bad)
 
 
+def test_full_argument():
+    """--full is off by default; the options that only size or record its extra measurements need it."""
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    assert bench.parse_args(["--full", "--cpu-side", "8"]).cpu_side == 8
+    assert bench.parse_args(["--cpu-side", "0"]).cpu_side == 0
+    assert bench.parse_args(["--layers-json", "l.json"]).layers_json == "l.json"
+    assert bench.parse_args(["--full", "--config", "wbcsph", "--layers-json", "l.json"]).full
+    for bad in (["--cpu-side", "8"], ["--config", "wbcsph", "--layers-json", "l.json"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 def test_dump_outputs_whole_and_sampled(tmp_path):
     rng = np.random.default_rng(5)
     pos, vel = rng.normal(size=(1000, 3)), rng.normal(size=(1000, 3)).astype(np.float32)

@@ -638,20 +638,23 @@ def test_fps_multiscale_2d(dev):
     assert [len(i) for i in ref.fps_idx[1:]] == [len(model.all_pos) // 2, len(model.all_pos) // 4]
 
 
-def test_bench_line_contract(tmp_path):
-    """bench.py prints ONE JSON line with the fields the driver reads (small workload so the test stays quick) and, with
-    --dump-outputs, writes the positions and velocities of its last timed step."""
+def _bench_line(*args):
     import json
     import subprocess
     import sys
-    from tools import scenes
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--side", "24", "--steps", "2", "--warmup", "1",
-                          "--cpu-side", "8", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600,
-                         cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--side", "24", "--steps", "2", "--warmup", "1", *args],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_line_contract(tmp_path):
+    """bench.py --full prints ONE JSON line with the fields the driver reads (small workload so the test stays quick) and, with
+    --dump-outputs, writes the positions and velocities of its last timed step."""
+    from tools import scenes
+    d = _bench_line("--full", "--cpu-side", "8", "--dump-outputs", str(tmp_path / "out"))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "roofline_groups", "cpu_baseline"):
         assert k in d, k
@@ -677,6 +680,22 @@ def test_bench_line_contract(tmp_path):
         a = np.load(tmp_path / "out" / f"{name}.npy")
         assert a.dtype == np.float32 and a.shape == (24 ** 3, 3) and np.isfinite(a).all(), name
     assert not np.array_equal(np.load(tmp_path / "out" / "pos.npy"), scenes.box_scene(24)["pos"])  # stepped, not the input
+
+
+def test_bench_plain_line(tmp_path):
+    """A plain bench.py run (no --full) prints the same headline fields without the CPU baseline, and its last timed step
+    computes what the --full run's does."""
+    d = _bench_line("--dump-outputs", str(tmp_path / "plain"))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "roofline"):
+        assert k in d, k
+    assert d["metric"] == "rollout_particle_steps_per_sec" and d["unit"] == "particle-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0
+    assert abs(d["value"] - 24 ** 3 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and d["outputs_dumped"]["rows"] == 24 ** 3
+    _bench_line("--full", "--cpu-side", "0", "--dump-outputs", str(tmp_path / "full"))
+    for name in ("pos", "vel"):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert np.abs(a - b).max() <= 1e-6 * np.abs(b).max(), name
 
 
 def test_full_size_step_against_the_oracle(dev):

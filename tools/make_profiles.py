@@ -19,7 +19,7 @@ def bench_lines(src, tag, P, b, d):
     json.dump(t, open(f"{P}/{tag}_cconv_hbm_traffic.json", "w"), indent=1)
     tb = t["by_kernel"]
     lines = [f"# Bench lines ({tag}, one MI355X, `gpurun`)\n",
-             "`python bench.py --steps 5 --warmup 3` (steps 4-8 of the rollout):\n", "```json", json.dumps(b), "```\n",
+             "`python bench.py --full --steps 5 --warmup 3` (steps 4-8 of the rollout):\n", "```json", json.dumps(b), "```\n",
              "`python bench.py --steps 20 --warmup 5 --cpu-side 0` (the driver's window, steps 6-25: the scene degrades while it runs -- particles "
              "leak through the shell from step ~10 on, rows get longer; `scene_state` in the line says by how much):\n", "```json", json.dumps(d), "```\n",
              "Per kernel (ms per step, fraction of 8 TB/s by the contract's algorithmic bytes, HBM bytes per launch from the PMC passes of "
@@ -272,10 +272,10 @@ def more_bench_lines(src, tag, P):
     path = f"{P}/{tag}_bench_lines.md"
     out = [open(path).read().rstrip(), ""]
     for name, title in (("bench_settled", "`python bench.py --scene settled --steps 20 --warmup 5 --cpu-side 0` (every timed step starts from the state after the warm-up)"),
-                        ("bench_waterramps", "`python bench.py --config waterramps --steps 600 --warmup 20` (BASELINE config 2)"),
-                        ("bench_wbcsph", "`python bench.py --config wbcsph --steps 600 --warmup 20` (BASELINE config 3)"),
-                        ("bench_liquid3d_dam_first20", "`python bench.py --config liquid3d_dam --steps 20 --warmup 1` (BASELINE config 4, steps 2 - 21)"),
-                        ("bench_liquid3d_dam", "`python bench.py --config liquid3d_dam --steps 200 --warmup 20 --cpu-side 0` (BASELINE config 4, steps 21 - 220: the scene dissolves)")):
+                        ("bench_waterramps", "`python bench.py --full --config waterramps --steps 600 --warmup 20` (BASELINE config 2)"),
+                        ("bench_wbcsph", "`python bench.py --full --config wbcsph --steps 600 --warmup 20` (BASELINE config 3)"),
+                        ("bench_liquid3d_dam_first20", "`python bench.py --full --config liquid3d_dam --steps 20 --warmup 1` (BASELINE config 4, steps 2 - 21)"),
+                        ("bench_liquid3d_dam", "`python bench.py --full --config liquid3d_dam --steps 200 --warmup 20 --cpu-side 0` (BASELINE config 4, steps 21 - 220: the scene dissolves)")):
         f = f"{src}/{name}.log"
         if not os.path.exists(f):
             continue

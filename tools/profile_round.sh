@@ -5,12 +5,12 @@
 set -u
 OUT=${1:-gpurun_out/profile_round}
 mkdir -p $OUT
-python bench.py --steps 5 --warmup 3 --layers-json $OUT/layers.json > $OUT/bench.log 2>&1
+python bench.py --full --steps 5 --warmup 3 --layers-json $OUT/layers.json > $OUT/bench.log 2>&1
 python bench.py --steps 20 --warmup 5 --cpu-side 0 > $OUT/bench_driver.log 2>&1
 python bench.py --scene settled --steps 20 --warmup 5 --cpu-side 0 > $OUT/bench_settled.log 2>&1
-for c in waterramps wbcsph; do python bench.py --config $c --steps 600 --warmup 20 > $OUT/bench_$c.log 2>&1; done
-python bench.py --config liquid3d_dam --steps 20 --warmup 1 > $OUT/bench_liquid3d_dam_first20.log 2>&1
-python bench.py --config liquid3d_dam --steps 200 --warmup 20 --cpu-side 0 > $OUT/bench_liquid3d_dam.log 2>&1
+for c in waterramps wbcsph; do python bench.py --full --config $c --steps 600 --warmup 20 > $OUT/bench_$c.log 2>&1; done
+python bench.py --full --config liquid3d_dam --steps 20 --warmup 1 > $OUT/bench_liquid3d_dam_first20.log 2>&1
+python bench.py --full --config liquid3d_dam --steps 200 --warmup 20 --cpu-side 0 > $OUT/bench_liquid3d_dam.log 2>&1
 timeout 300 python tools/bench_scatter.py > $OUT/bench_scatter.log 2>&1
 bash tools/sct_variants.sh > $OUT/sct_variants.log 2>&1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
