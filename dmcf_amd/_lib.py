@@ -219,6 +219,9 @@ SYMBOLS = [
     "dmcf_neighbor_dense_forward", "dmcf_neighbor_dense_backward_workspace_bytes", "dmcf_neighbor_dense_backward",
     "dmcf_neighbor_dense_kernel_names", "dmcf_adam_step_workspace_bytes", "dmcf_adam_step", "dmcf_adam_step_kernel_names",
     "dmcf_raster_workspace_bytes", "dmcf_raster_count", "dmcf_raster_discs",
+    "dmcf_nn_distance_backward_workspace_bytes", "dmcf_nn_distance_backward", "dmcf_match_cost_backward_workspace_bytes",
+    "dmcf_match_cost_backward", "dmcf_emd_with_levels", "dmcf_emd_backward_workspace_bytes", "dmcf_emd_backward",
+    "dmcf_gather_point_backward_workspace_bytes", "dmcf_gather_point_backward",
 ]
 
 
@@ -379,6 +382,28 @@ def lib():
     L.dmcf_raster_discs.restype = c.c_int
     L.dmcf_raster_discs.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_uint32, c.c_int32, c.c_int32, c.c_void_p,
                                     c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p]
+    # metric gradients (ABI 2.13)
+    for q in ("dmcf_nn_distance_backward_workspace_bytes", "dmcf_match_cost_backward_workspace_bytes",
+              "dmcf_emd_backward_workspace_bytes"):
+        getattr(L, q).restype = c.c_size_t
+        getattr(L, q).argtypes = [c.c_int64, c.c_int64, c.c_int64]
+    L.dmcf_nn_distance_backward.restype = c.c_int
+    L.dmcf_nn_distance_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
+                                            c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_match_cost_backward.restype = c.c_int
+    L.dmcf_match_cost_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
+                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_emd_with_levels.restype = c.c_int
+    L.dmcf_emd_with_levels.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, i32p, i32p, c.c_void_p, c.c_void_p,
+                                       c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_emd_backward.restype = c.c_int
+    L.dmcf_emd_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, i32p, i32p, c.c_void_p, c.c_void_p,
+                                    c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_gather_point_backward_workspace_bytes.restype = c.c_size_t
+    L.dmcf_gather_point_backward_workspace_bytes.argtypes = [c.c_int64, c.c_int64]
+    L.dmcf_gather_point_backward.restype = c.c_int
+    L.dmcf_gather_point_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int64, c.c_void_p, c.c_void_p,
+                                             c.c_size_t, c.c_void_p]
     _lib = L
     return L
 

@@ -21,39 +21,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "metrics_plan.h"
 
 namespace dmcf {
-
-constexpr int kMtThreads = 256;         // rows per workgroup, one per lane
-constexpr int kMtTile = 256;            // points of the other set per LDS tile
-constexpr int64_t kMtTargetBlocks = 2048;  // split the columns until rows x splits reaches this many workgroups
-constexpr int kMtMaxGridYZ = 65535;
-
-struct MtPlan {
-    int64_t row_blocks, nsplit, chunk;
-};
-
-// columns split into nsplit chunks of whole tiles; depends on (rows, cols, batch) only
-inline MtPlan mt_plan(int64_t rows, int64_t cols, int64_t batch = 1) {
-    MtPlan p;
-    p.row_blocks = (rows + kMtThreads - 1) / kMtThreads;
-    const int64_t tiles = cols > 0 ? (cols + kMtTile - 1) / kMtTile : 1;
-    const int64_t want = (kMtTargetBlocks + p.row_blocks * batch - 1) / (p.row_blocks * batch);
-    int64_t ns = want < tiles ? want : tiles;
-    if (ns < 1) ns = 1;
-    const int64_t per = (tiles + ns - 1) / ns;
-    p.nsplit = (tiles + per - 1) / per;
-    p.chunk = per * kMtTile;
-    return p;
-}
-
-// upper bound of nsplit * rows over every rows <= rows_max, cols <= cols_max (batch 1): the workspace of the passes
-inline int64_t mt_partial_bound(int64_t rows_max, int64_t cols_max) {
-    const int64_t tiles = cols_max > 0 ? (cols_max + kMtTile - 1) / kMtTile : 1;
-    const int64_t a = tiles * rows_max;
-    const int64_t b = kMtTargetBlocks * kMtThreads + rows_max + kMtThreads;
-    return a < b ? a : b;
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // nearest neighbour: per (batch, row) the smallest squared distance into the chunk and its lowest index
@@ -280,23 +250,31 @@ bool valid_counts(const int32_t* counts, int64_t b, int64_t limit) {
     return true;
 }
 
-// one batch item of the approximate match: match (dense, already zeroed) or costL (fused) and the final total into *cost
+// one batch item of the approximate match: match (dense, already zeroed) or costL (fused) and the final total into *cost;
+// levels (NULL: not wanted): per level L the copies of ratioL (after pass A) at levels[L * lvl_ld] and of ratioR (after pass B)
+// at levels[L * lvl_ld + lvl_r] (dmcf_emd_with_levels, the saved state of dmcf_emd_backward)
 int approx_match_item(const float* xyz1, const float* xyz2, int64_t ni, int64_t mi, float* match, int64_t ld, float* cost,
-                      const AmWork& w, hipStream_t st) {
+                      const AmWork& w, hipStream_t st, float* levels = nullptr, int64_t lvl_ld = 0, int64_t lvl_r = 0) {
     const float multiL = ni >= mi ? 1.0f : (float)(mi / ni);
     const float multiR = ni >= mi ? (float)(ni / mi) : 1.0f;
     const int64_t nm = ni > mi ? ni : mi;
     am_init_kernel<<<grid1(nm), kMtThreads, 0, st>>>(w.remainL, w.costL, ni, multiL, w.remainR, mi, multiR);
     const MtPlan pa = mt_plan(ni, mi), pb = mt_plan(mi, ni);
     const dim3 ga((unsigned)pa.row_blocks, (unsigned)pa.nsplit, 1), gb((unsigned)pb.row_blocks, (unsigned)pb.nsplit, 1);
-    for (int j = 7; j >= -2; --j) {
-        const float level = j == -2 ? 0.0f : -powf(4.0f, (float)j);
+    for (int L = 0; L < kAmLevels; ++L) {  // (the schedule of metrics_plan.h, shared with dmcf_emd_backward)
+        const float level = am_level(L);
         am_pass_kernel<kMtSumWeighted><<<ga, kMtThreads, 0, st>>>(xyz1, ni, 0, xyz2, mi, 0, pa.chunk, level, w.remainR, nullptr,
                                                                   nullptr, 0, 0, w.part, nullptr);
         am_finish_a_kernel<<<grid1(ni), kMtThreads, 0, st>>>(w.part, ni, pa.nsplit, w.remainL, w.ratioL);
+        float* lv = levels != nullptr ? levels + L * lvl_ld : nullptr;
+        if (lv != nullptr && hipMemcpyAsync(lv, w.ratioL, (size_t)ni * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return check_launch();
         am_pass_kernel<kMtSumWeighted><<<gb, kMtThreads, 0, st>>>(xyz2, mi, 0, xyz1, ni, 0, pb.chunk, level, w.ratioL, nullptr,
                                                                   nullptr, 0, 0, w.part, nullptr);
         am_finish_b_kernel<<<grid1(mi), kMtThreads, 0, st>>>(w.part, mi, pb.nsplit, w.remainR, w.ratioR);
+        if (lv != nullptr &&
+            hipMemcpyAsync(lv + lvl_r, w.ratioR, (size_t)mi * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return check_launch();
         if (match != nullptr)
             am_pass_kernel<kMtMatch><<<ga, kMtThreads, 0, st>>>(xyz1, ni, 0, xyz2, mi, 0, pa.chunk, level, w.ratioR, w.ratioL,
                                                                 match, ld, 0, w.part, nullptr);
@@ -312,7 +290,7 @@ int approx_match_item(const float* xyz1, const float* xyz2, int64_t ni, int64_t 
 
 int approx_match_common(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,
                         const int32_t* count2, float* match, float* cost, void* workspace, size_t workspace_bytes,
-                        dmcf_stream_t stream) {
+                        dmcf_stream_t stream, float* levels = nullptr) {
     if (b < 0 || n < 0 || m < 0 || n >= INT32_MAX || m >= INT32_MAX) return DMCF_EINVAL;
     if (!valid_counts(count1, b, n) || !valid_counts(count2, b, m)) return DMCF_EINVAL;
     if (b == 0) return DMCF_OK;
@@ -324,6 +302,9 @@ int approx_match_common(const float* xyz1, const float* xyz2, int64_t b, int64_t
     if (match != nullptr && n > 0 && m > 0) {
         if (hipMemsetAsync(match, 0, (size_t)b * n * m * sizeof(float), st) != hipSuccess) return check_launch();
     }
+    const int64_t lvl_ld = n + m;  // levels [b, kAmLevels, n + m]: ratioL in [0, n_i), ratioR in [n, n + m_i), zeros elsewhere
+    if (levels != nullptr && hipMemsetAsync(levels, 0, (size_t)b * kAmLevels * lvl_ld * sizeof(float), st) != hipSuccess)
+        return check_launch();
     for (int64_t i = 0; i < b; ++i) {
         const int64_t ni = count1 != nullptr ? count1[i] : n, mi = count2 != nullptr ? count2[i] : m;
         if (ni == 0 || mi == 0) {  // nothing to match: zero match rows (already), zero cost
@@ -331,7 +312,8 @@ int approx_match_common(const float* xyz1, const float* xyz2, int64_t b, int64_t
             continue;
         }
         const int rc = approx_match_item(xyz1 + i * n * 3, xyz2 + i * m * 3, ni, mi, match != nullptr ? match + i * n * m : nullptr,
-                                         n, match != nullptr ? nullptr : cost + i, w, st);
+                                         n, match != nullptr ? nullptr : cost + i, w, st,
+                                         levels != nullptr ? levels + i * kAmLevels * lvl_ld : nullptr, lvl_ld, n);
         if (rc != DMCF_OK) return rc;
     }
     return check_launch();
@@ -398,6 +380,13 @@ int dmcf_emd(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t
              float* cost, void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
     if (cost == nullptr) return DMCF_EINVAL;
     return approx_match_common(xyz1, xyz2, b, n, m, count1, count2, nullptr, cost, workspace, workspace_bytes, stream);
+}
+
+int dmcf_emd_with_levels(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,
+                         const int32_t* count2, float* cost, float* levels, void* workspace, size_t workspace_bytes,
+                         dmcf_stream_t stream) {
+    if (cost == nullptr || (levels == nullptr && b > 0)) return DMCF_EINVAL;
+    return approx_match_common(xyz1, xyz2, b, n, m, count1, count2, nullptr, cost, workspace, workspace_bytes, stream, levels);
 }
 
 size_t dmcf_match_cost_workspace_bytes(int64_t b, int64_t n, int64_t m) {

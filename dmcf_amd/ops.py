@@ -1631,17 +1631,93 @@ def farthest_point_sample(npoint, inp):
     return idx.unsqueeze(0)
 
 
-def gather_point(inp, idx):
-    """Mirror of ``gather_point(inp [1, n, c], idx [1, m]) -> [1, m, c]`` (utils/tools/sampling.py)."""
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
+
+
+def _dev_exact(t, name, dtype, shape, device):
+    """The operand ``t`` of a backward entry point: a tensor of ``dtype`` and exactly ``shape`` on ``device`` (a GPU), made
+    contiguous; anything else raises before a pointer reaches the library."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor")
+    if not t.is_cuda:
+        raise _lib.DmcfError(f"{name} is on {t.device}: the DMCF hot path runs on the GPU only (no CPU fallback)")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the point sets on {device}")
+    return t.contiguous()
+
+
+def _sets3(xyz1, xyz2):
+    """Both point sets of a backward entry point: float32 GPU tensors of shape exactly [b, n, 3] / [b, m, 3] (the padded batches
+    the forward works on), same b and device -> contiguous (xyz1, xyz2)."""
+    a, _ = _point_batch(xyz1, "xyz1")
+    b, _ = _point_batch(xyz2, "xyz2")
+    for t, name in ((xyz1, "xyz1"), (xyz2, "xyz2")):
+        if t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError(f"{name} must have shape [b, n, 3] here, got {tuple(t.shape)}")
+    if a.shape[0] != b.shape[0] or a.device != b.device:
+        raise ValueError(f"xyz1 {tuple(xyz1.shape)} and xyz2 {tuple(xyz2.shape)} must have the same batch size and device")
+    return a, b
+
+
+def _gather_point_impl(x, ii):
     L = _lib.lib()
+    out = torch.empty((ii.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
+    _lib.check(L.dmcf_gather_point(_ptr(x), _ptr(ii), ii.shape[0], x.shape[1], _ptr(out), _stream()), "dmcf_gather_point")
+    return out
+
+
+def gather_point_backward(grad_out, idx, n_inp):
+    """dmcf_gather_point_backward: grad_inp [n_inp, c] = sum of the rows of ``grad_out`` [m, c] whose ``idx`` [m] (int32) points
+    at the row; repeated indices sum, in ascending order of m (no atomics)."""
+    L = _lib.lib()
+    g = _dev_f32(grad_out, "grad_out")
+    if g.dim() != 2 or g.shape[1] == 0:
+        raise ValueError(f"grad_out must have shape [m, c] with c > 0, got {tuple(g.shape)}")
+    m, c = g.shape
+    idx = _dev_exact(idx, "idx", torch.int32, (m,), g.device)
+    n_inp = int(n_inp)
+    if n_inp < 0:
+        raise ValueError(f"n_inp must be >= 0, got {n_inp}")
+    grad_inp = torch.empty((n_inp, c), dtype=torch.float32, device=g.device)
+    nbytes = int(L.dmcf_gather_point_backward_workspace_bytes(m, n_inp))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=g.device)
+    _lib.check(L.dmcf_gather_point_backward(_ptr(g), _ptr(idx), m, c, int(n_inp), _ptr(grad_inp), _ptr(ws), nbytes, _stream()),
+               "dmcf_gather_point_backward")
+    return grad_inp
+
+
+class GatherPointFunction(torch.autograd.Function):
+    """Autograd node of ``gather_point`` (GatherPointGrad, sampling.py:78-83): the index gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, ii):
+        ctx.save_for_backward(ii)
+        ctx.n_inp = x.shape[0]
+        return _gather_point_impl(x, ii)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (ii,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return gather_point_backward(grad_out.contiguous(), ii, ctx.n_inp), None
+
+
+def gather_point(inp, idx):
+    """Mirror of ``gather_point(inp [1, n, c], idx [1, m]) -> [1, m, c]`` (utils/tools/sampling.py).  Differentiable in
+    ``inp`` (dmcf_gather_point_backward)."""
     if inp.dim() != 3 or inp.shape[0] != 1 or idx.dim() != 2 or idx.shape[0] != 1:
         raise ValueError("gather_point expects inp [1, n, c] and idx [1, m]")
     x = _dev_f32(inp[0], "inp")
     if idx.dtype != torch.int32 or not idx.is_cuda:
         raise TypeError("idx must be an int32 GPU tensor")
     ii = idx[0].contiguous()
-    out = torch.empty((ii.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
-    _lib.check(L.dmcf_gather_point(_ptr(x), _ptr(ii), ii.shape[0], x.shape[1], _ptr(out), _stream()), "dmcf_gather_point")
+    out = GatherPointFunction.apply(x, ii) if _wants_grad(x) else _gather_point_impl(x, ii)
     return out.unsqueeze(0)
 
 
@@ -1697,15 +1773,9 @@ def _counts_ptr(arr):
     return None if arr is None else arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
 
 
-def nn_distance(xyz1, xyz2):
-    """Mirror of ``utils/tools/nn_distance.py: nn_distance(xyz1, xyz2)`` -> ``(dist1, idx1, dist2, idx2)``: for each point of
-    xyz1 [b, n, 3] the squared distance to its nearest point of xyz2 [b, m, 3] and that point's int32 index ([b, n]), and the
-    same from xyz2 to xyz1 ([b, m]).  Equal distances go to the lowest index (dmcf_nn_distance)."""
+def _nn_distance_impl(a, b):
     L = _lib.lib()
-    a, b, batched = _pair_batch(xyz1, xyz2)
     nb, n, m = a.shape[0], a.shape[1], b.shape[1]
-    if nb > 0 and (n == 0 or m == 0):
-        raise ValueError("nn_distance needs two non-empty point sets")
     dev = a.device
     d1 = torch.empty((nb, n), dtype=torch.float32, device=dev)
     i1 = torch.empty((nb, n), dtype=torch.int32, device=dev)
@@ -1716,7 +1786,64 @@ def nn_distance(xyz1, xyz2):
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         _lib.check(L.dmcf_nn_distance(_ptr(a), _ptr(b), nb, n, m, _ptr(d1), _ptr(i1), _ptr(d2), _ptr(i2), _ptr(ws), nbytes,
                                       _stream()), "dmcf_nn_distance")
-    out = (d1, i1, d2, i2)
+    return d1, i1, d2, i2
+
+
+def nn_distance_backward(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, need1=True, need2=True):
+    """dmcf_nn_distance_backward on [b, n, 3] / [b, m, 3] point sets and the forward's int32 indices: (grad_xyz1, grad_xyz2)
+    (None where not wanted).  ``grad_dist1`` / ``grad_dist2`` None: zero.  No atomics: the scattered terms are gathered through a
+    sort of the index list."""
+    L = _lib.lib()
+    xyz1, xyz2 = _sets3(xyz1, xyz2)
+    nb, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    if nb > 0 and (n == 0 or m == 0):
+        raise ValueError("nn_distance needs two non-empty point sets")
+    dev = xyz1.device
+    g1 = None if grad_dist1 is None else _dev_exact(grad_dist1, "grad_dist1", torch.float32, (nb, n), dev)
+    g2 = None if grad_dist2 is None else _dev_exact(grad_dist2, "grad_dist2", torch.float32, (nb, m), dev)
+    idx1 = None if g1 is None else _dev_exact(idx1, "idx1", torch.int32, (nb, n), dev)
+    idx2 = None if g2 is None else _dev_exact(idx2, "idx2", torch.int32, (nb, m), dev)
+    gx1 = torch.empty((nb, n, 3), dtype=torch.float32, device=dev) if need1 else None
+    gx2 = torch.empty((nb, m, 3), dtype=torch.float32, device=dev) if need2 else None
+    if nb > 0 and (need1 or need2):
+        nbytes = int(L.dmcf_nn_distance_backward_workspace_bytes(nb, n, m))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dmcf_nn_distance_backward(_ptr(xyz1), _ptr(xyz2), nb, n, m, _ptr(idx1), _ptr(idx2), _ptr(g1), _ptr(g2),
+                                               _ptr(gx1), _ptr(gx2), _ptr(ws), nbytes, _stream()), "dmcf_nn_distance_backward")
+    return gx1, gx2
+
+
+class NnDistanceFunction(torch.autograd.Function):
+    """Autograd node of ``nn_distance`` (NnDistanceGrad, nn_distance.py:61-68): dist1 and dist2 are differentiable, the
+    indices are not.  A distance output that takes no part in the loss arrives as None and counts as zero."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ctx.set_materialize_grads(False)
+        d1, i1, d2, i2 = _nn_distance_impl(a, b)
+        ctx.mark_non_differentiable(i1, i2)
+        ctx.save_for_backward(a, b, i1, i2)
+        return d1, i1, d2, i2
+
+    @staticmethod
+    def backward(ctx, gd1, _gi1, gd2, _gi2):
+        a, b, i1, i2 = ctx.saved_tensors
+        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (gd1 is None and gd2 is None) or not (need1 or need2):
+            return None, None
+        return nn_distance_backward(a, b, i1, i2, gd1, gd2, need1, need2)
+
+
+def nn_distance(xyz1, xyz2):
+    """Mirror of ``utils/tools/nn_distance.py: nn_distance(xyz1, xyz2)`` -> ``(dist1, idx1, dist2, idx2)``: for each point of
+    xyz1 [b, n, 3] the squared distance to its nearest point of xyz2 [b, m, 3] and that point's int32 index ([b, n]), and the
+    same from xyz2 to xyz1 ([b, m]).  Equal distances go to the lowest index (dmcf_nn_distance).  dist1 and dist2 are
+    differentiable in both point sets (dmcf_nn_distance_backward)."""
+    a, b, batched = _pair_batch(xyz1, xyz2)
+    nb, n, m = a.shape[0], a.shape[1], b.shape[1]
+    if nb > 0 and (n == 0 or m == 0):
+        raise ValueError("nn_distance needs two non-empty point sets")
+    out = NnDistanceFunction.apply(a, b) if _wants_grad(a, b) else _nn_distance_impl(a, b)
     return out if batched else tuple(x[0] for x in out)
 
 
@@ -1746,36 +1873,151 @@ def approx_match(xyz1, xyz2, n=None, m=None):
     return match if batched else match[0]
 
 
+def match_cost_backward(xyz1, xyz2, match, grad_cost, need1=True, need2=True):
+    """dmcf_match_cost_backward: (grad_xyz1 [b, n, 3], grad_xyz2 [b, m, 3]) of ``match_cost`` for [b, n, 3] / [b, m, 3] sets, a
+    dense match [b, m, n] and grad_cost [b] (None where not wanted)."""
+    L = _lib.lib()
+    xyz1, xyz2 = _sets3(xyz1, xyz2)
+    nb, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    dev = xyz1.device
+    match = _dev_exact(match, "match", torch.float32, (nb, m, n), dev)
+    gc = _dev_exact(grad_cost, "grad_cost", torch.float32, (nb,), dev)
+    gx1 = torch.empty((nb, n, 3), dtype=torch.float32, device=dev) if need1 else None
+    gx2 = torch.empty((nb, m, 3), dtype=torch.float32, device=dev) if need2 else None
+    if nb > 0 and (need1 or need2):
+        nbytes = int(L.dmcf_match_cost_backward_workspace_bytes(nb, n, m))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dmcf_match_cost_backward(_ptr(xyz1), _ptr(xyz2), nb, n, m, _ptr(match), _ptr(gc), _ptr(gx1), _ptr(gx2), _ptr(ws),
+                                              nbytes, _stream()), "dmcf_match_cost_backward")
+    return gx1, gx2
+
+
+class MatchCostFunction(torch.autograd.Function):
+    """Autograd node of ``match_cost`` (MatchCostGrad, tf_approxmatch.cu:346-430): gradients for both point sets; the match
+    gets none (approx_match has no gradient)."""
+
+    @staticmethod
+    def forward(ctx, a, b, mt):
+        ctx.save_for_backward(a, b, mt)
+        return _match_cost_impl(a, b, mt)
+
+    @staticmethod
+    def backward(ctx, grad_cost):
+        a, b, mt = ctx.saved_tensors
+        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need1 or need2):
+            return None, None, None
+        gx1, gx2 = match_cost_backward(a, b, mt, grad_cost, need1, need2)
+        return gx1, gx2, None
+
+
 def match_cost(xyz1, xyz2, match):
     """Mirror of ``utils/tools/tf_approxmatch.py: match_cost(xyz1, xyz2, match)`` -> cost [b] =
-    sum_{l,k} match[l, k] |xyz2[l] - xyz1[k]| (dmcf_match_cost)."""
-    L = _lib.lib()
+    sum_{l,k} match[l, k] |xyz2[l] - xyz1[k]| (dmcf_match_cost).  Differentiable in xyz1 and xyz2 (dmcf_match_cost_backward);
+    the match is a constant."""
     a, b, batched = _pair_batch(xyz1, xyz2)
     nb, n, m = a.shape[0], a.shape[1], b.shape[1]
-    mt = _dev_f32(match, "match")
+    mt = _dev_f32(match, "match").detach()
     if not batched:
         mt = mt.unsqueeze(0)
     if tuple(mt.shape) != (nb, m, n):
         raise ValueError(f"match must have shape {(nb, m, n) if batched else (m, n)}, got {tuple(match.shape)}")
+    cost = MatchCostFunction.apply(a, b, mt) if _wants_grad(a, b) else _match_cost_impl(a, b, mt)
+    return cost if batched else cost[0]
+
+
+def _match_cost_impl(a, b, mt):
+    L = _lib.lib()
+    nb, n, m = a.shape[0], a.shape[1], b.shape[1]
     cost = torch.empty(nb, dtype=torch.float32, device=a.device)
     nbytes = int(L.dmcf_match_cost_workspace_bytes(nb, n, m))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
     _lib.check(L.dmcf_match_cost(_ptr(a), _ptr(b), nb, n, m, _ptr(mt), _ptr(cost), _ptr(ws), nbytes, _stream()), "dmcf_match_cost")
-    return cost if batched else cost[0]
+    return cost
+
+
+EMD_LEVELS = 10  # levels of the approximate match (dmcf_emd_with_levels records two ratios per point and level)
+
+
+def _emd_impl(a, b, c1, c2, levels=None):
+    L = _lib.lib()
+    nb, nn_, mm = a.shape[0], a.shape[1], b.shape[1]
+    cost = torch.empty(nb, dtype=torch.float32, device=a.device)
+    nbytes = int(L.dmcf_emd_workspace_bytes(nb, nn_, mm))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
+    if levels is None:
+        _lib.check(L.dmcf_emd(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(ws), nbytes,
+                              _stream()), "dmcf_emd")
+    else:
+        _lib.check(L.dmcf_emd_with_levels(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(levels),
+                                          _ptr(ws), nbytes, _stream()), "dmcf_emd_with_levels")
+    return cost
+
+
+def emd_with_levels(xyz1, xyz2, n=None, m=None):
+    """dmcf_emd_with_levels on float32 GPU sets of shape exactly [b, n, 3] / [b, m, 3] -> (cost [b], levels [b, 10, n + m]): the
+    cost of :func:`emd` (same bits) and, per level, ratioL after pass A ([:n]) and ratioR after pass B ([n:]), the state
+    :func:`emd_backward` needs."""
+    xyz1, xyz2 = _sets3(xyz1, xyz2)
+    nb, nn_, mm = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    c1, c2 = _host_counts(n, nb, nn_, "n"), _host_counts(m, nb, mm, "m")
+    levels = torch.empty((nb, EMD_LEVELS, nn_ + mm), dtype=torch.float32, device=xyz1.device)
+    return _emd_impl(xyz1, xyz2, c1, c2, levels), levels
+
+
+def emd_backward(xyz1, xyz2, levels, grad_cost, n=None, m=None, need1=True, need2=True):
+    """dmcf_emd_backward: (grad_xyz1 [b, n, 3], grad_xyz2 [b, m, 3]) of :func:`emd` with the match held constant, from the
+    ``levels`` of :func:`emd_with_levels` (same [b, n, 3] / [b, m, 3] sets and counts) and grad_cost [b], without forming the
+    match; rows past a count are 0."""
+    L = _lib.lib()
+    xyz1, xyz2 = _sets3(xyz1, xyz2)
+    nb, nn_, mm = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    c1, c2 = _host_counts(n, nb, nn_, "n"), _host_counts(m, nb, mm, "m")
+    dev = xyz1.device
+    levels = _dev_exact(levels, "levels", torch.float32, (nb, EMD_LEVELS, nn_ + mm), dev)
+    gc = _dev_exact(grad_cost, "grad_cost", torch.float32, (nb,), dev)
+    gx1 = torch.empty((nb, nn_, 3), dtype=torch.float32, device=dev) if need1 else None
+    gx2 = torch.empty((nb, mm, 3), dtype=torch.float32, device=dev) if need2 else None
+    if nb > 0 and (need1 or need2):
+        nbytes = int(L.dmcf_emd_backward_workspace_bytes(nb, nn_, mm))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dmcf_emd_backward(_ptr(xyz1), _ptr(xyz2), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(levels), _ptr(gc),
+                                       _ptr(gx1), _ptr(gx2), _ptr(ws), nbytes, _stream()), "dmcf_emd_backward")
+    return gx1, gx2
+
+
+class EmdFunction(torch.autograd.Function):
+    """Autograd node of :func:`emd`: the forward records the ratios of every level (dmcf_emd_with_levels, same cost bits as
+    dmcf_emd), the backward is dmcf_emd_backward (match-free)."""
+
+    @staticmethod
+    def forward(ctx, a, b, c1, c2):
+        levels = torch.empty((a.shape[0], EMD_LEVELS, a.shape[1] + b.shape[1]), dtype=torch.float32, device=a.device)
+        cost = _emd_impl(a, b, c1, c2, levels)
+        ctx.save_for_backward(a, b, levels)
+        ctx.counts = (c1, c2)
+        return cost
+
+    @staticmethod
+    def backward(ctx, grad_cost):
+        a, b, levels = ctx.saved_tensors
+        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need1 or need2):
+            return None, None, None, None
+        c1, c2 = ctx.counts
+        gx1, gx2 = emd_backward(a, b, levels, grad_cost, c1, c2, need1, need2)
+        return gx1, gx2, None, None
 
 
 def emd(xyz1, xyz2, n=None, m=None):
     """``match_cost(xyz1, xyz2, approx_match(xyz1, xyz2, n, m))`` without forming the match (dmcf_emd): cost [b] in O(n + m)
-    memory.  Same arguments as :func:`approx_match`."""
-    L = _lib.lib()
+    memory.  Same arguments as :func:`approx_match`.  Differentiable in xyz1 and xyz2 with the match held constant
+    (dmcf_emd_backward); only then, when grad mode is on and an input requires grad, does the forward record the ratios of
+    every level (dmcf_emd_with_levels, 40 (n + m) bytes per item more, same cost bits)."""
     a, b, batched = _pair_batch(xyz1, xyz2)
     nb, nn_, mm = a.shape[0], a.shape[1], b.shape[1]
     c1, c2 = _host_counts(n, nb, nn_, "n"), _host_counts(m, nb, mm, "m")
-    cost = torch.empty(nb, dtype=torch.float32, device=a.device)
-    nbytes = int(L.dmcf_emd_workspace_bytes(nb, nn_, mm))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
-    _lib.check(L.dmcf_emd(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(ws), nbytes, _stream()),
-               "dmcf_emd")
+    cost = EmdFunction.apply(a, b, c1, c2) if _wants_grad(a, b) else _emd_impl(a, b, c1, c2)
     return cost if batched else cost[0]
 
 

@@ -8,15 +8,16 @@
   compute_density   losses.py:285-306  windowed neighbour sum (fused into the search scan: ops.window_sum)
   compute_pressure  losses.py:367-377  Tait-style pressure from the density
   density_loss      losses.py:380-398  validation metric of pipelines/simulator.py:227-243
-  emd_loss          losses.py:401-409  approximate-match EMD per batch item (validation metric; ops.emd, no gradient)
+  emd_loss          losses.py:401-409  approximate-match EMD per batch item (ops.emd; differentiable in both sets with the
+                                       match held constant, dmcf_emd_backward)
 
   get_loss          losses.py:47-110   the training losses mse / weighted_mse / vel / weighted_vel / momentum
   get_optimizer     models/pbf_model.py:508-517  Adam (eps 1e-6), piecewise-constant learning rate (torch.optim.Adam)
   KerasAdam         the same optimizer with Keras' update rule and state, on dmcf_adam_step: what the training loop uses
 
 The density, Chamfer, EMD and histogram losses (losses.py:380-414, the last three on the reference's custom CUDA ops) are
-not implemented as training losses: get_loss returns a function that raises NotImplementedError for them (they would
-need the gradients of nn_distance / match_cost).  emd_loss and utils/evaluation_helper.py serve validation only.
+not wired into get_loss: it returns a function that raises NotImplementedError for them.  The ops under them are
+differentiable, so emd_loss and utils/tools/nn_distance.chamfer_loss can be added to an objective by hand.
 """
 import numpy as np
 import torch
@@ -226,7 +227,8 @@ def density_loss(gt, pred, gt_in=None, pred_in=None, radius=0.005, eps=0.01, win
 def emd_loss(y_true, y_pred, n=None, m=None):
     """losses.py:401-409: ``match_cost(approx_match(y_true, y_pred, n, m)) / max(n, m)`` per batch item, [b].  ``y_true``
     [b, n, 3], ``y_pred`` [b, m, 3] (2-D: z = 0); ``n`` / ``m`` per-batch point counts (None: all points).  Runs the fused
-    kernel (ops.emd), which never forms the [b, m, n] match.  No gradient."""
+    kernel (ops.emd), which never forms the [b, m, n] match.  Differentiable in ``y_true`` and ``y_pred`` with the match held
+    constant (approx_match has no gradient), through dmcf_emd_backward, which does not form the match either."""
     from ... import ops
     b = y_true.shape[0]
     nn_ = ops._host_counts(n, b, y_true.shape[1], "n")

@@ -585,6 +585,53 @@ int dmcf_emd(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t
              float* cost, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gradients of the point-cloud ops (ABI 2.13; dmcf_amd/csrc/metrics_bwd.hip): nn_distance (NnDistanceGrad,
+ * nn_distance.cu:158-183), match_cost (MatchCostGrad, tf_approxmatch.cu:346-430), the fused EMD with the match held constant
+ * (approx_match has no gradient) and gather_point (GatherPointGrad).  No float atomics: scattered terms are gathered through
+ * a stable sort of the index list (each target sums its sources in ascending source order, or, past 256 of them, in one
+ * workgroup's fixed order), all-pairs sums run in a fixed
+ * order with a size-only split plan, so two identical calls give identical bits.  Every call validates its arguments and
+ * workspace (DMCF_EINVAL / DMCF_EWORKSPACE) before anything is enqueued; an output pointer of NULL means "not wanted"
+ * (both NULL: DMCF_EINVAL).  Gradients are written, not accumulated.  Workspace queries return 0 for sizes < 0 (and for
+ * empty sets, where nothing is read).
+ * ---------------------------------------------------------------------------------------------- */
+/* nn_distance: idx1 [b, n] / idx2 [b, m] are the forward's indices; grad_dist1 [b, n] / grad_dist2 [b, m] may be NULL (zero;
+ * then its idx may be NULL too).  With g = 2 grad_dist1[i]:  grad_xyz1[i] += g (x1_i - x2_{idx1[i]}),
+ * grad_xyz2[idx1[i]] -= g (x1_i - x2_{idx1[i]}); the terms of dist2 are the same with the sets swapped.  Each point takes its
+ * own term first, then subtracts the scattered ones.  b n and b m < 2^31. */
+size_t dmcf_nn_distance_backward_workspace_bytes(int64_t b, int64_t n, int64_t m);
+int dmcf_nn_distance_backward(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* idx1,
+                              const int32_t* idx2, const float* grad_dist1, const float* grad_dist2, float* grad_xyz1,
+                              float* grad_xyz2, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* match_cost with a dense match [b, m, n] and grad_cost [b] (device):
+ *   grad_xyz1[k] = g_b sum_l match[l, k] (x1_k - x2_l) rsqrt(max(d2_kl, 1e-20)),
+ *   grad_xyz2[l] = g_b sum_k match[l, k] (x2_l - x1_k) rsqrt(max(d2_kl, 1e-20)). */
+size_t dmcf_match_cost_backward_workspace_bytes(int64_t b, int64_t n, int64_t m);
+int dmcf_match_cost_backward(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const float* match,
+                             const float* grad_cost, float* grad_xyz1, float* grad_xyz2, void* workspace, size_t workspace_bytes,
+                             dmcf_stream_t stream);
+/* dmcf_emd that also records the state its gradient needs: levels [b, 10, n + m] holds, for level j (in the order of the
+ * passes, -4^7 first, 0 last), ratioL after pass A in [0, n_i) and ratioR after pass B in [n, n + m_i); zeros elsewhere.  The
+ * launches of dmcf_emd plus asynchronous copies, so cost has dmcf_emd's bits.  Workspace: dmcf_emd_workspace_bytes. */
+int dmcf_emd_with_levels(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,
+                         const int32_t* count2, float* cost, float* levels, void* workspace, size_t workspace_bytes,
+                         dmcf_stream_t stream);
+/* Gradient of dmcf_emd with the match held constant, never forming it: w_kl = sum_j (e^(level_j d2_kl) ratioR_j[l]) ratioL_j[k]
+ * is recomputed per pair with the float32 expression of the forward's pass C (so it has the bits of dmcf_approx_match's
+ * match[l, k]), then the formulas of dmcf_match_cost_backward.  count1 / count2: the HOST counts given to
+ * dmcf_emd_with_levels; rows past a count get exact zeros.  Batch items run one after another, each with the split plan of
+ * its own counts (a padded item gives the bits of the same item alone). */
+size_t dmcf_emd_backward_workspace_bytes(int64_t b, int64_t n, int64_t m);
+int dmcf_emd_backward(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,
+                      const int32_t* count2, const float* levels, const float* grad_cost, float* grad_xyz1, float* grad_xyz2,
+                      void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* gather_point: grad_inp [n_inp, channels] = sum over s with index[s] == t of grad_out[s, :] (repeated indices sum; indices
+ * outside [0, n_inp) contribute nothing). */
+size_t dmcf_gather_point_backward_workspace_bytes(int64_t n_index, int64_t n_inp);
+int dmcf_gather_point_backward(const float* grad_out, const int32_t* index, int64_t n_index, int channels, int64_t n_inp,
+                               float* grad_inp, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PointNet's layer (models/pointnet.py:137-145): tf.keras.layers.Dense, tf.gather by neighbors_index and the ragged
  * tf.reduce_sum over the row splits, with the relu before the Dense and the residual after it.  Per output row r:
  *     out_r = (sum_{p in row r, 0 <= idx[p] < n_in} act(x_{idx[p]})) W + c_r b (+ residual_r)       (+ mask, below)
