@@ -222,6 +222,7 @@ SYMBOLS = [
     "dmcf_nn_distance_backward_workspace_bytes", "dmcf_nn_distance_backward", "dmcf_match_cost_backward_workspace_bytes",
     "dmcf_match_cost_backward", "dmcf_emd_with_levels", "dmcf_emd_backward_workspace_bytes", "dmcf_emd_backward",
     "dmcf_gather_point_backward_workspace_bytes", "dmcf_gather_point_backward",
+    "dmcf_frs_window_sum_backward",
 ]
 
 
@@ -404,6 +405,10 @@ def lib():
     L.dmcf_gather_point_backward.restype = c.c_int
     L.dmcf_gather_point_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int64, c.c_void_p, c.c_void_p,
                                              c.c_size_t, c.c_void_p]
+    # gradient of the window sum (ABI 2.14)
+    L.dmcf_frs_window_sum_backward.restype = c.c_int
+    L.dmcf_frs_window_sum_backward.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
+                                               c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
     _lib = L
     return L
 

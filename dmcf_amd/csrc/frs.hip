@@ -478,8 +478,47 @@ __device__ __forceinline__ bool o3d_visible(float px, float py, float pz, const 
     return false;
 }
 
+// d window / d(d^2) of window_value (fac = 1) at a hit: w'(q) / R^2 with q = d^2 / R^2; 1 for DMCF_WINDOW_EXPLICIT, the sum of
+// squared distances.  The clamps follow autodiff of the reference's formulas (utils/tools/losses.py:8-44): poly6 is flat where
+// (1 - q)^3 is clamped, cubic / cubic_grad beyond q = 1.  The sqrt-based windows are singular at d^2 = 0: the caller drops a
+// coincident pair (whose q - p is 0 anyway).
+// t = 1 - q comes from the caller in DOUBLE precision (rounded to float last): every slope vanishes like a power of (1 - q) or
+// of (1 - sqrt q) = t / (1 + sqrt q) at the rim of the sphere, and a float q carries ~3 ulp of 1 -- a relative error of
+// 6 ulp / (1 - q) in poly6's (1 - q)^2, above the gradient tests' bar of 256 ulp for the outermost 2.4 % of q (measured: a
+// gradient element made of one such term missed the bar by 2x).
+__device__ __forceinline__ float window_slope(int window, float q, float t, float inv_r2) {
+    if (window == DMCF_WINDOW_EXPLICIT) return 1.0f;
+    float g = 0.0f;
+    const float s = __builtin_amdgcn_sqrtf(q);
+    const float u = t / (1.0f + s);  // 1 - s
+    switch (window) {
+        case DMCF_WINDOW_POLY6: g = t > 0.0f ? -3.0f * t * t : 0.0f; break;
+        case DMCF_WINDOW_CUBIC:
+            if (q <= 1.0f) g = (s <= 0.5f) ? 9.0f * s - 6.0f : -3.0f * u * u / s;
+            g *= 4.0f / 3.0f;
+            break;
+        case DMCF_WINDOW_LINEAR: g = -0.5f / s; break;
+        case DMCF_WINDOW_PEAK: g = -u / s; break;  // 1 - 1 / s
+        case DMCF_WINDOW_CUBIC_GRAD:
+            if (q <= 1.0f) g = (s <= 0.5f) ? 18.0f - 6.0f / s : 6.0f * u / s;
+            g *= 4.0f / 3.0f;
+            break;
+    }
+    return g * inv_r2;
+}
+
+// what MODE 3 of frs_scan carries: the query's coefficient, the points' coefficients (by original index; may be NULL), 1 / R^2
+// and the per-lane sums of (cq + cp[p]) * dw/d(d^2) * (q - p)
+struct FrsGradAcc {
+    float coef_q;
+    const float* coef_p;
+    double inv_r2;
+    float g[3];
+};
+
 // The candidate scan of one query by one wavefront.  MODE 0: count the hits; MODE 1: write them to the CSR row at
-// out_base; MODE 2: add window(d^2 / R^2) of every hit to `wsum` (per lane; the caller reduces over the wave).
+// out_base; MODE 2: add window(d^2 / R^2) of every hit to `wsum` (per lane; the caller reduces over the wave); MODE 3: add the
+// hit's term of the window sum's gradient to `ga` (per lane, see frs_window_sum_grad).
 // Returns the number of hits.  Hits come out in a fixed order (cell rows, then position in the cell-sorted array).
 // EXACT (open3d visibility flags only): every hit that could lie outside the reference's 8 bins takes the exact
 // visibility test -- the form of the FIXUP kernel (frs_fix), which re-scans the few queries the hot kernels flag.  !EXACT is the
@@ -491,7 +530,7 @@ __device__ __forceinline__ int32_t frs_scan(float qx, float qy, float qz, const 
                                             const uint32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
                                             float radius, int flags, int64_t out_base, int32_t* __restrict__ nbr_index,
                                             float* __restrict__ nbr_dist, int window, float inv_r2, float& wsum,
-                                            uint32_t* marks, int32_t row_cap, bool& redo) {
+                                            uint32_t* marks, int32_t row_cap, bool& redo, FrsGradAcc* ga = nullptr) {
     const int lane = lane_id();
     int mark_tag = 0;
     for (int w = 0; w < kWin; ++w) marks[w * kWave + lane] = 0;  // LDS is not cleared between workgroups: stale tags of an earlier wave must not match ours
@@ -622,6 +661,19 @@ __device__ __forceinline__ int32_t frs_scan(float qx, float qy, float qz, const 
                     }
                 }
                 if (MODE == 2 && hit) wsum += window_value(window, d2, inv_r2, 1.0f);
+                if (MODE == 3 && hit) {
+                    float c = ga->coef_q;
+                    if (ga->coef_p) c += ga->coef_p[pidx];
+                    // (the hit was decided on the float d^2 above, as everywhere; only the window's argument is re-formed)
+                    const double ex = (double)qx - (double)p.x, ey = (double)qy - (double)p.y, ez = (double)qz - (double)p.z;
+                    const double e2 = ex * ex + ey * ey + ez * ez;
+                    const double qd = e2 * ga->inv_r2;
+                    c *= window_slope(window, (float)qd, (float)(1.0 - qd), inv_r2);
+                    if (window >= DMCF_WINDOW_CUBIC && e2 == 0.0) c = 0.0f;  // coincident pair of a sqrt-based window: no term
+                    ga->g[0] += c * (float)ex;
+                    ga->g[1] += c * (float)ey;
+                    ga->g[2] += c * (float)ez;
+                }
                 cnt += __popcll(mask);
             };
             // kWin windows per iteration: their lookups and candidate loads are in flight together
@@ -750,6 +802,39 @@ __global__ __launch_bounds__(256) void frs_window_sum(const float* __restrict__ 
     if (lane_id() == 0) {
         out[qi] = wsum;
         if (flags & kO3dFlags) qflags[qi] = redo ? 1 : 0;
+    }
+}
+
+// Gradient of the window sum w.r.t. the positions (dmcf_frs_window_sum_backward): the scan of frs_window_sum with three sums,
+//   grad[q] = 2 * sum over the hits p of (coef_q[q] + coef_p[p]) * dw/d(d^2) * (q - p).
+// Every term is added by the lane that tested the candidate, in the scan's fixed order, then the wave is reduced: no atomics,
+// identical calls give identical bits.  No open3d visibility flags here (the entry point refuses them).
+__global__ __launch_bounds__(256) void frs_window_sum_grad(const float* __restrict__ queries, int64_t m,
+                                                           const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
+                                                           const float4* __restrict__ sorted, float radius, int flags, int window,
+                                                           const float* __restrict__ coef_q, const float* __restrict__ coef_p,
+                                                           float* __restrict__ grad) {
+    __shared__ uint32_t marks[4][kWin * kWave + kWave];
+    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (qi >= m) return;
+    const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
+    FrsGradAcc ga;
+    ga.coef_q = coef_q ? coef_q[qi] : 0.0f;
+    ga.coef_p = coef_p;
+    ga.inv_r2 = 1.0 / ((double)radius * (double)radius);
+    ga.g[0] = ga.g[1] = ga.g[2] = 0.0f;
+    float unused = 0.0f;
+    bool redo = false;
+    frs_scan<3, false>(qx, qy, qz, h, cell_start, sorted, radius, flags, 0, nullptr, nullptr, window, 1.0f / (radius * radius), unused,
+                       marks[threadIdx.x >> 6], 0x7fffffff, redo, &ga);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) ga.g[a] += __shfl_xor(ga.g[a], d, kWave);
+    }
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) grad[3 * qi + a] = 2.0f * ga.g[a];
     }
 }
 
@@ -996,6 +1081,27 @@ int dmcf_frs_window_sum(const float* queries, int64_t m, int64_t n, float radius
         hipLaunchKernelGGL((frs_fix<3>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags,
                            (const uint8_t*)qflags, (int32_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, (int32_t*)nullptr,
                            (float*)nullptr, (int64_t)0, window, out);
+    return check_launch();
+}
+
+int dmcf_frs_window_sum_backward(const float* queries, int64_t m, int64_t n, float radius, int flags, int window,
+                                 const float* coef_queries, const float* coef_points, const void* workspace,
+                                 size_t workspace_bytes, float* grad, dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!frs_flags_ok(flags)) return DMCF_EINVAL;
+    if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || (m > 0 && (!queries || !grad))) return DMCF_EINVAL;
+    if (window < DMCF_WINDOW_NONE || window > DMCF_WINDOW_CUBIC_GRAD) return DMCF_EINVAL;
+    if (!coef_queries && !coef_points) return DMCF_EINVAL;
+    if (window == DMCF_WINDOW_NONE) return DMCF_EUNSUPPORTED;  // the count has no gradient
+    if (flags & kO3dFlags) return DMCF_EUNSUPPORTED;           // asymmetric pair sets: the caller differentiates on the pair list
+    if (m == 0) return DMCF_OK;
+    const FrsLayout L = frs_layout(n, m);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    const char* ws = (const char*)workspace;
+    const unsigned g = (unsigned)((m + 3) / 4);
+    hipLaunchKernelGGL(frs_window_sum_grad, dim3(g), dim3(256), 0, stream, queries, m, (const FrsHeader*)(ws + L.off_header),
+                       (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radius, flags, window, coef_queries,
+                       coef_points, grad);
     return check_launch();
 }
 

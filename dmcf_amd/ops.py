@@ -1592,16 +1592,9 @@ def ghost_select(pos, boxes, widths2):
     return GhostSelection(pos, boxes, widths2, ws, totals)
 
 
-def window_sum(points, queries, radius, window=None, ignore_query_point=False, hash_table=None):
-    """dmcf_frs_window_sum: out[q] = sum_{|p - q| <= R} window(|p - q|^2 / R^2) (``window``: a WINDOWS key; None counts
-    the neighbours, 'explicit' sums the squared distances).  The fused form of ``compute_density``
-    (utils/tools/losses.py:285-306): the candidate scan of the search with the sum inside, no pair list."""
+def _window_sum_impl(points, queries, radius, window, ignore_query_point, hash_table):
+    """-> (out, the search structure over ``points`` that served the call)."""
     L = _lib.lib()
-    points = _dev_f32(points, "points", 3)
-    queries = _dev_f32(queries, "queries", 3)
-    radius = float(radius)
-    if window not in WINDOWS:
-        raise NotImplementedError(f"window {window!r}")
     n, m = points.shape[0], queries.shape[0]
     if hash_table is None or hash_table.n_queries_capacity < m or hash_table.points.data_ptr() != points.data_ptr() \
             or hash_table.radius != radius:
@@ -1610,7 +1603,123 @@ def window_sum(points, queries, radius, window=None, ignore_query_point=False, h
     out = torch.empty(m, dtype=torch.float32, device=points.device)
     _lib.check(L.dmcf_frs_window_sum(_ptr(queries), m, n, radius, frs_flags(ignore_query_point), WINDOWS[window],
                                      _ptr(hash_table.workspace), nbytes, _ptr(out), _stream()), "dmcf_frs_window_sum")
-    return out
+    return out, hash_table
+
+
+def window_sum_backward(queries, hash_table, radius, window, coef_queries=None, coef_points=None, ignore_query_point=False):
+    """dmcf_frs_window_sum_backward on the structure ``hash_table`` of some point set: float32 [m, 3],
+    ``grad[q] = 2 sum_{|p - q| <= R} (coef_queries[q] + coef_points[p]) dw/d(d^2) (q - p)``.  ``coef_queries`` [m] and
+    ``coef_points`` [n points of the structure] may each be None (0), not both.  Distance set only (DMCF_FRS_SET=distance)."""
+    L = _lib.lib()
+    queries = _dev_f32(queries, "queries", 3)
+    radius = float(radius)
+    if window not in WINDOWS:
+        raise NotImplementedError(f"window {window!r}")
+    n, m = hash_table.points.shape[0], queries.shape[0]
+    if hash_table.n_queries_capacity < m or hash_table.radius != radius:
+        raise ValueError("hash_table was built for fewer queries or another radius")
+    dev = queries.device
+    cq = None if coef_queries is None else _dev_exact(coef_queries, "coef_queries", torch.float32, (m,), dev)
+    cp = None if coef_points is None else _dev_exact(coef_points, "coef_points", torch.float32, (n,), dev)
+    nbytes = L.dmcf_frs_workspace_bytes(n, hash_table.n_queries_capacity)
+    grad = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    _lib.check(L.dmcf_frs_window_sum_backward(_ptr(queries), m, n, radius, frs_flags(ignore_query_point), WINDOWS[window], _ptr(cq),
+                                              _ptr(cp), _ptr(hash_table.workspace), nbytes, _ptr(grad), _stream()),
+               "dmcf_frs_window_sum_backward")
+    return grad
+
+
+def _window_sum_backward_pairs(points, queries, radius, window, ignore_query_point, grad_out, need_points, need_queries):
+    """The gradient of ``window_sum`` on the explicit pair list with torch ops: the form for the open3d readings of the search
+    (DMCF_FRS_SET=open3d / open3d_corners), whose pair set is not symmetric -- swapping the roles of the two sets would scan other
+    pairs than the forward summed.  Correct but slow (a [P]-sized gather and scatter per operand)."""
+    from .utils.tools.losses import WindowFunction
+    nns = fixed_radius_search(points, queries, radius, ignore_query_point=ignore_query_point, return_distances=False)
+    idx, rs = nns.neighbors_index.long(), nns.neighbors_row_splits
+    m = queries.shape[0]
+    row = torch.repeat_interleave(torch.arange(m, device=queries.device), torch.diff(rs), output_size=idx.shape[0])
+    with torch.enable_grad():
+        p = points.detach().requires_grad_(need_points)
+        q = queries.detach().requires_grad_(need_queries)
+        d2 = ((p[idx] - q[row]) ** 2).sum(-1)
+        if window == "explicit":
+            w = d2
+        else:
+            keep = d2.detach() > 0 if window != "poly6" else None  # (a coincident pair of a sqrt-based window contributes 0)
+            if keep is not None:
+                d2, row = d2[keep], row[keep]
+            w = WindowFunction(window)(d2 / (radius * radius))
+        out = torch.zeros(m, dtype=torch.float32, device=queries.device).index_add(0, row, w)
+        wanted = [t for t, need in ((p, need_points), (q, need_queries)) if need]
+        grads = list(torch.autograd.grad(out, wanted, grad_out))
+    gp = grads.pop(0) if need_points else None
+    gq = grads.pop(0) if need_queries else None
+    return gp, gq
+
+
+class WindowSumFunction(torch.autograd.Function):
+    """Autograd node of ``window_sum``: the gradient w.r.t. both position sets through dmcf_frs_window_sum_backward -- the
+    forward's structure serves the query side, one built over the queries the point side; ``same``: the two sets are one tensor
+    and one scan with both coefficients gives the whole gradient (returned for ``points``)."""
+
+    @staticmethod
+    def forward(ctx, points, queries, radius, window, ignore_query_point, hash_table, same):
+        out, table = _window_sum_impl(points, queries, radius, window, ignore_query_point, hash_table)
+        if window is None:
+            ctx.mark_non_differentiable(out)  # (the count)
+        ctx.save_for_backward(points, queries)
+        ctx.radius, ctx.window, ctx.ignore, ctx.table, ctx.same, ctx.flags = radius, window, ignore_query_point, table, same, \
+            frs_flags(ignore_query_point)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        points, queries = ctx.saved_tensors
+        need_p, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        none5 = (None,) * 5
+        if ctx.window is None or not (need_p or need_q):
+            return (None, None) + none5
+        if frs_flags(ctx.ignore) != ctx.flags:
+            raise RuntimeError("DMCF_FRS_SET changed between the forward and the backward of window_sum")
+        g = grad_out.contiguous()
+        n, m = points.shape[0], queries.shape[0]
+        if n == 0 or m == 0:  # no pair
+            return (torch.zeros_like(points) if need_p else None, torch.zeros_like(queries) if need_q else None) + none5
+        if search_set() != "distance":
+            gp, gq = _window_sum_backward_pairs(points, queries, ctx.radius, ctx.window, ctx.ignore, g, need_p, need_q)
+            if ctx.same:
+                gp, gq = gp + gq, None
+            return (gp, gq) + none5
+        if ctx.same:
+            return (window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, g, ctx.ignore), None) + none5
+        gp = gq = None
+        if need_q:
+            gq = window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, None, ctx.ignore)
+        if need_p:
+            swapped = build_spatial_hash_table(queries, ctx.radius, n_queries=n)
+            gp = window_sum_backward(points, swapped, ctx.radius, ctx.window, None, g, ctx.ignore)
+        return (gp, gq) + none5
+
+
+def window_sum(points, queries, radius, window=None, ignore_query_point=False, hash_table=None):
+    """dmcf_frs_window_sum: out[q] = sum_{|p - q| <= R} window(|p - q|^2 / R^2) (``window``: a WINDOWS key; None counts
+    the neighbours, 'explicit' sums the squared distances).  The fused form of ``compute_density``
+    (utils/tools/losses.py:285-306): the candidate scan of the search with the sum inside, no pair list.
+
+    Differentiable in ``points`` and ``queries`` (dmcf_frs_window_sum_backward: the same scan with three sums; the count,
+    ``window=None``, is marked non-differentiable).  For the sqrt-based windows a coincident pair contributes no gradient, where
+    the reference's autodiff gives NaN.  Under DMCF_FRS_SET=open3d / open3d_corners the backward takes the explicit pair list and
+    torch ops instead: correct, but slow.  Without grad mode or an input that requires grad the call is the plain kernel launch."""
+    same = points is queries
+    points = _dev_f32(points, "points", 3)
+    queries = points if same else _dev_f32(queries, "queries", 3)
+    radius = float(radius)
+    if window not in WINDOWS:
+        raise NotImplementedError(f"window {window!r}")
+    if _wants_grad(points, queries):
+        return WindowSumFunction.apply(points, queries, radius, window, bool(ignore_query_point), hash_table, same)
+    return _window_sum_impl(points, queries, radius, window, ignore_query_point, hash_table)[0]
 
 
 def farthest_point_sample(npoint, inp):

@@ -17,7 +17,9 @@
 
 The density, Chamfer, EMD and histogram losses (losses.py:380-414, the last three on the reference's custom CUDA ops) are
 not wired into get_loss: it returns a function that raises NotImplementedError for them.  The ops under them are
-differentiable, so emd_loss and utils/tools/nn_distance.chamfer_loss can be added to an objective by hand.
+differentiable, so emd_loss and utils/tools/nn_distance.chamfer_loss can be added to an objective by hand.  So is the
+density: compute_density, compute_pressure and density_loss are differentiable in the positions (ops.window_sum records
+through dmcf_frs_window_sum_backward), which also carries the gradient of the models' dens_feats / pres_feats inputs.
 """
 import numpy as np
 import torch
@@ -172,7 +174,8 @@ def compute_density(out_pos, in_pos=None, radius=0.005, win=None):
     """losses.py:285-306: ``dens[i] = sum_j win(|in_pos[j] - out_pos[i]|^2 / radius^2)`` over the points within
     ``radius`` (the query point itself included).  ``win``: an object from :func:`get_window_func` (evaluated inside
     the search kernel, no pair list), None (the reference warns and uses the identity: sum of q), or any callable
-    on a tensor of q values (evaluated with torch on the pair list)."""
+    on a tensor of q values (evaluated with torch on the pair list).  Differentiable in both position sets for a window
+    object and for None (ops.window_sum); a callable is evaluated on the search's distances, which carry no gradient."""
     from ... import ops
     if in_pos is None:
         in_pos = out_pos
@@ -206,7 +209,8 @@ def compute_transformed_dx(pos, scale=None, rot=None, radius=0.005):
 
 
 def compute_pressure(out_pts, inp_pts=None, dens=None, rest_dens=3.5, stiffness=20.0, win=None):
-    """losses.py:367-377 (note: the reference ignores a radius here too: compute_density's default applies)."""
+    """losses.py:367-377 (note: the reference ignores a radius here too: compute_density's default applies).  Differentiable in
+    the positions through compute_density."""
     if inp_pts is None:
         inp_pts = out_pts
     if dens is None:
@@ -215,7 +219,7 @@ def compute_pressure(out_pts, inp_pts=None, dens=None, rest_dens=3.5, stiffness=
 
 
 def density_loss(gt, pred, gt_in=None, pred_in=None, radius=0.005, eps=0.01, win=None, use_max=False, **kwargs):
-    """losses.py:380-398."""
+    """losses.py:380-398.  Differentiable in ``pred`` and ``pred_in`` (compute_density); not wired into get_loss."""
     pred_dens = compute_density(pred, pred_in, radius, win=win)
     gt_dens = compute_density(gt, gt_in, radius, win=win)
     rest_dens = gt_dens.max()

@@ -131,6 +131,29 @@ int dmcf_frs_search_padded(const float* queries, int64_t n_queries, int64_t n_po
 int dmcf_frs_window_sum(const float* queries, int64_t n_queries, int64_t n_points, float radius, int flags, int window,
                         const void* workspace, size_t workspace_bytes, float* out, dmcf_stream_t stream);
 
+/* Gradient of dmcf_frs_window_sum w.r.t. the positions (ABI 2.14): the same candidate scan -- one wavefront per query on the
+ * workspace of dmcf_frs_build(points) -- with three sums instead of one.  For every query q it WRITES
+ *   grad[3 q .. 3 q + 2] = 2 * sum over the points p with |p - q|^2 <= radius^2 of
+ *                          (coef_queries[q] + coef_points[p]) * dw/d(d^2)(|p - q|^2) * (q - p)
+ * coef_queries [n_queries] and coef_points [n_points] (indexed by the point's ORIGINAL index) are the gradients arriving at the
+ * sums; either may be NULL, meaning 0, both NULL: DMCF_EINVAL.  One entry gives all three gradients of out = window_sum(points,
+ * queries):
+ *   d/d queries:  this workspace, coef_queries = grad_out;
+ *   d/d points:   the workspace of dmcf_frs_build(QUERIES), scanned from the points, coef_points = grad_out (the distance test
+ *                 is bit-symmetric in its two arguments, so the pairs are the forward's);
+ *   points and queries the same array: ONE call with coef_queries = coef_points = grad_out.
+ * dw/d(d^2) = w'(s) / radius^2 at s = d^2 / radius^2 for the named windows (poly6: -3 (1 - s)^2 / radius^2), 1 for
+ * DMCF_WINDOW_EXPLICIT (the sum of squared distances), and follows autodiff of utils/tools/losses.py:8-44 where a formula is
+ * clamped.  DMCF_WINDOW_NONE, the count, has no gradient: DMCF_EUNSUPPORTED.  The sqrt-based windows (cubic, linear, peak,
+ * cubic_grad) are singular at d^2 = 0, where the reference's autodiff yields NaN for the pair of a point with itself: HERE A
+ * COINCIDENT PAIR (d^2 == 0) CONTRIBUTES 0.
+ * flags: DMCF_FRS_IGNORE_QUERY_POINT as in the forward.  The DMCF_FRS_OPEN3D_* flags make the pair set asymmetric, so the swap
+ * of roles above would not reproduce the forward's pairs: DMCF_EUNSUPPORTED (differentiate on the explicit pair list).
+ * No atomics: identical calls give identical bits.  Arguments are validated before anything is enqueued. */
+int dmcf_frs_window_sum_backward(const float* queries, int64_t n_queries, int64_t n_points, float radius, int flags, int window,
+                                 const float* coef_queries, const float* coef_points, const void* workspace,
+                                 size_t workspace_bytes, float* grad, dmcf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Radius search: one radius per query.  Replaces ml3d.layers.RadiusSearch(metric='L2', ignore_query_point,
  * return_distances, normalize_distances)(points, queries, radii)  (utils/convolutions.py:212-216, 366-370 and
