@@ -428,3 +428,18 @@ int dmcf_ref_filter_coordinates(const float* rel /*[cnt,3]*/, int64_t cnt, float
     }
     return DMCF_REF_OK;
 }
+
+/* The same in double, with one extent per relative position (the float64 side of the tests' error bars). */
+int dmcf_ref_filter_coordinates_f64(const float* rel /*[cnt,3]*/, int64_t cnt, const float* extents /*[cnt]*/,
+                                    const int32_t ksize_zyx[3], int align_corners, int mapping,
+                                    double* coords /*[cnt,3] x,y,z in filter-array units*/) {
+    const int fs[3] = {ksize_zyx[2], ksize_zyx[1], ksize_zyx[0]};
+    for (int64_t i = 0; i < cnt; ++i) {
+        double x = rel[3 * i], y = rel[3 * i + 1], z = rel[3 * i + 2];
+        dmcf_ref_continuous_conv_f64_filter_coords(&x, &y, &z, fs, 1.0 / (double)extents[i], align_corners, mapping);
+        coords[3 * i] = x;
+        coords[3 * i + 1] = y;
+        coords[3 * i + 2] = z;
+    }
+    return DMCF_REF_OK;
+}

@@ -55,6 +55,9 @@ def lib():
         L.dmcf_ref_filter_coordinates.restype = c.c_int
         L.dmcf_ref_filter_coordinates.argtypes = [c.c_void_p, c.c_int64, c.c_float, c.c_void_p, c.c_int,
                                                   c.c_int, c.c_void_p]
+        L.dmcf_ref_filter_coordinates_f64.restype = c.c_int
+        L.dmcf_ref_filter_coordinates_f64.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int,
+                                                      c.c_int, c.c_void_p]
         _lib = L
     return _lib
 
@@ -161,24 +164,26 @@ def reduce_subarrays_sum(values, row_splits):
 # ---------------------------------------------------------------------------------------------
 # window functions -- utils/tools/losses.py:8-44 (input q = d^2 / R^2)
 # ---------------------------------------------------------------------------------------------
-def window(typ, q, fac=1.0):
-    q = np.asarray(q, dtype=np.float32)
-    one = np.float32(1)
+def window(typ, q, fac=1.0, dtype=np.float32):
+    """``dtype=np.float64``: the same expressions in double (the float64 side of the tests' error bars)."""
+    f = dtype
+    q = np.asarray(q, dtype=f)
+    one = f(1)
     if typ == "poly6":  # losses.py:11-12
-        return np.float32(fac) * np.clip((one - q) ** 3, 0, 1).astype(np.float32)
+        return f(fac) * np.clip((one - q) ** 3, 0, 1).astype(f)
     if typ == "cubic":  # losses.py:15-20
         s = np.sqrt(q)
         r = np.where(q <= 1, np.where(s <= 0.5, 6 * (s ** 3 - q) + 1, 2 * (1 - s) ** 3), 0.0)
-        return (np.float32(fac) * np.float32(4) / np.float32(3) * r).astype(np.float32)
+        return (f(fac) * f(4) / f(3) * r).astype(f)
     if typ == "linear":  # losses.py:23-25
-        return (np.float32(fac) * (one - np.sqrt(q))).astype(np.float32)
+        return (f(fac) * (one - np.sqrt(q))).astype(f)
     if typ == "peak":  # losses.py:28-30
         s = np.sqrt(q)
-        return (np.float32(fac) * (one - np.float32(2) * s + q)).astype(np.float32)
+        return (f(fac) * (one - f(2) * s + q)).astype(f)
     if typ == "cubic_grad":  # losses.py:33-39
         s = np.sqrt(q)
         r = np.where(q <= 1, np.where(s <= 0.5, 18 * q - 12 * s, -6 * (1 - s) ** 2), 0.0)
-        return (np.float32(fac) * np.float32(4) / np.float32(3) * r).astype(np.float32)
+        return (f(fac) * f(4) / f(3) * r).astype(f)
     if typ is None:
         return None
     raise NotImplementedError(typ)
@@ -223,10 +228,17 @@ def continuous_conv(filters, out_positions, extents, inp_positions, inp_features
 
 
 def filter_coordinates(rel, extent, kernel_size_zyx, align_corners=True,
-                       coordinate_mapping="ball_to_cube_volume_preserving"):
-    """Filter-array coordinates (x, y, z) of relative positions; for analytic mapping tests."""
+                       coordinate_mapping="ball_to_cube_volume_preserving", f64=False):
+    """Filter-array coordinates (x, y, z) of relative positions; for analytic mapping tests.  ``f64``: evaluated in double
+    (float64 result); ``extent`` may then be one extent per relative position."""
     rel = _f32(rel).reshape(-1, 3)
     ks = np.asarray(kernel_size_zyx, dtype=np.int32)
+    if f64:
+        ext = np.ascontiguousarray(np.broadcast_to(_f32(extent).reshape(-1), (rel.shape[0],)))
+        out = np.zeros(rel.shape, dtype=np.float64)
+        lib().dmcf_ref_filter_coordinates_f64(_ptr(rel), rel.shape[0], _ptr(ext), _ptr(ks), int(align_corners),
+                                              MAPPINGS[coordinate_mapping], _ptr(out))
+        return out
     out = np.zeros_like(rel)
     lib().dmcf_ref_filter_coordinates(_ptr(rel), rel.shape[0], float(extent), _ptr(ks), int(align_corners),
                                       MAPPINGS[coordinate_mapping], _ptr(out))

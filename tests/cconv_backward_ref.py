@@ -73,13 +73,28 @@ def rows_of(row_splits, n_pairs, row_count=None):
     return np.asarray(ii, dtype=np.int64), np.asarray(pp, dtype=np.int64)
 
 
+def _coordinates(rel, extent, dims, align_corners, mapping, f64):
+    """oracle.filter_coordinates per pair; ``extent``: a scalar or one extent per pair."""
+    if f64:
+        return oracle.filter_coordinates(rel, extent, dims, align_corners, mapping, f64=True)
+    if np.ndim(extent) == 0:
+        return oracle.filter_coordinates(rel, extent, dims, align_corners, mapping)
+    c = np.zeros(rel.shape, np.float32)
+    for e in np.unique(extent):
+        sel = extent == e
+        c[sel] = oracle.filter_coordinates(rel[sel], e, dims, align_corners, mapping)
+    return c
+
+
 class PairWeights:
     """The constants of a layer call: per pair (i, j), the window value (psi term), the pair weight a_p (times s_j), and the
-    8 (cell, interpolation weight) corners."""
+    8 (cell, interpolation weight) corners.  ``extent``: a scalar, or one extent per output row (dmcf_cconv_forward_extents).
+    ``f64``: the filter coordinates (kept in ``coords``) and the window are evaluated in double from the float32 relative
+    positions and squared distances, not taken from the float32 oracle."""
 
     def __init__(self, out_pos, inp_pos, idx, row_splits, extent, full_dims, window=None, window_fac=1.0, nval=None,
                  inp_importance=None, align_corners=True, mapping="ball_to_cube_volume_preserving", interpolation="linear",
-                 skip_self=False, row_count=None):
+                 skip_self=False, row_count=None, f64=False):
         out_pos = np.asarray(out_pos, dtype=np.float32)
         inp_pos = np.asarray(inp_pos, dtype=np.float32)
         idx = np.asarray(idx, dtype=np.int64)
@@ -87,7 +102,9 @@ class PairWeights:
         jj = idx[pp]
         self.i, self.j, self.p = ii, jj, pp
         rel = (inp_pos[jj] - out_pos[ii]).astype(np.float32)
-        radius = np.float32(0.5) * np.float32(extent)
+        if np.ndim(extent) > 0:
+            extent = np.asarray(extent, dtype=np.float32).reshape(-1)[ii]
+        radius = np.float32(0.5) * np.asarray(extent, dtype=np.float32)
         if window is None:
             a = np.ones(len(pp))
         elif window == "explicit":
@@ -97,7 +114,10 @@ class PairWeights:
                 d2 = np.asarray(nval, dtype=np.float32)[pp]
             else:
                 d2 = ((rel[:, 0] * rel[:, 0] + rel[:, 1] * rel[:, 1]) + rel[:, 2] * rel[:, 2]).astype(np.float32)
-            a = oracle.window(window, d2 * (np.float32(1) / (radius * radius)), window_fac).astype(np.float64)
+            if f64:
+                a = oracle.window(window, d2.astype(np.float64) / np.square(radius.astype(np.float64)), window_fac, dtype=np.float64)
+            else:
+                a = oracle.window(window, d2 * (np.float32(1) / (radius * radius)), window_fac).astype(np.float64)
         if skip_self:
             a = np.where((ii == jj) | np.all(rel == 0, axis=1), 0.0, a)
         self.norm_term = a.copy()
@@ -105,7 +125,8 @@ class PairWeights:
             a = a * np.asarray(inp_importance, dtype=np.float32)[jj].astype(np.float64)
         self.a = a
         dz, dy, dx = full_dims
-        c = oracle.filter_coordinates(rel, extent, (dz, dy, dx), align_corners, mapping) if len(pp) else np.zeros((0, 3), np.float32)
+        c = _coordinates(rel, extent, (dz, dy, dx), align_corners, mapping, f64) if len(pp) else np.zeros((0, 3), np.float32)
+        self.coords, self.dims = c, (dz, dy, dx)
         bx, wx0, wx1 = _axis(c[:, 0], dx, interpolation)
         by, wy0, wy1 = _axis(c[:, 1], dy, interpolation)
         bz, wz0, wz1 = _axis(c[:, 2], dz, interpolation)

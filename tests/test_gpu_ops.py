@@ -603,6 +603,11 @@ def test_filter_tile_mask_of_a_block_diagonal_pair(oracle, dev, monkeypatch, ker
     _close(hinted[:, oa:].cpu().numpy(), ref_b)
 
 
+# the name dmcf_cconv_kernel_name gives each forced kernel (DMCF_CCONV_KERNEL)
+_FORCED = {"lds": "cconv_kernel<", "mfma": "cconv_mfma_kernel", "blk": "cconv_blk_kernel<", "cls": "cconv_cls_kernel<",
+           "z3": "cconv_z3_kernel<", "pair": "cconv_pair_kernel<", "ws": "cconv_ws_kernel<", "g16": "cconv_p16_kernel<"}
+
+
 @pytest.mark.parametrize("kernel", ["lds", "mfma", "blk", "cls", "z3", "pair", "ws", "g16"])
 @pytest.mark.parametrize("cin,cout,ks,dim", [(16, 16, (4, 4, 4), 3), (4, 32, (4, 4, 4), 3), (24, 8, (1, 8, 8), 2), (32, 64, (1, 4, 4), 2),
                                             (7, 8, (1, 8, 1), 1), (9, 5, (3, 5, 2), 3)])
@@ -616,6 +621,11 @@ def test_both_splat_kernels_match_oracle(oracle, dev, monkeypatch, kernel, cin, 
     nns = ops.fixed_radius_search(_t(inp, dev), _t(out, dev), radius, return_distances=True)
     idx, rs, d = (x.cpu().numpy() for x in nns)
     ref = oracle.continuous_conv(filt, out, 2 * radius, inp, feat, idx, rs, oracle.window("poly6", d / np.float32(radius) ** 2), f64=True)
+    # "blk" .. "g16" exist for 4x4x4 filters only: on the other shapes no kernel accepts the forced name but the generic one
+    want = _FORCED[kernel] if kernel in ("lds", "mfma") or ks == (4, 4, 4) else "cconv_kernel<"
+    assert ops.cconv_forward(_t(filt, dev), _t(out, dev), 2 * radius, _t(inp, dev), _t(feat, dev), nns.neighbors_index,
+                             nns.neighbors_row_splits, neighbors_value=nns.neighbors_distance, window="poly6",
+                             name_only=True).startswith(want)
     y = ops.cconv_forward(_t(filt, dev), _t(out, dev), 2 * radius, _t(inp, dev), _t(feat, dev), nns.neighbors_index,
                           nns.neighbors_row_splits, neighbors_value=nns.neighbors_distance, window="poly6")
     _close(y.cpu().numpy(), ref)
@@ -630,6 +640,10 @@ def test_pair_per_instruction_kernel(oracle, dev, monkeypatch, kernel, cin, cout
     MFMA): rows from empty to several batches, every channel-chunk count, bias + accumulate, and the antisymmetric form."""
     from dmcf_amd import ops
     monkeypatch.setenv("DMCF_CCONV_KERNEL", kernel)
+    # "blk" and "cls" take every case; the others have no antisymmetric form and stop at 32 input channels ("g16": 16; "ws":
+    # 32 output channels too): those combinations are fallback-order cases, and only the generic kernel accepts the forced name
+    own = kernel in ("blk", "cls") or (not sym and cin <= (16 if kernel == "g16" else 32) and (kernel != "ws" or cout <= 32))
+    want = _FORCED[kernel] if own else "cconv_kernel<"
     rng = np.random.default_rng(5)
     if sym:
         n = 2500
@@ -639,6 +653,9 @@ def test_pair_per_instruction_kernel(oracle, dev, monkeypatch, kernel, cin, cout
         nns = ops.fixed_radius_search(_t(pos, dev), _t(pos, dev), radius, ignore_query_point=True, return_distances=True)
         conv = oracle.ContinuousConvRef(k, window_function="peak", ignore_query_points=True, symmetric=True, sym_axis=1, f64=True)
         ref = conv(feat, pos, pos, 2 * radius, nns=tuple(x.cpu().numpy() for x in nns))
+        assert ops.cconv_forward(_t(k, dev), _t(pos, dev), 2 * radius, _t(pos, dev), _t(feat, dev), nns.neighbors_index,
+                                 nns.neighbors_row_splits, neighbors_value=nns.neighbors_distance, window="peak",
+                                 symmetric=True, sym_axis=1, name_only=True).startswith(want)
         y = ops.cconv_forward(_t(k, dev), _t(pos, dev), 2 * radius, _t(pos, dev), _t(feat, dev), nns.neighbors_index,
                               nns.neighbors_row_splits, neighbors_value=nns.neighbors_distance, window="peak",
                               symmetric=True, sym_axis=1).cpu().numpy()
@@ -657,6 +674,10 @@ def test_pair_per_instruction_kernel(oracle, dev, monkeypatch, kernel, cin, cout
     ref = oracle.continuous_conv(filt, out, 2 * radius, inp, feat, idx, rs, oracle.window("poly6", d / np.float32(radius) ** 2),
                                  inp_importance=pimp, f64=True)
     acc = torch.full((out.shape[0], cout), 0.5, device=dev)
+    assert ops.cconv_forward(_t(filt, dev), _t(out, dev), 2 * radius, _t(inp, dev), _t(feat, dev), nns.neighbors_index,
+                             nns.neighbors_row_splits, neighbors_value=nns.neighbors_distance, window="poly6",
+                             inp_importance=_t(pimp, dev), bias=_t(bias, dev), out=acc, accumulate=True,
+                             name_only=True).startswith(want)
     ops.cconv_forward(_t(filt, dev), _t(out, dev), 2 * radius, _t(inp, dev), _t(feat, dev), nns.neighbors_index,
                       nns.neighbors_row_splits, neighbors_value=nns.neighbors_distance, window="poly6",
                       inp_importance=_t(pimp, dev), bias=_t(bias, dev), out=acc, accumulate=True)
