@@ -29,8 +29,6 @@
 //   * consecutive tiles go to the same XCD (blockIdx swizzle) so neighbouring outputs share one L2.
 //   * individual extents (continuous_conv with extents [n_out, 1], dmcf_cconv_forward_extents): the same kernel with the extent
 //     of each output row read once per row (cconv_ext_kernel; the body is cconv_generic_body.inc).
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include <stdio.h>
@@ -207,11 +205,6 @@ static int validate(const dmcf_cconv_args* a, bool forward = true) {
     return DMCF_OK;
 }
 
-static bool specialised(const dmcf_cconv_args* a) {
-    return a->coordinate_mapping == DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING && a->interpolation == DMCF_INTERP_LINEAR &&
-           (a->flags & DMCF_FLAG_ALIGN_CORNERS);
-}
-
 static void full_dims(const dmcf_cconv_args* a, int& dz, int& dy, int& dx) {
     dz = a->filter_dims[0]; dy = a->filter_dims[1]; dx = a->filter_dims[2];
     if (a->flags & DMCF_FLAG_SYMMETRIC) {
@@ -219,25 +212,6 @@ static void full_dims(const dmcf_cconv_args* a, int& dz, int& dy, int& dx) {
         if (a->sym_axis == 1) dy *= 2;
         if (a->sym_axis == 2) dx *= 2;
     }
-}
-
-size_t dmcf_cconv_workspace_bytes(const dmcf_cconv_args* a) {
-    if (!a || validate(a) != DMCF_OK) return 256;
-    int dz, dy, dx;
-    full_dims(a, dz, dy, dx);
-    const LaunchCfg cfg = make_cfg(dx, dy, dz, a->filter_dims[3], a->filter_dims[4]);
-    size_t floats = cfg.packed_floats;
-    size_t mf = cconv_mfma_packed_floats(dz * dy * dx, a->filter_dims[3], a->filter_dims[4]);
-    if (cconv_mfma_eligible(dz * dy * dx, a->filter_dims[3], a->filter_dims[4]))  // (+ the chunks' partial sums of a small launch)
-        mf = align_up(mf, 64) + cconv_mfma_partial_floats(dz * dy * dx, a->filter_dims[3], a->filter_dims[4], a->n_out);
-    if (floats < mf) floats = mf;
-    const size_t bf = cconv_blk_packed_floats(a->filter_dims[3], a->filter_dims[4]);
-    if (floats < bf) floats = bf;
-    const size_t cf = cconv_cls_packed_floats(a->filter_dims[3], a->filter_dims[4]);
-    if (floats < cf) floats = cf;
-    const size_t df = cconv_direct_packed_floats(dz, dy, dx, a->filter_dims[3]);
-    if (floats < df) floats = df;
-    return 256 + align_up(floats * sizeof(float), 256);
 }
 
 // the fields of CconvParams every form takes from the arguments as they are
@@ -273,23 +247,33 @@ static void fill_params(const dmcf_cconv_args* a, int dz, int dy, int dx, CconvP
     p.out = a->out;
 }
 
-// The generic LDS-splat kernel: its own filter packing and LDS budget (every specialised kernel packs its own layout into the
-// same workspace and has its own limits).  out_ext != NULL: cconv_ext_kernel, which always packs.
-static int launch_generic(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, const float* out_ext, void* workspace,
-                          hipStream_t stream) {
-    const bool ext = out_ext != nullptr;
+// ---- the generic LDS-splat form: any filter shape and flag set, its own filter packing and LDS budget.  Last in the table, and
+// alone behind dmcf_cconv_forward_extents (ext: cconv_ext_kernel, which always packs).
+static void generic_pick(const dmcf_cconv_args* a, int dz, int dy, int dx, bool ext, CconvPick& k) {
+    const LaunchCfg cfg = make_cfg(dx, dy, dz, a->filter_dims[3], a->filter_dims[4]);
+    // the flag set every DMCF model uses gets a specialised instantiation (the printed name does not tell the two apart)
+    const bool generic = !cconv_specialised(a);
+    CconvKernel f;
+    if (ext)
+        f = cfg.CC == 8 ? CCONV_KERNEL(cconv_ext_kernel<8>) : CCONV_KERNEL(cconv_ext_kernel<4>);
+    else if (cfg.CC == 8)
+        f = {generic ? (const void*)cconv_kernel<8, true> : (const void*)cconv_kernel<8, false>, "cconv_kernel<8>"};
+    else
+        f = {generic ? (const void*)cconv_kernel<4, true> : (const void*)cconv_kernel<4, false>, "cconv_kernel<4>"};
+    k = {f.fn, f.name, cfg.lds, kThreads, cfg.packed_floats};
+}
+
+static int generic_launch(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, const CconvPick& k, const float* out_ext,
+                          void* workspace, hipStream_t stream) {
     const LaunchCfg cfg = make_cfg(dx, dy, dz, p.cin, p.cout);
     if (cfg.lds > 160 * 1024) return DMCF_EUNSUPPORTED;
-    {
-        float* packed = (float*)workspace;
-        const int64_t total = (int64_t)cfg.packed_floats;
-        const unsigned g = (unsigned)((total + 255) / 256);
-        if (ext || !(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
-            hipLaunchKernelGGL(pack_filter, dim3(g < 2048u ? g : 2048u), dim3(256), 0, stream, a->filters, packed, dz, dy, dx,
+    float* packed = (float*)workspace;
+    const unsigned g = (unsigned)((cfg.packed_floats + 255) / 256);
+    if (out_ext || !(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
+        hipLaunchKernelGGL(pack_filter, dim3(g < 2048u ? g : 2048u), dim3(256), 0, stream, a->filters, packed, dz, dy, dx,
                            p.cin, p.cout, cfg.CC, cfg.PS, cfg.nchunks, cfg.nblocks, cfg.NT,
                            (a->flags & DMCF_FLAG_SYMMETRIC) ? 1 : 0, a->sym_axis);
-        p.Wp = packed;
-    }
+    p.Wp = packed;
     p.KCp = cfg.KCp;
     p.PS = cfg.PS;
     p.zgroup = cfg.zgroup;
@@ -297,30 +281,60 @@ static int launch_generic(CconvParams p, const dmcf_cconv_args* a, int dz, int d
     p.NT = cfg.NT;
     p.nchunks = cfg.nchunks;
     p.bfloats = (int)cfg.bfloats;
-    const int64_t ntiles = (a->n_out + TM - 1) / TM;
-    if (ntiles > 0x7fffffff / 8) return DMCF_EUNSUPPORTED;
-    p.ntiles = (int)ntiles;
-    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
-    const unsigned grid = (unsigned)p.tiles_per_xcd * 8u;
-    // the flag set every DMCF model uses (models/pbf_model.py:210-221) gets a specialised instantiation
-    const bool generic = !specialised(a);
-    const void* fn;
-    if (ext)
-        fn = cfg.CC == 8 ? (const void*)cconv_ext_kernel<8> : (const void*)cconv_ext_kernel<4>;
-    else if (cfg.CC == 8)
-        fn = generic ? (const void*)cconv_kernel<8, true> : (const void*)cconv_kernel<8, false>;
-    else
-        fn = generic ? (const void*)cconv_kernel<4, true> : (const void*)cconv_kernel<4, false>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return DMCF_ELAUNCH; }
+    if (!cconv_set_tiles(p, TM)) return DMCF_EUNSUPPORTED;
     void* kargs[] = {(void*)&p, (void*)&out_ext};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(kThreads), kargs, cfg.lds, stream);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return DMCF_ELAUNCH; }
-    return check_launch();
+    return cconv_launch_kernel(k, dim3((unsigned)p.tiles_per_xcd * 8u), kargs, stream);
+}
+
+static const CconvForm generic_form = {
+    0, [](const dmcf_cconv_args*, int, int, int, bool) { return true; },
+    [](const dmcf_cconv_args* a, int dz, int dy, int dx, CconvPick& k) { generic_pick(a, dz, dy, dx, false, k); },
+    [](const dmcf_cconv_args* a, int dz, int dy, int dx, bool) {
+        return make_cfg(dx, dy, dz, a->filter_dims[3], a->filter_dims[4]).packed_floats;
+    },
+    [](CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, const CconvPick& k, void* workspace, hipStream_t stream) {
+        return generic_launch(p, a, dz, dy, dx, k, nullptr, workspace, stream);
+    }};
+
+// ---- THE dispatch table of dmcf_cconv_forward: the first form that accepts a call takes it.  A new form is one more row here (and
+// its CconvForm next to its kernel); the kernel name, the workspace size and the launch all follow from the row.
+static const CconvForm* const kForms[] = {&cconv_direct_form, &cconv_ws_form,  &cconv_pair_form, &cconv_p16_form, &cconv_z3_form,
+                                          &cconv_cls_form,    &cconv_blk_form, &cconv_mfma_form, &generic_form};
+
+// could the dispatch give the call to this form, were no earlier one to take it?  forced: cconv_forced_key()
+static bool form_accepts(const CconvForm& f, const dmcf_cconv_args* a, int dz, int dy, int dx, int forced) {
+    if (f.key && forced >= 0 && forced != f.key) return false;
+    return f.eligible(a, dz, dy, dx, forced >= 0);
+}
+
+// The form validated arguments dispatch to, and what it launches for them.
+static int cconv_select(const dmcf_cconv_args* a, int dz, int dy, int dx, const CconvForm*& form, CconvPick& k) {
+    const int forced = cconv_forced_key();
+    for (const CconvForm* f : kForms) {
+        if (!form_accepts(*f, a, dz, dy, dx, forced)) continue;
+        // (only the direct form tests a pair's index against its row)
+        if ((a->flags & DMCF_FLAG_SKIP_SELF) && f != &cconv_direct_form) return DMCF_EUNSUPPORTED;
+        form = f;
+        f->pick(a, dz, dy, dx, k);
+        return DMCF_OK;
+    }
+    return DMCF_EUNSUPPORTED;  // (not reached: the generic form accepts everything)
+}
+
+size_t dmcf_cconv_workspace_bytes(const dmcf_cconv_args* a) {
+    if (!a || validate(a) != DMCF_OK) return 256;
+    int dz, dy, dx;
+    full_dims(a, dz, dy, dx);
+    const int forced = cconv_forced_key();
+    size_t floats = 0;
+    for (const CconvForm* f : kForms) {
+        const size_t ff = f->workspace_floats(a, dz, dy, dx, form_accepts(*f, a, dz, dy, dx, forced));
+        if (floats < ff) floats = ff;
+    }
+    return 256 + align_up(floats * sizeof(float), 256);
 }
 
 int dmcf_cconv_forward(const dmcf_cconv_args* a, void* workspace, size_t workspace_bytes, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     int rc = validate(a);
     if (rc != DMCF_OK) return rc;
     if (a->n_out == 0) return DMCF_OK;
@@ -331,16 +345,11 @@ int dmcf_cconv_forward(const dmcf_cconv_args* a, void* workspace, size_t workspa
     int dz, dy, dx;
     full_dims(a, dz, dy, dx);
     fill_params(a, dz, dy, dx, p);
-    if (cconv_direct_eligible(a, dz, dy, dx)) return cconv_direct_launch(p, a, dz, dy, dx, workspace, stream);
-    if (a->flags & DMCF_FLAG_SKIP_SELF) return DMCF_EUNSUPPORTED;  // (only the direct form tests the index against the row)
-    if (cconv_ws_eligible(a, dz, dy, dx)) return cconv_ws_launch(p, a, workspace, stream);
-    if (cconv_pair_eligible(a, dz, dy, dx)) return cconv_pair_launch(p, a, workspace, stream);
-    if (cconv_p16_eligible(a, dz, dy, dx)) return cconv_p16_launch(p, a, workspace, stream);
-    if (cconv_z3_eligible(a, dz, dy, dx)) return cconv_z3_launch(p, a, workspace, stream);
-    if (cconv_cls_eligible(a, dz, dy, dx)) return cconv_cls_launch(p, a, workspace, stream);
-    if (cconv_blk_eligible(a, dz, dy, dx)) return cconv_blk_launch(p, a, workspace, stream);
-    if (cconv_mfma_eligible(p.K, p.cin, p.cout)) return cconv_mfma_launch(p, a, dz, dy, dx, workspace, stream);
-    return launch_generic(p, a, dz, dy, dx, nullptr, workspace, stream);
+    const CconvForm* form;
+    CconvPick k;
+    rc = cconv_select(a, dz, dy, dx, form, k);
+    if (rc != DMCF_OK) return rc;
+    return form->launch(p, a, dz, dy, dx, k, workspace, (hipStream_t)stream_);
 }
 
 // dmcf_cconv_forward_extents ignores args->extent: validate (and size the workspace) as for any positive one
@@ -368,7 +377,9 @@ int dmcf_cconv_forward_extents(const dmcf_cconv_args* a, const float* out_extent
     int dz, dy, dx;
     full_dims(&b, dz, dy, dx);
     fill_params(&b, dz, dy, dx, p);
-    return launch_generic(p, &b, dz, dy, dx, out_extents, workspace, stream);
+    CconvPick k;
+    generic_pick(&b, dz, dy, dx, true, k);
+    return generic_launch(p, &b, dz, dy, dx, k, out_extents, workspace, stream);
 }
 
 int dmcf_cconv_kernel_name(const dmcf_cconv_args* a, char* name, size_t name_bytes) {
@@ -377,28 +388,11 @@ int dmcf_cconv_kernel_name(const dmcf_cconv_args* a, char* name, size_t name_byt
     if (rc != DMCF_OK) return rc;
     int dz, dy, dx;
     full_dims(a, dz, dy, dx);
-    const int cin = a->filter_dims[3], cout = a->filter_dims[4], NT = (cout + 15) / 16;
-    const int ntt = NT <= 1 ? 1 : (NT <= 2 ? 2 : 4);
-    const bool sym = (a->flags & DMCF_FLAG_SYMMETRIC) != 0;
-    if (cconv_direct_eligible(a, dz, dy, dx))
-        snprintf(name, name_bytes, "cconv_direct_kernel<%d, %s>", cout, specialised(a) ? "false" : "true");
-    else if (cconv_ws_eligible(a, dz, dy, dx))
-        snprintf(name, name_bytes, "cconv_ws_kernel<%d, %s>", ntt, cconv_plain(a) ? "true" : "false");
-    else if (cconv_pair_eligible(a, dz, dy, dx))
-        snprintf(name, name_bytes, "cconv_pair_kernel<%d, %s>", ntt, cconv_plain(a) ? "true" : "false");
-    else if (cconv_p16_eligible(a, dz, dy, dx))
-        snprintf(name, name_bytes, "cconv_p16_kernel<%d, %s>", ntt, cconv_plain(a) ? "true" : "false");
-    else if (cconv_z3_eligible(a, dz, dy, dx))
-        snprintf(name, name_bytes, "cconv_z3_kernel<%d, %s>", ntt, cconv_plain(a) ? "true" : "false");
-    else if (cconv_cls_eligible(a, dz, dy, dx))
-        snprintf(name, name_bytes, "cconv_cls_kernel<%d, %s, %s, %s, %s>", ntt, cin <= 8 ? "true" : "false", sym ? "true" : "false",
-                 cin <= 16 ? "true" : "false", !sym && cconv_plain(a) ? "true" : "false");
-    else if (cconv_blk_eligible(a, dz, dy, dx))
-        snprintf(name, name_bytes, "cconv_blk_kernel<%d>", ntt);
-    else if (cconv_mfma_eligible(dz * dy * dx, cin, cout))
-        snprintf(name, name_bytes, "cconv_mfma_kernel");
-    else
-        snprintf(name, name_bytes, "cconv_kernel<%d>", make_cfg(dx, dy, dz, cin, cout).CC);
+    const CconvForm* form;
+    CconvPick k;
+    rc = cconv_select(a, dz, dy, dx, form, k);
+    if (rc != DMCF_OK) return rc;
+    snprintf(name, name_bytes, "%s", k.name);
     return DMCF_OK;
 }
 
@@ -411,7 +405,9 @@ int dmcf_cconv_extents_kernel_name(const dmcf_cconv_args* a, char* name, size_t 
     if (a->flags & DMCF_FLAG_SKIP_SELF) return DMCF_EUNSUPPORTED;
     int dz, dy, dx;
     full_dims(&b, dz, dy, dx);
-    snprintf(name, name_bytes, "cconv_ext_kernel<%d>", make_cfg(dx, dy, dz, b.filter_dims[3], b.filter_dims[4]).CC);
+    CconvPick k;
+    generic_pick(&b, dz, dy, dx, true, k);
+    snprintf(name, name_bytes, "%s", k.name);
     return DMCF_OK;
 }
 

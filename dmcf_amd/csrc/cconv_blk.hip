@@ -25,7 +25,6 @@
 //
 // Accumulation order = the (fixed) ordered-batch order, one fmaf per pair and cell (the MFMA is an exact fp32 fma):
 // deterministic.
-#include <stdlib.h>
 
 #include "cconv_common.h"
 
@@ -408,7 +407,7 @@ __global__ __launch_bounds__(kBThreads, BLK_OCC) void cconv_blk_kernel(const Cco
 
 static constexpr size_t kBlkLds = (size_t)(BTM * kRow + kBWaves * kFst) * sizeof(float);
 
-size_t cconv_blk_packed_floats(int cin, int cout) {
+static size_t blk_packed_floats(int cin, int cout) {
     const int nchunks = (cin + BCH - 1) / BCH, NT = (cout + 15) / 16;
     return (size_t)nchunks * (kRow / 16) * 4 * NT * 16 * 4;
 }
@@ -416,31 +415,30 @@ size_t cconv_blk_packed_floats(int cin, int cout) {
 // 4x4x4 filter, the flag set every DMCF model uses, 16-byte addressable feature rows.  Measured on MI355X (16
 // channels): 7.3 ms against 9.3 ms for the 16x16x4 splat at 3.07e8 pairs / 265 per output, 4.0 against 4.35 ms
 // at 3.3e7 pairs / 29 per output (32 -> 32): picked for every layer with at least 12 input channels.
-bool cconv_blk_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx) {
-    const char* e = getenv("DMCF_CCONV_KERNEL");  // "lds" / "mfma" / "blk": force one implementation (A/B tests)
-    if (e && e[0] != 'b') return false;
-    if (dx != 4 || dy != 4 || dz != 4) return false;
-    if (a->coordinate_mapping != DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING || a->interpolation != DMCF_INTERP_LINEAR ||
-        !(a->flags & DMCF_FLAG_ALIGN_CORNERS) || (a->flags & DMCF_FLAG_NORMALIZE))
-        return false;
-    const int cin = a->filter_dims[3], cout = a->filter_dims[4];
-    if ((cin & 3) || cout > 16 * kBMaxNT) return false;
-    if ((uintptr_t)a->inp_features & 15) return false;
-    if (e) return true;
-    return cin >= 12;
+static bool blk_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced) {
+    if (!cconv_fast444(a, dz, dy, dx) || a->filter_dims[4] > 16 * kBMaxNT) return false;
+    if (forced) return true;
+    return a->filter_dims[3] >= 12;
 }
 
-int cconv_blk_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream) {
+static void blk_pick(const dmcf_cconv_args* a, int, int, int, CconvPick& k) {
+    const int NT = (a->filter_dims[4] + 15) / 16;
+    const CconvKernel f = NT <= 1 ? CCONV_KERNEL(cconv_blk_kernel<1>)
+                                  : (NT <= 2 ? CCONV_KERNEL(cconv_blk_kernel<2>) : CCONV_KERNEL(cconv_blk_kernel<4>));
+    k = {f.fn, f.name, kBlkLds, kBThreads, blk_packed_floats(a->filter_dims[3], a->filter_dims[4])};
+}
+
+static size_t blk_workspace_floats(const dmcf_cconv_args* a, int, int, int, bool) {
+    return blk_packed_floats(a->filter_dims[3], a->filter_dims[4]);
+}
+
+static int blk_launch(CconvParams p, const dmcf_cconv_args* a, int, int, int, const CconvPick& k, void* workspace, hipStream_t stream) {
     const int nchunks = (p.cin + BCH - 1) / BCH, NT = (p.cout + 15) / 16, nblocks = kRow / 16;
     float* packed = (float*)workspace;
-    {
-        const int64_t total = (int64_t)cconv_blk_packed_floats(p.cin, p.cout);
-        const unsigned g = (unsigned)((total + 255) / 256);
-        if (!(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
-            hipLaunchKernelGGL(pack_filter, dim3(g < 2048u ? g : 2048u), dim3(256), 0, stream, a->filters, packed, 4, 4, 4, p.cin,
-                           p.cout, BCH, 16 * BCH, nchunks, nblocks, NT, (a->flags & DMCF_FLAG_SYMMETRIC) ? 1 : 0,
-                           a->sym_axis);
-    }
+    const unsigned g = (unsigned)((k.packed_floats + 255) / 256);
+    if (!(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
+        hipLaunchKernelGGL(pack_filter, dim3(g < 2048u ? g : 2048u), dim3(256), 0, stream, a->filters, packed, 4, 4, 4, p.cin,
+                           p.cout, BCH, 16 * BCH, nchunks, nblocks, NT, (a->flags & DMCF_FLAG_SYMMETRIC) ? 1 : 0, a->sym_axis);
     p.Wp = packed;
     p.KT = 4;
     p.KCp = kRow;
@@ -448,25 +446,11 @@ int cconv_blk_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, h
     p.NT = NT;
     p.nchunks = nchunks;
     p.bfloats = BTM * kRow;
-    const int64_t ntiles = (p.n_out + BTM - 1) / BTM;
-    if (ntiles > 0x7fffffff / 8) return DMCF_EUNSUPPORTED;
-    p.ntiles = (int)ntiles;
-    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
-    const unsigned grid = (unsigned)p.tiles_per_xcd * 8u;
-    const void* fn = NT <= 1 ? (const void*)cconv_blk_kernel<1>
-                             : (NT <= 2 ? (const void*)cconv_blk_kernel<2> : (const void*)cconv_blk_kernel<4>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBlkLds);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
+    if (!cconv_set_tiles(p, BTM)) return DMCF_EUNSUPPORTED;
     void* kargs[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(kBThreads), kargs, kBlkLds, stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    return check_launch();
+    return cconv_launch_kernel(k, dim3((unsigned)p.tiles_per_xcd * 8u), kargs, stream);
 }
+
+CconvForm cconv_blk_form = {'b', blk_eligible, blk_pick, blk_workspace_floats, blk_launch};
 
 }  // namespace dmcf

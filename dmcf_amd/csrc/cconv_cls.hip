@@ -28,7 +28,6 @@
 // point, which is free until that point's tiles are merged.
 //
 // Accumulation order = the ordered-batch order (stable inside a class), then the fixed merge order: deterministic.
-#include <stdlib.h>
 
 #include "cconv_common.h"
 
@@ -624,74 +623,50 @@ __global__ void pack_filter_cls(const float* __restrict__ src, float* __restrict
 // 4.7 (LDS splat); at 29 pairs per output (32 -> 32, one batch per point) 4.2 against 4.1 ms.  Picked for at least 8 input
 // channels; the rule must not look at the list (capacity, padding): the same step gives bit-identical results whichever
 // neighbour-list representation it runs on.
-bool cconv_cls_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx) {
-    const char* e = getenv("DMCF_CCONV_KERNEL");  // "lds" / "mfma" / "blk" / "cls" / "direct": force one implementation
-    if (e && e[0] != 'c') return false;
-    if (dx != 4 || dy != 4 || dz != 4) return false;
-    if (a->coordinate_mapping != DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING || a->interpolation != DMCF_INTERP_LINEAR ||
-        !(a->flags & DMCF_FLAG_ALIGN_CORNERS) || (a->flags & DMCF_FLAG_NORMALIZE))
-        return false;
-    const int cin = a->filter_dims[3], cout = a->filter_dims[4];
-    if ((cin & 3) || cout > 16 * kCMaxNT) return false;
-    if ((uintptr_t)a->inp_features & 15) return false;
-    // 24-bit multiplies form the byte offsets of feature and position rows; the feature buffer must stay below 2 GB
-    if (a->n_inp >= (1 << 24) || a->n_inp * (int64_t)cin * 4 >= ((int64_t)1 << 31)) return false;
-    if (e) return true;
-    return cin >= 8;
+static bool cls_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced) {
+    if (!cconv_fast444(a, dz, dy, dx) || !cconv_offsets_fit_24bit(a)) return false;
+    if (a->filter_dims[4] > 16 * kCMaxNT) return false;
+    if (forced) return true;
+    return a->filter_dims[3] >= 8;
 }
 
-int cconv_cls_pack(const dmcf_cconv_args* a, float* packed, hipStream_t stream) {
-    const int cin = a->filter_dims[3], cout = a->filter_dims[4];
-    const int nchunks = (cin + CCH - 1) / CCH, NT = (cout + 15) / 16;
-    const int64_t total = (int64_t)cconv_cls_packed_floats(cin, cout);
+size_t cconv_cls_workspace_floats(const dmcf_cconv_args* a, int, int, int, bool) {
+    return cconv_cls_packed_floats(a->filter_dims[3], a->filter_dims[4]);
+}
+
+bool cconv_cls_prepare(CconvParams& p, const dmcf_cconv_args* a, int tm, void* workspace, hipStream_t stream) {
+    float* packed = (float*)workspace;
+    p.NT = (p.cout + 15) / 16;
+    p.nchunks = (p.cin + CCH - 1) / CCH;
+    const int64_t total = (int64_t)cconv_cls_packed_floats(p.cin, p.cout);
     const unsigned g = (unsigned)((total + 255) / 256);
     if (!(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
-        hipLaunchKernelGGL(pack_filter_cls, dim3(g < 2048u ? g : 2048u), dim3(256), 0, stream, a->filters, packed, cin, cout, nchunks,
-                       NT, (a->flags & DMCF_FLAG_SYMMETRIC) ? 1 : 0, a->sym_axis);
-    return nchunks;
+        hipLaunchKernelGGL(pack_filter_cls, dim3(g < 2048u ? g : 2048u), dim3(256), 0, stream, a->filters, packed, p.cin, p.cout,
+                           p.nchunks, p.NT, (a->flags & DMCF_FLAG_SYMMETRIC) ? 1 : 0, a->sym_axis);
+    p.Wp = packed;
+    return cconv_set_tiles(p, tm);
 }
 
-int cconv_cls_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream) {
-    const int NT = (p.cout + 15) / 16;
-    float* packed = (float*)workspace;
-    const int nchunks = cconv_cls_pack(a, packed, stream);
-    p.Wp = packed;
-    p.NT = NT;
-    p.nchunks = nchunks;
-    const int64_t ntiles = (p.n_out + CTM - 1) / CTM;
-    if (ntiles > 0x7fffffff / 8) return DMCF_EUNSUPPORTED;
-    p.ntiles = (int)ntiles;
-    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
-    const unsigned grid = (unsigned)p.tiles_per_xcd * 8u;
-    const bool sym = (p.flags & DMCF_FLAG_SYMMETRIC) != 0;
-    const void* fn;
+static void cls_pick(const dmcf_cconv_args* a, int, int, int, CconvPick& k) {
+    const int cin = a->filter_dims[3], NT = (a->filter_dims[4] + 15) / 16;
+    const bool sym = (a->flags & DMCF_FLAG_SYMMETRIC) != 0;
     const bool plain = !sym && cconv_plain(a);  // (ASCC's window is not poly6: no antisymmetric plain instantiations)
-#define CLS_PICK(NARROW, SYM, SINGLE, PLAIN)                                                                       \
-    (NT <= 1 ? (const void*)cconv_cls_kernel<1, NARROW, SYM, SINGLE, PLAIN>                                         \
-             : (NT <= 2 ? (const void*)cconv_cls_kernel<2, NARROW, SYM, SINGLE, PLAIN>                              \
-                        : (const void*)cconv_cls_kernel<4, NARROW, SYM, SINGLE, PLAIN>))
-#define CLS_PICK2(NARROW, SINGLE) \
-    (sym ? CLS_PICK(NARROW, true, SINGLE, false) : (plain ? CLS_PICK(NARROW, false, SINGLE, true) : CLS_PICK(NARROW, false, SINGLE, false)))
-    if (p.cin <= 8)
-        fn = CLS_PICK2(true, true);
-    else if (nchunks == 1)
-        fn = CLS_PICK2(false, true);
-    else
-        fn = CLS_PICK2(false, false);
-#undef CLS_PICK2
+#define CLS_PICK(NARROW, SINGLE)                                                                \
+    (sym ? CCONV_KERNEL_NT(NT, cconv_cls_kernel, NARROW, true, SINGLE, false)                   \
+         : (plain ? CCONV_KERNEL_NT(NT, cconv_cls_kernel, NARROW, false, SINGLE, true)          \
+                  : CCONV_KERNEL_NT(NT, cconv_cls_kernel, NARROW, false, SINGLE, false)))
+    // (narrow: at most 8 channels; single: one 16-channel chunk)
+    const CconvKernel f = cin <= 8 ? CLS_PICK(true, true) : (cin <= CCH ? CLS_PICK(false, true) : CLS_PICK(false, false));
 #undef CLS_PICK
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClsLds);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    void* kargs[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(kCThreads), kargs, kClsLds, stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    return check_launch();
+    k = {f.fn, f.name, kClsLds, kCThreads, cconv_cls_packed_floats(cin, a->filter_dims[4])};
 }
+
+static int cls_launch(CconvParams p, const dmcf_cconv_args* a, int, int, int, const CconvPick& k, void* workspace, hipStream_t stream) {
+    if (!cconv_cls_prepare(p, a, CTM, workspace, stream)) return DMCF_EUNSUPPORTED;
+    void* kargs[] = {(void*)&p};
+    return cconv_launch_kernel(k, dim3((unsigned)p.tiles_per_xcd * 8u), kargs, stream);
+}
+
+CconvForm cconv_cls_form = {'c', cls_eligible, cls_pick, cconv_cls_workspace_floats, cls_launch};
 
 }  // namespace dmcf

@@ -1,6 +1,10 @@
-// Device helpers shared by the two CConv kernels (cconv.hip: LDS read-modify-write splat, any filter size;
-// cconv_mfma.hip: matrix-core splat for filters of up to 64 cells).  Not part of the C ABI.
+// Shared by the forward CConv kernel files (cconv.hip and cconv_<form>.hip, one neighbour-list form each; the backward, lattice and
+// scatter files use the device half): the kernels' parameter block and per-pair math, and the host side of the forward dispatch
+// -- what a form registers in the table of cconv.hip, the predicates the forms' eligibility rules share, the launch helper.
+// Not part of the C ABI.
 #pragma once
+#include <stdlib.h>
+
 #include "common.h"
 
 namespace dmcf {
@@ -234,28 +238,10 @@ __device__ __forceinline__ void blk_divmod(int t, int nq, int& quot, int& rem) {
 
 
 
-// defined in cconv.hip, also used by the matrix-core path
+// defined in cconv.hip, also used by the matrix-core and the block-splat forms
 __global__ void pack_filter(const float* __restrict__ src, float* __restrict__ dst, int d0, int d1, int d2, int cin,
                             int cout, int CC, int PS, int nchunks, int nblocks, int NT, int symmetric, int sym_axis);
 
-// cconv_mfma.hip
-bool cconv_mfma_eligible(int K, int cin, int cout);
-size_t cconv_mfma_packed_floats(int K, int cin, int cout);
-size_t cconv_mfma_partial_floats(int K, int cin, int cout, int64_t n_out);  // (0: the launch does not split its chunks)
-int cconv_mfma_launch(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, void* workspace, hipStream_t stream);
-
-
-// cconv_blk.hip
-bool cconv_blk_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx);
-size_t cconv_blk_packed_floats(int cin, int cout);
-int cconv_blk_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream);
-
-
-// cconv_cls.hip
-bool cconv_cls_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx);
-size_t cconv_cls_packed_floats(int cin, int cout);
-int cconv_cls_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream);
-int cconv_cls_pack(const dmcf_cconv_args* a, float* packed, hipStream_t stream);  // enqueues the packing, returns the chunk count
 // DMCF_FLAG_ACCUMULATE: the value the epilogue adds to, requested EARLY (before the contraction): read in the epilogue itself it is
 // a dependent round trip at the very end of every tile, with nothing left to hide it -- as long as the elementwise kernel it
 // replaces.  A tile's outputs are contiguous (point-major): element e = point * cout + channel sits at out + pt0 * cout + e; this
@@ -266,6 +252,72 @@ __device__ __forceinline__ float epilogue_prefetch(const CconvParams& p, int64_t
     return tid < lim ? p.out[pt0 * p.cout + tid] : 0.0f;
 }
 
+// ---- host side: the forward dispatch (the table and the selection are in cconv.hip) ----------------------------------------------
+
+// What a form launches for one set of arguments.
+struct CconvPick {
+    const void* fn;        // the kernel instantiation ...
+    const char* name;      // ... and how dmcf_cconv_kernel_name prints it
+    size_t lds;            // dynamic LDS bytes
+    int threads;           // workgroup size
+    size_t packed_floats;  // the packed filter at the head of the workspace
+};
+
+// An instantiation and its printed name from one expression: CCONV_KERNEL(cconv_pair_kernel<2, true>).  CCONV_KERNEL_NT: the
+// instantiation for nt = ceil(cout / 16) column tiles of a kernel template whose first argument is 1, 2 or 4 of them.
+struct CconvKernel {
+    const void* fn;
+    const char* name;
+};
+#define CCONV_KERNEL(...) CconvKernel{(const void*)__VA_ARGS__, #__VA_ARGS__}
+#define CCONV_KERNEL_NT(nt, K, ...) \
+    ((nt) <= 1 ? CCONV_KERNEL(K<1, __VA_ARGS__>) : ((nt) <= 2 ? CCONV_KERNEL(K<2, __VA_ARGS__>) : CCONV_KERNEL(K<4, __VA_ARGS__>)))
+
+// One row of the dispatch table.  dz, dy, dx: the filter's full shape (an antisymmetric one unfolded).
+struct CconvForm {
+    char key;  // first letter of the DMCF_CCONV_KERNEL value that forces the form (0: the generic form, which nothing bars)
+    // the form's own limits, and -- unless forced -- its measured auto-rule
+    bool (*eligible)(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced);
+    // what an eligible call launches
+    void (*pick)(const dmcf_cconv_args* a, int dz, int dy, int dx, CconvPick& k);
+    // Workspace floats to reserve for the form.  A bound over everything the layer's dims admit, NOT over what these arguments
+    // select: a caller keeps one workspace per layer across calls whose flags, pointers and environment differ.  selectable: the
+    // dispatch could pick the form for these arguments (only the matrix-core form's partial sums depend on it).
+    size_t (*workspace_floats)(const dmcf_cconv_args* a, int dz, int dy, int dx, bool selectable);
+    int (*launch)(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, const CconvPick& k, void* workspace,
+                  hipStream_t stream);
+};
+// (not const: a const object with external linkage is emitted into the device code object too, where the host functions it
+// points to do not exist; nothing writes them)
+extern CconvForm cconv_direct_form, cconv_ws_form, cconv_pair_form, cconv_p16_form, cconv_z3_form, cconv_cls_form,
+    cconv_blk_form, cconv_mfma_form;
+
+// DMCF_CCONV_KERNEL forces one form for A/B tests by the first letter of its value: "direct", "ws", "pair", "g16", "z3", "cls",
+// "blk", "mfma"; any other value ("lds", a typo, the empty string) bars every specialised form, so the generic kernel takes the
+// call.  -1: unset.  Read at every call: tests switch it inside one process.
+inline int cconv_forced_key() {
+    const char* e = getenv("DMCF_CCONV_KERNEL");
+    return e ? (unsigned char)e[0] : -1;
+}
+
+// the flag set every DMCF model uses (models/pbf_model.py:210-221): the kernels have instantiations with it compiled in
+inline bool cconv_specialised(const dmcf_cconv_args* a) {
+    return a->coordinate_mapping == DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING && a->interpolation == DMCF_INTERP_LINEAR &&
+           (a->flags & DMCF_FLAG_ALIGN_CORNERS);
+}
+
+// The "fast 4x4x4 layer" every block / class splat is written for: 4x4x4 filter, the models' flag set without normalisation,
+// input channels in quads and 16-byte addressable feature rows.
+inline bool cconv_fast444(const dmcf_cconv_args* a, int dz, int dy, int dx) {
+    return dx == 4 && dy == 4 && dz == 4 && cconv_specialised(a) && !(a->flags & DMCF_FLAG_NORMALIZE) && !(a->filter_dims[3] & 3) &&
+           !((uintptr_t)a->inp_features & 15);
+}
+
+// 24-bit multiplies form the byte offsets of feature and position rows; the feature buffer must stay below 2 GB
+inline bool cconv_offsets_fit_24bit(const dmcf_cconv_args* a) {
+    return a->n_inp < (1 << 24) && a->n_inp * (int64_t)a->filter_dims[3] * 4 < ((int64_t)1 << 31);
+}
+
 // The "plain" layer: poly6 window on squared distances re-formed from the positions, no per-point importance -- every CConv of
 // the networks here once the lists carry no distances.  Splats D and E have instantiations with these three choices compiled
 // in: the window's branch ladder, the distance / importance loads and their predicates otherwise run once per batch.
@@ -273,29 +325,31 @@ inline bool cconv_plain(const dmcf_cconv_args* a) {
     return a->window == DMCF_WINDOW_POLY6 && !a->neighbors_value && !a->inp_importance;
 }
 
-// cconv_z3.hip
-bool cconv_z3_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx);
-int cconv_z3_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream);
+// Tiles of tm output points, an eighth of them per XCD (the kernels' blockIdx swizzle).  false: more than an int indexes.
+inline bool cconv_set_tiles(CconvParams& p, int tm) {
+    const int64_t ntiles = (p.n_out + tm - 1) / tm;
+    if (ntiles > 0x7fffffff / 8) return false;
+    p.ntiles = (int)ntiles;
+    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
+    return true;
+}
 
+// The launch of a pick: the LDS attribute, the kernel, the error of either kept for dmcf_last_hip_error.
+inline int cconv_launch_kernel(const CconvPick& k, dim3 grid, void** kargs, hipStream_t stream) {
+    hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+    if (e == hipSuccess) e = hipLaunchKernel(k.fn, grid, dim3(k.threads), kargs, k.lds, stream);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        return DMCF_ELAUNCH;
+    }
+    return check_launch();
+}
 
-// cconv_pair.hip
-bool cconv_pair_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx);
-int cconv_pair_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream);
-
-
-// cconv_ws.hip
-bool cconv_ws_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx);
-int cconv_ws_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream);
-
-
-// cconv_p16.hip
-bool cconv_p16_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx);
-int cconv_p16_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream);
-
-
-// cconv_direct.hip
-bool cconv_direct_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx);
-size_t cconv_direct_packed_floats(int dz, int dy, int dx, int cin);
-int cconv_direct_launch(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, void* workspace, hipStream_t stream);
+// cconv_cls.hip: the B-fragment filter layout of splat D (16 channels per chunk), which the ws, pair, p16 and z3 forms share.
+// cconv_cls_prepare packs it into the workspace (unless DMCF_FLAG_FILTER_PACKED says it is still there) and fills the fields of
+// p these forms have in common, for tiles of tm points; false as cconv_set_tiles.
+size_t cconv_cls_packed_floats(int cin, int cout);
+size_t cconv_cls_workspace_floats(const dmcf_cconv_args* a, int dz, int dy, int dx, bool selectable);  // (the table entry of all five)
+bool cconv_cls_prepare(CconvParams& p, const dmcf_cconv_args* a, int tm, void* workspace, hipStream_t stream);
 
 }  // namespace dmcf

@@ -16,7 +16,6 @@
 // coalesced 128-byte load per half-wave, issued four pairs ahead.  Geometry (gather, window, ball->cube map,
 // trilinear weights) is computed one lane per pair for 32 pairs of each half at a time, as in cconv.hip, and
 // parked in a small per-wave LDS area.  All interpolation / mapping modes are supported.
-#include <stdlib.h>
 
 #include "cconv_common.h"
 
@@ -289,67 +288,57 @@ static int direct_cfg(int dz, int dy, int dx, int cin, DirectParams& dp) {
     return nw >= 8;
 }
 
-bool cconv_direct_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx) {
-    const char* e = getenv("DMCF_CCONV_KERNEL");  // "direct" forces it where it is possible, any other value disables it
-    if (e && e[0] != 'd') return false;
+static bool direct_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced) {
     const int cin = a->filter_dims[3], cout = a->filter_dims[4];
     if (cout > 4 || cin > 32) return false;
     DirectParams dp;
     if (!direct_cfg(dz, dy, dx, cin, dp)) return false;
-    if (e) return true;
+    if (forced) return true;
     // Measured on MI355X: ~75 ps per pair whatever the filter (LDS-read bound: 8 corners x Cin x 16 bytes per pair).
     // The splat kernels need 60 ps per pair for a 24-channel 4x4x4 layer but 300 ps for the 32-channel 6x6x6 ASCC
     // layer, whose dense per-point tile (216 cells) dominates: large filters come here, 4x4x4 ones stay there.
     return dz * dy * dx > 64 && cin >= 8;
 }
 
-size_t cconv_direct_packed_floats(int dz, int dy, int dx, int cin) {
+static void direct_pick(const dmcf_cconv_args* a, int dz, int dy, int dx, CconvPick& k) {
     DirectParams dp;
-    if (!direct_cfg(dz, dy, dx, cin, dp)) return 0;
-    return (size_t)dp.image_f4 * 4;
+    direct_cfg(dz, dy, dx, a->filter_dims[3], dp);  // (fits: direct_eligible)
+    const int cout = a->filter_dims[4];
+#define DIRECT_PICK(G)                                                    \
+    (cout == 1 ? CCONV_KERNEL(cconv_direct_kernel<1, G>)                  \
+               : (cout == 2 ? CCONV_KERNEL(cconv_direct_kernel<2, G>)     \
+                            : (cout == 3 ? CCONV_KERNEL(cconv_direct_kernel<3, G>) : CCONV_KERNEL(cconv_direct_kernel<4, G>))))
+    const CconvKernel f = !cconv_specialised(a) ? DIRECT_PICK(true) : DIRECT_PICK(false);
+#undef DIRECT_PICK
+    k = {f.fn, f.name, (size_t)(dp.image_f4 + 1) * 16 + (size_t)dp.nwaves * kDStage * sizeof(float), dp.nwaves * 64,
+         (size_t)dp.image_f4 * 4};
 }
 
-int cconv_direct_launch(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, void* workspace, hipStream_t stream) {
+static size_t direct_workspace_floats(const dmcf_cconv_args* a, int dz, int dy, int dx, bool) {
+    DirectParams dp;
+    return direct_cfg(dz, dy, dx, a->filter_dims[3], dp) ? (size_t)dp.image_f4 * 4 : 0;
+}
+
+static int direct_launch(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, const CconvPick& k, void* workspace,
+                         hipStream_t stream) {
     DirectParams dp;
     if (!direct_cfg(dz, dy, dx, p.cin, dp)) return DMCF_EUNSUPPORTED;
     f32x4* image = (f32x4*)workspace;
-    {
-        const unsigned g = (unsigned)((dp.image_f4 + 255) / 256);
-        if (!(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
-            hipLaunchKernelGGL(pack_direct, dim3(g < 1024u ? g : 1024u), dim3(256), 0, stream, a->filters, image, dz, dy, dx, p.cin,
+    const unsigned g = (unsigned)((dp.image_f4 + 255) / 256);
+    if (!(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
+        hipLaunchKernelGGL(pack_direct, dim3(g < 1024u ? g : 1024u), dim3(256), 0, stream, a->filters, image, dz, dy, dx, p.cin,
                            p.cout, dp.sxp, (a->flags & DMCF_FLAG_SYMMETRIC) ? 1 : 0, a->sym_axis);
-    }
     p.Wp = (const float*)image;
     const int pts = 2 * dp.nwaves;
     const int64_t ntiles = (p.n_out + pts - 1) / pts;
     if (ntiles > 0x7fffffff) return DMCF_EUNSUPPORTED;
     p.ntiles = (int)ntiles;
-    const int ncu = device_cu_count();  // one persistent workgroup per CU
-    int nwg = (ncu + 7) / 8 * 8;
-    dp.nwg = nwg;
+    dp.nwg = (device_cu_count() + 7) / 8 * 8;  // one persistent workgroup per CU
     dp.p = p;
-    const size_t lds = (size_t)(dp.image_f4 + 1) * 16 + (size_t)dp.nwaves * kDStage * sizeof(float);
-    const bool generic = !(a->coordinate_mapping == DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING &&
-                           a->interpolation == DMCF_INTERP_LINEAR && (a->flags & DMCF_FLAG_ALIGN_CORNERS));
-    const void* fn;
-#define DMCF_PICK(G)                                                                                   \
-    (p.cout == 1 ? (const void*)cconv_direct_kernel<1, G>                                              \
-                 : (p.cout == 2 ? (const void*)cconv_direct_kernel<2, G>                               \
-                                : (p.cout == 3 ? (const void*)cconv_direct_kernel<3, G> : (const void*)cconv_direct_kernel<4, G>)))
-    fn = generic ? DMCF_PICK(true) : DMCF_PICK(false);
-#undef DMCF_PICK
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
     void* kargs[] = {(void*)&dp};
-    e = hipLaunchKernel(fn, dim3(nwg), dim3(dp.nwaves * 64), kargs, lds, stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    return check_launch();
+    return cconv_launch_kernel(k, dim3(dp.nwg), kargs, stream);
 }
+
+CconvForm cconv_direct_form = {'d', direct_eligible, direct_pick, direct_workspace_floats, direct_launch};
 
 }  // namespace dmcf

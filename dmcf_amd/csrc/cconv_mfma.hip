@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kMThreads, 2) void cconv_mfma_kernel(const CconvPar
 #pragma unroll
     for (int n = 0; n < NTT; ++n) acc[n] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 
-    // (small launches: one channel chunk per workgroup, blockIdx.y -- see cconv_mfma_launch)
+    // (small launches: one channel chunk per workgroup, blockIdx.y -- see mfma_launch)
     const int chunk_lo = p.csplit ? (int)blockIdx.y : 0, chunk_hi = p.csplit ? (int)blockIdx.y + 1 : p.nchunks;
     for (int chunk = chunk_lo; chunk < chunk_hi; ++chunk) {
         const int c0 = chunk * MCH;
@@ -433,11 +433,10 @@ static MfmaCfg mfma_cfg(int K, int cin, int cout) {
     return c;
 }
 
-bool cconv_mfma_eligible(int K, int cin, int cout) {
-    const char* e = getenv("DMCF_CCONV_KERNEL");  // "lds" / "mfma": force one implementation (A/B tests)
-    if (e && e[0] != 'm') return false;
-    if (K > 16 * kMaxKT || cout > 16 * kMMaxNT) return false;
-    if (e && e[0] == 'm') return true;
+static bool mfma_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced) {
+    const int cin = a->filter_dims[3], cout = a->filter_dims[4];
+    if (dz * dy * dx > 16 * kMaxKT || cout > 16 * kMMaxNT) return false;
+    if (forced) return true;
     // Measured on MI355X at 3.07e8 pairs (profiles/): the LDS splat costs ~6.9 ms per 8-channel pass (5.7 ms for a
     // 4-channel one), the matrix-core splat ~9.4 ms per 16-channel pass whatever the channel count.
     const double lds = cin <= 4 ? 5.7 : 6.9 * ((cin + 7) / 8);
@@ -445,45 +444,23 @@ bool cconv_mfma_eligible(int K, int cin, int cout) {
     return mfma < lds;
 }
 
-size_t cconv_mfma_packed_floats(int K, int cin, int cout) { return mfma_cfg(K, cin, cout).packed_floats; }
-
-size_t cconv_mfma_partial_floats(int K, int cin, int cout, int64_t n_out) {
+// floats of the chunks' partial sums (0: the launch does not split its chunks)
+static size_t mfma_partial_floats(int cin, int cout, int64_t n_out) {
     const int nchunks = (cin + MCH - 1) / MCH;
     const char* e = getenv("DMCF_MFMA_SPLIT");
     if (nchunks < 2 || n_out > kSplitMaxOut || !e || e[0] != '1') return 0;
     return (size_t)nchunks * (size_t)n_out * (size_t)cout;
 }
 
-int cconv_mfma_launch(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, void* workspace,
-                      hipStream_t stream) {
-    const MfmaCfg cfg = mfma_cfg(p.K, p.cin, p.cout);
-    float* packed = (float*)workspace;
-    {
-        const int64_t total = (int64_t)cfg.packed_floats;
-        const unsigned g = (unsigned)((total + 255) / 256);
-        // same packer as the LDS path with 16 channels per chunk and an unpadded plane stride
-        if (!(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
-            hipLaunchKernelGGL(pack_filter, dim3(g < 2048u ? g : 2048u), dim3(256), 0, stream, a->filters, packed, dz, dy, dx,
-                           p.cin, p.cout, MCH, dy * dx * MCH, cfg.nchunks, cfg.nblocks, cfg.NT,
-                           (a->flags & DMCF_FLAG_SYMMETRIC) ? 1 : 0, a->sym_axis);
-    }
-    p.Wp = packed;
-    p.KT = cfg.KT;
-    p.KCp = cfg.KCp;
-    p.nblocks = cfg.nblocks;
-    p.NT = cfg.NT;
-    p.nchunks = cfg.nchunks;
-    p.bfloats = (int)cfg.bfloats;
-    const int64_t ntiles = (p.n_out + MTM - 1) / MTM;
-    if (ntiles > 0x7fffffff / 8) return DMCF_EUNSUPPORTED;
-    p.ntiles = (int)ntiles;
-    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
-    const unsigned grid = (unsigned)p.tiles_per_xcd * 8u;
-    const size_t partial = (a->flags & DMCF_FLAG_NORMALIZE) ? 0 : cconv_mfma_partial_floats(p.K, p.cin, p.cout, p.n_out);
-    p.csplit = partial ? 1 : 0;
-    p.partial = partial ? packed + align_up(cfg.packed_floats, 64) : nullptr;
-    const bool generic = !(a->coordinate_mapping == DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING &&
-                           a->interpolation == DMCF_INTERP_LINEAR && (a->flags & DMCF_FLAG_ALIGN_CORNERS));
+static size_t mfma_workspace_floats(const dmcf_cconv_args* a, int dz, int dy, int dx, bool selectable) {
+    const int cin = a->filter_dims[3], cout = a->filter_dims[4];
+    const size_t packed = mfma_cfg(dz * dy * dx, cin, cout).packed_floats;
+    return selectable ? align_up(packed, 64) + mfma_partial_floats(cin, cout, a->n_out) : packed;
+}
+
+static void mfma_pick(const dmcf_cconv_args* a, int dz, int dy, int dx, CconvPick& k) {
+    const MfmaCfg cfg = mfma_cfg(dz * dy * dx, a->filter_dims[3], a->filter_dims[4]);
+    const bool generic = !cconv_specialised(a);
     const bool plane16 = !generic && dx * dy == 16;
     const int ntt = cfg.NT <= 1 ? 1 : (cfg.NT <= 2 ? 2 : 4);
     const void* fn;
@@ -501,23 +478,39 @@ int cconv_mfma_launch(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, i
     else
         fn = DMCF_PICK(false, false, 0);
 #undef DMCF_PICK
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
+    k = {fn, "cconv_mfma_kernel", cfg.lds, kMThreads, cfg.packed_floats};  // (the printed name carries no template arguments)
+}
+
+static int mfma_launch(CconvParams p, const dmcf_cconv_args* a, int dz, int dy, int dx, const CconvPick& k, void* workspace,
+                       hipStream_t stream) {
+    const MfmaCfg cfg = mfma_cfg(p.K, p.cin, p.cout);
+    float* packed = (float*)workspace;
+    const unsigned g = (unsigned)((cfg.packed_floats + 255) / 256);
+    // same packer as the LDS path with 16 channels per chunk and an unpadded plane stride
+    if (!(a->flags & DMCF_FLAG_FILTER_PACKED))  // (else the workspace still holds it: dmcf_hip.h)
+        hipLaunchKernelGGL(pack_filter, dim3(g < 2048u ? g : 2048u), dim3(256), 0, stream, a->filters, packed, dz, dy, dx,
+                           p.cin, p.cout, MCH, dy * dx * MCH, cfg.nchunks, cfg.nblocks, cfg.NT,
+                           (a->flags & DMCF_FLAG_SYMMETRIC) ? 1 : 0, a->sym_axis);
+    p.Wp = packed;
+    p.KT = cfg.KT;
+    p.KCp = cfg.KCp;
+    p.nblocks = cfg.nblocks;
+    p.NT = cfg.NT;
+    p.nchunks = cfg.nchunks;
+    p.bfloats = (int)cfg.bfloats;
+    if (!cconv_set_tiles(p, MTM)) return DMCF_EUNSUPPORTED;
+    const size_t partial = (a->flags & DMCF_FLAG_NORMALIZE) ? 0 : mfma_partial_floats(p.cin, p.cout, p.n_out);
+    p.csplit = partial ? 1 : 0;
+    p.partial = partial ? packed + align_up(cfg.packed_floats, 64) : nullptr;
     void* kargs[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid, p.csplit ? (unsigned)p.nchunks : 1u), dim3(kMThreads), kargs, cfg.lds, stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    if (p.csplit) {
-        const int64_t total = p.n_out * p.cout;
-        hipLaunchKernelGGL(cconv_mfma_sum_chunks, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p.partial, p.nchunks, p.n_out,
-                           p.cout, p.bias, p.out, (p.flags & DMCF_FLAG_ACCUMULATE) ? 1 : 0);
-    }
+    const int rc = cconv_launch_kernel(k, dim3((unsigned)p.tiles_per_xcd * 8u, p.csplit ? (unsigned)p.nchunks : 1u), kargs, stream);
+    if (rc != DMCF_OK || !p.csplit) return rc;
+    const int64_t total = p.n_out * p.cout;
+    hipLaunchKernelGGL(cconv_mfma_sum_chunks, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p.partial, p.nchunks, p.n_out,
+                       p.cout, p.bias, p.out, (p.flags & DMCF_FLAG_ACCUMULATE) ? 1 : 0);
     return check_launch();
 }
+
+CconvForm cconv_mfma_form = {'m', mfma_eligible, mfma_pick, mfma_workspace_floats, mfma_launch};
 
 }  // namespace dmcf

@@ -19,7 +19,6 @@
 //   LDS:       80 KB per workgroup: B tile 64 KB + 2 KB per wave (feature staging); records + indices in the second point's row
 //
 // Accumulation order = list order inside a class, then the fixed merge order: deterministic.
-#include <stdlib.h>
 
 #include "cconv_common.h"
 
@@ -363,55 +362,27 @@ __global__ __launch_bounds__(kGThreads, 4) __attribute__((amdgpu_num_vgpr(kGComp
 
 static constexpr size_t kP16Lds = (size_t)(GTM * kGRow + kGWaves * kGFst) * sizeof(float);
 
-// Same filters and flags as cconv_z3.hip / cconv_pair.hip (no antisymmetric form); 4 .. 16 input channels.
-bool cconv_p16_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx) {
-    const char* e = getenv("DMCF_CCONV_KERNEL");  // "g16": force, anything else: never
-    if (e && e[0] != 'g') return false;
-    if (dx != 4 || dy != 4 || dz != 4) return false;
-    if (a->flags & DMCF_FLAG_SYMMETRIC) return false;
-    if (a->coordinate_mapping != DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING || a->interpolation != DMCF_INTERP_LINEAR ||
-        !(a->flags & DMCF_FLAG_ALIGN_CORNERS) || (a->flags & DMCF_FLAG_NORMALIZE))
-        return false;
+// Same filters and flags as cconv_z3.hip / cconv_pair.hip (no antisymmetric form); 4 .. 16 input channels.  Never picked
+// unforced ("g16").
+static bool p16_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced) {
+    if (!cconv_fast444(a, dz, dy, dx) || !cconv_offsets_fit_24bit(a) || (a->flags & DMCF_FLAG_SYMMETRIC)) return false;
     const int cin = a->filter_dims[3], cout = a->filter_dims[4];
-    if ((cin & 3) || cin > 16 || cout > 16 * kGMaxNT) return false;
-    if ((uintptr_t)a->inp_features & 15) return false;
-    // 24-bit multiplies form the byte offsets of feature and position rows; the buffers must stay below 2 GB
-    if (a->n_inp >= (1 << 24) || a->n_inp * (int64_t)cin * 4 >= ((int64_t)1 << 31)) return false;
-    if (e) return true;
-    return false;
+    if (cin > 16 || cout > 16 * kGMaxNT) return false;
+    return forced;
 }
 
-int cconv_p16_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream) {
-    const int NT = (p.cout + 15) / 16;
-    float* packed = (float*)workspace;
-    const int nchunks = cconv_cls_pack(a, packed, stream);  // the B-fragment order of cconv_cls.hip (one 16-channel chunk)
-    p.Wp = packed;
-    p.NT = NT;
-    p.nchunks = nchunks;
-    const int64_t ntiles = (p.n_out + GTM - 1) / GTM;
-    if (ntiles > 0x7fffffff / 8) return DMCF_EUNSUPPORTED;
-    p.ntiles = (int)ntiles;
-    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
-    const unsigned grid = (unsigned)p.tiles_per_xcd * 8u;
-    const void* fn;
-    if (cconv_plain(a))
-        fn = NT <= 1 ? (const void*)cconv_p16_kernel<1, true>
-                     : (NT <= 2 ? (const void*)cconv_p16_kernel<2, true> : (const void*)cconv_p16_kernel<4, true>);
-    else
-        fn = NT <= 1 ? (const void*)cconv_p16_kernel<1, false>
-                     : (NT <= 2 ? (const void*)cconv_p16_kernel<2, false> : (const void*)cconv_p16_kernel<4, false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kP16Lds);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    void* kargs[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(kGThreads), kargs, kP16Lds, stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    return check_launch();
+static void p16_pick(const dmcf_cconv_args* a, int, int, int, CconvPick& k) {
+    const int NT = (a->filter_dims[4] + 15) / 16;
+    const CconvKernel f = cconv_plain(a) ? CCONV_KERNEL_NT(NT, cconv_p16_kernel, true) : CCONV_KERNEL_NT(NT, cconv_p16_kernel, false);
+    k = {f.fn, f.name, kP16Lds, kGThreads, cconv_cls_packed_floats(a->filter_dims[3], a->filter_dims[4])};
 }
+
+static int p16_launch(CconvParams p, const dmcf_cconv_args* a, int, int, int, const CconvPick& k, void* workspace, hipStream_t stream) {
+    if (!cconv_cls_prepare(p, a, GTM, workspace, stream)) return DMCF_EUNSUPPORTED;  // (one 16-channel chunk)
+    void* kargs[] = {(void*)&p};
+    return cconv_launch_kernel(k, dim3((unsigned)p.tiles_per_xcd * 8u), kargs, stream);
+}
+
+CconvForm cconv_p16_form = {'g', p16_eligible, p16_pick, cconv_cls_workspace_floats, p16_launch};
 
 }  // namespace dmcf

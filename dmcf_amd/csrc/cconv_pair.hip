@@ -40,7 +40,6 @@
 // swaps, 32 row-masked adds) and handed to the shared contraction in chunks of 16 channels.
 //
 // Accumulation order = list order inside a class, then the fixed merge order: deterministic.
-#include <stdlib.h>
 
 #include "cconv_common.h"
 
@@ -588,56 +587,28 @@ namespace dmcf {
 static constexpr size_t kPairLds = (size_t)(PTM * kPRow + kPWaves * kPWaveF) * sizeof(float);
 
 // Same filters and flags as cconv_z3.hip (no antisymmetric form); 4 .. 32 input channels.
-bool cconv_pair_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx) {
-    const char* e = getenv("DMCF_CCONV_KERNEL");  // "pair": force, anything else: never
-    if (e && e[0] != 'p') return false;
-    if (dx != 4 || dy != 4 || dz != 4) return false;
-    if (a->flags & DMCF_FLAG_SYMMETRIC) return false;
-    if (a->coordinate_mapping != DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING || a->interpolation != DMCF_INTERP_LINEAR ||
-        !(a->flags & DMCF_FLAG_ALIGN_CORNERS) || (a->flags & DMCF_FLAG_NORMALIZE))
-        return false;
+static bool pair_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced) {
+    if (!cconv_fast444(a, dz, dy, dx) || !cconv_offsets_fit_24bit(a) || (a->flags & DMCF_FLAG_SYMMETRIC)) return false;
     const int cin = a->filter_dims[3], cout = a->filter_dims[4];
-    if ((cin & 3) || cin > 32 || cout > 16 * kPMaxNT) return false;
-    if ((uintptr_t)a->inp_features & 15) return false;
-    // 24-bit multiplies form the byte offsets of feature and position rows; the buffers must stay below 2 GB
-    if (a->n_inp >= (1 << 24) || a->n_inp * (int64_t)cin * 4 >= ((int64_t)1 << 31)) return false;
-    if (e) return true;
+    if (cin > 32 || cout > 16 * kPMaxNT) return false;
+    if (forced) return true;
     // more than 16 channels (one walk instead of splat D's two) and rows long enough to pay for the per-point merge: the 3e8-pair
     // layers 24 -> 8 / 24 -> 4 take 7.7 / 4.8 ms here against 8.8 / 6.9 with splat E, the 33-pair layers 3.4 - 4.5 against 2.7 - 3.7
     return cin > 16 && a->row_length_hint == 2;
 }
 
-int cconv_pair_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream) {
-    const int NT = (p.cout + 15) / 16;
-    float* packed = (float*)workspace;
-    const int nchunks = cconv_cls_pack(a, packed, stream);  // the B-fragment order of cconv_cls.hip, 16 channels per chunk
-    p.Wp = packed;
-    p.NT = NT;
-    p.nchunks = nchunks;
-    const int64_t ntiles = (p.n_out + PTM - 1) / PTM;
-    if (ntiles > 0x7fffffff / 8) return DMCF_EUNSUPPORTED;
-    p.ntiles = (int)ntiles;
-    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
-    const unsigned grid = (unsigned)p.tiles_per_xcd * 8u;
-    const void* fn;
-    if (cconv_plain(a))
-        fn = NT <= 1 ? (const void*)cconv_pair_kernel<1, true>
-                     : (NT <= 2 ? (const void*)cconv_pair_kernel<2, true> : (const void*)cconv_pair_kernel<4, true>);
-    else
-        fn = NT <= 1 ? (const void*)cconv_pair_kernel<1, false>
-                     : (NT <= 2 ? (const void*)cconv_pair_kernel<2, false> : (const void*)cconv_pair_kernel<4, false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLds);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    void* kargs[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(kPThreads), kargs, kPairLds, stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    return check_launch();
+static void pair_pick(const dmcf_cconv_args* a, int, int, int, CconvPick& k) {
+    const int NT = (a->filter_dims[4] + 15) / 16;
+    const CconvKernel f = cconv_plain(a) ? CCONV_KERNEL_NT(NT, cconv_pair_kernel, true) : CCONV_KERNEL_NT(NT, cconv_pair_kernel, false);
+    k = {f.fn, f.name, kPairLds, kPThreads, cconv_cls_packed_floats(a->filter_dims[3], a->filter_dims[4])};
 }
+
+static int pair_launch(CconvParams p, const dmcf_cconv_args* a, int, int, int, const CconvPick& k, void* workspace, hipStream_t stream) {
+    if (!cconv_cls_prepare(p, a, PTM, workspace, stream)) return DMCF_EUNSUPPORTED;
+    void* kargs[] = {(void*)&p};
+    return cconv_launch_kernel(k, dim3((unsigned)p.tiles_per_xcd * 8u), kargs, stream);
+}
+
+CconvForm cconv_pair_form = {'p', pair_eligible, pair_pick, cconv_cls_workspace_floats, pair_launch};
 
 }  // namespace dmcf

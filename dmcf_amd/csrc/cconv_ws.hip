@@ -26,7 +26,6 @@
 //
 // Accumulation order = list order inside a class, the fixed merge order, then blocks in order per consumer and consumers in
 // order: deterministic, and independent of the grid.
-#include <stdlib.h>
 
 #include "cconv_common.h"
 
@@ -758,57 +757,35 @@ namespace dmcf {
 static constexpr size_t kWsLds = (size_t)(WTM * kWRow + kWProd * kWWaveF + kWRed) * sizeof(float);
 
 // Same filters and flags as cconv_pair.hip; 4 .. 32 input channels.
-bool cconv_ws_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx) {
-    const char* e = getenv("DMCF_CCONV_KERNEL");  // "ws": force, anything else: never
-    if (e && e[0] != 'w') return false;
-    if (dx != 4 || dy != 4 || dz != 4) return false;
-    if (a->flags & DMCF_FLAG_SYMMETRIC) return false;
-    if (a->coordinate_mapping != DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING || a->interpolation != DMCF_INTERP_LINEAR ||
-        !(a->flags & DMCF_FLAG_ALIGN_CORNERS) || (a->flags & DMCF_FLAG_NORMALIZE))
-        return false;
+static bool ws_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced) {
+    if (!cconv_fast444(a, dz, dy, dx) || !cconv_offsets_fit_24bit(a) || (a->flags & DMCF_FLAG_SYMMETRIC)) return false;
     const int cin = a->filter_dims[3], cout = a->filter_dims[4];
-    if ((cin & 3) || cin > 32 || cout > 16 * kWMaxNT) return false;
-    if ((uintptr_t)a->inp_features & 15) return false;
-    // 24-bit multiplies form the byte offsets of feature and position rows; the buffers must stay below 2 GB
-    if (a->n_inp >= (1 << 24) || a->n_inp * (int64_t)cin * 4 >= ((int64_t)1 << 31)) return false;
-    if (e) return true;
+    if (cin > 32 || cout > 16 * kWMaxNT) return false;
+    if (forced) return true;
     // short rows (the layers at the network's base radius) whose contraction is at least as much work as their splat: the 32 -> 32
     // layer takes 2.92 ms here against 3.39 with splat E, 24 -> 16 2.30 against 2.62; 16 -> 32 and 8 -> 16 lose (2.31 / 1.91 against
     // 1.84 / 1.28: the producers are alone on their SIMDs and every phase of theirs runs at its latency) -- profiles/r05_microbench.md
     return a->row_length_hint == 1 && cin >= 24;
 }
 
-int cconv_ws_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream) {
-    const int NT = (p.cout + 15) / 16;
-    float* packed = (float*)workspace;
-    const int nchunks = cconv_cls_pack(a, packed, stream);  // the B-fragment order of cconv_cls.hip, 16 channels per chunk
-    p.Wp = packed;
-    p.NT = NT;
-    p.nchunks = nchunks;
-    const int64_t ntiles = (p.n_out + WTM - 1) / WTM;
-    if (ntiles > 0x7fffffff / 8) return DMCF_EUNSUPPORTED;
-    p.ntiles = (int)ntiles;
-    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
+static void ws_pick(const dmcf_cconv_args* a, int, int, int, CconvPick& k) {
+    const int NT = (a->filter_dims[4] + 15) / 16;
+    CconvKernel f;
+    if (cconv_plain(a))
+        f = NT <= 1 ? CCONV_KERNEL(cconv_ws_kernel<1, true>) : CCONV_KERNEL(cconv_ws_kernel<2, true>);
+    else
+        f = NT <= 1 ? CCONV_KERNEL(cconv_ws_kernel<1, false>) : CCONV_KERNEL(cconv_ws_kernel<2, false>);
+    k = {f.fn, f.name, kWsLds, kWThreads, cconv_cls_packed_floats(a->filter_dims[3], a->filter_dims[4])};
+}
+
+static int ws_launch(CconvParams p, const dmcf_cconv_args* a, int, int, int, const CconvPick& k, void* workspace, hipStream_t stream) {
+    if (!cconv_cls_prepare(p, a, WTM, workspace, stream)) return DMCF_EUNSUPPORTED;
     // persistent: one workgroup per CU (the LDS admits no second one), an eighth of them per XCD
     const int per_xcd = max(1, min(device_cu_count() / 8, p.tiles_per_xcd));
-    const unsigned grid = (unsigned)per_xcd * 8u;
-    const void* fn;
-    if (cconv_plain(a))
-        fn = NT <= 1 ? (const void*)cconv_ws_kernel<1, true> : (const void*)cconv_ws_kernel<2, true>;
-    else
-        fn = NT <= 1 ? (const void*)cconv_ws_kernel<1, false> : (const void*)cconv_ws_kernel<2, false>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWsLds);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
     void* kargs[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(kWThreads), kargs, kWsLds, stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    return check_launch();
+    return cconv_launch_kernel(k, dim3((unsigned)per_xcd * 8u), kargs, stream);
 }
+
+CconvForm cconv_ws_form = {'w', ws_eligible, ws_pick, cconv_cls_workspace_floats, ws_launch};
 
 }  // namespace dmcf

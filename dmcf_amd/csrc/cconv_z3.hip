@@ -21,7 +21,6 @@
 // its group's class byte to the pair's slot, feature rows of half a batch at a time by 16-byte loads (lane = (slot, 4
 // channels)) into a 4 KB staging area; the splat of a half is one hand-scheduled block (tools/gen_z3_splat.py): groups of two
 // slots at static staging offsets, three ds_read_b32 and one multiply per matrix instruction, the tile picked by M0.
-#include <stdlib.h>
 
 #include "cconv_common.h"
 
@@ -483,54 +482,26 @@ namespace dmcf {
 static constexpr size_t kZ3Lds = (size_t)(ZTM * kZRow + kZWaves * kZWaveF) * sizeof(float);
 
 // Same filters and flags as cconv_cls.hip, without the antisymmetric form; 17 .. 32 input channels.
-bool cconv_z3_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx) {
-    const char* e = getenv("DMCF_CCONV_KERNEL");  // "z3": force, anything else: never
-    if (e && e[0] != 'z') return false;
-    if (dx != 4 || dy != 4 || dz != 4) return false;
-    if (a->flags & DMCF_FLAG_SYMMETRIC) return false;
-    if (a->coordinate_mapping != DMCF_MAP_BALL_TO_CUBE_VOLUME_PRESERVING || a->interpolation != DMCF_INTERP_LINEAR ||
-        !(a->flags & DMCF_FLAG_ALIGN_CORNERS) || (a->flags & DMCF_FLAG_NORMALIZE))
-        return false;
+static bool z3_eligible(const dmcf_cconv_args* a, int dz, int dy, int dx, bool forced) {
+    if (!cconv_fast444(a, dz, dy, dx) || !cconv_offsets_fit_24bit(a) || (a->flags & DMCF_FLAG_SYMMETRIC)) return false;
     const int cin = a->filter_dims[3], cout = a->filter_dims[4];
-    if ((cin & 3) || cin > 32 || cout > 16 * kZMaxNT) return false;
-    if ((uintptr_t)a->inp_features & 15) return false;
-    // 24-bit multiplies form the byte offsets of feature and position rows; the buffers must stay below 2 GB
-    if (a->n_inp >= (1 << 24) || a->n_inp * (int64_t)cin * 4 >= ((int64_t)1 << 31)) return false;
-    if (e) return true;
+    if (cin > 32 || cout > 16 * kZMaxNT) return false;
+    if (forced) return true;
     return cin > 16;
 }
 
-int cconv_z3_launch(CconvParams p, const dmcf_cconv_args* a, void* workspace, hipStream_t stream) {
-    const int NT = (p.cout + 15) / 16;
-    float* packed = (float*)workspace;
-    const int nchunks = cconv_cls_pack(a, packed, stream);  // the B-fragment order of cconv_cls.hip, 16 channels per chunk
-    p.Wp = packed;
-    p.NT = NT;
-    p.nchunks = nchunks;
-    const int64_t ntiles = (p.n_out + ZTM - 1) / ZTM;
-    if (ntiles > 0x7fffffff / 8) return DMCF_EUNSUPPORTED;
-    p.ntiles = (int)ntiles;
-    p.tiles_per_xcd = (int)((ntiles + 7) / 8);
-    const unsigned grid = (unsigned)p.tiles_per_xcd * 8u;
-    const void* fn;
-    if (cconv_plain(a))
-        fn = NT <= 1 ? (const void*)cconv_z3_kernel<1, true>
-                     : (NT <= 2 ? (const void*)cconv_z3_kernel<2, true> : (const void*)cconv_z3_kernel<4, true>);
-    else
-        fn = NT <= 1 ? (const void*)cconv_z3_kernel<1, false>
-                     : (NT <= 2 ? (const void*)cconv_z3_kernel<2, false> : (const void*)cconv_z3_kernel<4, false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kZ3Lds);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    void* kargs[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(kZThreads), kargs, kZ3Lds, stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return DMCF_ELAUNCH;
-    }
-    return check_launch();
+static void z3_pick(const dmcf_cconv_args* a, int, int, int, CconvPick& k) {
+    const int NT = (a->filter_dims[4] + 15) / 16;
+    const CconvKernel f = cconv_plain(a) ? CCONV_KERNEL_NT(NT, cconv_z3_kernel, true) : CCONV_KERNEL_NT(NT, cconv_z3_kernel, false);
+    k = {f.fn, f.name, kZ3Lds, kZThreads, cconv_cls_packed_floats(a->filter_dims[3], a->filter_dims[4])};
 }
+
+static int z3_launch(CconvParams p, const dmcf_cconv_args* a, int, int, int, const CconvPick& k, void* workspace, hipStream_t stream) {
+    if (!cconv_cls_prepare(p, a, ZTM, workspace, stream)) return DMCF_EUNSUPPORTED;
+    void* kargs[] = {(void*)&p};
+    return cconv_launch_kernel(k, dim3((unsigned)p.tiles_per_xcd * 8u), kargs, stream);
+}
+
+CconvForm cconv_z3_form = {'z', z3_eligible, z3_pick, cconv_cls_workspace_floats, z3_launch};
 
 }  // namespace dmcf

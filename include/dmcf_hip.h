@@ -281,7 +281,9 @@ int dmcf_cconv_forward(const dmcf_cconv_args* args, void* workspace, size_t work
                        dmcf_stream_t stream);
 /* Diagnostics: the name of the device kernel dmcf_cconv_forward dispatches these arguments to (the dispatch looks at the
  * layer -- filter shape, channel counts, flags -- never at the neighbour list), as rocprofv3 prints it without the
- * namespace, e.g. "cconv_z3_kernel<1, true>".  bench.py groups its per-launch HIP-event timings by it. */
+ * namespace, e.g. "cconv_z3_kernel<1, true>".  bench.py groups its per-launch HIP-event timings by it.  The same selection
+ * as dmcf_cconv_forward's, so also the same code where that one dispatches nowhere: DMCF_EUNSUPPORTED for DMCF_FLAG_SKIP_SELF on
+ * arguments the direct kernel does not take (`name` is then left as it was). */
 int dmcf_cconv_kernel_name(const dmcf_cconv_args* args, char* name, size_t name_bytes);
 
 /* CConv with INDIVIDUAL extents: ml3d.ops.continuous_conv with extents of shape [n_out, 1] (utils/convolutions.py:397-399
