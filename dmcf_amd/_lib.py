@@ -207,6 +207,7 @@ SYMBOLS = [
     "dmcf_cconv_forward_extents", "dmcf_cconv_extents_kernel_name",
     "dmcf_invert_neighbors_list_workspace_bytes", "dmcf_invert_neighbors_list",
     "dmcf_cconv_backward_workspace_bytes", "dmcf_cconv_backward", "dmcf_cconv_backward_kernel_names",
+    "dmcf_cconv_backward_extents", "dmcf_cconv_backward_extents_kernel_names",
     "dmcf_cconv_scatter_plan_bytes", "dmcf_cconv_scatter_plan", "dmcf_cconv_scatter_workspace_bytes", "dmcf_cconv_scatter_forward",
     "dmcf_lattice_conv_workspace_bytes", "dmcf_lattice_conv_forward",
     "dmcf_lattice_conv_batch_workspace_bytes", "dmcf_lattice_conv_forward_batch",
@@ -293,6 +294,12 @@ def lib():
     L.dmcf_cconv_backward.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_void_p, c.c_size_t, c.c_void_p]
     L.dmcf_cconv_backward_kernel_names.restype = c.c_int
     L.dmcf_cconv_backward_kernel_names.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_char_p, c.c_size_t]
+    # gradients through per-point extents (ABI 2.15)
+    L.dmcf_cconv_backward_extents.restype = c.c_int
+    L.dmcf_cconv_backward_extents.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_void_p, c.c_void_p, c.c_size_t,
+                                              c.c_void_p]
+    L.dmcf_cconv_backward_extents_kernel_names.restype = c.c_int
+    L.dmcf_cconv_backward_extents_kernel_names.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_char_p, c.c_size_t]
     L.dmcf_cconv_scatter_plan_bytes.restype = c.c_size_t
     L.dmcf_cconv_scatter_plan_bytes.argtypes = [c.c_int64]
     L.dmcf_cconv_scatter_plan.restype = c.c_int

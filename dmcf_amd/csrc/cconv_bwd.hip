@@ -24,6 +24,10 @@
 //   cconv_bwd_filter_gemm   per chunk: slab s = sum over its rows of B_r^T G_r, 64 x 64 tiles, one slab per z-block
 //   cconv_bwd_filter_reduce per chunk: the slabs summed in slab order into the full-kernel gradient
 //   cconv_bwd_filter_store  the full-kernel gradient (folded for ASCC) written, or added, to grad_filters
+// Individual extents (dmcf_cconv_backward_extents): the kernels that form a pair's geometry -- cconv_bwd_norm, cconv_bwd_input,
+// cconv_bwd_filter_splat -- have a second entry point each (suffix _ext) over the same body, in which 1 / e_i and 1 / (e_i / 2)^2
+// of the pair's OUTPUT row i replace p.inv_extent / p.inv_r2 (the arithmetic of the forward's EXT body, cconv_generic_body.inc);
+// a row whose extent is not positive and finite is an empty row.  The other kernels never see an extent.
 // Inversion: a stable rocPRIM radix sort of (input index, pair index) pairs keyed by input index, then a binary search per
 // input row for the row splits (invert_keys, invert_splits, invert_gather).
 #include <rocprim/device/device_radix_sort.hpp>
@@ -48,17 +52,17 @@ struct BwdGeo {
 };
 
 // The pair's geometry, as the generic forward body forms it: returns a_p (window, SKIP_SELF, importance), the base cell and
-// the 8 corner weights in Open3D's product order.
+// the 8 corner weights in Open3D's product order.  inv_extent, inv_r2: of the pair's output row (bwd_row_extent).
 __device__ __forceinline__ float bwd_pair(const CconvParams& p, int64_t i, int j, int64_t pp, float ox, float oy, float oz,
-                                          int& base, float (&w)[8]) {
+                                          float inv_extent, float inv_r2, int& base, float (&w)[8]) {
     const float gx = p.inp_pos[3 * (int64_t)j], gy = p.inp_pos[3 * (int64_t)j + 1], gz = p.inp_pos[3 * (int64_t)j + 2];
     float x = gx - ox;
     float y = gy - oy;
     float z = gz - oz;
-    float a = window_value(p.window, p.nval ? p.nval[pp] : rel_dist2(x, y, z), p.inv_r2, p.window_fac);
+    float a = window_value(p.window, p.nval ? p.nval[pp] : rel_dist2(x, y, z), inv_r2, p.window_fac);
     if ((p.flags & DMCF_FLAG_SKIP_SELF) && ((x == 0.0f && y == 0.0f && z == 0.0f) || j == (int)i)) a = 0.0f;
     if (p.inp_imp) a *= p.inp_imp[j];
-    filter_coords<true>(x, y, z, p, p.inv_extent);
+    filter_coords<true>(x, y, z, p, inv_extent);
     int bx, by, bz;
     float wx0, wx1, wy0, wy1, wz0, wz1;
     axis_weights(x, p.sx, p.interp, bx, wx0, wx1);
@@ -72,9 +76,10 @@ __device__ __forceinline__ float bwd_pair(const CconvParams& p, int64_t i, int j
 }
 
 // window value of a pair before the importance: what the forward sums into psi_i
-__device__ __forceinline__ float bwd_norm_term(const CconvParams& p, int64_t i, int j, int64_t pp, float ox, float oy, float oz) {
+__device__ __forceinline__ float bwd_norm_term(const CconvParams& p, int64_t i, int j, int64_t pp, float ox, float oy, float oz,
+                                               float inv_r2) {
     const float x = p.inp_pos[3 * (int64_t)j] - ox, y = p.inp_pos[3 * (int64_t)j + 1] - oy, z = p.inp_pos[3 * (int64_t)j + 2] - oz;
-    float a = window_value(p.window, p.nval ? p.nval[pp] : rel_dist2(x, y, z), p.inv_r2, p.window_fac);
+    float a = window_value(p.window, p.nval ? p.nval[pp] : rel_dist2(x, y, z), inv_r2, p.window_fac);
     if ((p.flags & DMCF_FLAG_SKIP_SELF) && ((x == 0.0f && y == 0.0f && z == 0.0f) || j == (int)i)) a = 0.0f;
     return a;
 }
@@ -87,23 +92,38 @@ __device__ __forceinline__ void bwd_row(const CconvParams& p, int64_t i, int64_t
 
 __device__ __forceinline__ bool bwd_valid_j(const CconvParams& p, int j) { return j >= 0 && (int64_t)j < p.n_inp; }
 
+// 1 / e_i and 1 / (e_i / 2)^2 of output row i.  EXT: from out_ext[i], with the operations of the forward's EXT body (which are
+// the host's of dmcf_cconv_forward for a scalar); false: the extent is not positive and finite -- the row is empty, as there.
+// !EXT: the call's two constants.
+template <bool EXT>
+__device__ __forceinline__ bool bwd_row_extent(const CconvParams& p, const float* __restrict__ out_ext, int64_t i, float& inv_extent,
+                                               float& inv_r2) {
+    if (!EXT) {
+        inv_extent = p.inv_extent;
+        inv_r2 = p.inv_r2;
+        return true;
+    }
+    const float e = out_ext[i];
+    inv_extent = __fdiv_rn(1.0f, e);
+    const float radius = __fmul_rn(0.5f, e);
+    inv_r2 = __fdiv_rn(1.0f, __fmul_rn(radius, radius));
+    return e > 0.0f && isfinite(e);
+}
+
+// The three kernels below have two entry points over one body each (cconv_bwd_*_body.inc, included rather than called: through
+// a shared __device__ function the scalar kernels compile to other code than they did on their own, see cconv_generic_body.inc).
+
 // psi_i: the forward's half-wave sum (lane pl takes pairs rb + pl, rb + pl + 32, ..., then a butterfly)
 __global__ __launch_bounds__(64) void cconv_bwd_norm(const CconvParams p, float* __restrict__ psi) {
-    const int lane = threadIdx.x & 63, h = lane >> 5, pl = lane & 31;
-    const int64_t i = (int64_t)blockIdx.x * 2 + h;
-    float nsum = 0.0f;
-    if (i < p.n_out) {
-        int64_t rb, re;
-        bwd_row(p, i, rb, re);
-        const float ox = p.out_pos[3 * i], oy = p.out_pos[3 * i + 1], oz = p.out_pos[3 * i + 2];
-        for (int64_t pp = rb + pl; pp < re; pp += 32) {
-            const int j = p.idx[pp];
-            if (bwd_valid_j(p, j)) nsum += bwd_norm_term(p, i, j, pp, ox, oy, oz);
-        }
-    }
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) nsum += __shfl_xor(nsum, d, 64);
-    if (pl == 0 && i < p.n_out) psi[i] = nsum;
+    constexpr bool EXT = false;
+    const float* const out_ext = nullptr;
+#include "cconv_bwd_norm_body.inc"
+}
+
+__global__ __launch_bounds__(64) void cconv_bwd_norm_ext(const CconvParams p, const float* __restrict__ out_ext,
+                                                         float* __restrict__ psi) {
+    constexpr bool EXT = true;
+#include "cconv_bwd_norm_body.inc"
 }
 
 __device__ __forceinline__ float bwd_scale(const float* psi, int64_t i) {
@@ -142,163 +162,41 @@ __device__ __forceinline__ void bwd_stage(float* ws, int* bs, int* js, int lane,
     js[lane] = valid ? partner : 0;
 }
 
-// Input-feature gradient: one wave per input row j.
+// Input-feature gradient: one wave per input row j.  EXT: a pair takes the constants of ITS output row -- one more load per
+// pair (out_ext[i], next to out_pos[3 * i]) and two divisions, in the lane that forms the pair's geometry.
 __global__ __launch_bounds__(64) void cconv_bwd_input(const CconvParams p, const BwdGeo geo, const float* __restrict__ Wfull,
                                                       const float* __restrict__ G, const float* __restrict__ psi,
                                                       const int32_t* __restrict__ inv_index, const int32_t* __restrict__ inv_pair,
                                                       const int64_t* __restrict__ inv_rs, int64_t inv_n_pairs, int symmetric,
                                                       float* __restrict__ dF, int accumulate) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int lane = threadIdx.x;
-    const int K = geo.K, cin = geo.cin, cout = geo.cout;
-    float* T = smem;                            // [K][cout]
-    float* ws = T + (size_t)K * cout;           // [64][kBwdWStride]
-    int* bs = (int*)(ws + 64 * kBwdWStride);    // [64]
-    int* js = bs + 64;                          // [64] output row of the staged pair
-    float* red = (float*)(js + 64);             // [64] contraction partials
-    const int64_t j = blockIdx.x;
-    for (int e = lane; e < K * cout; e += 64) T[e] = 0.0f;
-    const float jx = p.inp_pos[3 * j], jy = p.inp_pos[3 * j + 1], jz = p.inp_pos[3 * j + 2];
-    __syncthreads();
+    constexpr bool EXT = false;
+    const float* const out_ext = nullptr;
+#include "cconv_bwd_input_body.inc"
+}
 
-    auto splat = [&](int nq) {
-        for (int o = lane; o < cout; o += 64) {
-            for (int q = 0; q < nq; ++q) {
-                const float g = G[(int64_t)js[q] * cout + o];
-                float* tb = T + (size_t)bs[q] * cout + o;
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    if (geo.live & (1u << t)) tb[geo.off[t] * cout] += ws[q * kBwdWStride + t] * g;
-            }
-        }
-    };
-    // (1) the pairs that reference j: output row i = inv_index[q], forward pair inv_pair[q]
-    int64_t qb = inv_rs[j], qe = inv_rs[j + 1];
-    if (qb < 0) qb = 0;
-    if (qe > inv_n_pairs) qe = inv_n_pairs;
-    for (int64_t q0 = qb; q0 < qe; q0 += 64) {
-        const int64_t q = q0 + lane;
-        bool valid = q < qe;
-        int64_t i = 0, pp = 0;
-        if (valid) {
-            i = inv_index[q];
-            pp = inv_pair[q];
-            valid = i >= 0 && i < p.n_out && pp >= 0 && pp < p.pair_cap;
-        }
-        float w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int base = 0;
-        float coef = 0.0f;
-        if (valid) {
-            const float a = bwd_pair(p, i, (int)j, pp, p.out_pos[3 * i], p.out_pos[3 * i + 1], p.out_pos[3 * i + 2], base, w);
-            coef = a / bwd_scale(psi, i);
-        }
-        bwd_stage(ws, bs, js, lane, valid, coef, base, w, (int)i);
-        __syncthreads();
-        splat((int)min((int64_t)64, qe - q0));
-        __syncthreads();
-    }
-    // (2) ASCC centre term: row j of the forward list, every pair with G[j]
-    if (symmetric && j < p.n_out) {
-        int64_t rb, re;
-        bwd_row(p, j, rb, re);
-        const float sc = bwd_scale(psi, j);
-        for (int64_t b0 = rb; b0 < re; b0 += 64) {
-            const int64_t pp = b0 + lane;
-            bool valid = pp < re;
-            int jj = 0;
-            if (valid) {
-                jj = p.idx[pp];
-                valid = bwd_valid_j(p, jj);
-            }
-            float w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            int base = 0;
-            float coef = 0.0f;
-            if (valid) coef = bwd_pair(p, j, jj, pp, jx, jy, jz, base, w) / sc;
-            bwd_stage(ws, bs, js, lane, valid, coef, base, w, (int)j);
-            __syncthreads();
-            splat((int)min((int64_t)64, re - b0));
-            __syncthreads();
-        }
-    }
-    // dF_j[c] = sum_cell sum_o W[cell, c, o] T[cell, o]; lanes = (cell part, channel), parts summed in order
-    float* dst = dF + j * cin;
-    if (cin <= 64) {
-        const int P = 64 / cin, part = lane / cin, c = lane % cin;
-        float acc = 0.0f;
-        if (part < P) {
-            for (int cell = part; cell < K; cell += P) {
-                const float* wr = Wfull + ((size_t)cell * cin + c) * cout;
-                const float* tr = T + (size_t)cell * cout;
-                for (int o = 0; o < cout; ++o) acc += wr[o] * tr[o];
-            }
-        }
-        red[lane] = acc;
-        __syncthreads();
-        if (lane < cin) {
-            float v = 0.0f;
-            for (int q = 0; q < P; ++q) v += red[q * cin + lane];
-            dst[lane] = accumulate ? dst[lane] + v : v;
-        }
-    } else {
-        for (int c = lane; c < cin; c += 64) {
-            float acc = 0.0f;
-            for (int cell = 0; cell < K; ++cell) {
-                const float* wr = Wfull + ((size_t)cell * cin + c) * cout;
-                const float* tr = T + (size_t)cell * cout;
-                for (int o = 0; o < cout; ++o) acc += wr[o] * tr[o];
-            }
-            dst[c] = accumulate ? dst[c] + acc : acc;
-        }
-    }
+__global__ __launch_bounds__(64) void cconv_bwd_input_ext(const CconvParams p, const BwdGeo geo, const float* __restrict__ out_ext,
+                                                          const float* __restrict__ Wfull, const float* __restrict__ G,
+                                                          const float* __restrict__ psi, const int32_t* __restrict__ inv_index,
+                                                          const int32_t* __restrict__ inv_pair, const int64_t* __restrict__ inv_rs,
+                                                          int64_t inv_n_pairs, int symmetric, float* __restrict__ dF,
+                                                          int accumulate) {
+    constexpr bool EXT = true;
+#include "cconv_bwd_input_body.inc"
 }
 
 // Filter gradient, step 1: B_i [K, Cin] of output rows row0 .. row0 + gridDim.x - 1 into Bc [rows][K * Cin].
 __global__ __launch_bounds__(64) void cconv_bwd_filter_splat(const CconvParams p, const BwdGeo geo, const float* __restrict__ psi,
                                                              int symmetric, int64_t row0, float* __restrict__ Bc) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int lane = threadIdx.x;
-    const int K = geo.K, cin = geo.cin;
-    float* B = smem;                            // [K][cin]
-    float* ws = B + (size_t)K * cin;
-    int* bs = (int*)(ws + 64 * kBwdWStride);
-    int* js = bs + 64;
-    const int64_t i = row0 + blockIdx.x;
-    for (int e = lane; e < K * cin; e += 64) B[e] = 0.0f;
-    __syncthreads();
-    int64_t rb, re;
-    bwd_row(p, i, rb, re);
-    const float ox = p.out_pos[3 * i], oy = p.out_pos[3 * i + 1], oz = p.out_pos[3 * i + 2];
-    const float sc = bwd_scale(psi, i);
-    for (int64_t b0 = rb; b0 < re; b0 += 64) {
-        const int64_t pp = b0 + lane;
-        bool valid = pp < re;
-        int j = 0;
-        if (valid) {
-            j = p.idx[pp];
-            valid = bwd_valid_j(p, j);
-        }
-        float w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int base = 0;
-        float coef = 0.0f;
-        if (valid) coef = bwd_pair(p, i, j, pp, ox, oy, oz, base, w) / sc;
-        bwd_stage(ws, bs, js, lane, valid, coef, base, w, j);
-        __syncthreads();
-        const int nq = (int)min((int64_t)64, re - b0);
-        for (int c = lane; c < cin; c += 64) {
-            const float fi = symmetric ? p.inp_feat[i * cin + c] : 0.0f;
-            for (int q = 0; q < nq; ++q) {
-                float f = p.inp_feat[(int64_t)js[q] * cin + c];
-                if (symmetric) f += fi;
-                float* bb = B + (size_t)bs[q] * cin + c;
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    if (geo.live & (1u << t)) bb[geo.off[t] * cin] += ws[q * kBwdWStride + t] * f;
-            }
-        }
-        __syncthreads();
-    }
-    float* dst = Bc + (size_t)blockIdx.x * K * cin;
-    for (int e = lane; e < K * cin; e += 64) dst[e] = B[e];
+    constexpr bool EXT = false;
+    const float* const out_ext = nullptr;
+#include "cconv_bwd_filter_splat_body.inc"
+}
+
+__global__ __launch_bounds__(64) void cconv_bwd_filter_splat_ext(const CconvParams p, const BwdGeo geo,
+                                                                 const float* __restrict__ out_ext, const float* __restrict__ psi,
+                                                                 int symmetric, int64_t row0, float* __restrict__ Bc) {
+    constexpr bool EXT = true;
+#include "cconv_bwd_filter_splat_body.inc"
 }
 
 // Filter gradient, step 2: slab[z] [M, cout] = sum over rows r of slab z of Bc[r, :]^T G[row0 + r, :]; 64 x 64 tiles of
@@ -554,6 +452,130 @@ static void bwd_params(const dmcf_cconv_args* a, const BwdPlan& pl, CconvParams&
     }
 }
 
+// dmcf_cconv_backward (out_ext == NULL) and dmcf_cconv_backward_extents: one sequence of launches, the three kernels that form
+// pair geometry in their _ext form when there is an extent per output row.
+static int bwd_run(const dmcf_cconv_args* a, const dmcf_cconv_backward_args* b, const BwdPlan& pl, const float* out_ext,
+                   void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    int rc = DMCF_OK;
+    if (!pl.want_f && !pl.want_w) return DMCF_OK;
+    if (!workspace || ((uintptr_t)workspace & 255)) return DMCF_EINVAL;
+    if (workspace_bytes < pl.total) return DMCF_EWORKSPACE;
+    const int accumulate = (b->flags & DMCF_BWD_ACCUMULATE) ? 1 : 0;
+    char* w = (char*)workspace;
+    const int64_t n_full = (int64_t)pl.M * pl.cout;
+    const int64_t n_stored = (int64_t)a->filter_dims[0] * a->filter_dims[1] * a->filter_dims[2] * pl.cin * pl.cout;
+    // empty point sets: the gradients are zero
+    if (a->n_out == 0 || a->n_inp == 0) {
+        hipError_t e = hipSuccess;
+        if (pl.want_w && !accumulate) e = hipMemsetAsync(b->grad_filters, 0, sizeof(float) * (size_t)n_stored, stream);
+        if (e == hipSuccess && pl.want_f && !accumulate && a->n_inp > 0)
+            e = hipMemsetAsync(b->grad_inp_features, 0, sizeof(float) * (size_t)a->n_inp * pl.cin, stream);
+        if (e != hipSuccess) { g_last_hip_error = (int)e; return DMCF_ELAUNCH; }
+        return DMCF_OK;
+    }
+    CconvParams p;
+    BwdGeo geo;
+    bwd_params(a, pl, p, geo);
+    float* psi = nullptr;
+    if (a->flags & DMCF_FLAG_NORMALIZE) {
+        psi = (float*)(w + pl.off_psi);
+        const dim3 grid((unsigned)((a->n_out + 1) / 2));
+        if (out_ext)
+            hipLaunchKernelGGL(cconv_bwd_norm_ext, grid, dim3(64), 0, stream, p, out_ext, psi);
+        else
+            hipLaunchKernelGGL(cconv_bwd_norm, grid, dim3(64), 0, stream, p, psi);
+    }
+    if (pl.want_f) {
+        const float* Wfull = a->filters;
+        if (pl.sym) {
+            float* wf = (float*)(w + pl.off_wfull);
+            hipLaunchKernelGGL(cconv_bwd_expand, dim3(grid_for(n_full, 256)), dim3(256), 0, stream, a->filters, wf, pl.dz, pl.dy,
+                               pl.dx, pl.cin, pl.cout, a->sym_axis);
+            Wfull = wf;
+        }
+        hipError_t e = hipFuncSetAttribute(out_ext ? (const void*)cconv_bwd_input_ext : (const void*)cconv_bwd_input,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_input);
+        if (e != hipSuccess) { g_last_hip_error = (int)e; return DMCF_ELAUNCH; }
+        if (out_ext)
+            hipLaunchKernelGGL(cconv_bwd_input_ext, dim3((unsigned)a->n_inp), dim3(64), pl.lds_input, stream, p, geo, out_ext, Wfull,
+                               b->grad_out, (const float*)psi, b->inv_index, b->inv_pair, b->inv_row_splits, b->inv_n_pairs,
+                               pl.sym ? 1 : 0, b->grad_inp_features, accumulate);
+        else
+            hipLaunchKernelGGL(cconv_bwd_input, dim3((unsigned)a->n_inp), dim3(64), pl.lds_input, stream, p, geo, Wfull, b->grad_out,
+                               (const float*)psi, b->inv_index, b->inv_pair, b->inv_row_splits, b->inv_n_pairs, pl.sym ? 1 : 0,
+                               b->grad_inp_features, accumulate);
+        rc = check_launch();
+        if (rc != DMCF_OK) return rc;
+    }
+    if (pl.want_w) {
+        hipError_t e = hipFuncSetAttribute(out_ext ? (const void*)cconv_bwd_filter_splat_ext : (const void*)cconv_bwd_filter_splat,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_splat);
+        if (e != hipSuccess) { g_last_hip_error = (int)e; return DMCF_ELAUNCH; }
+        float* Bc = (float*)(w + pl.off_b);
+        float* slabs = (float*)(w + pl.off_slabs);
+        float* dfull = (float*)(w + pl.off_dfull);
+        int first = 1;
+        for (int64_t row0 = 0; row0 < a->n_out; row0 += pl.R) {
+            const int64_t rows = min(pl.R, a->n_out - row0);
+            const int64_t rps = (rows + pl.S - 1) / pl.S;
+            const int S = (int)((rows + rps - 1) / rps);
+            if (out_ext)
+                hipLaunchKernelGGL(cconv_bwd_filter_splat_ext, dim3((unsigned)rows), dim3(64), pl.lds_splat, stream, p, geo, out_ext,
+                                   (const float*)psi, pl.sym ? 1 : 0, row0, Bc);
+            else
+                hipLaunchKernelGGL(cconv_bwd_filter_splat, dim3((unsigned)rows), dim3(64), pl.lds_splat, stream, p, geo,
+                                   (const float*)psi, pl.sym ? 1 : 0, row0, Bc);
+            hipLaunchKernelGGL(cconv_bwd_filter_gemm, dim3((unsigned)((pl.M + 63) / 64), (unsigned)((pl.cout + 63) / 64), (unsigned)S),
+                               dim3(256), 0, stream, (const float*)Bc, b->grad_out + row0 * pl.cout, rows, pl.M, pl.cout, rps, slabs);
+            hipLaunchKernelGGL(cconv_bwd_filter_reduce, dim3(grid_for(n_full, 256)), dim3(256), 0, stream, (const float*)slabs, S, n_full,
+                               dfull, first);
+            first = 0;
+            rc = check_launch();
+            if (rc != DMCF_OK) return rc;
+        }
+        hipLaunchKernelGGL(cconv_bwd_filter_store, dim3(grid_for(n_stored, 256)), dim3(256), 0, stream, (const float*)dfull,
+                           b->grad_filters, pl.dz, pl.dy, pl.dx, pl.cin, pl.cout, pl.sym ? 1 : 0, a->sym_axis, accumulate);
+    }
+    return check_launch();
+}
+
+// the kernels bwd_run launches, in launch order, separated by ';' (ext: the names of the individual-extent call)
+static int bwd_names(const dmcf_cconv_args* a, const BwdPlan& pl, bool ext, char* names, size_t name_bytes) {
+    if (!names || name_bytes < 2) return DMCF_EINVAL;
+    char buf[256];
+    buf[0] = 0;
+    auto add = [&](const char* s) {
+        if (buf[0]) strncat(buf, ";", sizeof(buf) - strlen(buf) - 1);
+        strncat(buf, s, sizeof(buf) - strlen(buf) - 1);
+    };
+    if (a->flags & DMCF_FLAG_NORMALIZE) add(ext ? "cconv_bwd_norm_ext" : "cconv_bwd_norm");
+    if (pl.want_f) {
+        if (pl.sym) add("cconv_bwd_expand");
+        add(ext ? "cconv_bwd_input_ext" : "cconv_bwd_input");
+    }
+    if (pl.want_w) {
+        add(ext ? "cconv_bwd_filter_splat_ext" : "cconv_bwd_filter_splat");
+        add("cconv_bwd_filter_gemm");
+        add("cconv_bwd_filter_reduce");
+        add("cconv_bwd_filter_store");
+    }
+    if (strlen(buf) + 1 > name_bytes) return DMCF_EINVAL;
+    memcpy(names, buf, strlen(buf) + 1);
+    return DMCF_OK;
+}
+
+// bwd_plan of the individual-extent call: args->extent is ignored (planned with 1), and SKIP_SELF is refused as in
+// dmcf_cconv_forward_extents
+static int bwd_plan_extents(const dmcf_cconv_args* a, const dmcf_cconv_backward_args* b, BwdPlan& pl) {
+    if (!a) return DMCF_EINVAL;
+    dmcf_cconv_args a1 = *a;
+    a1.extent = 1.0f;
+    const int rc = bwd_plan(&a1, b, pl);
+    if (rc != DMCF_OK) return rc;
+    if (a->flags & DMCF_FLAG_SKIP_SELF) return DMCF_EUNSUPPORTED;
+    return DMCF_OK;
+}
+
 }  // namespace dmcf
 
 using namespace dmcf;
@@ -618,77 +640,20 @@ size_t dmcf_cconv_backward_workspace_bytes(const dmcf_cconv_args* fwd, const dmc
 }
 
 int dmcf_cconv_backward(const dmcf_cconv_args* a, const dmcf_cconv_backward_args* b, void* workspace, size_t workspace_bytes,
-                        dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                        dmcf_stream_t stream) {
     BwdPlan pl;
-    int rc = bwd_plan(a, b, pl);
+    const int rc = bwd_plan(a, b, pl);
     if (rc != DMCF_OK) return rc;
-    if (!pl.want_f && !pl.want_w) return DMCF_OK;
-    if (!workspace || ((uintptr_t)workspace & 255)) return DMCF_EINVAL;
-    if (workspace_bytes < pl.total) return DMCF_EWORKSPACE;
-    const int accumulate = (b->flags & DMCF_BWD_ACCUMULATE) ? 1 : 0;
-    char* w = (char*)workspace;
-    const int64_t n_full = (int64_t)pl.M * pl.cout;
-    const int64_t n_stored = (int64_t)a->filter_dims[0] * a->filter_dims[1] * a->filter_dims[2] * pl.cin * pl.cout;
-    // empty point sets: the gradients are zero
-    if (a->n_out == 0 || a->n_inp == 0) {
-        hipError_t e = hipSuccess;
-        if (pl.want_w && !accumulate) e = hipMemsetAsync(b->grad_filters, 0, sizeof(float) * (size_t)n_stored, stream);
-        if (e == hipSuccess && pl.want_f && !accumulate && a->n_inp > 0)
-            e = hipMemsetAsync(b->grad_inp_features, 0, sizeof(float) * (size_t)a->n_inp * pl.cin, stream);
-        if (e != hipSuccess) { g_last_hip_error = (int)e; return DMCF_ELAUNCH; }
-        return DMCF_OK;
-    }
-    CconvParams p;
-    BwdGeo geo;
-    bwd_params(a, pl, p, geo);
-    float* psi = nullptr;
-    if (a->flags & DMCF_FLAG_NORMALIZE) {
-        psi = (float*)(w + pl.off_psi);
-        hipLaunchKernelGGL(cconv_bwd_norm, dim3((unsigned)((a->n_out + 1) / 2)), dim3(64), 0, stream, p, psi);
-    }
-    if (pl.want_f) {
-        const float* Wfull = a->filters;
-        if (pl.sym) {
-            float* wf = (float*)(w + pl.off_wfull);
-            hipLaunchKernelGGL(cconv_bwd_expand, dim3(grid_for(n_full, 256)), dim3(256), 0, stream, a->filters, wf, pl.dz, pl.dy,
-                               pl.dx, pl.cin, pl.cout, a->sym_axis);
-            Wfull = wf;
-        }
-        hipError_t e = hipFuncSetAttribute((const void*)cconv_bwd_input, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_input);
-        if (e != hipSuccess) { g_last_hip_error = (int)e; return DMCF_ELAUNCH; }
-        hipLaunchKernelGGL(cconv_bwd_input, dim3((unsigned)a->n_inp), dim3(64), pl.lds_input, stream, p, geo, Wfull, b->grad_out,
-                           (const float*)psi, b->inv_index, b->inv_pair, b->inv_row_splits, b->inv_n_pairs, pl.sym ? 1 : 0,
-                           b->grad_inp_features, accumulate);
-        rc = check_launch();
-        if (rc != DMCF_OK) return rc;
-    }
-    if (pl.want_w) {
-        hipError_t e = hipFuncSetAttribute((const void*)cconv_bwd_filter_splat, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)pl.lds_splat);
-        if (e != hipSuccess) { g_last_hip_error = (int)e; return DMCF_ELAUNCH; }
-        float* Bc = (float*)(w + pl.off_b);
-        float* slabs = (float*)(w + pl.off_slabs);
-        float* dfull = (float*)(w + pl.off_dfull);
-        int first = 1;
-        for (int64_t row0 = 0; row0 < a->n_out; row0 += pl.R) {
-            const int64_t rows = min(pl.R, a->n_out - row0);
-            const int64_t rps = (rows + pl.S - 1) / pl.S;
-            const int S = (int)((rows + rps - 1) / rps);
-            hipLaunchKernelGGL(cconv_bwd_filter_splat, dim3((unsigned)rows), dim3(64), pl.lds_splat, stream, p, geo, (const float*)psi,
-                               pl.sym ? 1 : 0, row0, Bc);
-            hipLaunchKernelGGL(cconv_bwd_filter_gemm, dim3((unsigned)((pl.M + 63) / 64), (unsigned)((pl.cout + 63) / 64), (unsigned)S),
-                               dim3(256), 0, stream, (const float*)Bc, b->grad_out + row0 * pl.cout, rows, pl.M, pl.cout, rps, slabs);
-            hipLaunchKernelGGL(cconv_bwd_filter_reduce, dim3(grid_for(n_full, 256)), dim3(256), 0, stream, (const float*)slabs, S, n_full,
-                               dfull, first);
-            first = 0;
-            rc = check_launch();
-            if (rc != DMCF_OK) return rc;
-        }
-        hipLaunchKernelGGL(cconv_bwd_filter_store, dim3(grid_for(n_stored, 256)), dim3(256), 0, stream, (const float*)dfull,
-                           b->grad_filters, pl.dz, pl.dy, pl.dx, pl.cin, pl.cout, pl.sym ? 1 : 0, a->sym_axis, accumulate);
-    }
-    return check_launch();
+    return bwd_run(a, b, pl, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int dmcf_cconv_backward_extents(const dmcf_cconv_args* a, const dmcf_cconv_backward_args* b, const float* out_extents,
+                                void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    BwdPlan pl;
+    const int rc = bwd_plan_extents(a, b, pl);
+    if (rc != DMCF_OK) return rc;
+    if (a->n_out > 0 && !out_extents) return DMCF_EINVAL;
+    return bwd_run(a, b, pl, out_extents, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int dmcf_cconv_backward_kernel_names(const dmcf_cconv_args* a, const dmcf_cconv_backward_args* b, char* names, size_t name_bytes) {
@@ -696,26 +661,16 @@ int dmcf_cconv_backward_kernel_names(const dmcf_cconv_args* a, const dmcf_cconv_
     BwdPlan pl;
     const int rc = bwd_plan(a, b, pl);
     if (rc != DMCF_OK) return rc;
-    char buf[256];
-    buf[0] = 0;
-    auto add = [&](const char* s) {
-        if (buf[0]) strncat(buf, ";", sizeof(buf) - strlen(buf) - 1);
-        strncat(buf, s, sizeof(buf) - strlen(buf) - 1);
-    };
-    if (a->flags & DMCF_FLAG_NORMALIZE) add("cconv_bwd_norm");
-    if (pl.want_f) {
-        if (pl.sym) add("cconv_bwd_expand");
-        add("cconv_bwd_input");
-    }
-    if (pl.want_w) {
-        add("cconv_bwd_filter_splat");
-        add("cconv_bwd_filter_gemm");
-        add("cconv_bwd_filter_reduce");
-        add("cconv_bwd_filter_store");
-    }
-    if (strlen(buf) + 1 > name_bytes) return DMCF_EINVAL;
-    memcpy(names, buf, strlen(buf) + 1);
-    return DMCF_OK;
+    return bwd_names(a, pl, false, names, name_bytes);
+}
+
+int dmcf_cconv_backward_extents_kernel_names(const dmcf_cconv_args* a, const dmcf_cconv_backward_args* b, char* names,
+                                             size_t name_bytes) {
+    if (!names || name_bytes < 2) return DMCF_EINVAL;
+    BwdPlan pl;
+    const int rc = bwd_plan_extents(a, b, pl);
+    if (rc != DMCF_OK) return rc;
+    return bwd_names(a, pl, true, names, name_bytes);
 }
 
 }  // extern "C"

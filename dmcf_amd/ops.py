@@ -784,22 +784,27 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
                   align_corners=True, coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear",
                   normalize=False, symmetric=False, sym_axis=2, bias=None, out=None, accumulate=False,
                   n_pairs_ref=None, neighbors_row_count=None, filter_tile_mask=0, skip_self=False, name_only=False,
-                  row_length_hint=0, packed_cache=None):
+                  row_length_hint=0, packed_cache=None, record_per_point_extents=False):
     """One call of dmcf_cconv_forward (see ``_cconv_forward_impl`` for the arguments).
 
     When autograd records (``torch.is_grad_enabled()``) and ``filters`` or ``inp_features`` requires grad, the call goes
     through ``CconvFunction``: the same forward kernel, and a backward through dmcf_cconv_backward.  ``bias`` is then
-    differentiable too (torch adds it after the kernel).  ``out=`` / ``accumulate=True`` raise ValueError there, per-point
-    extents NotImplementedError.  Otherwise the call is exactly the inference path."""
+    differentiable too (torch adds it after the kernel).  ``out=`` / ``accumulate=True`` raise ValueError there.  Per-point
+    extents (a tensor [n_out] / [n_out, 1]) record only when the caller asks for it, ``record_per_point_extents=True``: the
+    backward is then dmcf_cconv_backward_extents, and the extents get no gradient (every pair is differentiated at the
+    extent of its output row, which for ASCC is not the momentum-conserving layer).  Without it such a call raises
+    NotImplementedError, as it always has.  Otherwise the call is exactly the inference path."""
     if not name_only and torch.is_grad_enabled() and (
             (isinstance(filters, torch.Tensor) and filters.requires_grad) or
             (isinstance(inp_features, torch.Tensor) and inp_features.requires_grad) or
             (isinstance(bias, torch.Tensor) and bias.requires_grad)):
         if out is not None or accumulate:
             raise ValueError("out= / accumulate=True cannot be recorded by autograd: use the returned tensor")
-        if per_point_extents(extent, out_positions.shape[0]) is not None:
-            raise NotImplementedError("the backward pass of CConv with per-point extents is not implemented")
-        kw = dict(out_positions=out_positions, extent=float(extent), inp_positions=inp_positions, neighbors_index=neighbors_index,
+        ext = per_point_extents(extent, out_positions.shape[0])
+        if ext is not None and not record_per_point_extents:
+            raise NotImplementedError("recording CConv with per-point extents is opt-in: pass record_per_point_extents=True "
+                                      "(the backward is dmcf_cconv_backward_extents; the extents get no gradient)")
+        kw = dict(out_positions=out_positions, extent=float(extent) if ext is None else ext.detach(), inp_positions=inp_positions, neighbors_index=neighbors_index,
                   neighbors_row_splits=neighbors_row_splits, neighbors_value=neighbors_value, window=window, window_fac=window_fac,
                   inp_importance=inp_importance, align_corners=align_corners, coordinate_mapping=coordinate_mapping,
                   interpolation=interpolation, normalize=normalize, symmetric=symmetric, sym_axis=sym_axis,
@@ -956,11 +961,19 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
     False: None is returned for it).  ``inverted``: an ``invert_neighbors_list`` result of the same list (formed here when
     the input-feature gradient is wanted and none is given).  ``grad_filters`` / ``grad_inp_features``: output tensors to
     write, or with ``accumulate=True`` to add into.  With ``symmetric`` the filter gradient is that of the stored half
-    kernel."""
+    kernel.  ``extent``: what ``cconv_forward`` accepts -- a scalar, or one extent per output row (a tensor [n_out] or
+    [n_out, 1], finite and positive: ValueError otherwise), which takes dmcf_cconv_backward_extents: every pair at the extent of
+    its output row.  Extents get no gradient."""
     L = _lib.lib()
     n_out, n_inp = out_positions.shape[0], inp_positions.shape[0]
     cin = filters.shape[3]
     dev = filters.device
+    ext = per_point_extents(extent, n_out)
+    if ext is not None:
+        ext = _dev_f32(ext, "extents")
+        if n_out > 0 and not bool((torch.isfinite(ext) & (ext > 0)).all()):
+            raise ValueError("per-point extents must be finite and positive")
+        extent = 1.0  # (args->extent is ignored by dmcf_cconv_backward_extents; the workspace query wants a positive one)
     grad_out = _dev_f32(grad_out, "grad_out", filters.shape[4])
     if grad_out.shape[0] != n_out:
         raise ValueError("grad_out must be [n_out, Cout]")
@@ -995,26 +1008,34 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
     nbytes = int(L.dmcf_cconv_backward_workspace_bytes(ctypes.byref(a), ctypes.byref(b)))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_cconv_backward(ctypes.byref(a), ctypes.byref(b), _ptr(ws), nbytes, _stream()), "dmcf_cconv_backward")
+    if ext is None:
+        _lib.check(L.dmcf_cconv_backward(ctypes.byref(a), ctypes.byref(b), _ptr(ws), nbytes, _stream()), "dmcf_cconv_backward")
+    else:
+        _lib.check(L.dmcf_cconv_backward_extents(ctypes.byref(a), ctypes.byref(b), _ptr(ext), _ptr(ws), nbytes, _stream()),
+                   "dmcf_cconv_backward_extents")
     if timer is not None:
         timer.end("cconv_backward", dict(n_out=n_out, cin=int(cin), cout=int(filters.shape[4]), filters=bool(need_filters),
-                                         features=bool(need_features), kernel=cconv_backward_kernel_names(a, b)), t0)
+                                         features=bool(need_features),
+                                         kernel=cconv_backward_kernel_names(a, b, extents=ext is not None)), t0)
     del keep
     return (grad_filters if need_filters else None), (grad_inp_features if need_features else None)
 
 
-def cconv_backward_kernel_names(a, b):
-    """';'-separated names of the kernels dmcf_cconv_backward launches for these (ctypes) arguments."""
+def cconv_backward_kernel_names(a, b, extents=False):
+    """';'-separated names of the kernels dmcf_cconv_backward -- ``extents``: dmcf_cconv_backward_extents, whose geometry kernels
+    carry the suffix _ext -- launches for these (ctypes) arguments."""
+    L = _lib.lib()
     name = ctypes.create_string_buffer(256)
-    _lib.check(_lib.lib().dmcf_cconv_backward_kernel_names(ctypes.byref(a), ctypes.byref(b), name, 256),
-               "dmcf_cconv_backward_kernel_names")
+    fn = L.dmcf_cconv_backward_extents_kernel_names if extents else L.dmcf_cconv_backward_kernel_names
+    _lib.check(fn(ctypes.byref(a), ctypes.byref(b), name, 256), "dmcf_cconv_backward_kernel_names")
     return name.value.decode()
 
 
 class CconvFunction(torch.autograd.Function):
     """Autograd node of ``cconv_forward``: the forward is whatever kernel the dispatch picks today (bias excluded: torch adds
-    it); the backward is dmcf_cconv_backward, with the neighbour list inverted once per backward when the input features want
-    a gradient.  Positions, extents and importances get no gradient (as in Open3D)."""
+    it); the backward is dmcf_cconv_backward (dmcf_cconv_backward_extents when ``kw["extent"]`` is a tensor of per-point
+    extents, which is kept for the backward and not differentiated), with the neighbour list inverted once per backward when
+    the input features want a gradient.  Positions, extents and importances get no gradient (as in Open3D)."""
 
     @staticmethod
     def forward(ctx, filters, inp_features, kw):

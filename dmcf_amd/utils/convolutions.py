@@ -9,7 +9,9 @@ search + one HIP kernel launch each (dmcf_amd/ops.py -> libdmcf_hip.so).
 
 Weights are built with ``requires_grad=False``: inference records no autograd history.  After
 ``layer.requires_grad_(True)`` (or with input features that require grad) a call records it and takes
-the neighbour-list form, whose backward is dmcf_cconv_backward (``ContinuousConv._forward_train``).
+the neighbour-list form, whose backward is dmcf_cconv_backward (``ContinuousConv._forward_train``).  Extents of rank 1, one
+per output point, record only in a layer built with ``record_per_point_extents=True`` (dmcf_cconv_backward_extents); any
+other layer refuses them while recording, as before.
 """
 import math
 import os
@@ -461,9 +463,12 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                  radius_search_ignore_query_points=False, radius_search_metric="L2", offset=None,
                  window_function=None, use_dense_layer_for_center=False,
                  dense_kernel_initializer="glorot_uniform", dense_kernel_regularizer=None, in_channels=None,
-                 symmetric=False, sym_axis=2, circular=False, name=None, trainable=True, device=None, **kwargs):
+                 symmetric=False, sym_axis=2, circular=False, name=None, trainable=True, device=None,
+                 record_per_point_extents=False, **kwargs):
         super().__init__()
         self.layer_name = name
+        # may a call with extents of rank 1 record autograd history (_forward_train; not a keyword of the reference)
+        self.record_per_point_extents = bool(record_per_point_extents)
         self.filters = filters
         self.kernel_size = [int(k) for k in kernel_size]
         if activation not in _ACTIVATIONS and not callable(activation):
@@ -585,25 +590,37 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
     def _forward_train(self, inp_features, inp_positions, out_positions, extents, inp_importance, hash_table,
                        user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance):
         """The layer while autograd records: always the neighbour-list form through ops.cconv_forward's autograd node
-        (dmcf_cconv_backward).  The lattice and scatter forms, the stray-row path, the step's list cache and the epilogue fusions
+        (dmcf_cconv_backward; extents of rank 1, one per output point, in a layer built with record_per_point_extents=True:
+        dmcf_cconv_backward_extents).  The lattice and scatter
+        forms, the stray-row path, the step's list cache and the epilogue fusions
         (accumulate_into / extra_bias, fused bias) are not taken: their kernels have no backward.  Bias, the dense centre term,
         the activation and the circular expansion are torch ops.  A pending accumulate_into / extra_bias request is honoured out
         of place: the result is ``accumulate_into + layer(x) + extra_bias`` (accumulate_into itself is not written)."""
         d = self.__dict__
         acc, extra_bias = self.accumulate_into, self.extra_bias
         d["accumulate_into"] = d["extra_bias"] = None
-        if _rank1_extents(extents, out_positions):
-            raise NotImplementedError("ContinuousConv with per-point extents (rank 1) has no backward pass: the training path "
-                                      "supports a scalar extent only")
-        if isinstance(extents, torch.Tensor):
+        window, window_fac, neighbors_value = None, 1.0, None
+        row_count = None
+        rank1 = _rank1_extents(extents, out_positions)
+        if rank1 and not self.record_per_point_extents:
+            raise NotImplementedError("ContinuousConv with per-point extents (rank 1) records only when built with "
+                                      "record_per_point_extents=True; without it the training path takes a scalar extent only")
+        if rank1:
+            # one extent per output point (:366-370): the search and the window of _forward_extents, then the same call -- the
+            # extents go to ops.cconv_forward as a tensor and get no gradient, as in Open3D
+            with torch.no_grad():
+                extent = extents.detach()
+                neighbors_index, neighbors_row_splits, window, window_fac, neighbors_value = self._extents_lists(
+                    inp_positions, out_positions, extent, user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
+        elif isinstance(extents, torch.Tensor):
             if extents.dim() > 0 and extents.numel() != 1:
                 raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:352-372)")
             extent = float(extents)
         else:
             extent = float(np.float32(extents))
-        window, window_fac, neighbors_value = None, 1.0, None
-        row_count = None
-        if user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
+        if rank1:
+            pass
+        elif user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
             neighbors_index, neighbors_row_splits = user_neighbors_index, user_neighbors_row_splits
             if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
                 window, neighbors_value = "explicit", user_neighbors_importance
@@ -638,7 +655,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             interpolation=self.interpolation, normalize=self.normalize, symmetric=symmetric, sym_axis=self.sym_axis,
             neighbors_row_count=row_count, row_length_hint=self.row_length_hint,
             packed_cache=self._packed if (kernel is self.kernel and os.environ.get("DMCF_CACHE_PACKED_FILTERS", "1") != "0")
-            else None)
+            else None, **({"record_per_point_extents": True} if rank1 else {}))
         if self.use_bias and not self.use_dense_layer_for_center:
             out_features = out_features + self.bias
         d["_conv_output"] = None
@@ -829,13 +846,11 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                                       "models/pbf_model.py:203)")
         return kernel, symmetric
 
-    def _forward_extents(self, inp_features, inp_positions, out_positions, extents, inp_importance, user_neighbors_index,
-                         user_neighbors_row_splits, user_neighbors_importance, acc, extra_bias):
-        """The branch for extents of rank 1 (convolutions.py:366-370, then :397-399): a radius per output point (RadiusSearch),
-        every row convolved at its own extent (ops.cconv_forward -> dmcf_cconv_forward_extents; with SYMMETRIC each pair at its
-        output row's extent, which does not conserve momentum).  Never the lattice / scatter forms or the step's neighbour
-        cache: all of them key on one radius."""
-        d = self.__dict__
+    def _extents_lists(self, inp_positions, out_positions, extents, user_neighbors_index, user_neighbors_row_splits,
+                       user_neighbors_importance):
+        """Search + window of the rank-1 branch, for the inference and the training call alike: (neighbors_index,
+        neighbors_row_splits, window, window_fac, neighbors_value) -- the caller's list (:341-349), or a RadiusSearch at
+        radii = extents / 2 (kept in ``.nns``).  Call under no_grad."""
         n_out = out_positions.shape[0]
         if extents.shape[0] != n_out:
             raise ValueError(f"extents of rank 1 must hold one value per output point ({n_out}), got {extents.shape[0]}")
@@ -849,7 +864,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             named = isinstance(self.window_function, WindowFunction)
             # (a named window is evaluated in the kernel on d^2 re-formed from the positions: no distances needed)
             search = self.radius_search.index_only() if named else self.radius_search
-            d["nns"] = search(inp_positions, out_positions, radii)
+            self.__dict__["nns"] = search(inp_positions, out_positions, radii)
             neighbors_index, neighbors_row_splits, dist = self.nns
             if self.window_function is not None:
                 # The reference's rank-1 branch never binds neighbors_distance_normalized (:366-379: only the rank-0 branch
@@ -859,6 +874,18 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                     window, window_fac = self.window_function.name, self.window_function.fac  # q = d^2 / r_i^2 in the kernel
                 else:
                     window, neighbors_value = "explicit", self.window_function(dist).to(torch.float32)
+        return neighbors_index, neighbors_row_splits, window, window_fac, neighbors_value
+
+    def _forward_extents(self, inp_features, inp_positions, out_positions, extents, inp_importance, user_neighbors_index,
+                         user_neighbors_row_splits, user_neighbors_importance, acc, extra_bias):
+        """The branch for extents of rank 1 (convolutions.py:366-370, then :397-399): a radius per output point (RadiusSearch),
+        every row convolved at its own extent (ops.cconv_forward -> dmcf_cconv_forward_extents; with SYMMETRIC each pair at its
+        output row's extent, which does not conserve momentum).  Never the lattice / scatter forms or the step's neighbour
+        cache: all of them key on one radius."""
+        d = self.__dict__
+        n_out = out_positions.shape[0]
+        neighbors_index, neighbors_row_splits, window, window_fac, neighbors_value = self._extents_lists(
+            inp_positions, out_positions, extents, user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
         d["_n_out_last"] = n_out
         d["_pairs_last"] = neighbors_index.shape[0]
         kernel, symmetric = self._conv_kernel()

@@ -15,7 +15,8 @@
  *   ASCC: mirror :410-412 + second continuous_conv :433-458      dmcf_cconv_forward(DMCF_FLAG_SYMMETRIC)
  *   ml3d.layers.RadiusSearch (utils/convolutions.py:212-216,     dmcf_frs_build / dmcf_radius_search_count /
  *     366-370, 1006-1010: extents of rank 1)                      dmcf_radius_search_write
- *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents
+ *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
+ *                                                                 dmcf_cconv_backward_extents)
  *   o3dml.ops.reduce_subarrays_sum (models/pbf_model.py:450-453) dmcf_reduce_subarrays_sum
  *   tf.keras.layers.Dense (models/hrnet.py:49,93-99;             dmcf_dense_forward
  *     models/pbf_model.py:134-152)
@@ -334,7 +335,7 @@ int dmcf_invert_neighbors_list(int64_t n_inp, const int32_t* neighbors_index, co
  * and grad_filters is the gradient of the stored HALF kernel (the full kernel's gradient folded back:
  * dHalf = dFull[upper] - flip_zyx(dFull[lower])); n_inp != n_out (the sharded layout) is DMCF_EUNSUPPORTED.
  * Every option of dmcf_cconv_forward is supported: mappings, interpolations, ALIGN_CORNERS, windows (neighbors_value == NULL
- * included), NORMALIZE, inp_importance, SYMMETRIC, SKIP_SELF, padded lists.  Per-point extents are not.
+ * included), NORMALIZE, inp_importance, SYMMETRIC, SKIP_SELF, padded lists.  Per-point extents: dmcf_cconv_backward_extents.
  * The geometry of each pair is formed as in the generic forward kernel; only the order of the sums differs.  No float
  * atomics: two identical calls give identical bits.  K * Cin and K * Cout above 16384 (K the full kernel's cells):
  * DMCF_EUNSUPPORTED.
@@ -360,6 +361,27 @@ int dmcf_cconv_backward(const dmcf_cconv_args* fwd, const dmcf_cconv_backward_ar
  * (names as rocprofv3 prints them without the namespace, e.g. "cconv_bwd_input") */
 int dmcf_cconv_backward_kernel_names(const dmcf_cconv_args* fwd, const dmcf_cconv_backward_args* bwd, char* names,
                                      size_t name_bytes);
+
+/* Backward pass of dmcf_cconv_forward_extents (ABI 2.15): dmcf_cconv_backward with INDIVIDUAL extents.  Every pair of output
+ * row i is evaluated at e_i = out_extents[i] (device, [n_out]): 1 / e_i and 1 / (e_i / 2)^2, formed with the forward's
+ * operations, take the place of the scalar's two constants, so the gradients are those of the function the forward computed.
+ * The extents themselves get no gradient.  fwd->extent is ignored.  Everything else is dmcf_cconv_backward's contract: the same
+ * options, the struct_size check, the K * Cin / K * Cout limits, no float atomics (two identical calls give identical bits),
+ * and the workspace of dmcf_cconv_backward_workspace_bytes(fwd, bwd), which asks for a positive fwd->extent (any value: the
+ * size does not depend on it).
+ *   SYMMETRIC  each pair at the extent of its OUTPUT row, as in the forward: pair (i, j) and pair (j, i) see different extents;
+ *              the centre term of row i uses e_i; grad_filters is folded onto the stored half as in dmcf_cconv_backward.
+ *   A row whose extent is not positive and finite is an empty row, as in the forward: it adds nothing to grad_filters nor to
+ *   any row of grad_inp_features (the centre term included), and its psi_i is 0.
+ *   out_extents == NULL with n_out > 0: DMCF_EINVAL.  DMCF_FLAG_SKIP_SELF: DMCF_EUNSUPPORTED (the forward rejects it too).
+ *   Every argument error is returned before anything is enqueued.
+ * The kernels that form a pair's geometry run in their individual-extent form, which dmcf_cconv_backward_extents_kernel_names
+ * reports with the suffix _ext ("cconv_bwd_norm_ext", "cconv_bwd_input_ext", "cconv_bwd_filter_splat_ext"); the others are
+ * dmcf_cconv_backward's. */
+int dmcf_cconv_backward_extents(const dmcf_cconv_args* fwd, const dmcf_cconv_backward_args* bwd, const float* out_extents,
+                                void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+int dmcf_cconv_backward_extents_kernel_names(const dmcf_cconv_args* fwd, const dmcf_cconv_backward_args* bwd, char* names,
+                                             size_t name_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * ml3d.ops.continuous_conv (utils/convolutions.py:414-431) FROM particles ONTO a coarse grid_pos lattice with few output
