@@ -18,6 +18,8 @@
 //                       matrices are staged through LDS in chunks and shared by the 4 waves x 2 tiles of a workgroup.  A
 //                       first version gathered rows through a cell -> point table in point order: 2.3 ms for the s1 -> s1
 //                       layer of the 1M-particle scene, bound by 9.5 GB of scattered 32-byte reads.
+// The backward of this form (dmcf_lattice_conv_backward) is cconv_lat_bwd.inc, included below: it reuses the filter build and the
+// row list.
 // The offsets are nominal (d * voxel in fp32); the reference forms fl(x_in) - fl(x_out), which differs by ~1 ulp of |x|:
 // up to 1e-5 of the output scale at |x| ~ 6.  Pairs at exactly the radius have window 0 either way.
 #include "cconv_common.h"
@@ -138,6 +140,27 @@ __global__ __launch_bounds__(256) void lat_rows_write(const LatBatch b) {
     }
 }
 
+// Everything the operator evaluates per neighbour pair, for stencil offset s: the window value and, per axis, the first of the
+// two filter cells and their trilinear weights.  lat_build_filters and the backward's fold (cconv_lat_bwd.inc) share it, so
+// the gradient is taken of the very matrices the forward multiplied with.
+struct LatTaps {
+    float a;
+    int bx, by, bz;
+    float wx[2], wy[2], wz[2];
+};
+__device__ __forceinline__ LatTaps lat_offset_taps(const int32_t* __restrict__ stencil, int s, const CconvParams& p, float vx, float vy,
+                                                   float vz, float sx, float sy, float sz) {
+    LatTaps g;
+    float x = (float)stencil[4 * s] * vx - sx, y = (float)stencil[4 * s + 1] * vy - sy, z = (float)stencil[4 * s + 2] * vz - sz;
+    const float d2 = (x * x + y * y) + z * z;
+    g.a = window_value(p.window, d2, p.inv_r2, p.window_fac);
+    filter_coords<true>(x, y, z, p);
+    axis_weights(x, p.sx, p.interp, g.bx, g.wx[0], g.wx[1]);
+    axis_weights(y, p.sy, p.interp, g.by, g.wy[0], g.wy[1]);
+    axis_weights(z, p.sz, p.interp, g.bz, g.wz[0], g.wz[1]);
+    return g;
+}
+
 __global__ __launch_bounds__(256) void lat_build_filters(const float* __restrict__ W, float* __restrict__ Wp,
                                                          const int32_t* __restrict__ stencil, int S, int KS, int NT, CconvParams p,
                                                          float vx, float vy, float vz, float sx, float sy, float sz) {
@@ -153,24 +176,16 @@ __global__ __launch_bounds__(256) void lat_build_filters(const float* __restrict
         const int s = (int)t * 4 + q, o = nt * 16 + n;
         float v = 0.0f;
         if (s < S && c < p.cin && o < p.cout) {
-            float x = (float)stencil[4 * s] * vx - sx, y = (float)stencil[4 * s + 1] * vy - sy, z = (float)stencil[4 * s + 2] * vz - sz;
-            const float d2 = (x * x + y * y) + z * z;
-            const float a = window_value(p.window, d2, p.inv_r2, p.window_fac);
-            filter_coords<true>(x, y, z, p);
-            int bx, by, bz;
-            float wx[2], wy[2], wz[2];
-            axis_weights(x, p.sx, p.interp, bx, wx[0], wx[1]);
-            axis_weights(y, p.sy, p.interp, by, wy[0], wy[1]);
-            axis_weights(z, p.sz, p.interp, bz, wz[0], wz[1]);
+            const LatTaps g = lat_offset_taps(stencil, s, p, vx, vy, vz, sx, sy, sz);
             for (int iz = 0; iz < 2; ++iz)
                 for (int iy = 0; iy < 2; ++iy)
                     for (int ix = 0; ix < 2; ++ix) {
-                        const float w = wz[iz] * wy[iy] * wx[ix];
+                        const float w = g.wz[iz] * g.wy[iy] * g.wx[ix];
                         if (w == 0.0f) continue;  // also the "+1" cells that do not exist on size-1 axes
-                        const int cz = min(bz + iz, p.sz - 1), cy = min(by + iy, p.sy - 1), cx = min(bx + ix, p.sx - 1);
+                        const int cz = min(g.bz + iz, p.sz - 1), cy = min(g.by + iy, p.sy - 1), cx = min(g.bx + ix, p.sx - 1);
                         v += w * W[((((int64_t)cz * p.sy + cy) * p.sx + cx) * p.cin + c) * p.cout + o];
                     }
-            v *= a;
+            v *= g.a;
         }
         Wp[e] = v;
     }
@@ -347,6 +362,23 @@ static int lat_validate(const dmcf_lattice_conv_args* a) {
 
 namespace dmcf {
 
+// the operator's options in the form the shared geometry code reads them
+static CconvParams lat_cconv_params(const dmcf_lattice_conv_args* a) {
+    CconvParams cp = {};
+    cp.sz = a->filter_dims[0]; cp.sy = a->filter_dims[1]; cp.sx = a->filter_dims[2];
+    cp.K = cp.sx * cp.sy * cp.sz;
+    cp.cin = a->filter_dims[3]; cp.cout = a->filter_dims[4];
+    cp.inv_extent = 1.0f / a->extent;
+    const float radius = 0.5f * a->extent;
+    cp.inv_r2 = 1.0f / (radius * radius);
+    cp.window_fac = a->window_fac;
+    cp.window = a->window;
+    cp.mapping = a->coordinate_mapping;
+    cp.interp = a->interpolation;
+    cp.flags = a->flags;
+    return cp;
+}
+
 // validates one launch, enqueues its filter build into `packed`, fills the kernel parameters
 static int lat_prepare(const dmcf_lattice_conv_args* a, float* packed, hipStream_t stream, LatParams& p, int64_t& groups) {
     const int cin = a->filter_dims[3], cout = a->filter_dims[4];
@@ -358,18 +390,7 @@ static int lat_prepare(const dmcf_lattice_conv_args* a, float* packed, hipStream
         if (a->reach[k] < 0 || lo < a->inp_min[k] || hi > (int64_t)a->inp_min[k] + a->inp_dims[k] - 1) return DMCF_EINVAL;
     }
     if ((int64_t)a->inp_dims[0] * a->inp_dims[1] * a->inp_dims[2] * cin > 0x1fffffff) return DMCF_EUNSUPPORTED;  // 32-bit byte offsets
-    CconvParams cp = {};
-    cp.sz = a->filter_dims[0]; cp.sy = a->filter_dims[1]; cp.sx = a->filter_dims[2];
-    cp.K = cp.sx * cp.sy * cp.sz;
-    cp.cin = cin; cp.cout = cout;
-    cp.inv_extent = 1.0f / a->extent;
-    const float radius = 0.5f * a->extent;
-    cp.inv_r2 = 1.0f / (radius * radius);
-    cp.window_fac = a->window_fac;
-    cp.window = a->window;
-    cp.mapping = a->coordinate_mapping;
-    cp.interp = a->interpolation;
-    cp.flags = a->flags;
+    const CconvParams cp = lat_cconv_params(a);
     if (a->n_offsets > 0) {
         const int64_t total = (int64_t)lat_packed_floats(a);
         const unsigned g = (unsigned)((total + 255) / 256);
@@ -425,20 +446,24 @@ static LatLayout lat_layout(const dmcf_lattice_conv_args* parts, int n_parts) {
     return L;
 }
 
-static int lat_launch(const dmcf_lattice_conv_args* parts, int n_parts, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// the parts of one call: each valid, one kernel instantiation and one output for the whole grid
+static int lat_check(const dmcf_lattice_conv_args* parts, int n_parts) {
     for (int i = 0; i < n_parts; ++i) {
         const int rc = lat_validate(parts + i);
         if (rc != DMCF_OK) return rc;
         if (parts[i].filter_dims[3] != parts[0].filter_dims[3] || parts[i].filter_dims[4] != parts[0].filter_dims[4] ||
             parts[i].n_out != parts[0].n_out || parts[i].out != parts[0].out)
-            return DMCF_EINVAL;  // one kernel instantiation and one output for the whole grid
+            return DMCF_EINVAL;
     }
-    if (parts[0].n_out == 0) return DMCF_OK;
+    return DMCF_OK;
+}
+
+// (n_out > 0) enqueues the filter builds and the row compaction of every part into the workspace, fills b
+static int lat_rows(const dmcf_lattice_conv_args* parts, int n_parts, void* workspace, size_t workspace_bytes, size_t need,
+                    hipStream_t stream, LatBatch& b, const LatLayout& L) {
     if (!workspace || ((uintptr_t)workspace & 255)) return DMCF_EINVAL;
-    const LatLayout L = lat_layout(parts, n_parts);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    if (workspace_bytes < need) return DMCF_EWORKSPACE;
     if (L.nblk > 0x7ffffffe) return DMCF_EUNSUPPORTED;
-    LatBatch b;
     b.n = n_parts;
     char* ws = (char*)workspace;
     char* wp = ws;
@@ -465,6 +490,17 @@ static int lat_launch(const dmcf_lattice_conv_args* parts, int n_parts, void* wo
     b.blk = (uint32_t*)(ws + L.off_scan);
     hipLaunchKernelGGL(lat_rows_starts, dim3(1), dim3(64), 0, stream, b);
     hipLaunchKernelGGL(lat_rows_write, dim3((unsigned)L.nblk), dim3(256), 0, stream, b);
+    return DMCF_OK;
+}
+
+static int lat_launch(const dmcf_lattice_conv_args* parts, int n_parts, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    int rc = lat_check(parts, n_parts);
+    if (rc != DMCF_OK) return rc;
+    if (parts[0].n_out == 0) return DMCF_OK;
+    const LatLayout L = lat_layout(parts, n_parts);
+    LatBatch b;
+    rc = lat_rows(parts, n_parts, workspace, workspace_bytes, L.total, stream, b, L);
+    if (rc != DMCF_OK) return rc;
     const dim3 grid((unsigned)(L.rows_capacity / kLatRowsPerGroup)), block(256);
     const int KS = b.part[0].KS, NT = b.part[0].NT;
     if (KS == 1 && NT == 1) hipLaunchKernelGGL((lat_conv_kernel<1, 1>), grid, block, 0, stream, b);
@@ -473,6 +509,8 @@ static int lat_launch(const dmcf_lattice_conv_args* parts, int n_parts, void* wo
     else hipLaunchKernelGGL((lat_conv_kernel<2, 2>), grid, block, 0, stream, b);
     return check_launch();
 }
+
+#include "cconv_lat_bwd.inc"
 
 }  // namespace dmcf
 
@@ -501,6 +539,17 @@ int dmcf_lattice_conv_forward_batch(const dmcf_lattice_conv_args* parts, int32_t
                                     dmcf_stream_t stream_) {
     if (!parts || n_parts < 1 || n_parts > kLatMaxParts) return DMCF_EINVAL;
     return lat_launch(parts, n_parts, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+size_t dmcf_lattice_conv_backward_workspace_bytes(const dmcf_lattice_conv_args* parts, int32_t n_parts) {
+    dmcf_lattice_conv_args own[kLatMaxParts];
+    if (lat_bwd_parts(parts, n_parts, own) != DMCF_OK) return 256;
+    return lat_bwd_layout(own, n_parts).total;
+}
+
+int dmcf_lattice_conv_backward(const dmcf_lattice_conv_args* parts, int32_t n_parts, const float* grad_out, float* grad_volume,
+                               float* grad_filters, void* workspace, size_t workspace_bytes, dmcf_stream_t stream_) {
+    return lat_backward(parts, n_parts, grad_out, grad_volume, grad_filters, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 }  // extern "C"

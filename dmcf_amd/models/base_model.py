@@ -104,6 +104,18 @@ class BaseModel(PlainAttributes, torch.nn.Module):
         out-of-place forms (the fused epilogues and paired launches have no backward)."""
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
+    def record_lattice_form(self, on=True):
+        """Sets ``record_lattice_form`` on every ContinuousConv of the model: while autograd records, the layers between two
+        grid_pos lattices then keep the stencil form and take dmcf_lattice_conv_backward (off: every recording layer takes the
+        neighbour-list form, the default).  Inference is not affected.  Returns the number of layers set."""
+        from ..utils.convolutions import ContinuousConv
+        n = 0
+        for m in self.modules():
+            if isinstance(m, ContinuousConv):
+                m.record_lattice_form = bool(on)
+                n += 1
+        return n
+
     def loss(self, results, data):
         raise NotImplementedError(f"{type(self).__name__} defines no loss")
 

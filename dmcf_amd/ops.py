@@ -720,16 +720,26 @@ def lattice_conv(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel,
     ``a * out_stride + out_phase`` for the base vectors a of the box (``base_min``, ``base_dims``; default: the whole output
     table with stride 1); their stencil is ``a * inp_step + d`` (see include/dmcf_hip.h).
     ``parts``: a list of up to 8 dicts (out_phase, rel_shift, base_min, base_dims) that replace those four arguments and
-    run as ONE grid (dmcf_lattice_conv_forward_batch); every part writes rows of its own."""
-    L = _lib.lib()
-    dev = filters.device
-    cin, cout = filters.shape[3], filters.shape[4]
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs an out tensor")
-        out = torch.zeros((n_out, cout), dtype=torch.float32, device=dev)  # rows without a cell stay 0
-    filters = filters.contiguous()
-    if inp_volume.dim() != 4 or inp_volume.shape[3] != cin or not inp_volume.is_contiguous() or not out_table.is_contiguous():
+    run as ONE grid (dmcf_lattice_conv_forward_batch); every part writes rows of its own.
+    While autograd records and ``filters``, ``inp_volume`` or ``bias`` requires grad, the call is a node of the graph
+    (:class:`LatticeConvFunction`; ``out`` / ``accumulate`` are refused then); otherwise it is the plain forward call."""
+    kw = dict(inp_step=inp_step, out_stride=out_stride, out_phase=out_phase, rel_shift=rel_shift, base_min=base_min,
+              base_dims=base_dims, window=window, window_fac=window_fac, align_corners=align_corners,
+              coordinate_mapping=coordinate_mapping, interpolation=interpolation, parts=parts)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (filters, inp_volume, bias)):
+        if out is not None or accumulate:
+            raise ValueError("lattice_conv: out / accumulate cannot be recorded for autograd")
+        geo = dict(kw, inp_min=inp_min, out_table=out_table, out_min=out_min, n_out=n_out, voxel=voxel, extent=extent)
+        return LatticeConvFunction.apply(filters, inp_volume, bias, geo, dict(fill=fill, n_out_launch=n_out_launch))
+    return _lattice_conv_impl(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, bias=bias, out=out,
+                              accumulate=accumulate, fill=fill, n_out_launch=n_out_launch, **kw)
+
+
+def _lattice_parts(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step, out_stride, out_phase, rel_shift,
+                   base_min, base_dims, window, window_fac, align_corners, coordinate_mapping, interpolation, bias, out, accumulate,
+                   parts):
+    """(ctypes array of dmcf_lattice_conv_args, tensors to keep alive, stencil offsets of all parts) of one call."""
+    if inp_volume.dim() != 4 or inp_volume.shape[3] != filters.shape[3] or not inp_volume.is_contiguous() or not out_table.is_contiguous():
         raise ValueError("inp_volume must be a contiguous [dz, dy, dx, Cin] tensor, out_table a contiguous [dz, dy, dx] one")
     if parts is None:
         parts = [dict(out_phase=out_phase, rel_shift=rel_shift, base_min=base_min, base_dims=base_dims)]
@@ -741,6 +751,26 @@ def lattice_conv(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel,
                                       align_corners, coordinate_mapping, interpolation, bias, out, accumulate)
         keep.append(k)
         n_off += no
+    return arr, keep, n_off
+
+
+def _lattice_conv_impl(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step=1, out_stride=1,
+                       out_phase=(0, 0, 0), rel_shift=(0.0, 0.0, 0.0), base_min=None, base_dims=None, window="poly6",
+                       window_fac=1.0, align_corners=True, coordinate_mapping="ball_to_cube_volume_preserving",
+                       interpolation="linear", bias=None, out=None, accumulate=False, fill=1.0, n_out_launch=None, parts=None):
+    """The forward launch of :func:`lattice_conv` (no autograd)."""
+    L = _lib.lib()
+    dev = filters.device
+    cin, cout = filters.shape[3], filters.shape[4]
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs an out tensor")
+        out = torch.zeros((n_out, cout), dtype=torch.float32, device=dev)  # rows without a cell stay 0
+    filters = filters.contiguous()
+    arr, keep, n_off = _lattice_parts(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step, out_stride,
+                                      out_phase, rel_shift, base_min, base_dims, window, window_fac, align_corners, coordinate_mapping,
+                                      interpolation, bias, out, accumulate, parts)
+    parts = arr  # (only its length is used below)
     if len(parts) == 1:
         nbytes = L.dmcf_lattice_conv_workspace_bytes(arr)
     else:
@@ -763,6 +793,73 @@ def lattice_conv(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel,
                                 volume_bytes=int(inp_volume.numel()) * 4, table_bytes=int(out_table.numel()) * 4,
                                 accumulate=bool(accumulate)), t0)
     return out
+
+
+def lattice_conv_backward(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, grad_out, inp_step=1,
+                          out_stride=1, out_phase=(0, 0, 0), rel_shift=(0.0, 0.0, 0.0), base_min=None, base_dims=None,
+                          window="poly6", window_fac=1.0, align_corners=True,
+                          coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", parts=None,
+                          need_volume=True, need_filters=True, **_ignored):
+    """dmcf_lattice_conv_backward: ``(grad_volume | None, grad_filters | None)`` of the convolution :func:`lattice_conv`
+    computes with these arguments, for ``grad_out`` = dL/d out [n_out, Cout].  ``grad_volume`` has the shape of
+    ``inp_volume`` (zero in cells no output reaches), ``grad_filters`` that of ``filters`` (summed over all ``parts``).  Rows
+    of ``grad_out`` whose point is not in ``out_table`` contribute nothing.  One call of the entry point; no neighbour
+    list, no inversion, no float atomics (two calls return the same bits)."""
+    L = _lib.lib()
+    filters = _dev_f32(filters, "filters")
+    dev = filters.device
+    grad_out = _dev_f32(grad_out, "grad_out", filters.shape[4])
+    if grad_out.shape[0] != n_out:
+        raise ValueError("grad_out must be [n_out, Cout]")
+    if not need_volume and not need_filters:
+        return None, None
+    arr, keep, _ = _lattice_parts(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step, out_stride,
+                                  out_phase, rel_shift, base_min, base_dims, window, window_fac, align_corners, coordinate_mapping,
+                                  interpolation, None, grad_out, False, parts)
+    gv = torch.empty_like(inp_volume) if need_volume else None
+    gw = torch.empty_like(filters) if need_filters else None
+    nbytes = int(L.dmcf_lattice_conv_backward_workspace_bytes(arr, len(arr)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_lattice_conv_backward(arr, len(arr), _ptr(grad_out), _ptr(gv), _ptr(gw), _ptr(ws), nbytes, _stream()),
+               "dmcf_lattice_conv_backward")
+    if timer is not None:
+        timer.end("cconv_backward", dict(n_out=int(n_out), cin=int(filters.shape[3]), cout=int(filters.shape[4]),
+                                         filters=bool(need_filters), features=bool(need_volume), lattice=True, parts=len(arr),
+                                         kernel="lat_bwd_filter;lat_bwd_input"), t0)
+    del keep
+    return gv, gw
+
+
+class LatticeConvFunction(torch.autograd.Function):
+    """Autograd node of :func:`lattice_conv`.  It keeps the volume, the cell -> point table, the filters and the parts
+    themselves (``geo``), not the lattices they came from: the per-step cache forgets those when the step ends.  The backward
+    is one dmcf_lattice_conv_backward; the bias takes ``grad_out`` summed over the rows that are in the table (the rows the
+    forward adds it to).  The volume's gradient reaches per-point features through the indexing that built the volume."""
+
+    @staticmethod
+    def forward(ctx, filters, inp_volume, bias, geo, info):
+        ctx.geo = geo
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(filters, inp_volume)
+        return _lattice_conv_impl(filters, inp_volume, bias=bias, **geo, **info)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        filters, inp_volume = ctx.saved_tensors
+        need_w, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        grad_out = grad_out.contiguous()
+        gv, gw = lattice_conv_backward(filters.detach(), inp_volume.detach(), grad_out=grad_out, need_volume=need_v,
+                                       need_filters=need_w, **ctx.geo)
+        gb = None
+        if need_b:
+            n_out = int(ctx.geo["n_out"])
+            rows = ctx.geo["out_table"].reshape(-1).long()
+            hit = torch.zeros(n_out + 1, dtype=grad_out.dtype, device=grad_out.device)
+            hit[torch.where(rows >= 0, rows, torch.full_like(rows, n_out))] = 1.0  # (the spare slot takes the empty cells)
+            gb = (grad_out * hit[:n_out, None]).sum(0)
+        return gw, gv, gb, None, None
 
 
 def block_diagonal_tile_mask(blocks):

@@ -522,6 +522,10 @@ class Simulator:
             log.setLevel(logging.INFO)
         log.addHandler(handler)
         try:
+            # pipeline key train_lattice_form (default false): recording layers between two grid_pos lattices keep the stencil
+            # form and its own backward (ContinuousConv(record_lattice_form=True))
+            if hasattr(model, "record_lattice_form"):
+                model.record_lattice_form(bool(cfg.get("train_lattice_form", False)))
             schedule = TrainSchedule(cfg)
             loader = self.train_loader(schedule)
             first = next(loader)

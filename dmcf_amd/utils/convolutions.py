@@ -464,11 +464,13 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                  window_function=None, use_dense_layer_for_center=False,
                  dense_kernel_initializer="glorot_uniform", dense_kernel_regularizer=None, in_channels=None,
                  symmetric=False, sym_axis=2, circular=False, name=None, trainable=True, device=None,
-                 record_per_point_extents=False, **kwargs):
+                 record_per_point_extents=False, record_lattice_form=False, **kwargs):
         super().__init__()
         self.layer_name = name
         # may a call with extents of rank 1 record autograd history (_forward_train; not a keyword of the reference)
         self.record_per_point_extents = bool(record_per_point_extents)
+        # may a recording call between two grid_pos lattices keep the stencil form (_forward_train; dmcf_lattice_conv_backward)
+        self.record_lattice_form = bool(record_lattice_form)
         self.filters = filters
         self.kernel_size = [int(k) for k in kernel_size]
         if activation not in _ACTIVATIONS and not callable(activation):
@@ -589,10 +591,13 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
 
     def _forward_train(self, inp_features, inp_positions, out_positions, extents, inp_importance, hash_table,
                        user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance):
-        """The layer while autograd records: always the neighbour-list form through ops.cconv_forward's autograd node
+        """The layer while autograd records: the neighbour-list form through ops.cconv_forward's autograd node
         (dmcf_cconv_backward; extents of rank 1, one per output point, in a layer built with record_per_point_extents=True:
-        dmcf_cconv_backward_extents).  The lattice and scatter
-        forms, the stray-row path, the step's list cache and the epilogue fusions
+        dmcf_cconv_backward_extents).  A layer built with record_lattice_form=True keeps the stencil form between two grid_pos
+        lattices (ops.lattice_conv's autograd node, dmcf_lattice_conv_backward: no search, no inversion) when the pair is whole --
+        no stray rows -- and its spacings are in the ratio 1, 2 or 1/2; opt-in, because that form uses the nominal offsets
+        d * voxel (dmcf_amd/lattice.py) where the neighbour-list form subtracts rounded positions.  The scatter
+        form, the stray-row path, the step's list cache and the epilogue fusions
         (accumulate_into / extra_bias, fused bias) are not taken: their kernels have no backward.  Bias, the dense centre term,
         the activation and the circular expansion are torch ops.  A pending accumulate_into / extra_bias request is honoured out
         of place: the result is ``accumulate_into + layer(x) + extra_bias`` (accumulate_into itself is not written)."""
@@ -618,6 +623,21 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             extent = float(extents)
         else:
             extent = float(np.float32(extents))
+        lat = None
+        if self.record_lattice_form and not rank1 and (user_neighbors_index is None or user_neighbors_row_splits is None):
+            lat = self._lattice_form(inp_features, inp_positions, out_positions, inp_importance, hash_table, extent)
+            if lat is not None and (lat.cropped or lat.ratio not in (1, 2, 0.5)):
+                lat = None  # (stray rows would need the neighbour-list form beside it: the whole layer takes that form)
+        if lat is not None:
+            d["nns"] = None
+            d["_n_out_last"] = out_positions.shape[0]
+            d["_pairs_last"] = 0
+            d["_conv_values"] = None
+            out_features = lat.conv(ops, self.kernel, inp_features, out_positions.shape[0], extent,
+                                    window=self.window_function.name, window_fac=self.window_function.fac,
+                                    align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
+                                    interpolation=self.interpolation)
+            return self._train_epilogue(out_features, inp_features, acc, extra_bias)
         if rank1:
             pass
         elif user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
@@ -656,9 +676,13 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             neighbors_row_count=row_count, row_length_hint=self.row_length_hint,
             packed_cache=self._packed if (kernel is self.kernel and os.environ.get("DMCF_CACHE_PACKED_FILTERS", "1") != "0")
             else None, **({"record_per_point_extents": True} if rank1 else {}))
+        return self._train_epilogue(out_features, inp_features, acc, extra_bias)
+
+    def _train_epilogue(self, out_features, inp_features, acc, extra_bias):
+        """What follows the convolution of a recording call, as torch ops: bias, dense centre term, activation, the sums."""
         if self.use_bias and not self.use_dense_layer_for_center:
             out_features = out_features + self.bias
-        d["_conv_output"] = None
+        self.__dict__["_conv_output"] = None
         # (where the inference path puts the extra bias: inside the activation, unless the call also accumulates)
         out_features = self._finish(out_features, inp_features, extra_bias if acc is None else None)
         if acc is not None:

@@ -17,6 +17,8 @@
  *     366-370, 1006-1010: extents of rank 1)                      dmcf_radius_search_write
  *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
  *                                                                 dmcf_cconv_backward_extents)
+ *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
+ *     (models/hrnet.py:85-92)                                     dmcf_lattice_conv_backward)
  *   o3dml.ops.reduce_subarrays_sum (models/pbf_model.py:450-453) dmcf_reduce_subarrays_sum
  *   tf.keras.layers.Dense (models/hrnet.py:49,93-99;             dmcf_dense_forward
  *     models/pbf_model.py:134-152)
@@ -499,6 +501,28 @@ int dmcf_lattice_conv_forward(const dmcf_lattice_conv_args* args, void* workspac
 size_t dmcf_lattice_conv_batch_workspace_bytes(const dmcf_lattice_conv_args* parts, int32_t n_parts);
 int dmcf_lattice_conv_forward_batch(const dmcf_lattice_conv_args* parts, int32_t n_parts, void* workspace,
                                     size_t workspace_bytes, dmcf_stream_t stream);
+
+/* Backward pass of the lattice form (ABI 2.16; dmcf_amd/csrc/cconv_lat_bwd.inc).  `parts` are exactly the structs of the
+ * forward call: 1 for outputs on the same or a coarser lattice, up to 8 -- the parity classes of
+ * dmcf_lattice_conv_forward_batch -- for outputs on the 2x finer lattice.  All parts share filters, inp_volume (pointer, min,
+ * dims), the steps and n_out (DMCF_EINVAL otherwise); bias, out and DMCF_FLAG_ACCUMULATE are ignored (the bias gradient is a
+ * column sum of grad_out the caller forms).  With out_i = sum_d W_d^T f_{cell(i)+d}:
+ *   grad_volume  [inp_dims z][y][x][Cin] or NULL: df_v = sum_d W_d grad_out_{row of the output cell that reaches v through d};
+ *                written in full, zero in cells nothing reaches;
+ *   grad_filters [D][H][W][Cin][Cout] or NULL: the transpose of the forward's filter interpolation applied to
+ *                dW_d = sum_i f_{cell(i)+d} (x) grad_out_i, summed over all parts; written in full.
+ * Rows of grad_out whose point is not in out_table (or outside a part's base box) contribute nothing: the forward leaves those
+ * rows untouched.  W_d are the forward's own matrices (same device code, same bits).  No float atomics: partial sums over
+ * slabs of 1024 output rows go to buffers of their own and are added in slab order, the fold onto the filter walks parts and
+ * offsets in ascending order -- two identical calls return identical bits.
+ * Errors mirror the forward: DMCF_EUNSUPPORTED for the options it refuses (SYMMETRIC, NORMALIZE, DMCF_WINDOW_EXPLICIT,
+ * Cin other than 4 or 8, Cout > 32) and for (inp_step, out_stride) other than (1,1), (2,1), (1,2); DMCF_EINVAL for n_parts
+ * outside 1..8, parts that do not belong together, a volume that does not hold every reachable cell, grad_out == NULL with
+ * n_out > 0, or both outputs NULL; DMCF_EWORKSPACE for a short workspace.  Nothing is allocated. */
+size_t dmcf_lattice_conv_backward_workspace_bytes(const dmcf_lattice_conv_args* parts, int32_t n_parts);
+int dmcf_lattice_conv_backward(const dmcf_lattice_conv_args* parts, int32_t n_parts, const float* grad_out,
+                               float* grad_volume, float* grad_filters, void* workspace, size_t workspace_bytes,
+                               dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * o3dml.ops.reduce_subarrays_sum(values, row_splits) (models/pbf_model.py:450-453):

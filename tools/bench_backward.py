@@ -9,7 +9,11 @@ Reports
     the neighbour-list inversion and the backward (both gradients);
   * split: for a 24-channel 4x4x4 layer on the box's own list at the second scale's radius (hundreds of neighbours per
     row, like the two 24-channel layers of the network), the forward, the inversion, the input-feature gradient alone and
-    the filter gradient alone."""
+    the filter gradient alone;
+  * lattice: the s1 -> s1 and s1 -> s2 lattice layers of the box (grid_pos at 2x and 4x the voxel size, extents 0.4 and
+    0.8, 8 -> 8 channels), forward plus both gradients in the stencil form (ops.lattice_conv, ops.lattice_conv_backward:
+    no list) against the neighbour-list route (search + inversion + forward + ops.cconv_backward).
+--lattice-form records the training step with model.record_lattice_form(True)."""
 import argparse
 import json
 import os
@@ -38,11 +42,55 @@ def timed(fn, n=5):
     return dict(ms_median=float(np.median(ts)), ms_min=float(np.min(ts)), ms_max=float(np.max(ts)))
 
 
+def lattice_layers(cfg, pos, dev):
+    """The two longest-row lattice layers of the box, stencil route against neighbour-list route (ms, medians)."""
+    from dmcf_amd import lattice
+    vs = np.float32(cfg["voxel_size"])
+    s1 = ops.grid_pos(pos, vs * 2, centralize=True)
+    s2 = ops.grid_pos(pos, vs * 4, centralize=True)
+    res = {}
+    for tag, A, B, extent in (("s1->s1", s1, s1, 0.4), ("s1->s2", s1, s2, 0.8)):
+        cin = cout = 8
+        rng = np.random.default_rng(0)
+        n_in, n_out = A.shape[0], B.shape[0]
+        F = torch.from_numpy(rng.normal(size=(n_in, cin)).astype(np.float32)).to(dev)
+        W = torch.from_numpy(rng.uniform(-0.1, 0.1, size=(4, 4, 4, cin, cout)).astype(np.float32)).to(dev)
+        G = torch.from_numpy(rng.normal(size=(n_out, cout)).astype(np.float32)).to(dev)
+        lp = lattice.pair(A, B, extent)
+        vmin, vdim, parts = lp.plan(ops, extent, dev)
+        table, tmin = lp.out.table(), lp.out.minp
+        kw = dict(inp_step=int(lp.ratio), window="poly6")
+        row = dict(n_in=n_in, n_out=n_out, offsets=int(ops.lattice_offsets(lp.inp.voxel, 0.5 * extent, dev).shape[0]))
+        row["stencil_forward"] = timed(lambda: ops.lattice_conv(W, lp.inp.volume(F, vmin, vdim), vmin, table, tmin, n_out,
+                                                                lp.inp.voxel, extent, **kw))
+        vol = lp.inp.volume(F, vmin, vdim)
+        row["stencil_backward"] = timed(lambda: ops.lattice_conv_backward(W, vol, vmin, table, tmin, n_out, lp.inp.voxel, extent, G, **kw))
+        radius = 0.5 * extent
+        row["list_search"] = timed(lambda: ops.fixed_radius_search(A, B, radius, return_distances=False))
+        nns = ops.fixed_radius_search(A, B, radius, return_distances=False)
+        idx, rs = nns.neighbors_index, nns.neighbors_row_splits
+        row["pairs"] = int(rs[-1])
+        row["list_forward"] = timed(lambda: ops.cconv_forward(W, B, extent, A, F, idx, rs, window="poly6", row_length_hint=2))
+        row["list_invert"] = timed(lambda: ops.invert_neighbors_list(n_in, idx, rs))
+        inv = ops.invert_neighbors_list(n_in, idx, rs)
+        row["list_grad_inp_features"] = timed(lambda: ops.cconv_backward(W, B, extent, A, F, idx, rs, G, window="poly6",
+                                                                         need_filters=False, inverted=inv))
+        row["list_grad_filters"] = timed(lambda: ops.cconv_backward(W, B, extent, A, F, idx, rs, G, window="poly6",
+                                                                    need_features=False))
+        row["stencil_total_ms"] = row["stencil_forward"]["ms_median"] + row["stencil_backward"]["ms_median"]
+        row["list_total_ms"] = sum(row[k]["ms_median"] for k in ("list_search", "list_forward", "list_invert",
+                                                                  "list_grad_inp_features", "list_grad_filters"))
+        res[tag] = row
+        print(json.dumps({f"lattice {tag}": row}), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=100)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lattice-form", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_backward needs a GPU")
@@ -55,6 +103,7 @@ def main():
     with torch.no_grad():
         model(data)
     model.requires_grad_(True)
+    model.record_lattice_form(args.lattice_form)
     opt, sched = model.get_optimizer({"lr_boundaries": [1000], "lr_values": [1e-4, 1e-5]})
     target = data[0] + model.timestep * data[1]
 
@@ -119,6 +168,7 @@ def main():
         split[f"{cin}->{cout}"] = row
         print(json.dumps({f"split {cin}->{cout}": row}), flush=True)
     result["split"] = split
+    result["lattice"] = lattice_layers(cfg, data[0], dev)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
