@@ -198,6 +198,23 @@ class AdamArgs(ctypes.Structure):
     ]
 
 
+class Sph1dParams(ctypes.Structure):
+    """struct dmcf_sph1d_params (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("bcnt", ctypes.c_int32),
+        ("max_iter", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("h", ctypes.c_double),
+        ("rest_dens", ctypes.c_double),
+        ("stiffness", ctypes.c_double),
+        ("visc", ctypes.c_double),
+        ("gravity", ctypes.c_double),
+        ("dt", ctypes.c_double),
+        ("eps", ctypes.c_double),
+    ]
+
+
 # names every entry point include/dmcf_hip.h declares (tests/test_abi.py cross-checks against the header)
 SYMBOLS = [
     "dmcf_version", "dmcf_error_string", "dmcf_last_hip_error",
@@ -225,6 +242,7 @@ SYMBOLS = [
     "dmcf_match_cost_backward", "dmcf_emd_with_levels", "dmcf_emd_backward_workspace_bytes", "dmcf_emd_backward",
     "dmcf_gather_point_backward_workspace_bytes", "dmcf_gather_point_backward",
     "dmcf_frs_window_sum_backward",
+    "dmcf_sph1d_rollout",
 ]
 
 
@@ -423,6 +441,10 @@ def lib():
     L.dmcf_frs_window_sum_backward.restype = c.c_int
     L.dmcf_frs_window_sum_backward.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
                                                c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+    # the column datasets' 1-D SPH solver (ABI 2.17)
+    L.dmcf_sph1d_rollout.restype = c.c_int
+    L.dmcf_sph1d_rollout.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int32, c.POINTER(Sph1dParams), c.c_int32, c.c_void_p,
+                                     c.c_void_p, c.c_void_p, c.c_void_p]
     _lib = L
     return L
 

@@ -2361,3 +2361,55 @@ def rgba8(image):
     255."""
     q = torch.clamp(torch.round(image * 255.0), 0.0, 255.0).to(torch.uint8)
     return torch.cat([q, torch.full_like(q[..., :1], 255)], dim=-1)
+
+
+SPH1D_MAX_POINTS = 64  # dmcf_sph1d_rollout: one 64-lane wavefront per scene, lane = point
+SPH1D_LAUNCH_ITERS = 100_000  # worst-case solver iterations (frames * max_iter) one launch may cover: about 1 s at 64 points
+
+
+def sph1d_rollout(state, n_tot, frames, h, rest_dens, stiffness, visc, gravity, dt, eps=0.01, max_iter=10000, bcnt=2,
+                  launch_iters=SPH1D_LAUNCH_ITERS):
+    """``frames`` steps of the reference's 1-D SPH solver (SPH1D.step, datasets/column_gen.py:159-186) for a batch of
+    independent scenes (dmcf_sph1d_rollout; formulas and precision in include/dmcf_hip.h).
+
+    ``state``: float32 CUDA ``[S, P, 3]`` = (position, velocity, mass) per point as ``SPH1D.setup`` lays it out, the ``bcnt``
+    boundary points first; scene ``s`` holds ``n_tot[s]`` points (``n_tot``: int32 CUDA ``[S]``, or a sequence of ints), the
+    rest of its slot is padding.  ``P > 64`` raises NotImplementedError (a scene is one wavefront).  Returns
+    ``(sequence [frames, S, P, 2], state_out [S, P, 3], iterations [frames, S] int32)``: (position, velocity) BEFORE each
+    step, the state after the last one, and the pressure iterations every step took.
+
+    The rollout is cut into launches of ``max(1, launch_iters // max_iter)`` frames, so that no launch covers more than
+    ``launch_iters`` solver iterations in the worst case (one frame's ``max_iter`` cannot be cut further); the state is carried
+    from launch to launch, and the result has the bits of a single launch."""
+    L = _lib.lib()
+    state = _dev_f32(state, "state")
+    if state.dim() != 3 or state.shape[2] != 3:
+        raise ValueError(f"state must have shape [S, P, 3], got {tuple(state.shape)}")
+    S, P = int(state.shape[0]), int(state.shape[1])
+    if P > SPH1D_MAX_POINTS:
+        raise NotImplementedError(f"sph1d_rollout: a scene of {P} points (boundary included) exceeds the limit of "
+                                  f"{SPH1D_MAX_POINTS}: the solver runs one 64-lane wavefront per scene")
+    frames, max_iter, bcnt = int(frames), int(max_iter), int(bcnt)
+    if frames < 0 or max_iter < 1 or P < 1 or not 0 <= bcnt < P:
+        raise ValueError(f"sph1d_rollout: frames={frames}, max_iter={max_iter}, bcnt={bcnt}, P={P}")
+    if not isinstance(n_tot, torch.Tensor):
+        n_tot = torch.as_tensor(np.asarray(n_tot, dtype=np.int32), device=state.device)
+    if n_tot.dtype != torch.int32 or n_tot.device != state.device or tuple(n_tot.shape) != (S,):
+        raise ValueError(f"n_tot must be int32 [{S}] on {state.device}, got {n_tot.dtype} {tuple(n_tot.shape)} on {n_tot.device}")
+    n_tot = n_tot.contiguous()
+    p = _lib.Sph1dParams()
+    p.struct_size = ctypes.sizeof(p)
+    p.bcnt, p.max_iter = bcnt, max_iter
+    p.h, p.rest_dens, p.stiffness, p.visc = float(h), float(rest_dens), float(stiffness), float(visc)
+    p.gravity, p.dt, p.eps = float(gravity), float(dt), float(eps)
+    seq = torch.empty((frames, S, P, 2), dtype=torch.float32, device=state.device)
+    iters = torch.empty((frames, S), dtype=torch.int32, device=state.device)
+    out = state.clone()  # advanced in place, launch by launch
+    if S == 0:
+        return seq, out, iters
+    per = max(1, int(launch_iters) // max_iter)
+    for t0 in range(0, max(frames, 1), per):
+        k = min(per, frames - t0)
+        _lib.check(L.dmcf_sph1d_rollout(_ptr(out), _ptr(n_tot), S, P, ctypes.byref(p), k, _ptr(seq[t0:]) if k else None, _ptr(out),
+                                        _ptr(iters[t0:]) if k else None, _stream()), "dmcf_sph1d_rollout")
+    return seq, out, iters

@@ -9,8 +9,11 @@ the rollouts (``Simulator.run_test``); ``--split valid`` rolls out the validatio
 (``Simulator.run_valid``: MSE, Chamfer, density, EMD, velocity histograms); ``--split train`` (the default, as in the
 reference) runs the training loop (``Simulator.run_train``: scenes from ``<dataset_path>/train``, checkpoints with the Adam
 state in ``<logs_dir>/checkpoint``, resumed from the newest one there unless ``--ckpt_path`` is given; ``--restart`` clears
-the run's logs and outputs first).  A config without ``dataset_path`` (the generated column / free-fall datasets) raises
-NotImplementedError in every split.
+the run's logs and outputs first).  A config without ``dataset_path`` and with ``dataset.type: column`` or ``free_fall`` (the
+reference's configs/column/*.yml) has the scenes of the splits it needs GENERATED from the config's ``train`` / ``valid`` /
+``test`` sections (datasets/column_gen.py: a HIP 1-D SPH solver; datasets/free_fall_gen.py) and cached under ``cache/``
+(``dataset.cache_dir``); ``--regen`` discards the cached scenes.  ``type: tank``, or no type, raises NotImplementedError as the
+reference does.
 """
 import argparse
 import random

@@ -27,6 +27,8 @@
  *   farthest_point_sample / gather_point (utils/tools/sampling.cu) dmcf_farthest_point_sample / dmcf_gather_point
  *   grid_pos: candidate cells + tf.unique + decode               dmcf_grid_pos_bounds / _count / _write
  *     (utils/tools/losses.py:136-181, called from :266-272)
+ *   SPH1D.step in gen_data's time loop                           dmcf_sph1d_rollout (ABI 2.17: the column
+ *     (datasets/column_gen.py:159-186, 305-312)                    datasets' generator)
  *
  * Conventions
  *   - plain C: raw DEVICE pointers, sizes, a stream handle (hipStream_t passed as void*); no
@@ -844,6 +846,54 @@ int dmcf_raster_count(const float* xy, int64_t n_points, int64_t n_frames, int64
 int dmcf_raster_discs(const float* xy, int64_t n_points, int64_t n_frames, int64_t frame_stride, float radius, uint32_t color_argb,
                       int32_t width, int32_t height, float* image, void* workspace, size_t workspace_bytes, float* bins,
                       int64_t bin_capacity, dmcf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The 1-D SPH solver that generates the column datasets (ABI 2.17; dmcf_amd/csrc/sph1d.hip): SPH1D.step of
+ * datasets/column_gen.py:159-186 for a batch of independent scenes, n_frames steps per call.  One 64-lane wavefront per
+ * scene, lane = point, so a scene holds at most 64 points: max_points > 64 is DMCF_EINVAL.
+ *
+ * A point is (x, v, m), float32; the first bcnt points of a scene are the boundary and never move.  With d = x_i - x_j
+ * (float32), the splines W(|d|) and W'(d) of column_gen.py:51-54 and :68-73 evaluated in float32 on the RAW distance (not
+ * d / h; the factor 4 / (3 h) and the softening 0.01 h^2 rounded to float32), and sums over j in float64, one step is
+ *   dens_i = sum_j m_j W(|d|)
+ *   f_visc = visc * 2 sum_j m_j / dens_j (v_i - v_j) d W'(d) / (d^2 + 0.01 h^2)
+ *   v += dt (gravity + f_visc);  x += dt v  (this one in float32)                                   fluid points only
+ *   up to max_iter times:
+ *     dens_i as above;  p_i = max(stiffness ((dens_i / rest_dens)^7 - 1), 0), boundary points: p of the first fluid point
+ *     err = max over the fluid points of max(dens_i - rest_dens, 0)
+ *     f_i = -(m_i / dens_i) dens_i sum_j m_j (p_i / dens_i^2 + p_j / dens_j^2) W'(d)
+ *     v += dt f / m;  x += dt^2 f / m   (formed in float64, rounded to float32 once)                  fluid points only
+ *     stop when err < eps -- AFTER the update, so every step runs at least one iteration.
+ * The j sums run in index order; numpy's pairwise order is not reproduced, so results agree with the reference to rounding,
+ * not bit for bit.  Two calls on equal inputs give equal bits, whatever else is in the batch; and since the whole solver
+ * state is the (x, v, m) array, a rollout cut into several calls (state_out of one as the state of the next) gives the bits
+ * of one call.
+ *
+ * state      float32 [n_scenes, max_points, 3]: scene s holds n_tot[s] points, the rest of its slot is ignored
+ * n_tot      int32 [n_scenes] (device); values outside [0, max_points] are clamped
+ * sequence   float32 [n_frames, n_scenes, max_points, 2]: (x, v) BEFORE each step (gen_data :309-312); zeros past n_tot[s]
+ * state_out  float32 [n_scenes, max_points, 3]: the state after the last step; may be `state` itself
+ * iterations int32 [n_frames, n_scenes]: pressure iterations of each step, in [1, max_iter]
+ * sequence and iterations may be NULL when n_frames == 0.  No workspace.  A step costs up to max_iter iterations of
+ * O(n_tot^2) work on one wavefront: callers bound n_frames * max_iter per call (dmcf_amd/ops.py:sph1d_rollout does).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dmcf_sph1d_params {
+    uint32_t struct_size; /* sizeof(dmcf_sph1d_params) of the caller; smaller: DMCF_EINVAL */
+    int32_t bcnt;         /* boundary points per scene, 0 <= bcnt < max_points */
+    int32_t max_iter;     /* >= 1 */
+    int32_t reserved;
+    double h;             /* > 0 */
+    double rest_dens;     /* > 0 */
+    double stiffness;
+    double visc;
+    double gravity;
+    double dt;
+    double eps;
+} dmcf_sph1d_params;
+
+int dmcf_sph1d_rollout(const float* state, const int32_t* n_tot, int64_t n_scenes, int32_t max_points,
+                       const dmcf_sph1d_params* params, int32_t n_frames, float* sequence, float* state_out,
+                       int32_t* iterations, dmcf_stream_t stream);
 
 #ifdef __cplusplus
 }
