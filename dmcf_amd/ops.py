@@ -1388,6 +1388,10 @@ def scatter_plan(inp_positions, out_positions, voxel, radius, block_cells=None):
     out = _dev_f32(out_positions, "out_positions", 3)
     m = int(block_cells or SCATTER_BLOCK_CELLS)
     n = inp.shape[0]
+    if n == 0 or out.shape[0] == 0:
+        # (nothing to sort, and the C ABI rejects NULL point arrays: cconv_scatter_forward returns the bias for such a call
+        # without reading the plan)
+        return ScatterPlan(torch.empty(0, dtype=torch.uint8, device=inp.device), voxel, m, scatter_reach(radius, voxel), n, (inp, out))
     nbytes = L.dmcf_cconv_scatter_plan_bytes(n)
     buf = torch.empty(nbytes, dtype=torch.uint8, device=inp.device)
     t0 = timer.begin() if timer is not None else None
@@ -1416,13 +1420,32 @@ def cconv_scatter_supported(filters, block_cells, reach):
     return block_cells + 2 * reach + 1 <= (13 if filters.shape[4] == 4 else 11)
 
 
+def _dev_exact_1d(t, name, dtype, device, length=None):
+    """A 1-D operand the library reads through a raw pointer: ValueError unless it is a contiguous ``dtype`` tensor on ``device``
+    (of ``length`` elements)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1:
+        raise ValueError(f"{name} must be a 1-D {dtype} tensor, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the filters on {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if length is not None and t.shape[0] != length:
+        raise ValueError(f"{name} must have {length} elements, got {t.shape[0]}")
+    return t
+
+
 def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_features, t_index, t_row_begin, t_row_count, plan,
                           window=None, window_fac=1.0, bias=None, out=None, accumulate=False, error_flag=None, n_pairs_ref=None):
     """One call of dmcf_cconv_scatter_forward (splat S: filter first, input stationary, 64-bit fixed-point sums): the operator
     of cconv_forward for particles -> coarse lattice layers with 4 or 8 output channels, walking the TRANSPOSED list (row j = the
-    output points within extent / 2 of input point j; ``t_row_count`` None for CSR row splits)."""
+    output points within extent / 2 of input point j; ``t_row_count`` None for CSR row splits).  ``t_index`` int32,
+    ``t_row_begin`` int64, ``t_row_count`` int32, ``bias`` float32 [Cout], ``error_flag`` int32: contiguous and on the filters'
+    device (ValueError otherwise, before anything is launched).  An empty point set or an empty ``t_index`` gives the bias
+    (prior content + bias under ``accumulate``) without a launch, as cconv_forward does."""
     L = _lib.lib()
     filters = _dev_f32(filters, "filters")
+    if filters.dim() != 5:
+        raise ValueError("filters must have shape [D,H,W,Cin,Cout]")
     out_positions = _dev_f32(out_positions, "out_positions", 3)
     inp_positions = _dev_f32(inp_positions, "inp_positions", 3)
     cin, cout = int(filters.shape[3]), int(filters.shape[4])
@@ -1432,12 +1455,40 @@ def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_fea
         raise ValueError("the plan was made for another input point set")
     if window not in (None, "poly6"):
         raise NotImplementedError("cconv_scatter_forward: window must be None or 'poly6'")
+    dev = filters.device
+    _dev_exact_1d(t_index, "t_index", torch.int32, dev)
+    _dev_exact_1d(t_row_begin, "t_row_begin", torch.int64, dev)
+    if t_row_count is not None:
+        _dev_exact_1d(t_row_count, "t_row_count", torch.int32, dev)
+    if bias is not None:
+        _dev_exact_1d(bias, "bias", torch.float32, dev, cout)
+    if error_flag is not None:
+        _dev_exact_1d(error_flag, "error_flag", torch.int32, dev)
+        if error_flag.shape[0] < 1:
+            raise ValueError("error_flag must have at least one element")
+    if inp_features.shape[0] != n_inp:
+        raise ValueError("inp_features and inp_positions disagree on the number of points")
+    if t_row_begin.shape[0] < n_inp + (1 if t_row_count is None else 0):
+        raise ValueError("t_row_begin has fewer entries than the input points have rows")
+    if t_row_count is not None and t_row_count.shape[0] < n_inp:
+        raise ValueError("t_row_count has fewer entries than the input points have rows")
     if out is None:
         if accumulate:
             raise ValueError("accumulate=True needs an out tensor")
         out = torch.empty((n_out, cout), dtype=torch.float32, device=filters.device)
-    elif out.shape != (n_out, cout) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out has the wrong shape / dtype / layout")
+    elif out.shape != (n_out, cout) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out has the wrong shape / dtype / layout / device")
+    if n_out == 0 or n_inp == 0 or t_index.shape[0] == 0:
+        # every row is empty: the result is the bias; nothing to launch (the C ABI rejects empty sets, and the kernel clamps its
+        # index loads to the last entry of a list that has none)
+        b = 0.0 if bias is None else bias
+        if accumulate:
+            out += b
+        else:
+            out[:] = b
+        return out
+    if plan.buf.numel() == 0:
+        raise ValueError("the plan was made for an empty point set: make one for these points (scatter_plan)")
     a = _lib.CconvScatterArgs()
     a.filters = _ptr(filters)
     for k in range(5):

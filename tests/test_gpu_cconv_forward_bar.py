@@ -1,4 +1,6 @@
-"""Every forward CConv / ASCC kernel against the float64 reference, element by element (tests/cconv_forward_ref.py):
+"""Every forward CConv / ASCC kernel that walks a neighbour list or a lattice stencil against the float64 reference, element by
+element (tests/cconv_forward_ref.py; the scatter form, dmcf_cconv_scatter_forward, has the same bar plus the term of its
+fixed-point sums in tests/test_gpu_cconv_scatter_bar.py):
 
     |gpu - ref| <= (kbar * A + C_GEO * A1) * 2^-24
 
