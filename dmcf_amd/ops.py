@@ -560,11 +560,34 @@ def _empty(t):
     return t is None or (isinstance(t, torch.Tensor) and t.numel() == 0)
 
 
-def _cconv_args(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
-                neighbors_value, window, window_fac, inp_importance, align_corners, coordinate_mapping, interpolation,
-                normalize, symmetric, sym_axis, bias, out, accumulate, neighbors_row_count=None, filter_tile_mask=0,
+def _extent_operands(extent, n_out):
+    """``extent`` as the CConv calls take it -> (float32 device tensor [n_out] of per-point extents | None for a scalar, the
+    scalar for args->extent).  Per-point extents must be finite and positive (ValueError otherwise: one host read)."""
+    ext = per_point_extents(extent, n_out)
+    if ext is None:
+        return None, extent
+    ext = _dev_f32(ext, "extents")
+    if n_out > 0 and not bool((torch.isfinite(ext) & (ext > 0)).all()):
+        raise ValueError("per-point extents must be finite and positive")
+    return ext, 1.0  # (args->extent is ignored by the *_extents entry points; the workspace query wants a positive one)
+
+
+def _kernel_name(fn, *args, size=96, what=None):
+    """The string (bytes) the ``*_kernel_name(s)`` entry point ``fn`` writes for ``args`` into a buffer of ``size`` bytes.
+    ``what``: the name to check its status under (None: unchecked)."""
+    name = ctypes.create_string_buffer(size)
+    rc = fn(*args, name, size)
+    if what is not None:
+        _lib.check(rc, what)
+    return name.value
+
+
+def _cconv_args(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits, *,
+                neighbors_value=None, window=None, window_fac=1.0, inp_importance=None, align_corners=True,
+                coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", normalize=False, symmetric=False,
+                sym_axis=2, bias=None, out=None, accumulate=False, neighbors_row_count=None, filter_tile_mask=0,
                 skip_self=False, row_length_hint=0):
-    """Validate the operands and fill a ``dmcf_cconv_args``; returns (args, keepalive tensors, out)."""
+    """Validate the operands and fill a ``dmcf_cconv_args``; returns (args, keepalive tensors)."""
     filters = _dev_f32(filters, "filters")
     if filters.dim() != 5:
         raise ValueError("filters must have shape [D,H,W,Cin,Cout]")
@@ -639,6 +662,17 @@ _STENCILS = {}
 def lattice_offsets(voxel, radius, device, shift=(0.0, 0.0, 0.0)):
     """int32 [S, 4] device tensor: the integer offsets d (x, y, z, 0) of input cells with |d * voxel - shift| <= radius,
     decided like the search decides a pair (fp32, un-fused squared distance), ordered z, y, x."""
+    return _stencil(voxel, radius, device, shift)[0]
+
+
+def lattice_reach(voxel, radius, device, shift=(0.0, 0.0, 0.0)):
+    """max |d| per axis (x, y, z) over :func:`lattice_offsets`: how far around the cells it covers a launch reads the input
+    volume (the volume handed to :func:`lattice_conv` must be padded with zero cells that far)."""
+    return list(_stencil(voxel, radius, device, shift)[1])
+
+
+def _stencil(voxel, radius, device, shift):
+    """(offsets, reach) of :func:`lattice_offsets` / :func:`lattice_reach`, formed once per key."""
     key = (tuple(float(v) for v in voxel), float(radius), tuple(float(v) for v in shift), str(device))
     st = _STENCILS.get(key)
     if st is None:
@@ -653,14 +687,7 @@ def lattice_offsets(voxel, radius, device, shift=(0.0, 0.0, 0.0)):
         rch = [int(np.abs(off[:, k]).max()) if off.shape[0] else 0 for k in range(3)]
         st = (torch.from_numpy(np.ascontiguousarray(off)).to(device), rch)
         _STENCILS[key] = st
-    return st[0]
-
-
-def lattice_reach(voxel, radius, device, shift=(0.0, 0.0, 0.0)):
-    """max |d| per axis (x, y, z) over :func:`lattice_offsets`: how far around the cells it covers a launch reads the input
-    volume (the volume handed to :func:`lattice_conv` must be padded with zero cells that far)."""
-    lattice_offsets(voxel, radius, device, shift)
-    return list(_STENCILS[(tuple(float(v) for v in voxel), float(radius), tuple(float(v) for v in shift), str(device))][1])
+    return st
 
 
 def lattice_volume_box(base_min, base_dims, inp_step, reach, points_min=None, points_dims=None):
@@ -678,35 +705,43 @@ def lattice_volume_box(base_min, base_dims, inp_step, reach, points_min=None, po
     return lo, [hi[k] - lo[k] + 1 for k in range(3)]
 
 
-def _lattice_args(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step, out_stride, out_phase,
-                  rel_shift, base_min, base_dims, window, window_fac, align_corners, coordinate_mapping, interpolation, bias,
-                  out, accumulate):
-    """dmcf_lattice_conv_args for one launch; returns (args, tensors to keep alive, number of stencil offsets)."""
-    dev = filters.device
-    offsets = lattice_offsets(voxel, 0.5 * float(extent), dev, rel_shift)
-    if base_min is None:
-        base_min, base_dims = out_min, [int(out_table.shape[2 - k]) for k in range(3)]
-    a = _lib.LatticeConvArgs()
-    a.filters = _ptr(filters)
-    for k in range(5):
-        a.filter_dims[k] = int(filters.shape[k])
-    a.inp_volume, a.out_table = _ptr(inp_volume), _ptr(out_table)
-    for k in range(3):
-        a.inp_min[k], a.inp_dims[k] = int(inp_min[k]), int(inp_volume.shape[2 - k])
-        a.out_min[k], a.out_dims[k] = int(out_min[k]), int(out_table.shape[2 - k])
-        a.out_phase[k], a.base_min[k], a.base_dims[k] = int(out_phase[k]), int(base_min[k]), int(base_dims[k])
-        a.rel_shift[k], a.voxel[k] = float(rel_shift[k]), float(voxel[k])
-    a.n_out, a.inp_step, a.out_stride = int(n_out), int(inp_step), int(out_stride)
-    a.offsets, a.n_offsets = _ptr(offsets), int(offsets.shape[0])
-    for k, r in enumerate(lattice_reach(voxel, 0.5 * float(extent), dev, rel_shift)):
-        a.reach[k] = r
-    a.extent, a.window_fac = float(extent), float(window_fac)
-    a.window = WINDOWS[window]
-    a.coordinate_mapping, a.interpolation = MAPPINGS[coordinate_mapping], INTERPOLATIONS[interpolation]
-    a.flags = (FLAG_ALIGN_CORNERS if align_corners else 0) | (FLAG_ACCUMULATE if accumulate else 0)
-    a.bias = _ptr(bias) if bias is not None else None
-    a.out = _ptr(out)
-    return a, (offsets,), int(offsets.shape[0])
+def _lattice_args(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, *, inp_step=1, out_stride=1,
+                  out_phase=(0, 0, 0), rel_shift=(0.0, 0.0, 0.0), base_min=None, base_dims=None, window="poly6", window_fac=1.0,
+                  align_corners=True, coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", bias=None,
+                  out=None, accumulate=False, parts=None):
+    """(ctypes array of dmcf_lattice_conv_args, one per part; tensors to keep alive; stencil offsets of all parts) of one
+    call of :func:`lattice_conv` / :func:`lattice_conv_backward` (``out``: the rows written, resp. ``grad_out``)."""
+    if inp_volume.dim() != 4 or inp_volume.shape[3] != filters.shape[3] or not inp_volume.is_contiguous() or not out_table.is_contiguous():
+        raise ValueError("inp_volume must be a contiguous [dz, dy, dx, Cin] tensor, out_table a contiguous [dz, dy, dx] one")
+    if parts is None:
+        parts = [dict(out_phase=out_phase, rel_shift=rel_shift, base_min=base_min, base_dims=base_dims)]
+    arr = (_lib.LatticeConvArgs * len(parts))()
+    keep, n_off = [], 0
+    for a, pt in zip(arr, parts):  # (a: a view of element i, so the fields are written into the array itself)
+        ph, sh, bmin, bdims = pt["out_phase"], pt["rel_shift"], pt["base_min"], pt["base_dims"]
+        offsets, reach = _stencil(voxel, 0.5 * float(extent), filters.device, sh)
+        if bmin is None:
+            bmin, bdims = out_min, [int(out_table.shape[2 - k]) for k in range(3)]
+        a.filters = _ptr(filters)
+        for k in range(5):
+            a.filter_dims[k] = int(filters.shape[k])
+        a.inp_volume, a.out_table = _ptr(inp_volume), _ptr(out_table)
+        for k in range(3):
+            a.inp_min[k], a.inp_dims[k] = int(inp_min[k]), int(inp_volume.shape[2 - k])
+            a.out_min[k], a.out_dims[k] = int(out_min[k]), int(out_table.shape[2 - k])
+            a.out_phase[k], a.base_min[k], a.base_dims[k] = int(ph[k]), int(bmin[k]), int(bdims[k])
+            a.rel_shift[k], a.voxel[k], a.reach[k] = float(sh[k]), float(voxel[k]), reach[k]
+        a.n_out, a.inp_step, a.out_stride = int(n_out), int(inp_step), int(out_stride)
+        a.offsets, a.n_offsets = _ptr(offsets), int(offsets.shape[0])
+        a.extent, a.window_fac = float(extent), float(window_fac)
+        a.window = WINDOWS[window]
+        a.coordinate_mapping, a.interpolation = MAPPINGS[coordinate_mapping], INTERPOLATIONS[interpolation]
+        a.flags = (FLAG_ALIGN_CORNERS if align_corners else 0) | (FLAG_ACCUMULATE if accumulate else 0)
+        a.bias = _ptr(bias) if bias is not None else None
+        a.out = _ptr(out)
+        keep.append(offsets)
+        n_off += int(offsets.shape[0])
+    return arr, keep, n_off
 
 
 def lattice_conv(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step=1, out_stride=1,
@@ -723,42 +758,14 @@ def lattice_conv(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel,
     run as ONE grid (dmcf_lattice_conv_forward_batch); every part writes rows of its own.
     While autograd records and ``filters``, ``inp_volume`` or ``bias`` requires grad, the call is a node of the graph
     (:class:`LatticeConvFunction`; ``out`` / ``accumulate`` are refused then); otherwise it is the plain forward call."""
-    kw = dict(inp_step=inp_step, out_stride=out_stride, out_phase=out_phase, rel_shift=rel_shift, base_min=base_min,
-              base_dims=base_dims, window=window, window_fac=window_fac, align_corners=align_corners,
-              coordinate_mapping=coordinate_mapping, interpolation=interpolation, parts=parts)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (filters, inp_volume, bias)):
         if out is not None or accumulate:
             raise ValueError("lattice_conv: out / accumulate cannot be recorded for autograd")
-        geo = dict(kw, inp_min=inp_min, out_table=out_table, out_min=out_min, n_out=n_out, voxel=voxel, extent=extent)
+        geo = dict(inp_min=inp_min, out_table=out_table, out_min=out_min, n_out=n_out, voxel=voxel, extent=extent,
+                   inp_step=inp_step, out_stride=out_stride, out_phase=out_phase, rel_shift=rel_shift, base_min=base_min,
+                   base_dims=base_dims, window=window, window_fac=window_fac, align_corners=align_corners,
+                   coordinate_mapping=coordinate_mapping, interpolation=interpolation, parts=parts)
         return LatticeConvFunction.apply(filters, inp_volume, bias, geo, dict(fill=fill, n_out_launch=n_out_launch))
-    return _lattice_conv_impl(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, bias=bias, out=out,
-                              accumulate=accumulate, fill=fill, n_out_launch=n_out_launch, **kw)
-
-
-def _lattice_parts(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step, out_stride, out_phase, rel_shift,
-                   base_min, base_dims, window, window_fac, align_corners, coordinate_mapping, interpolation, bias, out, accumulate,
-                   parts):
-    """(ctypes array of dmcf_lattice_conv_args, tensors to keep alive, stencil offsets of all parts) of one call."""
-    if inp_volume.dim() != 4 or inp_volume.shape[3] != filters.shape[3] or not inp_volume.is_contiguous() or not out_table.is_contiguous():
-        raise ValueError("inp_volume must be a contiguous [dz, dy, dx, Cin] tensor, out_table a contiguous [dz, dy, dx] one")
-    if parts is None:
-        parts = [dict(out_phase=out_phase, rel_shift=rel_shift, base_min=base_min, base_dims=base_dims)]
-    arr = (_lib.LatticeConvArgs * len(parts))()
-    keep, n_off = [], 0
-    for i, pt in enumerate(parts):
-        arr[i], k, no = _lattice_args(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step, out_stride,
-                                      pt["out_phase"], pt["rel_shift"], pt["base_min"], pt["base_dims"], window, window_fac,
-                                      align_corners, coordinate_mapping, interpolation, bias, out, accumulate)
-        keep.append(k)
-        n_off += no
-    return arr, keep, n_off
-
-
-def _lattice_conv_impl(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step=1, out_stride=1,
-                       out_phase=(0, 0, 0), rel_shift=(0.0, 0.0, 0.0), base_min=None, base_dims=None, window="poly6",
-                       window_fac=1.0, align_corners=True, coordinate_mapping="ball_to_cube_volume_preserving",
-                       interpolation="linear", bias=None, out=None, accumulate=False, fill=1.0, n_out_launch=None, parts=None):
-    """The forward launch of :func:`lattice_conv` (no autograd)."""
     L = _lib.lib()
     dev = filters.device
     cin, cout = filters.shape[3], filters.shape[4]
@@ -767,29 +774,30 @@ def _lattice_conv_impl(filters, inp_volume, inp_min, out_table, out_min, n_out, 
             raise ValueError("accumulate=True needs an out tensor")
         out = torch.zeros((n_out, cout), dtype=torch.float32, device=dev)  # rows without a cell stay 0
     filters = filters.contiguous()
-    arr, keep, n_off = _lattice_parts(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step, out_stride,
-                                      out_phase, rel_shift, base_min, base_dims, window, window_fac, align_corners, coordinate_mapping,
-                                      interpolation, bias, out, accumulate, parts)
-    parts = arr  # (only its length is used below)
-    if len(parts) == 1:
+    arr, keep, n_off = _lattice_args(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step=inp_step,
+                                     out_stride=out_stride, out_phase=out_phase, rel_shift=rel_shift, base_min=base_min,
+                                     base_dims=base_dims, window=window, window_fac=window_fac, align_corners=align_corners,
+                                     coordinate_mapping=coordinate_mapping, interpolation=interpolation, bias=bias, out=out,
+                                     accumulate=accumulate, parts=parts)
+    if len(arr) == 1:
         nbytes = L.dmcf_lattice_conv_workspace_bytes(arr)
     else:
-        nbytes = L.dmcf_lattice_conv_batch_workspace_bytes(arr, len(parts))
+        nbytes = L.dmcf_lattice_conv_batch_workspace_bytes(arr, len(arr))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     t0 = timer.begin() if timer is not None else None
-    if len(parts) == 1:
+    if len(arr) == 1:
         _lib.check(L.dmcf_lattice_conv_forward(arr, _ptr(ws), nbytes, _stream()), "dmcf_lattice_conv_forward")
     else:
-        _lib.check(L.dmcf_lattice_conv_forward_batch(arr, len(parts), _ptr(ws), nbytes, _stream()), "dmcf_lattice_conv_forward_batch")
+        _lib.check(L.dmcf_lattice_conv_forward_batch(arr, len(arr), _ptr(ws), nbytes, _stream()), "dmcf_lattice_conv_forward_batch")
     if timer is not None:
         # bench accounting: this form reads no neighbour list, so it is charged what it does read and write -- the input
         # volume once, the per-offset matrices, the cell -> point table and the output rows (``pairs_equiv`` = the pairs the
         # neighbour-list form would have had, for information only: outputs x stencil offsets x the fraction of occupied
         # cells of the input lattice's box)
         no = int(n_out if n_out_launch is None else n_out_launch)
-        timer.end("cconv", dict(pairs=0, pairs_equiv=int(no * (n_off / len(parts)) * float(fill)), n_out=no, cin=int(cin),
+        timer.end("cconv", dict(pairs=0, pairs_equiv=int(no * (n_off / len(arr)) * float(fill)), n_out=no, cin=int(cin),
                                 cout=int(cout), K=int(filters.shape[0] * filters.shape[1] * filters.shape[2]), symmetric=False,
-                                lattice=True, kernel="lat_conv_kernel", n_offsets=int(n_off), parts=len(parts),
+                                lattice=True, kernel="lat_conv_kernel", n_offsets=int(n_off), parts=len(arr),
                                 volume_bytes=int(inp_volume.numel()) * 4, table_bytes=int(out_table.numel()) * 4,
                                 accumulate=bool(accumulate)), t0)
     return out
@@ -799,7 +807,7 @@ def lattice_conv_backward(filters, inp_volume, inp_min, out_table, out_min, n_ou
                           out_stride=1, out_phase=(0, 0, 0), rel_shift=(0.0, 0.0, 0.0), base_min=None, base_dims=None,
                           window="poly6", window_fac=1.0, align_corners=True,
                           coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", parts=None,
-                          need_volume=True, need_filters=True, **_ignored):
+                          need_volume=True, need_filters=True):
     """dmcf_lattice_conv_backward: ``(grad_volume | None, grad_filters | None)`` of the convolution :func:`lattice_conv`
     computes with these arguments, for ``grad_out`` = dL/d out [n_out, Cout].  ``grad_volume`` has the shape of
     ``inp_volume`` (zero in cells no output reaches), ``grad_filters`` that of ``filters`` (summed over all ``parts``).  Rows
@@ -813,9 +821,10 @@ def lattice_conv_backward(filters, inp_volume, inp_min, out_table, out_min, n_ou
         raise ValueError("grad_out must be [n_out, Cout]")
     if not need_volume and not need_filters:
         return None, None
-    arr, keep, _ = _lattice_parts(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step, out_stride,
-                                  out_phase, rel_shift, base_min, base_dims, window, window_fac, align_corners, coordinate_mapping,
-                                  interpolation, None, grad_out, False, parts)
+    arr, keep, _ = _lattice_args(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel, extent, inp_step=inp_step,
+                                 out_stride=out_stride, out_phase=out_phase, rel_shift=rel_shift, base_min=base_min,
+                                 base_dims=base_dims, window=window, window_fac=window_fac, align_corners=align_corners,
+                                 coordinate_mapping=coordinate_mapping, interpolation=interpolation, out=grad_out, parts=parts)
     gv = torch.empty_like(inp_volume) if need_volume else None
     gw = torch.empty_like(filters) if need_filters else None
     nbytes = int(L.dmcf_lattice_conv_backward_workspace_bytes(arr, len(arr)))
@@ -842,7 +851,8 @@ class LatticeConvFunction(torch.autograd.Function):
         ctx.geo = geo
         ctx.has_bias = bias is not None
         ctx.save_for_backward(filters, inp_volume)
-        return _lattice_conv_impl(filters, inp_volume, bias=bias, **geo, **info)
+        # (grad mode is off in here, so this is the plain call; a replaced ``ops.lattice_conv`` is re-entered by it)
+        return lattice_conv(filters, inp_volume, bias=bias, **geo, **info)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -882,7 +892,15 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
                   normalize=False, symmetric=False, sym_axis=2, bias=None, out=None, accumulate=False,
                   n_pairs_ref=None, neighbors_row_count=None, filter_tile_mask=0, skip_self=False, name_only=False,
                   row_length_hint=0, packed_cache=None, record_per_point_extents=False):
-    """One call of dmcf_cconv_forward (see ``_cconv_forward_impl`` for the arguments).
+    """One call of dmcf_cconv_forward.  ``row_length_hint``: 0 unknown / 1 tens / 2 hundreds of neighbours per row -- what the
+    caller knows about the LAYER from its configuration (include/dmcf_hip.h).  ``skip_self``: DMCF_FLAG_SKIP_SELF (the list
+    holds the query points, the layer ignores them; only the direct kernel).  ``name_only``: no launch, returns the name of the
+    kernel these arguments dispatch to.  ``filter_tile_mask``: see ``block_diagonal_tile_mask`` (0 = no hint).
+    ``neighbors_row_count``: int32 [n_out] for padded lists (PaddedNeighborList).  ``window``: None | 'explicit'
+    (neighbors_value = importance) | 'poly6' | 'cubic' | 'linear' | 'peak' | 'cubic_grad' (neighbors_value = squared distances).
+    ``extent``: a scalar, or one extent per output row -- a tensor of shape [n_out] or [n_out, 1] (dmcf_cconv_forward_extents:
+    row i maps its pairs with extents[i] and evaluates a distance window on d^2 / (extents[i] / 2)^2).  Per-point extents must
+    be finite and positive (ValueError otherwise: one host read); that call always packs the filter (``packed_cache`` unused).
 
     When autograd records (``torch.is_grad_enabled()``) and ``filters`` or ``inp_features`` requires grad, the call goes
     through ``CconvFunction``: the same forward kernel, and a backward through dmcf_cconv_backward.  ``bias`` is then
@@ -901,43 +919,19 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
         if ext is not None and not record_per_point_extents:
             raise NotImplementedError("recording CConv with per-point extents is opt-in: pass record_per_point_extents=True "
                                       "(the backward is dmcf_cconv_backward_extents; the extents get no gradient)")
-        kw = dict(out_positions=out_positions, extent=float(extent) if ext is None else ext.detach(), inp_positions=inp_positions, neighbors_index=neighbors_index,
-                  neighbors_row_splits=neighbors_row_splits, neighbors_value=neighbors_value, window=window, window_fac=window_fac,
-                  inp_importance=inp_importance, align_corners=align_corners, coordinate_mapping=coordinate_mapping,
-                  interpolation=interpolation, normalize=normalize, symmetric=symmetric, sym_axis=sym_axis,
-                  neighbors_row_count=neighbors_row_count, filter_tile_mask=filter_tile_mask, skip_self=skip_self,
-                  row_length_hint=row_length_hint, n_pairs_ref=n_pairs_ref, packed_cache=packed_cache)
-        res = CconvFunction.apply(filters, inp_features, kw)
+        geo = dict(out_positions=out_positions, extent=float(extent) if ext is None else ext.detach(), inp_positions=inp_positions,
+                   neighbors_index=neighbors_index, neighbors_row_splits=neighbors_row_splits, neighbors_value=neighbors_value,
+                   window=window, window_fac=window_fac, inp_importance=inp_importance, align_corners=align_corners,
+                   coordinate_mapping=coordinate_mapping, interpolation=interpolation, normalize=normalize, symmetric=symmetric,
+                   sym_axis=sym_axis, neighbors_row_count=neighbors_row_count, skip_self=skip_self)
+        res = CconvFunction.apply(filters, inp_features, geo, dict(filter_tile_mask=filter_tile_mask, row_length_hint=row_length_hint,
+                                                                   n_pairs_ref=n_pairs_ref, packed_cache=packed_cache))
         if bias is not None:
             res = res + bias
         return res
-    return _cconv_forward_impl(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
-                               neighbors_value, window, window_fac, inp_importance, align_corners, coordinate_mapping,
-                               interpolation, normalize, symmetric, sym_axis, bias, out, accumulate, n_pairs_ref,
-                               neighbors_row_count, filter_tile_mask, skip_self, name_only, row_length_hint, packed_cache)
-
-
-def _cconv_forward_impl(filters, out_positions, extent, inp_positions, inp_features, neighbors_index,
-                        neighbors_row_splits, neighbors_value=None, window=None, window_fac=1.0, inp_importance=None,
-                        align_corners=True, coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear",
-                        normalize=False, symmetric=False, sym_axis=2, bias=None, out=None, accumulate=False,
-                        n_pairs_ref=None, neighbors_row_count=None, filter_tile_mask=0, skip_self=False, name_only=False,
-                        row_length_hint=0, packed_cache=None):
-    """One call of dmcf_cconv_forward.  ``row_length_hint``: 0 unknown / 1 tens / 2 hundreds of neighbours per row -- what the
-    caller knows about the LAYER from its configuration (include/dmcf_hip.h).  ``skip_self``: DMCF_FLAG_SKIP_SELF (the list holds the query points, the layer ignores them; only the direct kernel).  ``name_only``: no launch, returns the name of the kernel these arguments dispatch to.  ``filter_tile_mask``: see ``block_diagonal_tile_mask`` (0 = no hint).  ``neighbors_row_count``: int32 [n_out] for padded lists (PaddedNeighborList).  ``window``: None | 'explicit' (neighbors_value = importance) |
-    'poly6' | 'cubic' | 'linear' | 'peak' | 'cubic_grad' (neighbors_value = squared distances).
-    ``extent``: a scalar, or one extent per output row -- a tensor of shape [n_out] or [n_out, 1] (dmcf_cconv_forward_extents:
-    row i maps its pairs with extents[i] and evaluates a distance window on d^2 / (extents[i] / 2)^2).  Per-point extents must
-    be finite and positive (ValueError otherwise: one host read); that call always packs the filter (``packed_cache`` unused).
-    """
     L = _lib.lib()
     n_out, cout = out_positions.shape[0], filters.shape[4]
-    ext = per_point_extents(extent, n_out)
-    if ext is not None:
-        ext = _dev_f32(ext, "extents")
-        if n_out > 0 and not bool((torch.isfinite(ext) & (ext > 0)).all()):
-            raise ValueError("per-point extents must be finite and positive")
-        extent = 1.0  # (args->extent is ignored by dmcf_cconv_forward_extents; the workspace query wants a positive one)
+    ext, extent = _extent_operands(extent, n_out)
     if out is None:
         if accumulate:
             raise ValueError("accumulate=True needs an out tensor")
@@ -953,28 +947,27 @@ def _cconv_forward_impl(filters, out_positions, extent, inp_positions, inp_featu
         else:
             out[:] = b
         return out
-    a, keep = _cconv_args(filters, out_positions, extent, inp_positions, inp_features, neighbors_index,
-                          neighbors_row_splits, neighbors_value, window, window_fac, inp_importance, align_corners,
-                          coordinate_mapping, interpolation, normalize, symmetric, sym_axis, bias, out, accumulate,
-                          neighbors_row_count, filter_tile_mask, skip_self, row_length_hint)
+    a, keep = _cconv_args(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
+                          neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
+                          align_corners=align_corners, coordinate_mapping=coordinate_mapping, interpolation=interpolation,
+                          normalize=normalize, symmetric=symmetric, sym_axis=sym_axis, bias=bias, out=out, accumulate=accumulate,
+                          neighbors_row_count=neighbors_row_count, filter_tile_mask=filter_tile_mask, skip_self=skip_self,
+                          row_length_hint=row_length_hint)
     kernel_name = L.dmcf_cconv_kernel_name if ext is None else L.dmcf_cconv_extents_kernel_name
     if name_only:
-        name = ctypes.create_string_buffer(96)
-        _lib.check(kernel_name(ctypes.byref(a), name, 96), "dmcf_cconv_kernel_name")
-        return name.value.decode()
+        return _kernel_name(kernel_name, ctypes.byref(a), what="dmcf_cconv_kernel_name").decode()
     nbytes = L.dmcf_cconv_workspace_bytes(ctypes.byref(a))
     ws = None
     if packed_cache is not None and ext is None:
         # ``packed_cache``: a dict the calling LAYER owns.  It keeps the workspace of the layer's last call; while the filter
         # tensor (storage, version), its interpretation and the kernel the dispatch picks are the same, the packed filter in it
         # is still valid and is not formed again (DMCF_FLAG_FILTER_PACKED: one launch less per layer and step)
-        name = ctypes.create_string_buffer(96)
-        L.dmcf_cconv_kernel_name(ctypes.byref(a), name, 96)
         # Identity of the filter VALUES: the tensor object itself (held by the cache, so neither its address nor its id can be
         # reused by another tensor while the entry lives) + its version counter.  In-place writes through autograd-visible
         # calls (copy_, load_state_dict, optimiser steps) bump the counter; a write through ``.data`` does not -- after one,
         # call ``layer.invalidate_packed()``.  Derived tensors (a fresh object per call) never hit.
-        key = (filters._version, tuple(filters.shape), bool(symmetric), int(sym_axis), name.value, str(filters.device))
+        key = (filters._version, tuple(filters.shape), bool(symmetric), int(sym_axis),
+               _kernel_name(L.dmcf_cconv_kernel_name, ctypes.byref(a)), str(filters.device))
         ws = packed_cache.get("ws")
         if packed_cache.get("src") is filters and packed_cache.get("key") == key and ws is not None and ws.numel() >= nbytes:
             a.flags |= FLAG_FILTER_PACKED
@@ -995,10 +988,8 @@ def _cconv_forward_impl(filters, out_positions, extent, inp_positions, inp_featu
         kdims = [int(d) for d in filters.shape[:3]]
         if symmetric:
             kdims[int(sym_axis)] *= 2
-        name = ctypes.create_string_buffer(96)
-        kernel_name(ctypes.byref(a), name, 96)
         timer.end("cconv", dict(pairs=n_pairs_ref if n_pairs_ref is not None else int(a.n_pairs), n_out=n_out, cin=int(filters.shape[3]), cout=cout,
-                                K=kdims[0] * kdims[1] * kdims[2], symmetric=bool(symmetric), kernel=name.value.decode(),
+                                K=kdims[0] * kdims[1] * kdims[2], symmetric=bool(symmetric), kernel=_kernel_name(kernel_name, ctypes.byref(a)).decode(),
                                 pair_values=bool(a.neighbors_value), accumulate=bool(accumulate)), t0)
     return out
 
@@ -1052,7 +1043,7 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
                    neighbors_value=None, window=None, window_fac=1.0, inp_importance=None, align_corners=True,
                    coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", normalize=False, symmetric=False,
                    sym_axis=2, neighbors_row_count=None, skip_self=False, need_filters=True, need_features=True, inverted=None,
-                   grad_filters=None, grad_inp_features=None, accumulate=False, **_ignored):
+                   grad_filters=None, grad_inp_features=None, accumulate=False):
     """dmcf_cconv_backward: ``(grad_filters, grad_inp_features)`` of the CConv ``cconv_forward`` computes with these
     arguments, for ``grad_out`` = dL/d out [n_out, Cout].  Either can be skipped (``need_filters`` / ``need_features``
     False: None is returned for it).  ``inverted``: an ``invert_neighbors_list`` result of the same list (formed here when
@@ -1065,12 +1056,7 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
     n_out, n_inp = out_positions.shape[0], inp_positions.shape[0]
     cin = filters.shape[3]
     dev = filters.device
-    ext = per_point_extents(extent, n_out)
-    if ext is not None:
-        ext = _dev_f32(ext, "extents")
-        if n_out > 0 and not bool((torch.isfinite(ext) & (ext > 0)).all()):
-            raise ValueError("per-point extents must be finite and positive")
-        extent = 1.0  # (args->extent is ignored by dmcf_cconv_backward_extents; the workspace query wants a positive one)
+    ext, extent = _extent_operands(extent, n_out)
     grad_out = _dev_f32(grad_out, "grad_out", filters.shape[4])
     if grad_out.shape[0] != n_out:
         raise ValueError("grad_out must be [n_out, Cout]")
@@ -1085,8 +1071,10 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
     if not need_filters and not need_features:
         return None, None
     a, keep = _cconv_args(filters, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
-                          neighbors_value, window, window_fac, inp_importance, align_corners, coordinate_mapping, interpolation,
-                          normalize, symmetric, sym_axis, None, None, False, neighbors_row_count, 0, skip_self, 0)
+                          neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
+                          align_corners=align_corners, coordinate_mapping=coordinate_mapping, interpolation=interpolation,
+                          normalize=normalize, symmetric=symmetric, sym_axis=sym_axis, neighbors_row_count=neighbors_row_count,
+                          skip_self=skip_self)
     b = _lib.CconvBackwardArgs()
     b.struct_size = ctypes.sizeof(_lib.CconvBackwardArgs)
     b.flags = 1 if accumulate else 0
@@ -1122,25 +1110,22 @@ def cconv_backward_kernel_names(a, b, extents=False):
     """';'-separated names of the kernels dmcf_cconv_backward -- ``extents``: dmcf_cconv_backward_extents, whose geometry kernels
     carry the suffix _ext -- launches for these (ctypes) arguments."""
     L = _lib.lib()
-    name = ctypes.create_string_buffer(256)
     fn = L.dmcf_cconv_backward_extents_kernel_names if extents else L.dmcf_cconv_backward_kernel_names
-    _lib.check(fn(ctypes.byref(a), ctypes.byref(b), name, 256), "dmcf_cconv_backward_kernel_names")
-    return name.value.decode()
+    return _kernel_name(fn, ctypes.byref(a), ctypes.byref(b), size=256, what="dmcf_cconv_backward_kernel_names").decode()
 
 
 class CconvFunction(torch.autograd.Function):
     """Autograd node of ``cconv_forward``: the forward is whatever kernel the dispatch picks today (bias excluded: torch adds
-    it); the backward is dmcf_cconv_backward (dmcf_cconv_backward_extents when ``kw["extent"]`` is a tensor of per-point
+    it); the backward is dmcf_cconv_backward (dmcf_cconv_backward_extents when ``geo["extent"]`` is a tensor of per-point
     extents, which is kept for the backward and not differentiated), with the neighbour list inverted once per backward when
     the input features want a gradient.  Positions, extents and importances get no gradient (as in Open3D)."""
 
     @staticmethod
-    def forward(ctx, filters, inp_features, kw):
-        ctx.kw = kw
+    def forward(ctx, filters, inp_features, geo, info):
+        ctx.geo = geo
         ctx.save_for_backward(filters, inp_features)
-        f = dict(kw)
-        return _cconv_forward_impl(filters, f.pop("out_positions"), f.pop("extent"), f.pop("inp_positions"), inp_features,
-                                   f.pop("neighbors_index"), f.pop("neighbors_row_splits"), **f)
+        # (grad mode is off in here, so this is the plain call; a replaced ``ops.cconv_forward`` is re-entered by it)
+        return cconv_forward(filters, inp_features=inp_features, **geo, **info)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -1148,13 +1133,10 @@ class CconvFunction(torch.autograd.Function):
         need_w = ctx.needs_input_grad[0]
         need_f = ctx.needs_input_grad[1] and inp_features is not None
         if not need_w and not need_f:
-            return None, None, None
-        kw = dict(ctx.kw)
-        gw, gf = cconv_backward(filters.detach(), kw.pop("out_positions"), kw.pop("extent"), kw.pop("inp_positions"),
-                                None if inp_features is None else inp_features.detach(), kw.pop("neighbors_index"),
-                                kw.pop("neighbors_row_splits"), grad_out.contiguous(), need_filters=need_w, need_features=need_f,
-                                **kw)
-        return gw, gf, None
+            return None, None, None, None
+        gw, gf = cconv_backward(filters.detach(), inp_features=None if inp_features is None else inp_features.detach(),
+                                grad_out=grad_out.contiguous(), need_filters=need_w, need_features=need_f, **ctx.geo)
+        return gw, gf, None, None
 
 
 ND_RELU, ND_W_TRANSPOSED = 1, 2
@@ -1249,11 +1231,8 @@ def _nd_forward(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, re
 def neighbor_dense_kernel_names(fwd, bwd):
     """';'-separated names of the kernels dmcf_neighbor_dense_forward (``fwd``) and / or _backward (``bwd``) launch for these
     (ctypes) arguments."""
-    name = ctypes.create_string_buffer(256)
-    _lib.check(_lib.lib().dmcf_neighbor_dense_kernel_names(None if fwd is None else ctypes.byref(fwd),
-                                                           None if bwd is None else ctypes.byref(bwd), name, 256),
-               "dmcf_neighbor_dense_kernel_names")
-    return name.value.decode()
+    return _kernel_name(_lib.lib().dmcf_neighbor_dense_kernel_names, None if fwd is None else ctypes.byref(fwd),
+                        None if bwd is None else ctypes.byref(bwd), size=256, what="dmcf_neighbor_dense_kernel_names").decode()
 
 
 def neighbor_dense_backward(x, kernel, grad_out, s, count, n_in=None, relu=True, inverted=None, neighbors_index=None,
@@ -2327,9 +2306,7 @@ def adam_step_kernel_names(params, grads, ms, vs, clip_norm=None):
     """';'-separated names of the kernels dmcf_adam_step launches for these tensors (rocprofv3's kernel names)."""
     a, recs = _adam_args(params, grads, ms, vs, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, clip_norm)
     a.device_tensors = 1 if len(params) else None  # (validated for presence only: nothing is read)
-    name = ctypes.create_string_buffer(64)
-    _lib.check(_lib.lib().dmcf_adam_step_kernel_names(ctypes.byref(a), name, 64), "dmcf_adam_step_kernel_names")
-    return name.value.decode()
+    return _kernel_name(_lib.lib().dmcf_adam_step_kernel_names, ctypes.byref(a), size=64, what="dmcf_adam_step_kernel_names").decode()
 
 
 def adam_step(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, beta_2_power, clip_norm=None):

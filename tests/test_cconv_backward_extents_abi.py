@@ -148,3 +148,5 @@ def test_ops_surface_before_launch():
         ops.cconv_backward(W.detach(), P, torch.full((9,), 0.2), P, F, idx, rs, G)       # one extent per output row
     with pytest.raises(NotImplementedError):
         ops.cconv_backward(W.detach(), P, torch.full((10, 3), 0.2), P, F, idx, rs, G)    # anisotropic
+    with pytest.raises(TypeError):
+        ops.cconv_backward(W.detach(), P, 0.2, P, F, idx, rs, G, normalise=True)             # a misspelt option is not dropped

@@ -195,9 +195,11 @@ def _raw_backward(W, P_out, P_inp, F, idx, rs, G, ext, **kw):
     """dmcf_cconv_backward_extents through the C ABI (ops.cconv_backward refuses extents that are not finite and positive)."""
     from dmcf_amd import _lib, ops
     L = _lib.lib()
-    a, keep = ops._cconv_args(W, P_out, 1.0, P_inp, F, idx, rs, None, kw.get("window", "poly6"), 1.0, None, True,
-                              "ball_to_cube_volume_preserving", "linear", kw.get("normalize", False), kw.get("symmetric", False),
-                              kw.get("sym_axis", 2), None, None, False)
+    a, keep = ops._cconv_args(W, P_out, 1.0, P_inp, F, idx, rs, neighbors_value=None, window=kw.get("window", "poly6"),
+                              window_fac=1.0, inp_importance=None, align_corners=True,
+                              coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear",
+                              normalize=kw.get("normalize", False), symmetric=kw.get("symmetric", False),
+                              sym_axis=kw.get("sym_axis", 2), bias=None, out=None, accumulate=False)
     inv = ops.invert_neighbors_list(P_inp.shape[0], idx, rs)
     gw = torch.full(tuple(W.shape), 7.0, device=W.device)
     gf = torch.full((P_inp.shape[0], W.shape[3]), 7.0, device=W.device)

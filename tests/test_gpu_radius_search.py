@@ -285,8 +285,10 @@ def test_cconv_extents_invalid_rows_give_the_bias(dev):
     E[3], E[50], E[77], E[120] = 0.0, -0.1, float("inf"), float("nan")
     res = torch.empty_like(good)
     keep = [_t(a, dev) for a in (filt, out, inp, feat, idx, rs)]
-    a, _k = ops._cconv_args(keep[0], keep[1], 1.0, keep[2], keep[3], keep[4], keep[5], None, None, 1.0, None, True,
-                            "ball_to_cube_volume_preserving", "linear", False, False, 2, bias, res, False)
+    a, _k = ops._cconv_args(keep[0], keep[1], 1.0, keep[2], keep[3], keep[4], keep[5], neighbors_value=None, window=None,
+                            window_fac=1.0, inp_importance=None, align_corners=True,
+                            coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", normalize=False,
+                            symmetric=False, sym_axis=2, bias=bias, out=res, accumulate=False)
     L = _lib.lib()
     nbytes = L.dmcf_cconv_workspace_bytes(ctypes.byref(a))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)

@@ -132,3 +132,12 @@ def test_volume_must_hold_every_reachable_cell(hip_lib):
     short = _part()
     short.inp_dims[0] -= 1
     assert _call(hip_lib, _arr(short), 1, nbytes=1 << 30) == EINVAL
+
+
+def test_ops_refuses_unknown_keywords():
+    """A misspelt option must not be dropped: the gradient would be that of another convolution (raised at call binding)."""
+    torch = pytest.importorskip("torch")
+    from dmcf_amd import ops
+    W, vol, table = torch.zeros(4, 4, 4, 8, 16), torch.zeros(9, 9, 9, 8), torch.zeros(5, 5, 5, dtype=torch.int32)
+    with pytest.raises(TypeError):
+        ops.lattice_conv_backward(W, vol, (-2, -2, -2), table, (0, 0, 0), 10, (0.125,) * 3, 0.6, torch.zeros(10, 16), windw="poly6")
