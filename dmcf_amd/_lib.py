@@ -169,6 +169,31 @@ class CconvScatterArgs(ctypes.Structure):
     ]
 
 
+class SparseConvArgs(ctypes.Structure):
+    """struct dmcf_sparse_conv_args (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_int32),
+        ("filters", ctypes.c_void_p),
+        ("filter_dims", ctypes.c_int32 * 5),
+        ("reserved", ctypes.c_int32),
+        ("row_positions", ctypes.c_void_p),
+        ("n_rows", ctypes.c_int64),
+        ("col_positions", ctypes.c_void_p),
+        ("n_cols", ctypes.c_int64),
+        ("col_features", ctypes.c_void_p),
+        ("row_scale", ctypes.c_void_p),
+        ("col_scale", ctypes.c_void_p),
+        ("neighbors_index", ctypes.c_void_p),
+        ("neighbors_row_splits", ctypes.c_void_p),
+        ("n_pairs", ctypes.c_int64),
+        ("extent", ctypes.c_float),
+        ("offset", ctypes.c_float * 3),
+        ("bias", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+    ]
+
+
 class AdamTensor(ctypes.Structure):
     """struct dmcf_adam_tensor (include/dmcf_hip.h)."""
     _fields_ = [
@@ -243,6 +268,8 @@ SYMBOLS = [
     "dmcf_gather_point_backward_workspace_bytes", "dmcf_gather_point_backward",
     "dmcf_frs_window_sum_backward",
     "dmcf_sph1d_rollout",
+    "dmcf_sparse_conv_forward", "dmcf_sparse_conv_backward_workspace_bytes", "dmcf_sparse_conv_backward",
+    "dmcf_sparse_conv_kernel_names",
 ]
 
 
@@ -445,6 +472,16 @@ def lib():
     L.dmcf_sph1d_rollout.restype = c.c_int
     L.dmcf_sph1d_rollout.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int32, c.POINTER(Sph1dParams), c.c_int32, c.c_void_p,
                                      c.c_void_p, c.c_void_p, c.c_void_p]
+    # the voxel convolution of SparseConv / SparseConvTranspose (ABI 2.18)
+    L.dmcf_sparse_conv_forward.restype = c.c_int
+    L.dmcf_sparse_conv_forward.argtypes = [c.POINTER(SparseConvArgs), c.c_void_p]
+    L.dmcf_sparse_conv_backward_workspace_bytes.restype = c.c_size_t
+    L.dmcf_sparse_conv_backward_workspace_bytes.argtypes = [c.POINTER(SparseConvArgs), c.c_int]
+    L.dmcf_sparse_conv_backward.restype = c.c_int
+    L.dmcf_sparse_conv_backward.argtypes = [c.POINTER(SparseConvArgs), c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                            c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_sparse_conv_kernel_names.restype = c.c_int
+    L.dmcf_sparse_conv_kernel_names.argtypes = [c.POINTER(SparseConvArgs), c.c_int, c.c_char_p, c.c_size_t]
     _lib = L
     return L
 

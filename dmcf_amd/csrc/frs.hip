@@ -883,13 +883,96 @@ __global__ __launch_bounds__(256) void frs_fix(const float* __restrict__ queries
     }
 }
 
+
+// ---- max-norm search (DMCF_FRS_METRIC_LINF): the pair set of SparseConv / SparseConvTranspose (utils/convolutions.py:561-562,
+// 634-639) -- { p : max_a |p_a - q_a| <= R }, float32 differences, inclusive.  Kernels of their own: the scan above narrows every
+// x-run to the chord of the search sphere, which would drop the corners of the box.  Same structure (the cells of
+// dmcf_frs_build(points, R) cover q +- R), same row order (ascending cell, then index), no distances, no open3d emulation.
+// One wavefront per query: lane r takes the x-run of cell row r of the box, the runs' lengths are prefix-summed over the wave,
+// and the lanes stride the flattened candidate list; a 6-step binary search over the sums (per-wave LDS) finds a candidate's run.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void frs_query_linf(const float* __restrict__ queries, int64_t m, const FrsHeader* __restrict__ h,
+                                                      const uint32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
+                                                      float radius, int flags, int32_t* __restrict__ counts,
+                                                      const int64_t* __restrict__ row_splits, int32_t* __restrict__ nbr_index,
+                                                      int64_t capacity) {
+    __shared__ int32_t s_incl[4][kWave], s_rel[4][kWave];
+    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (qi >= m) return;  // whole wave leaves
+    if (WRITE && row_splits[qi + 1] > capacity) return;  // (as frs_query: the caller sees the overflow in row_splits[m])
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const float q[3] = {queries[3 * qi], queries[3 * qi + 1], queries[3 * qi + 2]};
+    const int64_t out_base = WRITE ? row_splits[qi] : 0;
+    const int32_t row_cap = WRITE ? (int32_t)min(row_splits[qi + 1] - out_base, (int64_t)0x7fffffff) : 0;
+    const bool ignore = (flags & DMCF_FRS_IGNORE_QUERY_POINT) != 0;
+    int lo[3], hi[3];
+    bool empty = h->ncells <= 0 || h->n_points <= 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        // (slack and clamps as in frs_scan: a superset of the box, the border cells hold what was binned from beyond the grid)
+        const float slack = 1e-4f * radius + 4.8e-7f * (fabsf(q[a]) + radius);
+        lo[a] = min(max(cell_coord(q[a] - radius - slack, h->origin[a], h->inv_cell[a], h->dims[a]), 0), h->dims[a] - 1);
+        hi[a] = max(min(cell_coord(q[a] + radius + slack, h->origin[a], h->inv_cell[a], h->dims[a]), h->dims[a] - 1), 0);
+        empty |= lo[a] > hi[a];
+    }
+    int32_t cnt = 0;
+    if (!empty) {
+        const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
+        for (int row0 = 0; row0 < ny * nz; row0 += kWave) {
+            const int r = row0 + lane;
+            int32_t start = 0, len = 0;
+            if (r < ny * nz) {
+                const int cy = lo[1] + r % ny, cz = lo[2] + r / ny;
+                const int32_t base = (cz * h->dims[1] + cy) * h->dims[0];
+                start = (int32_t)cell_start[base + lo[0]];
+                len = (int32_t)cell_start[base + hi[0] + 1] - start;
+            }
+            const int32_t incl = wave_inclusive_add(len);
+            const int32_t total = __builtin_amdgcn_readlane(incl, kWave - 1);
+            // (lanes talk through LDS: fences as in frs_scan's locate; the barrier in front keeps the previous batch's reads ahead)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            s_incl[w][lane] = incl;
+            s_rel[w][lane] = start - (incl - len);  // candidate f of this run sits at sorted[rel + f]
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int32_t f0 = 0; f0 < total; f0 += kWave) {
+                const int32_t f = f0 + lane;
+                bool hit = false;
+                int32_t pidx = 0;
+                if (f < total) {
+                    int run = 0;  // the first run whose inclusive sum exceeds f
+#pragma unroll
+                    for (int step = 32; step >= 1; step >>= 1)
+                        if (s_incl[w][run + step - 1] <= f) run += step;
+                    const float4 p = sorted[s_rel[w][run] + f];
+                    hit = fabsf(__fsub_rn(p.x, q[0])) <= radius && fabsf(__fsub_rn(p.y, q[1])) <= radius &&
+                          fabsf(__fsub_rn(p.z, q[2])) <= radius;
+                    if (ignore && p.x == q[0] && p.y == q[1] && p.z == q[2]) hit = false;
+                    pidx = __float_as_int(p.w);
+                }
+                const unsigned long long mask = __ballot(hit);
+                if (WRITE && hit) {
+                    const int32_t slot = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+                    if (slot < row_cap) nbr_index[out_base + slot] = pidx;  // (never beyond the row the count pass sized)
+                }
+                cnt += __popcll(mask);
+            }
+        }
+    }
+    if (!WRITE && lane == 0) counts[qi] = cnt;
+}
+
 }  // namespace dmcf
 
 using namespace dmcf;
 
 static bool frs_flags_ok(int flags) {  // known bits, and at most one reading of the reference's walk
-    return (flags & ~(DMCF_FRS_IGNORE_QUERY_POINT | kO3dFlags)) == 0 && (flags & kO3dFlags) != kO3dFlags;
+    return (flags & ~(DMCF_FRS_IGNORE_QUERY_POINT | kO3dFlags | DMCF_FRS_METRIC_LINF)) == 0 && (flags & kO3dFlags) != kO3dFlags;
 }
+// DMCF_FRS_METRIC_LINF: index lists only (dmcf_frs_count / dmcf_frs_write without distances, no open3d emulation)
+static bool frs_linf(int flags) { return (flags & DMCF_FRS_METRIC_LINF) != 0; }
 
 static constexpr unsigned kFixGrid = 1024;  // 4096 waves walk the query flags (frs_fix)
 
@@ -954,6 +1037,7 @@ int dmcf_frs_count(const float* queries, int64_t m, int64_t n, float radius, int
     hipStream_t stream = (hipStream_t)stream_;
     if (!frs_flags_ok(flags)) return DMCF_EINVAL;
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || !row_splits || (m > 0 && !queries)) return DMCF_EINVAL;
+    if (frs_linf(flags) && (flags & kO3dFlags)) return DMCF_EUNSUPPORTED;
     const FrsLayout L = frs_layout(n, m);
     if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
     char* ws = (char*)workspace;
@@ -961,7 +1045,10 @@ int dmcf_frs_count(const float* queries, int64_t m, int64_t n, float radius, int
     const uint32_t* cell_start = (const uint32_t*)(ws + L.off_cell_start);
     const float4* sorted = (const float4*)(ws + L.off_sorted);
     int32_t* counts = (int32_t*)(ws + L.off_counts);
-    if (m > 0) {
+    if (m > 0 && frs_linf(flags)) {
+        hipLaunchKernelGGL((frs_query_linf<false>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, queries, m, h, cell_start, sorted,
+                           radius, flags, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0);
+    } else if (m > 0) {
         const unsigned g = (unsigned)((m + 3) / 4);
         uint8_t* qflags = (uint8_t*)(ws + L.off_flags);
         hipLaunchKernelGGL((frs_query<false>), dim3(g), dim3(256), 0, stream, queries, m, h, cell_start, sorted,
@@ -980,6 +1067,7 @@ int dmcf_frs_write(const float* queries, int64_t m, int64_t n, float radius, int
     hipStream_t stream = (hipStream_t)stream_;
     if (!frs_flags_ok(flags)) return DMCF_EINVAL;
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || !row_splits || (m > 0 && !queries)) return DMCF_EINVAL;
+    if (frs_linf(flags) && ((flags & kO3dFlags) || neighbors_distance)) return DMCF_EUNSUPPORTED;
     if (m == 0) return DMCF_OK;
     if (!neighbors_index || pair_capacity < 0) return DMCF_EINVAL;
     const FrsLayout L = frs_layout(n, m);
@@ -989,6 +1077,11 @@ int dmcf_frs_write(const float* queries, int64_t m, int64_t n, float radius, int
     const uint32_t* cell_start = (const uint32_t*)(ws + L.off_cell_start);
     const float4* sorted = (const float4*)(ws + L.off_sorted);
     const unsigned g = (unsigned)((m + 3) / 4);
+    if (frs_linf(flags)) {
+        hipLaunchKernelGGL((frs_query_linf<true>), dim3(g), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags,
+                           (int32_t*)nullptr, row_splits, neighbors_index, pair_capacity);
+        return check_launch();
+    }
     uint8_t* qflags = (uint8_t*)(ws + L.off_flags);  // (written by the count pass of this search)
     hipLaunchKernelGGL((frs_query<true>), dim3(g), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius,
                        flags, (int32_t*)nullptr, row_splits, neighbors_index, neighbors_distance, pair_capacity, qflags);
@@ -1040,6 +1133,7 @@ int dmcf_frs_search_padded(const float* queries, int64_t m, int64_t n, float rad
                            int32_t* neighbors_index, float* neighbors_distance, int32_t* max_count, dmcf_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!frs_flags_ok(flags)) return DMCF_EINVAL;
+    if (frs_linf(flags)) return DMCF_EUNSUPPORTED;  // the max-norm search returns index lists only
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || !row_begin || !max_count || (m > 0 && (!queries || !row_count)))
         return DMCF_EINVAL;
     if (row_stride < 0 || (m > 0 && row_stride > 0 && !neighbors_index)) return DMCF_EINVAL;
@@ -1065,6 +1159,7 @@ int dmcf_frs_window_sum(const float* queries, int64_t m, int64_t n, float radius
                         const void* workspace, size_t workspace_bytes, float* out, dmcf_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!frs_flags_ok(flags)) return DMCF_EINVAL;
+    if (frs_linf(flags)) return DMCF_EUNSUPPORTED;  // the max-norm search returns index lists only
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || (m > 0 && (!queries || !out))) return DMCF_EINVAL;
     if (window < DMCF_WINDOW_NONE || window > DMCF_WINDOW_CUBIC_GRAD) return DMCF_EINVAL;
     if (m == 0) return DMCF_OK;
@@ -1088,7 +1183,7 @@ int dmcf_frs_window_sum_backward(const float* queries, int64_t m, int64_t n, flo
                                  const float* coef_queries, const float* coef_points, const void* workspace,
                                  size_t workspace_bytes, float* grad, dmcf_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!frs_flags_ok(flags)) return DMCF_EINVAL;
+    if (!frs_flags_ok(flags) || frs_linf(flags)) return DMCF_EINVAL;  // (the metric flag was never a flag of this entry point)
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || (m > 0 && (!queries || !grad))) return DMCF_EINVAL;
     if (window < DMCF_WINDOW_NONE || window > DMCF_WINDOW_CUBIC_GRAD) return DMCF_EINVAL;
     if (!coef_queries && !coef_points) return DMCF_EINVAL;

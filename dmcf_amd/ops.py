@@ -295,7 +295,7 @@ def _size_class(x):
     return (x + g - 1) // g * g
 
 
-FRS_IGNORE_QUERY_POINT, FRS_OPEN3D_CORNER_VOXELS, FRS_OPEN3D_VOXEL_WALK = 1, 2, 4
+FRS_IGNORE_QUERY_POINT, FRS_OPEN3D_CORNER_VOXELS, FRS_OPEN3D_VOXEL_WALK, FRS_METRIC_LINF = 1, 2, 4, 8
 
 # Which neighbour SET the searches return (include/dmcf_hip.h, DMCF_FRS_*):
 #   "distance"        every point with d^2 <= R^2 -- what open3d's walk over the query's own voxel and the 8 corner voxels of
@@ -343,9 +343,13 @@ def frs_flags(ignore_query_point):
 
 
 def fixed_radius_search(points, queries, radius, ignore_query_point=False, return_distances=True,
-                        hash_table=None, capacity_hint=None, row_stride=None, max_count=None):
+                        hash_table=None, capacity_hint=None, row_stride=None, max_count=None, metric="L2"):
     """-> NeighborSearchResult(neighbors_index int32 [P], neighbors_row_splits int64 [m+1],
     neighbors_distance float32 [P] (squared L2; empty if not return_distances)).
+
+    ``metric``: "L2", or "Linf" -- the max-norm set { max_a |p_a - q_a| <= radius } of the sparse layers (DMCF_FRS_METRIC_LINF:
+    the same structure and row order, index lists only: ``return_distances`` and ``row_stride`` raise, and DMCF_FRS_SET does
+    not apply).
 
     ``capacity_hint``: an estimate of P.  With it count, scan and write are enqueued back to back with buffers of
     that size and NO host synchronisation; the result is validated later (see NeighborSearchResult).
@@ -357,6 +361,10 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
     radius = float(radius)
     if not radius > 0:
         raise ValueError("radius must be positive")
+    if metric not in ("L2", "Linf"):
+        raise NotImplementedError(f"metric {metric!r}: 'L2' and 'Linf' are implemented on the HIP path")
+    if metric == "Linf" and (return_distances or row_stride is not None):
+        raise NotImplementedError("the 'Linf' search returns index lists only (no distances, no padded rows)")
     n, m = points.shape[0], queries.shape[0]
     if hash_table is None or hash_table.n_queries_capacity < m or hash_table.points.data_ptr() != points.data_ptr() \
             or hash_table.radius != radius:
@@ -364,6 +372,8 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
     ws = hash_table.workspace
     nbytes = L.dmcf_frs_workspace_bytes(n, hash_table.n_queries_capacity)
     flags = frs_flags(ignore_query_point)
+    if metric == "Linf":
+        flags = (FRS_IGNORE_QUERY_POINT if ignore_query_point else 0) | FRS_METRIC_LINF
     dev = points.device
     row_splits = torch.empty(m + 1, dtype=torch.int64, device=dev)
     if row_stride is not None:
@@ -435,9 +445,12 @@ class FixedRadiusSearch:
 
     def __init__(self, metric="L2", ignore_query_point=False, return_distances=False,
                  max_hash_table_size=32 * 2 ** 20, index_dtype=torch.int32, **kwargs):
-        if metric != "L2":
-            # every DMCF config uses the default radius_search_metric='L2' (utils/convolutions.py:165)
-            raise NotImplementedError(f"metric {metric!r}: only 'L2' is implemented on the HIP path")
+        if metric not in ("L2", "Linf"):
+            # every DMCF config uses the default radius_search_metric='L2' (utils/convolutions.py:165); the sparse layers
+            # search with 'Linf' (:561-562, :760-761)
+            raise NotImplementedError(f"metric {metric!r}: 'L2' and 'Linf' are implemented on the HIP path")
+        if metric == "Linf" and return_distances:
+            raise NotImplementedError("metric 'Linf' returns index lists only (return_distances must be False)")
         if index_dtype != torch.int32:
             raise NotImplementedError("index_dtype must be int32 (Open3D 0.15.2 returns int32 indices)")
         self.metric = metric
@@ -452,8 +465,10 @@ class FixedRadiusSearch:
                                       "pipelines/simulator.py:68-70)")
         if isinstance(radius, torch.Tensor):
             radius = float(radius)
+        metric = {} if self.metric == "L2" else {"metric": self.metric}  # (an L2 call is the call it always was)
         return fixed_radius_search(points, queries, radius, self.ignore_query_point, self.return_distances,
-                                   hash_table=hash_table, capacity_hint=capacity_hint, row_stride=row_stride, max_count=max_count)
+                                   hash_table=hash_table, capacity_hint=capacity_hint, row_stride=row_stride, max_count=max_count,
+                                   **metric)
 
     call = __call__
 
@@ -1516,6 +1531,241 @@ def continuous_conv(filters, out_positions, extents, offset, inp_positions, inp_
                          neighbors_row_splits, neighbors_value=neighbors_importance, window=window,
                          inp_importance=inp_importance, align_corners=align_corners,
                          coordinate_mapping=coordinate_mapping, interpolation=interpolation, normalize=normalize)
+
+
+SPARSE_NEGATE, SPARSE_W_TRANSPOSED, SPARSE_ACCUMULATE = 1, 2, 4
+
+
+def _sparse_offset(offset):
+    o = [0.0, 0.0, 0.0] if offset is None else [float(v) for v in torch.as_tensor(offset).reshape(-1).tolist()]
+    if len(o) != 3:
+        raise ValueError("offset must have shape [3]")
+    return o
+
+
+def _sparse_vec(t, name, n, device):
+    """An optional per-point scale: None / empty -> None, else a float32 [n] device tensor."""
+    if _empty(t):
+        return None
+    t = _dev_f32(t, name)
+    if t.dim() != 1 or t.shape[0] != n or t.device != device:
+        raise ValueError(f"{name} must be a float32 [{n}] tensor on {device}")
+    return t
+
+
+def _sparse_bias(bias, channels, device):
+    """None, or a float32 [channels] tensor on ``device`` (DmcfError for a CPU tensor, as for every operand of the hot path)."""
+    if bias is None:
+        return None
+    bias = _dev_f32(bias, "bias")
+    if bias.dim() != 1 or bias.shape[0] != channels or bias.device != device:
+        raise ValueError(f"bias must be a float32 [{channels}] tensor on {device}, got {tuple(bias.shape)} on {bias.device}")
+    return bias
+
+
+def _sparse_args(filters, row_positions, col_positions, col_features, index, row_splits, extent, offset, flags, row_scale=None,
+                 col_scale=None, bias=None, out=None):
+    """struct dmcf_sparse_conv_args for the row-gather operator of include/dmcf_hip.h, and the tensors it points to."""
+    filters = _dev_f32(filters, "filters")
+    if filters.dim() != 5:
+        raise ValueError("filters must have shape [kz, ky, kx, Cin, Cout]")
+    dev = filters.device
+    bias = _sparse_bias(bias, filters.shape[3] if flags & SPARSE_W_TRANSPOSED else filters.shape[4], dev)
+    row_positions = _dev_f32(row_positions, "row positions", 3)
+    col_positions = _dev_f32(col_positions, "col positions", 3)
+    xc = filters.shape[4] if flags & SPARSE_W_TRANSPOSED else filters.shape[3]
+    col_features = _dev_f32(col_features, "features", xc)
+    n_rows, n_cols = row_positions.shape[0], col_positions.shape[0]
+    if col_features.shape[0] != n_cols:
+        raise ValueError("one feature row per column point")
+    if index.dtype != torch.int32 or row_splits.dtype != torch.int64 or not index.is_cuda or not row_splits.is_cuda:
+        raise TypeError("neighbors_index must be int32 and neighbors_row_splits int64, both on the GPU")
+    if row_splits.shape[0] != n_rows + 1:
+        raise ValueError("neighbors_row_splits must have n_rows + 1 entries")
+    index, row_splits = index.contiguous(), row_splits.contiguous()
+    row_scale = _sparse_vec(row_scale, "row scale", n_rows, dev)
+    col_scale = _sparse_vec(col_scale, "col scale", n_cols, dev)
+    a = _lib.SparseConvArgs()
+    a.struct_size = ctypes.sizeof(_lib.SparseConvArgs)
+    a.flags = flags
+    a.filters = filters.data_ptr()
+    for k in range(5):
+        a.filter_dims[k] = filters.shape[k]
+    a.row_positions, a.n_rows = row_positions.data_ptr(), n_rows
+    a.col_positions, a.n_cols = col_positions.data_ptr(), n_cols
+    a.col_features = col_features.data_ptr()
+    a.row_scale = None if row_scale is None else row_scale.data_ptr()
+    a.col_scale = None if col_scale is None else col_scale.data_ptr()
+    a.neighbors_index = index.data_ptr()
+    a.neighbors_row_splits = row_splits.data_ptr()
+    a.n_pairs = index.shape[0]
+    a.extent = float(extent)
+    for k in range(3):
+        a.offset[k] = offset[k]
+    a.bias = None if bias is None else bias.data_ptr()
+    a.out = None if out is None else out.data_ptr()
+    keep = (filters, row_positions, col_positions, col_features, index, row_splits, row_scale, col_scale, bias, out)
+    return a, keep, dev
+
+
+def sparse_conv_kernel_names(a, backward=0):
+    """';'-separated kernels dmcf_sparse_conv_forward (``backward`` 0) / _backward (1: filters, 2: features, 3: both) launches."""
+    return _kernel_name(_lib.lib().dmcf_sparse_conv_kernel_names, ctypes.byref(a), int(backward), size=128,
+                        what="dmcf_sparse_conv_kernel_names").decode()
+
+
+def sparse_gather(filters, row_positions, col_positions, col_features, index, row_splits, extent, offset, flags=0, row_scale=None,
+                  col_scale=None, bias=None, out=None):
+    """dmcf_sparse_conv_forward: ``out[r] = row_scale[r] * sum_p col_scale[j] * W[cell(+-(col_pos[j] - row_pos[r]))]^T x[j] (+ bias)``
+    over the CSR list (index, row_splits); see include/dmcf_hip.h.  No list, no rows or no columns: the bias-only result,
+    without a launch."""
+    offset = _sparse_offset(offset)
+    a, keep, dev = _sparse_args(filters, row_positions, col_positions, col_features, index, row_splits, extent, offset, flags,
+                                row_scale, col_scale, bias, None)
+    oc = filters.shape[3] if flags & SPARSE_W_TRANSPOSED else filters.shape[4]
+    if out is None:
+        if flags & SPARSE_ACCUMULATE:
+            raise ValueError("SPARSE_ACCUMULATE adds into ``out``: pass the tensor to add into")
+        out = torch.empty((a.n_rows, oc), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (a.n_rows, oc) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous float32 [{a.n_rows}, {oc}] tensor on {dev}")
+    if a.n_rows == 0 or a.n_cols == 0 or a.n_pairs == 0:
+        if not flags & SPARSE_ACCUMULATE:
+            out.zero_()
+        if keep[8] is not None:
+            out += keep[8]
+        return out
+    a.out = out.data_ptr()
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(_lib.lib().dmcf_sparse_conv_forward(ctypes.byref(a), _stream()), "dmcf_sparse_conv_forward")
+    if timer is not None:
+        timer.end("sparse_conv", dict(n_rows=int(a.n_rows), cin=int(filters.shape[3]), cout=int(filters.shape[4])), t0)
+    del keep
+    return out
+
+
+def sparse_gather_backward(filters, row_positions, col_positions, col_features, index, row_splits, extent, offset, grad_out, flags=0,
+                           row_scale=None, col_scale=None, need_filters=True, need_features=True, inverted=None):
+    """dmcf_sparse_conv_backward: ``(grad_filters, grad_col_features)`` of :func:`sparse_gather` with these arguments.
+    ``inverted``: an ``invert_neighbors_list(n_cols, index, row_splits)`` result (formed here when the feature gradient is
+    wanted and none is given)."""
+    L = _lib.lib()
+    offset = _sparse_offset(offset)
+    a, keep, dev = _sparse_args(filters, row_positions, col_positions, col_features, index, row_splits, extent, offset,
+                                flags & ~SPARSE_ACCUMULATE, row_scale, col_scale)
+    oc = filters.shape[3] if flags & SPARSE_W_TRANSPOSED else filters.shape[4]
+    grad_out = _dev_f32(grad_out, "grad_out", oc)
+    if grad_out.shape[0] != a.n_rows:
+        raise ValueError("grad_out must have one row per output row")
+    gw = gf = None
+    if need_filters:
+        gw = torch.empty(tuple(filters.shape), dtype=torch.float32, device=dev)
+    if need_features:
+        gf = torch.empty(tuple(col_features.shape), dtype=torch.float32, device=dev)
+    if a.n_rows == 0 or a.n_cols == 0 or a.n_pairs == 0:
+        return (None if gw is None else gw.zero_()), (None if gf is None else gf.zero_())
+    if not need_filters and not need_features:
+        return None, None
+    inv_index = inv_rs = None
+    inv_pairs = 0
+    if need_features:
+        if inverted is None:
+            inverted = invert_neighbors_list(a.n_cols, keep[4], keep[5])
+        inv_index, inv_rs = inverted.neighbors_index, inverted.neighbors_row_splits
+        inv_pairs = inv_index.shape[0]
+    nbytes = int(L.dmcf_sparse_conv_backward_workspace_bytes(ctypes.byref(a), 1 if need_filters else 0))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_sparse_conv_backward(ctypes.byref(a), _ptr(grad_out), _ptr(inv_index), _ptr(inv_rs), inv_pairs, _ptr(gw), _ptr(gf),
+                                           _ptr(ws), nbytes, _stream()), "dmcf_sparse_conv_backward")
+    if timer is not None:
+        timer.end("sparse_conv_backward", dict(n_rows=int(a.n_rows), filters=bool(need_filters), features=bool(need_features)), t0)
+    del keep
+    return gw, gf
+
+
+class SparseGatherFunction(torch.autograd.Function):
+    """Autograd node of :func:`sparse_gather` (bias excluded: torch adds it): the backward is dmcf_sparse_conv_backward, the list
+    inverted once when the features want a gradient.  Positions and scales get no gradient here (a scale that wants one is
+    applied by torch outside the node, see sparse_conv)."""
+
+    @staticmethod
+    def forward(ctx, filters, col_features, geo):
+        ctx.geo = geo
+        ctx.save_for_backward(filters, col_features)
+        return sparse_gather(filters, col_features=col_features, **geo)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        filters, col_features = ctx.saved_tensors
+        need_w, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not need_w and not need_f:
+            return None, None, None
+        gw, gf = sparse_gather_backward(filters.detach(), col_features=col_features.detach(), grad_out=grad_out.contiguous(),
+                                        need_filters=need_w, need_features=need_f, **ctx.geo)
+        return gw, gf, None
+
+
+def _sparse_call(filters, features, bias, row_scale, col_scale, geo):
+    """The fused call, or -- when something wants a gradient -- the autograd node with torch around it for what the node does
+    not differentiate: a scale that requires grad is applied outside, the bias is added outside."""
+    wants = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (filters, features, bias, row_scale, col_scale))
+    bias = _sparse_bias(bias, filters.shape[3] if geo["flags"] & SPARSE_W_TRANSPOSED else filters.shape[4], filters.device)
+    if not wants:
+        return sparse_gather(filters, col_features=features, bias=bias, row_scale=row_scale, col_scale=col_scale, **geo)
+    if col_scale is not None and col_scale.requires_grad:
+        features, col_scale = features * col_scale[:, None], None
+    outer = None
+    if row_scale is not None and row_scale.requires_grad:
+        outer, row_scale = row_scale, None
+    geo = dict(geo, row_scale=None if row_scale is None else row_scale.detach(), col_scale=None if col_scale is None else col_scale.detach())
+    out = SparseGatherFunction.apply(filters, features, geo)
+    if outer is not None:
+        out = out * outer[:, None]
+    return out if bias is None else out + bias
+
+
+def _row_count_scale(row_splits):
+    """1 / |row| per row of a CSR list, 0 for an empty row (float32, on the device)."""
+    cnt = torch.diff(row_splits).to(torch.float32)
+    return torch.where(cnt > 0, 1.0 / cnt.clamp(min=1.0), torch.zeros_like(cnt))
+
+
+def sparse_conv(filters, out_positions, voxel_size, offset, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
+                inp_importance=None, normalize=False, bias=None):
+    """What ``SparseConv`` asks of ``ml3d.ops.continuous_conv`` (utils/convolutions.py:645-664: identity mapping, align_corners
+    False, nearest neighbour, extent = voxel_size * kernel_size[-1]) on the voxel-convolution kernel:
+    ``out_i = s_i sum_j imp_j W[cell(inp_j - out_i)]^T f_j (+ bias)`` over the list's row i, ``s_i = 1 / |row i|`` with
+    ``normalize`` (0 for an empty row).  ``filters`` [kz, ky, kx, Cin, Cout]; ``offset`` [3] in cells.  Differentiable in
+    filters, features, bias and importance."""
+    filters = _dev_f32(filters, "filters")
+    n_out, n_inp = out_positions.shape[0], inp_positions.shape[0]
+    dev = filters.device
+    imp = _sparse_vec(inp_importance, "inp_importance", n_inp, dev)
+    rs = _row_count_scale(neighbors_row_splits) if normalize else None
+    geo = dict(row_positions=out_positions, col_positions=inp_positions, index=neighbors_index, row_splits=neighbors_row_splits,
+               extent=float(np.float32(voxel_size) * np.float32(filters.shape[2])), offset=_sparse_offset(offset), flags=0)
+    return _sparse_call(filters, inp_features, bias, rs, imp, geo)
+
+
+def sparse_conv_transpose(filters, out_positions, voxel_size, offset, inp_positions, inp_features, inp_neighbors_index,
+                          inp_neighbors_row_splits, neighbors_index, neighbors_row_splits, out_importance=None, normalize=False,
+                          bias=None):
+    """What ``SparseConvTranspose`` asks of ``ml3d.ops.continuous_conv_transpose`` (utils/convolutions.py:852-874):
+    ``out_i = oimp_i sum_{j in row i} n_j W[cell(out_i - inp_j)]^T f_j (+ bias)`` over the INVERTED list (neighbors_index,
+    neighbors_row_splits: for every output point the input points whose search found it); ``n_j = 1 / |N_T(j)|`` with
+    ``normalize``, from the input points' list (inp_neighbors_row_splits).  The direction of the relative position (output
+    minus input) is this project's reading of Open3D's operator."""
+    filters = _dev_f32(filters, "filters")
+    n_out, n_inp = out_positions.shape[0], inp_positions.shape[0]
+    dev = filters.device
+    oimp = _sparse_vec(out_importance, "out_importance", n_out, dev)
+    if inp_neighbors_row_splits.shape[0] != n_inp + 1:
+        raise ValueError("inp_neighbors_row_splits must have n_inp + 1 entries")
+    cs = _row_count_scale(inp_neighbors_row_splits) if normalize else None
+    geo = dict(row_positions=out_positions, col_positions=inp_positions, index=neighbors_index, row_splits=neighbors_row_splits,
+               extent=float(np.float32(voxel_size) * np.float32(filters.shape[2])), offset=_sparse_offset(offset), flags=SPARSE_NEGATE)
+    return _sparse_call(filters, inp_features, bias, oimp, cs, geo)
 
 
 def dense_supported(x, kernel):

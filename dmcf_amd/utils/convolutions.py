@@ -12,6 +12,9 @@ Weights are built with ``requires_grad=False``: inference records no autograd hi
 the neighbour-list form, whose backward is dmcf_cconv_backward (``ContinuousConv._forward_train``).  Extents of rank 1, one
 per output point, record only in a layer built with ``record_per_point_extents=True`` (dmcf_cconv_backward_extents); any
 other layer refuses them while recording, as before.
+
+``SparseConv`` and ``SparseConvTranspose`` (the reference's :476-885) sit on a path of their own: a max-norm search
+(``ops.FixedRadiusSearch(metric="Linf")``) and the voxel-convolution kernel (``ops.sparse_conv`` / ``ops.sparse_conv_transpose``).
 """
 import math
 import os
@@ -23,7 +26,7 @@ import torch
 from .. import ops
 from .tools.losses import WindowFunction
 
-__all__ = ["ContinuousConv", "neighbor_cache"]
+__all__ = ["ContinuousConv", "SparseConv", "SparseConvTranspose", "neighbor_cache"]
 
 # dmcf_cconv_scatter_forward (splat S) is taken for particles -> coarse-lattice layers with these output channel counts (8 is
 # implemented and tested but measures slower than the gather kernels: tools/bench_scatter.py) ...
@@ -1101,5 +1104,125 @@ class PointSampling(PlainAttributes, torch.nn.Module):
                                 neighbors_row_count=row_count)
         self._conv_output = None if _CACHE.depth > 0 else out  # see ContinuousConv.forward
         return out
+
+    call = forward
+
+
+class _SparseBase(PlainAttributes, torch.nn.Module):
+    """What SparseConv and SparseConvTranspose share (the reference's :525-588 and :724-787): constructor keywords, the lazy
+    weights, the max-norm search."""
+
+    def __init__(self, filters, kernel_size, activation=None, use_bias=True, kernel_initializer="uniform", bias_initializer="zeros",
+                 kernel_regularizer=None, bias_regularizer=None, normalize=False, offset=None, in_channels=None, name=None,
+                 trainable=True, device=None, **kwargs):
+        super().__init__()
+        self.layer_name = name
+        self.filters = filters
+        self.kernel_size = [int(k) for k in kernel_size]
+        if len(self.kernel_size) != 3:
+            raise ValueError("kernel_size must be [kz, ky, kx]")
+        if activation not in _ACTIVATIONS and not callable(activation):
+            raise NotImplementedError(f"activation {activation!r}")
+        self.activation = _ACTIVATIONS.get(activation, activation) if not callable(activation) else activation
+        self.use_bias = use_bias
+        self.kernel_initializer = kernel_initializer
+        self.bias_initializer = bias_initializer
+        self.normalize = normalize
+        if offset is None:  # :553-559
+            offset = torch.zeros(3) if self.kernel_size[0] % 2 else torch.full((3,), -0.5)
+        self.offset = torch.as_tensor(offset, dtype=torch.float32).reshape(3).cpu()
+        self.fixed_radius_search = ops.FixedRadiusSearch(metric="Linf", ignore_query_point=False, return_distances=False)
+        self.in_channels = None
+        self.kernel = None
+        self.bias = None
+        self._device = device
+        self._avg_neighbors = None
+        self._conv_values = None
+        self._conv_output = None
+
+    def build(self, in_channels, device=None):
+        device = device or self._device or "cuda"
+        self.in_channels = int(in_channels)
+        kshape = (*self.kernel_size, self.in_channels, self.filters)
+        self.kernel = torch.nn.Parameter(_init_tensor(self.kernel_initializer, kshape, device), requires_grad=False)
+        if self.use_bias:
+            self.bias = torch.nn.Parameter(_init_tensor(self.bias_initializer, (self.filters,), device), requires_grad=False)
+
+    def _prepare(self, inp_features, voxel_size):
+        if self.kernel is None:
+            with torch.no_grad():
+                self.build(inp_features.shape[-1], inp_features.device)
+        if isinstance(voxel_size, torch.Tensor):
+            if voxel_size.dim() != 0:
+                raise ValueError("voxel_size must be a scalar")
+            voxel_size = float(voxel_size)
+        elif np.ndim(voxel_size) != 0:
+            raise ValueError("voxel_size must be a scalar")
+        voxel = np.float32(voxel_size)
+        # :637 radius = kernel_size[-1] * voxel_size * 0.51, in float32
+        radius = np.float32(np.float32(np.float32(self.kernel_size[-1]) * voxel) * np.float32(0.51))
+        return float(voxel), float(radius)
+
+    def _finish(self, out_features):
+        self._conv_output = out_features
+        if self.activation is not None:
+            out_features = self.activation(out_features)
+        return out_features
+
+
+class SparseConv(_SparseBase):
+    """Mirror of the reference's ``SparseConv`` (utils/convolutions.py:476-675): a convolution evaluated at the output positions
+    only, for points on a regular grid -- each neighbour within ``kernel_size[-1] * voxel_size * 0.51`` in the max norm multiplies
+    the one filter cell its relative position rounds to.  Same constructor keywords and ``call`` signature; ``kernel`` and
+    ``bias`` are built at the first call with ``requires_grad=False`` (``requires_grad_(True)`` makes a call record).
+    ``fixed_radius_search_hash_table``: an ``ops.build_spatial_hash_table`` result of ``inp_positions`` at that radius.
+
+    Two side attributes differ from the reference's (both layers): ``_conv_output`` is the output with the bias already added --
+    the kernel fuses it, where the reference keeps the operator's output before the bias (:666, :876) -- and ``_conv_values``
+    holds the keywords of ``ops.sparse_conv`` / ``ops.sparse_conv_transpose`` (``voxel_size`` in place of ``extents``,
+    ``align_corners``, ``coordinate_mapping`` and ``interpolation``, which are fixed on this path)."""
+
+    def forward(self, inp_features, inp_positions, out_positions, voxel_size, inp_importance=None,
+                fixed_radius_search_hash_table=None):
+        voxel, radius = self._prepare(inp_features, voxel_size)
+        offset = self.offset
+        queries = out_positions - (offset * voxel).to(out_positions.device) if bool(offset.ne(0).any()) else out_positions
+        self.nns = self.fixed_radius_search(inp_positions, queries=queries, radius=radius, hash_table_size_factor=1 / 64,
+                                            hash_table=fixed_radius_search_hash_table)
+        self._avg_neighbors = self.nns.neighbors_index.shape[0] / max(out_positions.shape[0], 1)
+        self._conv_values = {
+            "filters": self.kernel, "out_positions": out_positions, "voxel_size": voxel, "offset": offset,
+            "inp_positions": inp_positions, "inp_features": inp_features, "inp_importance": inp_importance,
+            "neighbors_index": self.nns.neighbors_index, "neighbors_row_splits": self.nns.neighbors_row_splits,
+            "normalize": self.normalize,
+        }
+        return self._finish(ops.sparse_conv(**self._conv_values, bias=self.bias if self.use_bias else None))
+
+    call = forward
+
+
+class SparseConvTranspose(_SparseBase):
+    """Mirror of the reference's ``SparseConvTranspose`` (utils/convolutions.py:678-885): the search runs from the INPUT points
+    over the output points (``nns_inp``), the list is inverted, and every output point sums ``W[cell(out - inp)]^T f`` over the
+    input points that found it; ``normalize`` divides an input's features by the number of outputs it reaches."""
+
+    def forward(self, inp_features, inp_positions, out_positions, voxel_size, out_importance=None,
+                fixed_radius_search_hash_table=None):
+        voxel, radius = self._prepare(inp_features, voxel_size)
+        offset = self.offset
+        queries = inp_positions - (offset * voxel).to(inp_positions.device) if bool(offset.ne(0).any()) else inp_positions
+        self.nns_inp = self.fixed_radius_search(out_positions, queries=queries, radius=radius, hash_table_size_factor=1 / 64,
+                                                hash_table=fixed_radius_search_hash_table)
+        inv = ops.invert_neighbors_list(out_positions.shape[0], self.nns_inp.neighbors_index, self.nns_inp.neighbors_row_splits)
+        total = self.nns_inp.neighbors_index.shape[0]
+        self._avg_neighbors = total / max(out_positions.shape[0], 1)
+        self._conv_values = {
+            "filters": self.kernel, "out_positions": out_positions, "voxel_size": voxel, "offset": offset,
+            "inp_positions": inp_positions, "inp_features": inp_features, "out_importance": out_importance,
+            "inp_neighbors_index": self.nns_inp.neighbors_index, "inp_neighbors_row_splits": self.nns_inp.neighbors_row_splits,
+            "neighbors_index": inv.neighbors_index, "neighbors_row_splits": inv.neighbors_row_splits,
+            "normalize": self.normalize,
+        }
+        return self._finish(ops.sparse_conv_transpose(**self._conv_values, bias=self.bias if self.use_bias else None))
 
     call = forward

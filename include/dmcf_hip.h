@@ -29,6 +29,9 @@
  *     (utils/tools/losses.py:136-181, called from :266-272)
  *   SPH1D.step in gen_data's time loop                           dmcf_sph1d_rollout (ABI 2.17: the column
  *     (datasets/column_gen.py:159-186, 305-312)                    datasets' generator)
+ *   SparseConv / SparseConvTranspose: FixedRadiusSearch('Linf')  DMCF_FRS_METRIC_LINF, dmcf_sparse_conv_forward /
+ *     + continuous_conv / continuous_conv_transpose with         dmcf_sparse_conv_backward (ABI 2.18)
+ *     nearest-neighbour cells (utils/convolutions.py:476-885)
  *
  * Conventions
  *   - plain C: raw DEVICE pointers, sizes, a stream handle (hipStream_t passed as void*); no
@@ -93,6 +96,13 @@ int dmcf_last_hip_error(void); /* hipError_t of the last failed enqueue on this 
  * the library implements is one of the questions tools/capture_golden.py settles.  At most one of them may be set. */
 #define DMCF_FRS_OPEN3D_CORNER_VOXELS 2
 #define DMCF_FRS_OPEN3D_VOXEL_WALK 4
+/* ABI 2.18: the max-norm search of ml3d.layers.FixedRadiusSearch(metric='Linf') (utils/convolutions.py:561-562, 760-761):
+ *   { j : max(|dx|, |dy|, |dz|) <= radius }     float32 differences, inclusive,
+ * on the structure of dmcf_frs_build(points, radius), rows in the same order.  dmcf_frs_count and dmcf_frs_write only, index
+ * lists only: with this flag a distance output, an OPEN3D_* flag, dmcf_frs_search_padded and dmcf_frs_window_sum are
+ * DMCF_EUNSUPPORTED (dmcf_frs_window_sum_backward, which has always refused every flag it does not know, keeps answering
+ * DMCF_EINVAL). */
+#define DMCF_FRS_METRIC_LINF 8
 
 /* bytes of workspace for a search structure over n_points that will serve up to n_queries queries */
 size_t dmcf_frs_workspace_bytes(int64_t n_points, int64_t n_queries);
@@ -894,6 +904,67 @@ typedef struct dmcf_sph1d_params {
 int dmcf_sph1d_rollout(const float* state, const int32_t* n_tot, int64_t n_scenes, int32_t max_points,
                        const dmcf_sph1d_params* params, int32_t n_frames, float* sequence, float* state_out,
                        int32_t* iterations, dmcf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Voxel convolution (ABI 2.18).  Replaces what SparseConv and SparseConvTranspose (utils/convolutions.py:476-885) ask of
+ * ml3d.ops.continuous_conv / continuous_conv_transpose: identity mapping, align_corners = False, nearest-neighbour
+ * interpolation, an offset.  Each pair then touches ONE filter cell with weight 1, and both layers and both feature gradients
+ * are one row-gather operator over a CSR list (rows r, columns idx[p]):
+ *
+ *     out[r,:] = row_scale[r] * sum_{p in row r} col_scale[idx[p]] * W[cell(sign * (col_pos[idx[p]] - row_pos[r]))]^T x[idx[p],:]  (+ bias)
+ *
+ * cell(d), per axis a with k_a cells: t = d_a * (1 / extent) * k_a + k_a / 2 (integer division), minus 0.5 for even k_a -- the
+ * operations of dmcf_cconv_forward's identity mapping without ALIGN_CORNERS -- then + offset[a]; the cell is
+ * clamp((int)roundf(t), 0, k_a - 1).  offset is (x, y, z); filter_dims is (z, y, x, Cin, Cout) as everywhere.
+ *   SparseConv           rows = output points, columns = input points, sign +1, row_scale = 1 / |row| (normalize),
+ *                        col_scale = inp_importance
+ *   SparseConvTranspose  rows = output points over the INVERTED list, columns = input points, DMCF_SPARSE_NEGATE,
+ *                        row_scale = out_importance, col_scale = 1 / |N_T(j)| (normalize)
+ *   feature gradients    the same call on the inverted list with rows and columns swapped, the other sign,
+ *                        DMCF_SPARSE_W_TRANSPOSED toggled and the two scales swapped (dmcf_sparse_conv_backward does that)
+ * Any filter shape and channel count; channels that do not fill a block of the matrix cores are padded inside the kernel.
+ * Deterministic: no atomics anywhere, two identical calls give identical bits.
+ * ---------------------------------------------------------------------------------------------- */
+#define DMCF_SPARSE_NEGATE 1        /* sign = -1: the cell of row_pos - col_pos */
+#define DMCF_SPARSE_W_TRANSPOSED 2  /* x has filter_dims[4] channels, out has filter_dims[3]: W[cell] instead of W[cell]^T */
+#define DMCF_SPARSE_ACCUMULATE 4    /* out += result */
+typedef struct dmcf_sparse_conv_args {
+    uint32_t struct_size;                 /* sizeof(dmcf_sparse_conv_args) of the caller; smaller: DMCF_EINVAL */
+    int32_t flags;                        /* DMCF_SPARSE_* */
+    const float* filters;                 /* [kz][ky][kx][Cin][Cout] */
+    int32_t filter_dims[5];
+    int32_t reserved;                     /* 0 */
+    const float* row_positions;           /* [n_rows, 3] */
+    int64_t n_rows;
+    const float* col_positions;           /* [n_cols, 3] */
+    int64_t n_cols;
+    const float* col_features;            /* x: [n_cols, Cin] ([n_cols, Cout] with DMCF_SPARSE_W_TRANSPOSED) */
+    const float* row_scale;               /* [n_rows] or NULL = 1 */
+    const float* col_scale;               /* [n_cols] or NULL = 1 */
+    const int32_t* neighbors_index;       /* [n_pairs] column of each pair; entries outside [0, n_cols) are skipped */
+    const int64_t* neighbors_row_splits;  /* [n_rows + 1]; rows reaching past n_pairs are treated as empty */
+    int64_t n_pairs;
+    float extent;                         /* voxel_size * kernel_size[-1] */
+    float offset[3];                      /* (x, y, z), in cells */
+    const float* bias;                    /* [channels of out] or NULL */
+    float* out;                           /* [n_rows, Cout] ([n_rows, Cin] with DMCF_SPARSE_W_TRANSPOSED) */
+} dmcf_sparse_conv_args;
+
+int dmcf_sparse_conv_forward(const dmcf_sparse_conv_args* args, dmcf_stream_t stream);
+
+/* Gradients of dmcf_sparse_conv_forward(fwd) for grad_out = dL/d out (bias and DMCF_SPARSE_ACCUMULATE of fwd are ignored):
+ *   grad_filters [shape of filters], or NULL: dW[c] = sum_{p : cell(p) = c} row_scale * col_scale * x_j (x) G_r -- per-slab
+ *       partial sums over contiguous pair ranges, added in slab order;
+ *   grad_col_features [shape of col_features], or NULL: the forward kernel over the inverted list
+ *       (dmcf_invert_neighbors_list(n_cols, ...): inv_index [inv_n_pairs] = the row of each entry, inv_row_splits [n_cols + 1]).
+ * The scales and the bias get no gradient here (they are elementwise: the caller's framework forms them). */
+size_t dmcf_sparse_conv_backward_workspace_bytes(const dmcf_sparse_conv_args* fwd, int want_grad_filters);
+int dmcf_sparse_conv_backward(const dmcf_sparse_conv_args* fwd, const float* grad_out, const int32_t* inv_index,
+                              const int64_t* inv_row_splits, int64_t inv_n_pairs, float* grad_filters, float* grad_col_features,
+                              void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* Diagnostics: the device kernels the forward (backward = 0) or the backward (backward = 1: filter gradient, 2: feature
+ * gradient, 3: both) launches, in launch order, separated by ';' */
+int dmcf_sparse_conv_kernel_names(const dmcf_sparse_conv_args* args, int backward, char* names, size_t name_bytes);
 
 #ifdef __cplusplus
 }
