@@ -169,6 +169,17 @@ class CconvScatterArgs(ctypes.Structure):
     ]
 
 
+class CconvScatterBackwardArgs(ctypes.Structure):
+    """struct dmcf_cconv_scatter_backward_args (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_int32),
+        ("grad_out", ctypes.c_void_p),
+        ("grad_filters", ctypes.c_void_p),
+        ("grad_inp_features", ctypes.c_void_p),
+    ]
+
+
 class SparseConvArgs(ctypes.Structure):
     """struct dmcf_sparse_conv_args (include/dmcf_hip.h)."""
     _fields_ = [
@@ -251,6 +262,7 @@ SYMBOLS = [
     "dmcf_cconv_backward_workspace_bytes", "dmcf_cconv_backward", "dmcf_cconv_backward_kernel_names",
     "dmcf_cconv_backward_extents", "dmcf_cconv_backward_extents_kernel_names",
     "dmcf_cconv_scatter_plan_bytes", "dmcf_cconv_scatter_plan", "dmcf_cconv_scatter_workspace_bytes", "dmcf_cconv_scatter_forward",
+    "dmcf_cconv_scatter_backward_workspace_bytes", "dmcf_cconv_scatter_backward",
     "dmcf_lattice_conv_workspace_bytes", "dmcf_lattice_conv_forward",
     "dmcf_lattice_conv_batch_workspace_bytes", "dmcf_lattice_conv_forward_batch",
     "dmcf_lattice_conv_backward_workspace_bytes", "dmcf_lattice_conv_backward",
@@ -355,6 +367,12 @@ def lib():
     L.dmcf_cconv_scatter_workspace_bytes.argtypes = [c.POINTER(CconvScatterArgs)]
     L.dmcf_cconv_scatter_forward.restype = c.c_int
     L.dmcf_cconv_scatter_forward.argtypes = [c.POINTER(CconvScatterArgs), c.c_void_p, c.c_size_t, c.c_void_p]
+    # the backward of the scatter form (ABI 2.19)
+    L.dmcf_cconv_scatter_backward_workspace_bytes.restype = c.c_size_t
+    L.dmcf_cconv_scatter_backward_workspace_bytes.argtypes = [c.POINTER(CconvScatterArgs), c.POINTER(CconvScatterBackwardArgs)]
+    L.dmcf_cconv_scatter_backward.restype = c.c_int
+    L.dmcf_cconv_scatter_backward.argtypes = [c.POINTER(CconvScatterArgs), c.POINTER(CconvScatterBackwardArgs), c.c_void_p, c.c_size_t,
+                                              c.c_void_p]
     L.dmcf_lattice_conv_workspace_bytes.restype = c.c_size_t
     L.dmcf_lattice_conv_workspace_bytes.argtypes = [c.POINTER(LatticeConvArgs)]
     L.dmcf_lattice_conv_forward.restype = c.c_int

@@ -36,6 +36,9 @@
 // Restrictions (the dispatch in dmcf_amd/utils/convolutions.py checks them, the entry point returns DMCF_EUNSUPPORTED): 4x4x4 filter,
 // Cout 4 or 8, Cin <= 32, linear interpolation, align_corners, volume-preserving map, poly6 or no window (formed from the positions),
 // no per-point importance, no normalisation; output points on a lattice of spacing `voxel` (cell = rint((x - x_0) / voxel)).
+//
+// The backward of this form (dmcf_cconv_scatter_backward) is cconv_sct_bwd.inc, included below: the same order of evaluation run
+// backwards, on the same transposed list, without a plan.
 #include <algorithm>
 
 #include "cconv_common.h"
@@ -594,6 +597,8 @@ static int sct_waves(int cout, int D) {
     return 0;
 }
 
+#include "cconv_sct_bwd.inc"
+
 }  // namespace dmcf
 
 using namespace dmcf;
@@ -716,4 +721,13 @@ extern "C" int dmcf_cconv_scatter_forward(const dmcf_cconv_scatter_args* a, void
     hipLaunchKernelGGL(cconv_sct_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const long long*)workspace,
                        (const uint32_t*)(tail + 2), a->bias, a->out, n, cout, (a->flags & DMCF_FLAG_ACCUMULATE) ? 1 : 0, a->window_fac);
     return check_launch();
+}
+
+extern "C" size_t dmcf_cconv_scatter_backward_workspace_bytes(const dmcf_cconv_scatter_args* fwd, const dmcf_cconv_scatter_backward_args* bwd) {
+    return sct_bwd_workspace_bytes(fwd, bwd);
+}
+
+extern "C" int dmcf_cconv_scatter_backward(const dmcf_cconv_scatter_args* fwd, const dmcf_cconv_scatter_backward_args* bwd, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    return sct_backward(fwd, bwd, workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -116,6 +116,19 @@ class BaseModel(PlainAttributes, torch.nn.Module):
                 n += 1
         return n
 
+    def record_scatter_form(self, on=True):
+        """Sets ``record_scatter_form`` on every ContinuousConv of the model: while autograd records, the layers that gather
+        particles onto a grid_pos lattice with 4 or 8 output channels then take dmcf_cconv_scatter_backward on the transposed list
+        (off: the neighbour-list backward with its list inversion, the default).  Inference is not affected.  Returns the number
+        of layers set."""
+        from ..utils.convolutions import ContinuousConv
+        n = 0
+        for m in self.modules():
+            if isinstance(m, ContinuousConv):
+                m.record_scatter_form = bool(on)
+                n += 1
+        return n
+
     def loss(self, results, data):
         raise NotImplementedError(f"{type(self).__name__} defines no loss")
 

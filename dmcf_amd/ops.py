@@ -1428,6 +1428,32 @@ def _dev_exact_1d(t, name, dtype, device, length=None):
     return t
 
 
+def _scatter_operands(what, filters, out_positions, inp_positions, inp_features, t_index, t_row_begin, t_row_count, window):
+    """The operand checks dmcf_cconv_scatter_forward and dmcf_cconv_scatter_backward share (ValueError / NotImplementedError
+    before anything is launched); returns (filters, out_positions, inp_positions, inp_features) as the library reads them."""
+    filters = _dev_f32(filters, "filters")
+    if filters.dim() != 5:
+        raise ValueError("filters must have shape [D,H,W,Cin,Cout]")
+    out_positions = _dev_f32(out_positions, "out_positions", 3)
+    inp_positions = _dev_f32(inp_positions, "inp_positions", 3)
+    inp_features = _dev_f32(inp_features, "inp_features", int(filters.shape[3]))
+    n_inp = inp_positions.shape[0]
+    if window not in (None, "poly6"):
+        raise NotImplementedError(f"{what}: window must be None or 'poly6'")
+    dev = filters.device
+    _dev_exact_1d(t_index, "t_index", torch.int32, dev)
+    _dev_exact_1d(t_row_begin, "t_row_begin", torch.int64, dev)
+    if t_row_count is not None:
+        _dev_exact_1d(t_row_count, "t_row_count", torch.int32, dev)
+    if inp_features.shape[0] != n_inp:
+        raise ValueError("inp_features and inp_positions disagree on the number of points")
+    if t_row_begin.shape[0] < n_inp + (1 if t_row_count is None else 0):
+        raise ValueError("t_row_begin has fewer entries than the input points have rows")
+    if t_row_count is not None and t_row_count.shape[0] < n_inp:
+        raise ValueError("t_row_count has fewer entries than the input points have rows")
+    return filters, out_positions, inp_positions, inp_features
+
+
 def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_features, t_index, t_row_begin, t_row_count, plan,
                           window=None, window_fac=1.0, bias=None, out=None, accumulate=False, error_flag=None, n_pairs_ref=None):
     """One call of dmcf_cconv_scatter_forward (splat S: filter first, input stationary, 64-bit fixed-point sums): the operator
@@ -1435,37 +1461,39 @@ def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_fea
     output points within extent / 2 of input point j; ``t_row_count`` None for CSR row splits).  ``t_index`` int32,
     ``t_row_begin`` int64, ``t_row_count`` int32, ``bias`` float32 [Cout], ``error_flag`` int32: contiguous and on the filters'
     device (ValueError otherwise, before anything is launched).  An empty point set or an empty ``t_index`` gives the bias
-    (prior content + bias under ``accumulate``) without a launch, as cconv_forward does."""
+    (prior content + bias under ``accumulate``) without a launch, as cconv_forward does.
+
+    When autograd records (``torch.is_grad_enabled()``) and ``filters``, ``inp_features`` or ``bias`` requires grad, the call
+    goes through ``ScatterConvFunction``: the same forward kernel, and a backward through dmcf_cconv_scatter_backward on the same
+    transposed list.  ``bias`` is differentiable there (torch adds it after the kernel: its gradient is the column sum of the
+    output's).  Every operand is checked as in a plain call, before the node is made.  ``out=`` / ``accumulate=True`` raise
+    ValueError there.  Otherwise the call is exactly the inference path."""
+    recording = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (filters, inp_features, bias))
     L = _lib.lib()
-    filters = _dev_f32(filters, "filters")
-    if filters.dim() != 5:
-        raise ValueError("filters must have shape [D,H,W,Cin,Cout]")
-    out_positions = _dev_f32(out_positions, "out_positions", 3)
-    inp_positions = _dev_f32(inp_positions, "inp_positions", 3)
-    cin, cout = int(filters.shape[3]), int(filters.shape[4])
-    inp_features = _dev_f32(inp_features, "inp_features", cin)
-    n_out, n_inp = out_positions.shape[0], inp_positions.shape[0]
+    checked = _scatter_operands("cconv_scatter_forward", filters, out_positions, inp_positions, inp_features, t_index, t_row_begin,
+                                t_row_count, window)
+    cin, cout = int(checked[0].shape[3]), int(checked[0].shape[4])
+    n_out, n_inp = checked[1].shape[0], checked[2].shape[0]
     if plan.n_inp != n_inp:
         raise ValueError("the plan was made for another input point set")
-    if window not in (None, "poly6"):
-        raise NotImplementedError("cconv_scatter_forward: window must be None or 'poly6'")
-    dev = filters.device
-    _dev_exact_1d(t_index, "t_index", torch.int32, dev)
-    _dev_exact_1d(t_row_begin, "t_row_begin", torch.int64, dev)
-    if t_row_count is not None:
-        _dev_exact_1d(t_row_count, "t_row_count", torch.int32, dev)
+    dev = checked[0].device
     if bias is not None:
         _dev_exact_1d(bias, "bias", torch.float32, dev, cout)
     if error_flag is not None:
         _dev_exact_1d(error_flag, "error_flag", torch.int32, dev)
         if error_flag.shape[0] < 1:
             raise ValueError("error_flag must have at least one element")
-    if inp_features.shape[0] != n_inp:
-        raise ValueError("inp_features and inp_positions disagree on the number of points")
-    if t_row_begin.shape[0] < n_inp + (1 if t_row_count is None else 0):
-        raise ValueError("t_row_begin has fewer entries than the input points have rows")
-    if t_row_count is not None and t_row_count.shape[0] < n_inp:
-        raise ValueError("t_row_count has fewer entries than the input points have rows")
+    if recording:
+        if out is not None or accumulate:
+            raise ValueError("out= / accumulate=True cannot be recorded by autograd: use the returned tensor")
+        # (the node takes the caller's own tensors, so that the graph reaches them; the call inside it checks them again)
+        geo = dict(extent=float(extent), window=window, window_fac=window_fac)
+
+        def run(w, f, **lists):
+            return cconv_scatter_forward(w, inp_features=f, plan=plan, error_flag=error_flag, n_pairs_ref=n_pairs_ref, **lists, **geo)
+        res = ScatterConvFunction.apply(filters, inp_features, out_positions, inp_positions, t_index, t_row_begin, t_row_count, geo, run)
+        return res if bias is None else res + bias
+    filters, out_positions, inp_positions, inp_features = checked
     if out is None:
         if accumulate:
             raise ValueError("accumulate=True needs an out tensor")
@@ -1509,6 +1537,93 @@ def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_fea
         timer.end("cconv", dict(pairs=pairs, n_out=n_out, cin=cin, cout=cout, K=64, symmetric=False,
                                 kernel=scatter_kernel_name(cout, plan.block_cells, plan.reach), pair_values=False, accumulate=bool(accumulate)), t0)
     return out
+
+
+def _scatter_args(filters, out_positions, extent, inp_positions, inp_features, t_index, t_row_begin, t_row_count, window, window_fac):
+    a = _lib.CconvScatterArgs()
+    a.filters = _ptr(filters)
+    for k in range(5):
+        a.filter_dims[k] = int(filters.shape[k])
+    a.out_positions, a.n_out = _ptr(out_positions), out_positions.shape[0]
+    a.inp_positions, a.n_inp = _ptr(inp_positions), inp_positions.shape[0]
+    a.inp_features = _ptr(inp_features)
+    a.t_index, a.t_row_begin = _ptr(t_index), _ptr(t_row_begin)
+    a.t_row_count = _ptr(t_row_count) if t_row_count is not None else None
+    a.t_capacity = int(t_index.shape[0])
+    a.extent, a.window_fac, a.window = float(extent), float(window_fac), WINDOWS[window]
+    a.flags = FLAG_ALIGN_CORNERS
+    return a
+
+
+def cconv_scatter_backward(filters, out_positions, extent, inp_positions, inp_features, t_index, t_row_begin, t_row_count, grad_out,
+                           window=None, window_fac=1.0, need_filters=True, need_features=True):
+    """dmcf_cconv_scatter_backward: ``(grad_filters | None, grad_inp_features | None)`` of the convolution
+    :func:`cconv_scatter_forward` computes with these arguments (bias excluded), for ``grad_out`` = dL/d out [n_out, Cout].  One
+    walk over the TRANSPOSED list (row j = the output points within extent / 2 of input point j; ``t_row_count`` None for CSR
+    row splits) gives both: no plan, no list inversion, no float atomics (two calls return the same bits).  Operands as
+    cconv_scatter_forward takes them, checked as strictly.  Rows of ``grad_inp_features`` of input points without pairs are
+    zero.  Empty point sets or an empty ``t_index`` give zero gradients without a launch."""
+    L = _lib.lib()
+    filters, out_positions, inp_positions, inp_features = _scatter_operands(
+        "cconv_scatter_backward", filters, out_positions, inp_positions, inp_features, t_index, t_row_begin, t_row_count, window)
+    cin, cout = int(filters.shape[3]), int(filters.shape[4])
+    n_out, n_inp = out_positions.shape[0], inp_positions.shape[0]
+    dev = filters.device
+    grad_out = _dev_f32(grad_out, "grad_out", cout)
+    if grad_out.shape[0] != n_out or grad_out.device != dev:
+        raise ValueError("grad_out must be [n_out, Cout] on the filters' device")
+    if not need_filters and not need_features:
+        return None, None
+    if n_out == 0 or n_inp == 0 or t_index.shape[0] == 0:
+        # every row is empty: no pair, no gradient; nothing to launch (the C ABI rejects empty sets)
+        return (torch.zeros_like(filters) if need_filters else None,
+                torch.zeros((n_inp, cin), dtype=torch.float32, device=dev) if need_features else None)
+    gw = torch.empty(tuple(filters.shape), dtype=torch.float32, device=dev) if need_filters else None
+    gf = torch.empty((n_inp, cin), dtype=torch.float32, device=dev) if need_features else None
+    a = _scatter_args(filters, out_positions, extent, inp_positions, inp_features, t_index, t_row_begin, t_row_count, window, window_fac)
+    b = _lib.CconvScatterBackwardArgs()
+    b.struct_size = ctypes.sizeof(_lib.CconvScatterBackwardArgs)
+    b.flags = 0
+    b.grad_out = _ptr(grad_out)
+    b.grad_filters = _ptr(gw) if need_filters else None
+    b.grad_inp_features = _ptr(gf) if need_features else None
+    nbytes = int(L.dmcf_cconv_scatter_backward_workspace_bytes(ctypes.byref(a), ctypes.byref(b)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_cconv_scatter_backward(ctypes.byref(a), ctypes.byref(b), _ptr(ws), nbytes, _stream()), "dmcf_cconv_scatter_backward")
+    if timer is not None:
+        timer.end("cconv_backward", dict(n_out=n_out, n_inp=n_inp, cin=cin, cout=cout, filters=bool(need_filters),
+                                         features=bool(need_features), kernel="cconv_sct_bwd"), t0)
+    return gw, gf
+
+
+class ScatterConvFunction(torch.autograd.Function):
+    """Autograd node of the input-stationary CConv: ``run(filters, inp_features, out_positions=, inp_positions=, t_index=,
+    t_row_begin=, t_row_count=)`` is the forward (cconv_scatter_forward, or any kernel that computes the same operator on the same
+    pairs; bias excluded: torch adds it), the backward is one dmcf_cconv_scatter_backward over the same transposed list with the
+    options in ``geo`` (extent, window, window_fac).  The node saves the filters, the features, both position tensors and the list
+    themselves -- the per-step cache forgets them when the step ends --, so a tensor changed in place between forward and
+    backward is an error, not another gradient.  Positions get no gradient; the backward is not differentiable again."""
+
+    @staticmethod
+    def forward(ctx, filters, inp_features, out_positions, inp_positions, t_index, t_row_begin, t_row_count, geo, run):
+        ctx.geo = geo
+        ctx.save_for_backward(filters, inp_features, out_positions, inp_positions, t_index, t_row_begin, t_row_count)
+        # (grad mode is off in here, so this is the plain call)
+        return run(filters, inp_features, out_positions=out_positions, inp_positions=inp_positions, t_index=t_index,
+                   t_row_begin=t_row_begin, t_row_count=t_row_count)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        filters, inp_features, out_positions, inp_positions, t_index, t_row_begin, t_row_count = ctx.saved_tensors
+        need_w, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gw = gf = None
+        if need_w or need_f:
+            gw, gf = cconv_scatter_backward(filters, out_positions, ctx.geo["extent"], inp_positions, inp_features, t_index,
+                                            t_row_begin, t_row_count, grad_out.contiguous(), window=ctx.geo["window"],
+                                            window_fac=ctx.geo["window_fac"], need_filters=need_w, need_features=need_f)
+        return gw, gf, None, None, None, None, None, None, None
 
 
 def continuous_conv(filters, out_positions, extents, offset, inp_positions, inp_features, inp_importance,

@@ -526,6 +526,10 @@ class Simulator:
             # form and its own backward (ContinuousConv(record_lattice_form=True))
             if hasattr(model, "record_lattice_form"):
                 model.record_lattice_form(bool(cfg.get("train_lattice_form", False)))
+            # pipeline key train_scatter_form (default false): recording particles -> lattice layers with 4 or 8 output channels
+            # take the input-stationary backward on the transposed list (ContinuousConv(record_scatter_form=True))
+            if hasattr(model, "record_scatter_form"):
+                model.record_scatter_form(bool(cfg.get("train_scatter_form", False)))
             schedule = TrainSchedule(cfg)
             loader = self.train_loader(schedule)
             first = next(loader)

@@ -467,13 +467,16 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                  window_function=None, use_dense_layer_for_center=False,
                  dense_kernel_initializer="glorot_uniform", dense_kernel_regularizer=None, in_channels=None,
                  symmetric=False, sym_axis=2, circular=False, name=None, trainable=True, device=None,
-                 record_per_point_extents=False, record_lattice_form=False, **kwargs):
+                 record_per_point_extents=False, record_lattice_form=False, record_scatter_form=False, **kwargs):
         super().__init__()
         self.layer_name = name
         # may a call with extents of rank 1 record autograd history (_forward_train; not a keyword of the reference)
         self.record_per_point_extents = bool(record_per_point_extents)
         # may a recording call between two grid_pos lattices keep the stencil form (_forward_train; dmcf_lattice_conv_backward)
         self.record_lattice_form = bool(record_lattice_form)
+        # may a recording call from particles onto a grid_pos lattice with 4 or 8 output channels take the input-stationary
+        # backward on the transposed list (_forward_train; dmcf_cconv_scatter_backward)
+        self.record_scatter_form = bool(record_scatter_form)
         self.filters = filters
         self.kernel_size = [int(k) for k in kernel_size]
         if activation not in _ACTIVATIONS and not callable(activation):
@@ -599,8 +602,13 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         dmcf_cconv_backward_extents).  A layer built with record_lattice_form=True keeps the stencil form between two grid_pos
         lattices (ops.lattice_conv's autograd node, dmcf_lattice_conv_backward: no search, no inversion) when the pair is whole --
         no stray rows -- and its spacings are in the ratio 1, 2 or 1/2; opt-in, because that form uses the nominal offsets
-        d * voxel (dmcf_amd/lattice.py) where the neighbour-list form subtracts rounded positions.  The scatter
-        form, the stray-row path, the step's list cache and the epilogue fusions
+        d * voxel (dmcf_amd/lattice.py) where the neighbour-list form subtracts rounded positions.  A layer built with
+        record_scatter_form=True that gathers particles onto a grid_pos lattice with 4 or 8 output channels (_scatter_train_form;
+        scalar extent, no user-supplied list) takes ops.ScatterConvFunction: its backward is one dmcf_cconv_scatter_backward over
+        the transposed list, which a search with the roles swapped returns -- no inversion; its forward is the scatter form where
+        inference would take it (_scatter_form), otherwise the neighbour-list form on the layer's own forward list.  A layer with
+        either flag that is not eligible takes the neighbour-list route and gives the bits it gives with the flag off.  The
+        stray-row path, the step's list cache and the epilogue fusions
         (accumulate_into / extra_bias, fused bias) are not taken: their kernels have no backward.  Bias, the dense centre term,
         the activation and the circular expansion are torch ops.  A pending accumulate_into / extra_bias request is honoured out
         of place: the result is ``accumulate_into + layer(x) + extra_bias`` (accumulate_into itself is not written)."""
@@ -641,6 +649,10 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                                     align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
                                     interpolation=self.interpolation)
             return self._train_epilogue(out_features, inp_features, acc, extra_bias)
+        if (self.record_scatter_form and not rank1 and user_neighbors_index is None and user_neighbors_row_splits is None
+                and self._scatter_train_form(inp_features, inp_positions, out_positions, inp_importance, hash_table)):
+            out_features = self._scatter_train(inp_features, inp_positions, out_positions, extent)
+            return self._train_epilogue(out_features, inp_features, acc, extra_bias)
         if rank1:
             pass
         elif user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
@@ -680,6 +692,43 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             packed_cache=self._packed if (kernel is self.kernel and os.environ.get("DMCF_CACHE_PACKED_FILTERS", "1") != "0")
             else None, **({"record_per_point_extents": True} if rank1 else {}))
         return self._train_epilogue(out_features, inp_features, acc, extra_bias)
+
+    def _scatter_train(self, inp_features, inp_positions, out_positions, extent):
+        """The convolution (no bias) of a recording call on the record_scatter_form route: ops.ScatterConvFunction over the
+        transposed list of an exact search with the roles swapped (the neighbour set is symmetric, so the list holds the forward's
+        pairs).  The forward inside the node is what inference computes for these operands."""
+        d = self.__dict__
+        radius = float(np.float32(0.5) * np.float32(extent))  # :353
+        window, window_fac = self.window_function.name, self.window_function.fac
+        with torch.no_grad():
+            # (a search of its own, outside the step's list cache: the backward needs the list after the step)
+            tl = ops.fixed_radius_search(out_positions, inp_positions, radius, return_distances=False)
+            t_idx, t_rb, _ = tl.raw()
+            t_cnt = getattr(tl, "row_count", None)
+            sct = self._scatter_form(inp_features, inp_positions, out_positions, None, None, radius)
+        d["nns"] = None
+        d["_n_out_last"] = out_positions.shape[0]
+        d["_pairs_last"] = t_idx.shape[0]
+        d["_conv_values"] = None
+        geo = dict(extent=extent, window=window, window_fac=window_fac)
+        if sct is not None:
+            voxel, m = sct
+
+            def run(w, f, **lists):
+                flag = torch.zeros(1, dtype=torch.int32, device=inp_positions.device)
+                out = ops.cconv_scatter_forward(w, inp_features=f, plan=_CACHE.scatter_plan(inp_positions, out_positions, voxel, radius, m),
+                                                error_flag=flag, **lists, **geo)
+                _CACHE.report(flag, _scatter_guard)
+                return out
+        else:
+            def run(w, f, **lists):
+                nns = self.fixed_radius_search(inp_positions, out_positions, radius)
+                idx, rs, raw_dist = nns.raw()
+                return ops.cconv_forward(w, out_positions, extent, inp_positions, f, idx, rs, neighbors_value=raw_dist, window=window,
+                                         window_fac=window_fac, align_corners=True, coordinate_mapping=self.coordinate_mapping,
+                                         interpolation=self.interpolation, neighbors_row_count=getattr(nns, "row_count", None),
+                                         row_length_hint=self.row_length_hint)
+        return ops.ScatterConvFunction.apply(self.kernel, inp_features, out_positions, inp_positions, t_idx, t_rb, t_cnt, geo, run)
 
     def _train_epilogue(self, out_features, inp_features, acc, extra_bias):
         """What follows the convolution of a recording call, as torch ops: bias, dense centre term, activation, the sums."""
@@ -987,6 +1036,22 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         if m < 1 or out_positions.shape[0] * 4 > inp_positions.shape[0]:
             return None  # (a fine lattice: few pairs per flushed slot, the gather form is faster -- DESIGN.md section 4.2, splat S)
         return info.voxel[0], m
+
+    def _scatter_train_form(self, inp_features, inp_positions, out_positions, inp_importance, hash_table):
+        """Does dmcf_cconv_scatter_backward apply to this recording call: _scatter_form's conditions with 4 or 8 output channels
+        and without those that only decide which FORWARD is faster (the input count, the lattice's fineness, the box fit, the
+        channel list, DMCF_SCATTER_CONV)."""
+        from .. import lattice
+        if (not lattice.enabled() or hash_table is not None
+                or inp_importance is not None or self.symmetric or self.circular or self.normalize
+                or not isinstance(self.window_function, WindowFunction) or self.window_function.name != "poly6"
+                or self.radius_search_ignore_query_points or self.radius_search_metric != "L2" or not inp_features.is_cuda
+                or self.kernel_size != [4, 4, 4] or self.in_channels > 32 or self.filters not in (4, 8)
+                or not self.align_corners or self.coordinate_mapping != "ball_to_cube_volume_preserving"
+                or self.interpolation != "linear"):
+            return False
+        info = lattice.lookup(out_positions)
+        return info is not None and info.voxel[0] == info.voxel[1] == info.voxel[2] and max(info.dims) <= SCATTER_MAX_LATTICE_CELLS
 
     def _lattice_form(self, inp_features, inp_positions, out_positions, inp_importance, hash_table, extent):
         """The LatticePair for this call if dmcf_lattice_conv_forward applies: both position tensors registered grid_pos

@@ -19,6 +19,8 @@
  *                                                                 dmcf_cconv_backward_extents)
  *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
  *     (models/hrnet.py:85-92)                                     dmcf_lattice_conv_backward)
+ *   continuous_conv from particles onto a grid_pos lattice,      dmcf_cconv_scatter_forward (gradients, ABI 2.19:
+ *     4 or 8 output channels (models/hrnet.py:83-93)              dmcf_cconv_scatter_backward)
  *   o3dml.ops.reduce_subarrays_sum (models/pbf_model.py:450-453) dmcf_reduce_subarrays_sum
  *   tf.keras.layers.Dense (models/hrnet.py:49,93-99;             dmcf_dense_forward
  *     models/pbf_model.py:134-152)
@@ -453,6 +455,42 @@ typedef struct dmcf_cconv_scatter_args {
 size_t dmcf_cconv_scatter_workspace_bytes(const dmcf_cconv_scatter_args* args);
 int dmcf_cconv_scatter_forward(const dmcf_cconv_scatter_args* args, void* workspace, size_t workspace_bytes,
                                dmcf_stream_t stream);
+
+/* Backward pass of the scatter form (ABI 2.19; dmcf_amd/csrc/cconv_sct_bwd.inc): the gradients of the function
+ * dmcf_cconv_scatter_forward computes, with respect to the filters and the input features, in the forward's order of evaluation
+ * run backwards.  Per input point j one walk over row j of the TRANSPOSED list forms T_j[cell][o] = sum_pairs a_p w_k(p)
+ * grad_out[i][o] (64 x cout values, in LDS), then grad_inp_features[j] = W . T_j and grad_filters += f_j (x) T_j on the matrix
+ * cores: no list inversion, nothing of size pairs x channels in memory.  Positions get no gradient.
+ *
+ * `fwd` carries the forward's arguments.  plan, block_cells, reach, out, bias, error_flag and DMCF_FLAG_ACCUMULATE are ignored
+ * (plan and out may be NULL: the backward needs no plan).  Restrictions as the forward's (DMCF_EUNSUPPORTED otherwise): 4x4x4
+ * filters, cout 4 or 8, cin <= 32, DMCF_WINDOW_NONE / POLY6 evaluated from the positions, volume-preserving map, linear
+ * interpolation, DMCF_FLAG_ALIGN_CORNERS required.  Row conventions as the forward's: CSR, or t_row_begin + t_row_count; a row
+ * that reaches past t_capacity is empty.  Each pair's geometry is formed by the device functions the forward kernel calls.
+ *
+ * Sums into T_j are 64-bit fixed point, as the forward's: a term enters as round(term * 2^s), 2^s * max |grad_out| * max(1,
+ * |window_fac|) <= 2^46, the maximum formed on the device inside the call.  The filter gradient is reduced from per-workgroup
+ * partial sums in workgroup order, rows are assigned to workgroups statically, and the number of workgroups depends on n_inp
+ * only: no float atomics, two identical calls return identical bits.
+ *
+ * grad_out must be aligned to 16 bytes (its rows of 4 or 8 floats are read with 16-byte loads).
+ *
+ * Every argument error is returned before anything is enqueued: DMCF_EINVAL for a NULL operand, grad_out == NULL or not aligned
+ * to 16 bytes, both outputs NULL, n_out / n_inp <= 0, extent <= 0, struct_size smaller than the struct, flags != 0;
+ * DMCF_EWORKSPACE for a workspace
+ * smaller than dmcf_cconv_scatter_backward_workspace_bytes; DMCF_EINVAL for a missing workspace or one not aligned to 256
+ * bytes.  Nothing is allocated. */
+typedef struct dmcf_cconv_scatter_backward_args {
+    uint32_t struct_size;        /* sizeof of the caller's struct; smaller: DMCF_EINVAL */
+    int32_t flags;               /* must be 0 */
+    const float* grad_out;       /* [n_out][cout], aligned to 16 bytes */
+    float* grad_filters;         /* [4][4][4][cin][cout] or NULL; written in full */
+    float* grad_inp_features;    /* [n_inp][cin] or NULL; written in full, zero rows for inputs without pairs */
+} dmcf_cconv_scatter_backward_args;
+
+size_t dmcf_cconv_scatter_backward_workspace_bytes(const dmcf_cconv_scatter_args* fwd, const dmcf_cconv_scatter_backward_args* bwd);
+int dmcf_cconv_scatter_backward(const dmcf_cconv_scatter_args* fwd, const dmcf_cconv_scatter_backward_args* bwd,
+                                void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ml3d.ops.continuous_conv (utils/convolutions.py:414-431) between two point sets on ALIGNED REGULAR LATTICES -- the
