@@ -282,6 +282,8 @@ SYMBOLS = [
     "dmcf_sph1d_rollout",
     "dmcf_sparse_conv_forward", "dmcf_sparse_conv_backward_workspace_bytes", "dmcf_sparse_conv_backward",
     "dmcf_sparse_conv_kernel_names",
+    "dmcf_frs_workspace_bytes_batched", "dmcf_frs_build_batched", "dmcf_frs_count_batched", "dmcf_frs_write_batched",
+    "dmcf_radius_search_count_batched", "dmcf_radius_search_write_batched",
 ]
 
 
@@ -500,6 +502,24 @@ def lib():
                                             c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
     L.dmcf_sparse_conv_kernel_names.restype = c.c_int
     L.dmcf_sparse_conv_kernel_names.argtypes = [c.POINTER(SparseConvArgs), c.c_int, c.c_char_p, c.c_size_t]
+    # both searches with points_row_splits / queries_row_splits (ABI 2.20)
+    L.dmcf_frs_workspace_bytes_batched.restype = c.c_size_t
+    L.dmcf_frs_workspace_bytes_batched.argtypes = [c.c_int64, c.c_int64, c.c_int64]
+    L.dmcf_frs_build_batched.restype = c.c_int
+    L.dmcf_frs_build_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_float, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_frs_count_batched.restype = c.c_int
+    L.dmcf_frs_count_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_void_p,
+                                         c.c_size_t, c.c_void_p, c.c_void_p]
+    L.dmcf_frs_write_batched.restype = c.c_int
+    L.dmcf_frs_write_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_void_p,
+                                         c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
+    L.dmcf_radius_search_count_batched.restype = c.c_int
+    L.dmcf_radius_search_count_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float,
+                                                   c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+    L.dmcf_radius_search_write_batched.restype = c.c_int
+    L.dmcf_radius_search_write_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float,
+                                                   c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
+                                                   c.c_void_p]
     _lib = L
     return L
 

@@ -13,7 +13,9 @@
 //   * one 64-lane wavefront per query: lanes stride the flattened candidate list, hits are compacted
 //     with a ballot + mbcnt prefix (no atomics, no LDS), rows come out in a deterministic order;
 //   * everything that sizes the grid (bounding box, cell edge, dims) is computed on the device into a
-//     header inside the workspace, so the build needs no host round trip.
+//     header inside the workspace, so the build needs no host round trip;
+//   * a batch of point sets (Open3D's points_row_splits / queries_row_splits, ABI 2.20) shares one grid geometry, with the
+//     batch item as the outermost digit of the cell index: see frs_query_batched.
 #include "cconv_common.h"  // window_value
 
 namespace dmcf {
@@ -51,11 +53,14 @@ static int64_t frs_table_size(int64_t n) {
     return t;
 }
 
-static FrsLayout frs_layout(int64_t n, int64_t m) {
+// batch > 1: the structure of a batched build (dmcf_frs_build_batched) -- the cell table holds `batch` slabs of the one grid,
+// so it has at least one entry per item
+static FrsLayout frs_layout(int64_t n, int64_t m, int64_t batch = 1) {
     FrsLayout L;
     L.n = n;
     L.m = m;
     L.table = frs_table_size(n);
+    if (L.table < batch) L.table = batch;
     size_t off = 0;
     L.off_header = off;        off += align_up(sizeof(FrsHeader), 256);
     L.off_cell_start = off;    off += align_up((size_t)(L.table + 1) * 4, 256);
@@ -146,7 +151,10 @@ __global__ __launch_bounds__(256) void frs_bbox(const float* __restrict__ pts, i
 
 // one thread: choose the cell edge (>= 1.001 R so that [q-R, q+R] spans at most 3 cells) and coarsen
 // it until the dense grid fits the cell table.  Coarser cells only add candidates, never lose any.
-__device__ void frs_finish_header_one(FrsHeader* h, int64_t table) {
+// batch > 1 (dmcf_frs_build_batched): the table holds `batch` copies of the grid, one slab per item, so the grid gets
+// table / batch cells and is filled by n_points / batch points.
+__device__ void frs_finish_header_one(FrsHeader* h, int64_t table, int64_t batch = 1) {
+    const double slab_table = (double)(table / batch), fill = (double)batch;
     float lo[3], ext[3];
     for (int a = 0; a < 3; ++a) {
         lo[a] = ord2f(h->bb_min[a]);
@@ -183,7 +191,7 @@ __device__ void frs_finish_header_one(FrsHeader* h, int64_t table) {
         const float c = h->radius * 1.001f / (float)div;
         double prod = 1.0;
         for (int a = 0; a < 3; ++a) prod *= floor((double)ext[a] / (double)c) + 1.0;
-        if (prod <= (double)table && (double)h->n_points >= 0.5 * prod) {
+        if (prod <= slab_table && (double)h->n_points >= 0.5 * prod * fill) {
             cell = c;
             break;
         }
@@ -195,8 +203,8 @@ __device__ void frs_finish_header_one(FrsHeader* h, int64_t table) {
             d[a] = cnt > 2.0e9 ? 2000000000 : (int32_t)cnt;
             prod *= cnt;
         }
-        if (prod <= (double)table) break;
-        const float grow = (float)cbrt(prod / (double)table) * 1.02f;
+        if (prod <= slab_table) break;
+        const float grow = (float)cbrt(prod / slab_table) * 1.02f;
         cell *= grow > 1.05f ? grow : 1.05f;
     }
     for (int a = 0; a < 3; ++a) {
@@ -520,6 +528,7 @@ struct FrsGradAcc {
 // out_base; MODE 2: add window(d^2 / R^2) of every hit to `wsum` (per lane; the caller reduces over the wave); MODE 3: add the
 // hit's term of the window sum's gradient to `ga` (per lane, see frs_window_sum_grad).
 // Returns the number of hits.  Hits come out in a fixed order (cell rows, then position in the cell-sorted array).
+// slab_base: see frs_query_batched.
 // EXACT (open3d visibility flags only): every hit that could lie outside the reference's 8 bins takes the exact
 // visibility test -- the form of the FIXUP kernel (frs_fix), which re-scans the few queries the hot kernels flag.  !EXACT is the
 // hot form: it only NOTICES such a hit (d^2 above r2_inner: one compare per window) and reports it through `redo`.  The test
@@ -530,7 +539,8 @@ __device__ __forceinline__ int32_t frs_scan(float qx, float qy, float qz, const 
                                             const uint32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
                                             float radius, int flags, int64_t out_base, int32_t* __restrict__ nbr_index,
                                             float* __restrict__ nbr_dist, int window, float inv_r2, float& wsum,
-                                            uint32_t* marks, int32_t row_cap, bool& redo, FrsGradAcc* ga = nullptr) {
+                                            uint32_t* marks, int32_t row_cap, bool& redo, FrsGradAcc* ga = nullptr,
+                                            int32_t slab_base = 0) {
     const int lane = lane_id();
     int mark_tag = 0;
     for (int w = 0; w < kWin; ++w) marks[w * kWave + lane] = 0;  // LDS is not cleared between workgroups: stale tags of an earlier wave must not match ours
@@ -563,7 +573,9 @@ __device__ __forceinline__ int32_t frs_scan(float qx, float qy, float qz, const 
             int32_t start = 0, len = 0;
             if (r < ny * nz) {
                 const int cy = lo[1] + r % ny, cz = lo[2] + r / ny;
-                const int32_t base = (cz * h->dims[1] + cy) * h->dims[0];
+                // (slab_base: the first cell of the query's batch item in a batched structure, 0 otherwise; every clamp above and
+                // below acts on the coordinates INSIDE the slab, so a walk never leaves its item)
+                const int32_t base = slab_base + (cz * h->dims[1] + cy) * h->dims[0];
                 // Trim the row to the chord of the search sphere: the box of cells around the query holds 15.6 R^3 of
                 // candidates for a 4.2 R^3 sphere.  gap = distance (in cells) from the query to the row's slab of cells along
                 // y / z -- the outermost cells also hold everything binned from beyond the grid, so they have no outer face --
@@ -964,7 +976,96 @@ __global__ __launch_bounds__(256) void frs_query_linf(const float* __restrict__ 
     if (!WRITE && lane == 0) counts[qi] = cnt;
 }
 
+// ---- batched search (ABI 2.20): Open3D's points_row_splits / queries_row_splits ------------------------------------------------
+// One structure for a whole batch of point sets that were concatenated into one array: ONE grid geometry (box, cell edge, dims:
+// the header, sized from all points together), and the batch item as the outermost digit of the cell index,
+//   cell = ((b * dims[2] + cz) * dims[1] + cy) * dims[0] + cx,
+// so the table holds `batch` slabs of ncells cells and the cell-sorted array holds the items one after the other.  A point is
+// clamped into the grid of ITS slab (the border cells hold what was binned from beyond the box, per item), a query walks the
+// cells of ITS slab only: the scan is frs_scan with the slab's first cell added to every row of cells, nothing else.  Points of
+// different items never meet, wherever they lie -- the items may overlap or coincide.  The header's ncells stays the cells of
+// ONE slab.
+
+// The batch item of element i: the b with splits[b] <= i < splits[b + 1] (empty items are stepped over).  The result always
+// lies in [0, batch): row splits that are not what the caller promised give wrong neighbours, never an index beyond the table.
+__device__ __forceinline__ int32_t frs_item_of(const int64_t* __restrict__ splits, int32_t batch, int64_t i) {
+    int32_t lo = 0, hi = batch - 1;
+    while (lo < hi) {  // the first b with splits[b + 1] > i
+        const int32_t mid = (lo + hi) >> 1;
+        if (splits[mid + 1] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// (if the coarsening of frs_finish_header_one did not get the grid into its share of the table -- its 64 rounds always have so
+// far -- one cell per item still serves every query)
+__global__ void frs_finish_header_batched(FrsHeader* h, int64_t table, int64_t batch) {
+    if (threadIdx.x == 0) {
+        frs_finish_header_one(h, table, batch);
+        if ((double)h->dims[0] * (double)h->dims[1] * (double)h->dims[2] * (double)batch > (double)table || h->ncells < 1) {
+            h->dims[0] = h->dims[1] = h->dims[2] = 1;
+            h->ncells = 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void frs_count_cells_batched(const float* __restrict__ pts, int64_t n,
+                                                               const int64_t* __restrict__ points_row_splits, int32_t batch,
+                                                               const FrsHeader* __restrict__ h, int32_t* __restrict__ point_cell,
+                                                               uint32_t* __restrict__ cell_count, uint32_t* __restrict__ slot_of) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        c[a] = cell_coord(pts[3 * i + a], h->origin[a], h->inv_cell[a], h->dims[a]);
+        c[a] = min(max(c[a], 0), h->dims[a] - 1);  // (into the grid of the point's OWN slab: a stray never lands in a neighbouring item)
+    }
+    const int32_t b = frs_item_of(points_row_splits, batch, i);
+    const int32_t cell = b * h->ncells + (c[2] * h->dims[1] + c[1]) * h->dims[0] + c[0];
+    point_cell[i] = cell;
+    slot_of[i] = atomicAdd(&cell_count[cell], 1u);
+}
+
+// frs_query / frs_query_radii (RADII: a radius per query, `radius` is the build's max_radius) on a batched structure.  The
+// query's item -- and with it the slab -- is the same for the whole wave (one query per wave): found by a search over
+// queries_row_splits on the wave-uniform query index, so that the walk stays scalar.  DMCF_FRS_IGNORE_QUERY_POINT is the only flag.
+template <bool WRITE, bool RADII>
+__global__ __launch_bounds__(256) void frs_query_batched(const float* __restrict__ queries, int64_t m,
+                                                         const int64_t* __restrict__ queries_row_splits, int32_t batch,
+                                                         const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
+                                                         const float4* __restrict__ sorted, float radius,
+                                                         const float* __restrict__ radii, int flags, int32_t* __restrict__ counts,
+                                                         const int64_t* __restrict__ row_splits, int32_t* __restrict__ nbr_index,
+                                                         float* __restrict__ nbr_dist, int64_t capacity) {
+    __shared__ uint32_t marks[4][kWin * kWave + kWave];
+    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (qi >= m) return;  // whole wave leaves
+    if (WRITE && row_splits[qi + 1] > capacity) return;  // (as frs_query: the caller sees the overflow in row_splits[m])
+    float r = radius;
+    bool live = true;
+    if (RADII) {
+        r = radii[qi];
+        live = r >= 0.0f && r <= radius;  // (as frs_query_radii; wave uniform)
+    }
+    int32_t cnt = 0;
+    if (live) {
+        const int64_t qu = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(qi >> 32)) << 32) |
+                           (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)qi);
+        const int32_t item = __builtin_amdgcn_readfirstlane(frs_item_of(queries_row_splits, batch, qu));
+        const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
+        float unused = 0.0f;
+        bool redo = false;
+        cnt = frs_scan<WRITE ? 1 : 0, false>(qx, qy, qz, h, cell_start, sorted, r, flags & DMCF_FRS_IGNORE_QUERY_POINT,
+                                             WRITE ? row_splits[qi] : 0, nbr_index, nbr_dist, 0, 0.0f, unused, marks[threadIdx.x >> 6],
+                                             0x7fffffff, redo, nullptr, item * h->ncells);
+    }
+    if (!WRITE && lane_id() == 0) counts[qi] = cnt;
+}
+
 }  // namespace dmcf
+
 
 using namespace dmcf;
 
@@ -975,6 +1076,38 @@ static bool frs_flags_ok(int flags) {  // known bits, and at most one reading of
 static bool frs_linf(int flags) { return (flags & DMCF_FRS_METRIC_LINF) != 0; }
 
 static constexpr unsigned kFixGrid = 1024;  // 4096 waves walk the query flags (frs_fix)
+
+// ---- batched entry points (ABI 2.20) ---------------------------------------------------------------------------------------------
+static constexpr int64_t kFrsMaxBatch = (int64_t)1 << 26;  // the largest cell table: one cell per item at least
+
+static bool frs_batch_ok(int64_t batch) { return batch >= 1 && batch <= kFrsMaxBatch; }
+
+// what the four batched searches share: validation, then one launch of frs_query_batched
+template <bool WRITE, bool RADII>
+static int frs_search_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                              const float* radii, float radius, int flags, const void* workspace, size_t workspace_bytes,
+                              const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance, int64_t pair_capacity,
+                              hipStream_t stream) {
+    if (!RADII && (flags & kO3dFlags)) return DMCF_EINVAL;               // the walk emulations know nothing of items
+    if (!RADII && (flags & DMCF_FRS_METRIC_LINF)) return DMCF_EUNSUPPORTED;
+    if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
+    if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || !row_splits || (m > 0 && (!queries || (RADII && !radii)))) return DMCF_EINVAL;
+    if (!queries_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
+    if (WRITE && m == 0) return DMCF_OK;
+    if (WRITE && (!neighbors_index || pair_capacity < 0)) return DMCF_EINVAL;
+    const FrsLayout L = frs_layout(n, m, batch);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    char* ws = (char*)workspace;
+    int32_t* counts = (int32_t*)(ws + L.off_counts);
+    if (m > 0)
+        hipLaunchKernelGGL((frs_query_batched<WRITE, RADII>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, queries, m,
+                           queries_row_splits, (int32_t)batch, (const FrsHeader*)(ws + L.off_header),
+                           (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radius, radii, flags,
+                           WRITE ? (int32_t*)nullptr : counts, WRITE ? row_splits : (const int64_t*)nullptr, neighbors_index,
+                           neighbors_distance, pair_capacity);
+    if (WRITE) return check_launch();
+    return scan_counts_to_row_splits(counts, (int64_t*)row_splits, m, ws + L.off_scan, L.scan_bytes, stream);
+}
 
 extern "C" {
 
@@ -1198,6 +1331,75 @@ int dmcf_frs_window_sum_backward(const float* queries, int64_t m, int64_t n, flo
                        (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radius, flags, window, coef_queries,
                        coef_points, grad);
     return check_launch();
+}
+
+size_t dmcf_frs_workspace_bytes_batched(int64_t n_points, int64_t n_queries, int64_t batch) {
+    if (n_points < 0 || n_queries < 0 || !frs_batch_ok(batch)) return 0;
+    return frs_layout(n_points, n_queries, batch).total;
+}
+
+int dmcf_frs_build_batched(const float* points, int64_t n, const int64_t* points_row_splits, int64_t batch, float radius,
+                           void* workspace, size_t workspace_bytes, dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || n > 0x7fffffff || !workspace || !(radius > 0.0f) || (n > 0 && !points)) return DMCF_EINVAL;
+    if (!points_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
+    if (((uintptr_t)workspace & 255) != 0) return DMCF_EINVAL;
+    const FrsLayout L = frs_layout(n, 0, batch);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    const size_t scan_need = scan_tmp_bytes(L.table + 1);  // (in the tail of the workspace, as in dmcf_frs_build)
+    if (workspace_bytes < L.off_counts + scan_need) return DMCF_EWORKSPACE;
+    char* ws = (char*)workspace;
+    FrsHeader* h = (FrsHeader*)(ws + L.off_header);
+    uint32_t* cell_start = (uint32_t*)(ws + L.off_cell_start);
+    uint32_t* cell_fill = (uint32_t*)(ws + L.off_cell_fill);
+    int32_t* point_cell = (int32_t*)(ws + L.off_point_cell);
+    int32_t* tmp_idx = (int32_t*)(ws + L.off_tmp_idx);
+    float4* sorted = (float4*)(ws + L.off_sorted);
+    // the phases of dmcf_frs_build's general path (the single-workgroup build is not taken: it has no slabs); the box and the
+    // sums are those of all items together
+    hipLaunchKernelGGL(frs_init_header, dim3(1), dim3(64), 0, stream, h, radius, (int32_t)n);
+    const unsigned g = (unsigned)((n + 255) / 256);
+    if (n > 0) hipLaunchKernelGGL(frs_bbox, dim3(g < 512u ? g : 512u), dim3(256), 0, stream, points, n, h);
+    hipLaunchKernelGGL(frs_finish_header_batched, dim3(1), dim3(64), 0, stream, h, L.table, batch);
+    if (hipMemsetAsync(cell_fill, 0, (size_t)(L.table + 1) * 4, stream) != hipSuccess) return DMCF_ELAUNCH;
+    if (n > 0)
+        hipLaunchKernelGGL(frs_count_cells_batched, dim3(g), dim3(256), 0, stream, points, n, points_row_splits, (int32_t)batch,
+                           (const FrsHeader*)h, point_cell, cell_fill, (uint32_t*)sorted);
+    int rc = scan_exclusive_u32(cell_fill, cell_start, L.table + 1, ws + workspace_bytes - scan_need, scan_need, stream);
+    if (rc != DMCF_OK) return rc;
+    if (n > 0) {
+        hipLaunchKernelGGL(frs_scatter, dim3(g), dim3(256), 0, stream, n, point_cell, cell_start, (const uint32_t*)sorted, tmp_idx);
+        hipLaunchKernelGGL(frs_rank_and_place, dim3(g), dim3(256), 0, stream, points, n, point_cell, cell_start, tmp_idx, sorted);
+    }
+    return check_launch();
+}
+
+int dmcf_frs_count_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius,
+                           int flags, void* workspace, size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream) {
+    return frs_search_batched<false, false>(queries, m, queries_row_splits, batch, n, nullptr, radius, flags, workspace, workspace_bytes,
+                                            row_splits, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+int dmcf_frs_write_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius,
+                           int flags, const void* workspace, size_t workspace_bytes, const int64_t* row_splits,
+                           int32_t* neighbors_index, float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream) {
+    return frs_search_batched<true, false>(queries, m, queries_row_splits, batch, n, nullptr, radius, flags, workspace, workspace_bytes,
+                                           row_splits, neighbors_index, neighbors_distance, pair_capacity, (hipStream_t)stream);
+}
+
+int dmcf_radius_search_count_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                                     const float* radii, float max_radius, int flags, void* workspace, size_t workspace_bytes,
+                                     int64_t* row_splits, dmcf_stream_t stream) {
+    return frs_search_batched<false, true>(queries, m, queries_row_splits, batch, n, radii, max_radius, flags, workspace,
+                                           workspace_bytes, row_splits, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+int dmcf_radius_search_write_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                                     const float* radii, float max_radius, int flags, const void* workspace, size_t workspace_bytes,
+                                     const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance,
+                                     int64_t pair_capacity, dmcf_stream_t stream) {
+    return frs_search_batched<true, true>(queries, m, queries_row_splits, batch, n, radii, max_radius, flags, workspace, workspace_bytes,
+                                          row_splits, neighbors_index, neighbors_distance, pair_capacity, (hipStream_t)stream);
 }
 
 }  // extern "C"

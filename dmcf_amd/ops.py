@@ -231,16 +231,89 @@ class SpatialHashTable:
     which the reference can pass as ``fixed_radius_search_hash_table`` (utils/convolutions.py:283,358).
     """
 
-    def __init__(self, points, radius, workspace, n_queries_capacity):
+    def __init__(self, points, radius, workspace, n_queries_capacity, row_splits=None, row_splits_dev=None):
         self.points = points
         self.radius = float(radius)
         self.workspace = workspace
         self.n_queries_capacity = n_queries_capacity
+        # a batched structure (dmcf_frs_build_batched) remembers the points_row_splits it was built with: a tuple of ints
+        # and the device copy the kernels read; None for the structure of one point set
+        self.row_splits = row_splits
+        self.row_splits_dev = row_splits_dev
 
 
-def build_spatial_hash_table(points, radius, n_queries=None, **_ignored):
+def _host_row_splits(row_splits, name):
+    """Row splits as given (a sequence, a CPU int64 tensor or a device int64 tensor) -> (tuple of ints, the device tensor or
+    None).  A device tensor is read back here: one small synchronising copy."""
+    dev = None
+    if isinstance(row_splits, torch.Tensor):
+        if row_splits.dtype != torch.int64:
+            raise TypeError(f"{name} must be int64, got {row_splits.dtype}")
+        if row_splits.dim() != 1:
+            raise ValueError(f"{name} must have rank 1, got shape {tuple(row_splits.shape)}")
+        if row_splits.is_cuda:
+            dev = row_splits.contiguous()
+        host = tuple(row_splits.tolist())
+    else:
+        host = tuple(int(v) for v in row_splits)
+        if any(h != v for h, v in zip(host, row_splits)):
+            raise ValueError(f"{name} must hold integers")
+    return host, dev
+
+
+def _check_row_splits(host, total, name):
+    """ValueError unless `host` starts at 0, does not decrease, ends at `total` and has at least 2 entries."""
+    if len(host) < 2:
+        raise ValueError(f"{name} must have at least 2 entries (batch + 1), got {len(host)}")
+    if host[0] != 0:
+        raise ValueError(f"{name} must start at 0, got {host[0]}")
+    if any(b < a for a, b in zip(host, host[1:])):
+        raise ValueError(f"{name} must not decrease")
+    if host[-1] != total:
+        raise ValueError(f"{name} must end at the number of rows ({total}), got {host[-1]}")
+
+
+def _batched_row_splits(points, queries, points_row_splits, queries_row_splits):
+    """The host-side checks of a batched search, in the order the callers rely on -- all of them before a device is touched:
+    both or neither (NotImplementedError), then well-formed (ValueError).  -> ((host, dev), (host, dev))."""
+    if points_row_splits is None or queries_row_splits is None:
+        raise NotImplementedError("batched search needs both points_row_splits and queries_row_splits")
+    p = _host_row_splits(points_row_splits, "points_row_splits")
+    q = _host_row_splits(queries_row_splits, "queries_row_splits")
+    _check_row_splits(p[0], points.shape[0], "points_row_splits")
+    _check_row_splits(q[0], queries.shape[0], "queries_row_splits")
+    if len(p[0]) != len(q[0]):
+        raise ValueError(f"points_row_splits and queries_row_splits must have equal lengths (batch + 1), got {len(p[0])} and {len(q[0])}")
+    return p, q
+
+
+def _row_splits_on(host, dev, device):
+    return dev if dev is not None and dev.device == device else torch.tensor(host, dtype=torch.int64, device=device)
+
+
+def build_spatial_hash_table(points, radius, n_queries=None, points_row_splits=None, **_ignored):
     """ml3d.ops.build_spatial_hash_table equivalent (hash_table_size_factor etc. are accepted and ignored:
-    the structure is a dense cell-sorted grid, see dmcf_amd/csrc/frs.hip)."""
+    the structure is a dense cell-sorted grid, see dmcf_amd/csrc/frs.hip).
+
+    ``points_row_splits`` (a sequence, a CPU or a device int64 tensor; a device tensor costs one small synchronising copy for
+    its validation): the structure of a BATCH of point sets (dmcf_frs_build_batched), which remembers its splits and serves
+    searches with those splits only."""
+    if points_row_splits is not None:
+        host, dev = _host_row_splits(points_row_splits, "points_row_splits")
+        _check_row_splits(host, points.shape[0], "points_row_splits")
+        L = _lib.lib()
+        points = _dev_f32(points, "points", 3)
+        n, batch = points.shape[0], len(host) - 1
+        m = n if n_queries is None else int(n_queries)
+        nbytes = L.dmcf_frs_workspace_bytes_batched(n, m, batch)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+        rs_dev = _row_splits_on(host, dev, points.device)
+        t0 = timer.begin() if timer is not None else None
+        _lib.check(L.dmcf_frs_build_batched(_ptr(points), n, _ptr(rs_dev), batch, float(radius), _ptr(ws), nbytes, _stream()),
+                   "dmcf_frs_build_batched")
+        if timer is not None:
+            timer.end("frs_build_batched", dict(n_points=n, batch=batch), t0)
+        return SpatialHashTable(points, radius, ws, m, row_splits=host, row_splits_dev=rs_dev)
     L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     n = points.shape[0]
@@ -342,8 +415,71 @@ def frs_flags(ignore_query_point):
     return (FRS_IGNORE_QUERY_POINT if ignore_query_point else 0) | SEARCH_SETS[search_set()]
 
 
+def _batched_table(points, radius, m, p_host, p_dev, hash_table):
+    """The batched structure of (points, radius, these splits): the caller's when it is one, else a new one."""
+    if (hash_table is None or hash_table.n_queries_capacity < m or hash_table.points.data_ptr() != points.data_ptr()
+            or hash_table.radius != radius or hash_table.row_splits != p_host):
+        hash_table = build_spatial_hash_table(points, radius, n_queries=m, points_row_splits=p_host if p_dev is None else p_dev)
+    return hash_table
+
+
+def _fixed_radius_search_batched(points, queries, radius, ignore_query_point, return_distances, hash_table, capacity_hint, row_stride,
+                                 metric, points_row_splits, queries_row_splits):
+    """fixed_radius_search with row splits (dmcf_frs_*_batched).  Host checks first, in this order: both or neither; the
+    options that have no batched form; well-formed row splits; only then the operands' device."""
+    if points_row_splits is None or queries_row_splits is None:
+        raise NotImplementedError("batched search needs both points_row_splits and queries_row_splits")
+    if row_stride is not None:
+        raise NotImplementedError("row_stride (padded rows) has no batched form: pass row splits or row_stride, not both")
+    if metric != "L2":
+        raise NotImplementedError(f"metric {metric!r} has no batched form: a search with row splits is 'L2'")
+    if SEARCH_SETS[search_set()] != 0:
+        raise NotImplementedError(f"DMCF_FRS_SET={search_set()} has no batched form: the open3d walk emulations know nothing of items")
+    (p_host, p_dev), (q_host, q_dev) = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
+    L = _lib.lib()
+    points = _dev_f32(points, "points", 3)
+    queries = _dev_f32(queries, "queries", 3)
+    radius = float(radius)
+    if not radius > 0:
+        raise ValueError("radius must be positive")
+    n, m, batch = points.shape[0], queries.shape[0], len(p_host) - 1
+    dev = points.device
+    hash_table = _batched_table(points, radius, m, p_host, p_dev, hash_table)
+    ws = hash_table.workspace
+    nbytes = L.dmcf_frs_workspace_bytes_batched(n, hash_table.n_queries_capacity, batch)
+    q_rs = _row_splits_on(q_host, q_dev, dev)
+    flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
+    row_splits = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_frs_count_batched(_ptr(queries), m, _ptr(q_rs), batch, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
+                                        _stream()), "dmcf_frs_count_batched")
+
+    def write(capacity):
+        index = torch.empty(capacity, dtype=torch.int32, device=dev)
+        dist = torch.empty(capacity if return_distances else 0, dtype=torch.float32, device=dev)
+        if capacity > 0 and m > 0:
+            _lib.check(L.dmcf_frs_write_batched(_ptr(queries), m, _ptr(q_rs), batch, n, radius, flags, _ptr(ws), nbytes,
+                                                _ptr(row_splits), _ptr(index), _ptr(dist) if return_distances else None, capacity,
+                                                _stream()), "dmcf_frs_write_batched")
+        return index, dist
+
+    if capacity_hint is None:
+        total = int(row_splits[-1].item())  # the one host round trip of the two-phase search
+        index, dist = write(pair_capacity(total) if total else 0)
+        res = NeighborSearchResult(index, row_splits, dist, total=total)
+    else:
+        index, dist = write(pair_capacity(capacity_hint))
+        keep = (points, queries, ws, q_rs)  # noqa: F841  (the closure keeps the operands alive for a possible redo)
+        res = NeighborSearchResult(index, row_splits, dist, total=None, redo=write)
+    if timer is not None:
+        timer.end("frs_search_batched", dict(n_points=n, n_queries=m, batch=batch, pairs=res.total_ref,
+                                             distances=bool(return_distances)), t0)
+    return res
+
+
 def fixed_radius_search(points, queries, radius, ignore_query_point=False, return_distances=True,
-                        hash_table=None, capacity_hint=None, row_stride=None, max_count=None, metric="L2"):
+                        hash_table=None, capacity_hint=None, row_stride=None, max_count=None, metric="L2",
+                        points_row_splits=None, queries_row_splits=None):
     """-> NeighborSearchResult(neighbors_index int32 [P], neighbors_row_splits int64 [m+1],
     neighbors_distance float32 [P] (squared L2; empty if not return_distances)).
 
@@ -354,7 +490,15 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
     ``capacity_hint``: an estimate of P.  With it count, scan and write are enqueued back to back with buffers of
     that size and NO host synchronisation; the result is validated later (see NeighborSearchResult).
     ``row_stride``: an upper bound of the row lengths.  With it ONE pass writes padded rows (PaddedNeighborList): no
-    count pass at all; validated later through ``max_count``."""
+    count pass at all; validated later through ``max_count``.
+    ``points_row_splits`` / ``queries_row_splits`` (both or neither; each a sequence, a CPU int64 tensor or a device int64
+    tensor -- a device tensor costs one small synchronising copy, because the splits are validated on the host): Open3D's
+    batched search.  Item b of the batch is points[prs[b]:prs[b+1]] and queries[qrs[b]:qrs[b+1]]; a query finds points of its
+    own item only, neighbors_index indexes the concatenated points, the row splits of the result run over all queries.  'L2'
+    and DMCF_FRS_SET=distance only, no ``row_stride``; ``capacity_hint`` as without row splits."""
+    if points_row_splits is not None or queries_row_splits is not None:
+        return _fixed_radius_search_batched(points, queries, radius, ignore_query_point, return_distances, hash_table, capacity_hint,
+                                            row_stride, metric, points_row_splits, queries_row_splits)
     L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     queries = _dev_f32(queries, "queries", 3)
@@ -367,7 +511,7 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
         raise NotImplementedError("the 'Linf' search returns index lists only (no distances, no padded rows)")
     n, m = points.shape[0], queries.shape[0]
     if hash_table is None or hash_table.n_queries_capacity < m or hash_table.points.data_ptr() != points.data_ptr() \
-            or hash_table.radius != radius:
+            or hash_table.radius != radius or hash_table.row_splits is not None:  # (a batched structure does not serve this search)
         hash_table = build_spatial_hash_table(points, radius, n_queries=m)
     ws = hash_table.workspace
     nbytes = L.dmcf_frs_workspace_bytes(n, hash_table.n_queries_capacity)
@@ -460,12 +604,13 @@ class FixedRadiusSearch:
 
     def __call__(self, points, queries, radius, points_row_splits=None, queries_row_splits=None,
                  hash_table_size_factor=1 / 64, hash_table=None, capacity_hint=None, row_stride=None, max_count=None):
-        if points_row_splits is not None or queries_row_splits is not None:
-            raise NotImplementedError("batched row_splits are not used by DMCF (batch items are looped, "
-                                      "pipelines/simulator.py:68-70)")
+        if (points_row_splits is None) != (queries_row_splits is None):  # (before anything reads a device)
+            raise NotImplementedError("batched search needs both points_row_splits and queries_row_splits")
         if isinstance(radius, torch.Tensor):
             radius = float(radius)
         metric = {} if self.metric == "L2" else {"metric": self.metric}  # (an L2 call is the call it always was)
+        if points_row_splits is not None or queries_row_splits is not None:  # Open3D's batched search (both or neither)
+            metric.update(points_row_splits=points_row_splits, queries_row_splits=queries_row_splits)
         return fixed_radius_search(points, queries, radius, self.ignore_query_point, self.return_distances,
                                    hash_table=hash_table, capacity_hint=capacity_hint, row_stride=row_stride, max_count=max_count,
                                    **metric)
@@ -480,14 +625,20 @@ class FixedRadiusSearch:
         return twin
 
 
-def radius_search(points, queries, radii, ignore_query_point=False, return_distances=True, normalize_distances=True):
+def radius_search(points, queries, radii, ignore_query_point=False, return_distances=True, normalize_distances=True,
+                  points_row_splits=None, queries_row_splits=None):
     """A radius per query (dmcf_radius_search_count / _write) -> NeighborSearchResult(neighbors_index int32 [P],
     neighbors_row_splits int64 [m+1], neighbors_distance float32 [P] (empty if not return_distances)).
 
     Row i holds the points within ``radii[i]`` of query i (the set of include/dmcf_hip.h; always the distance set, whatever
     DMCF_FRS_SET says: the open3d emulations are of FixedRadiusSearch's hash walk).  ``normalize_distances``: d^2 / r_i^2 --
     the L2 form of Open3D's normalize_distances, restated, not pinned against the library; 0 in a row
-    of radius 0.  One host read checks the radii and forms max_radius, the grid is built at max_radius, a second reads P."""
+    of radius 0.  One host read checks the radii and forms max_radius, the grid is built at max_radius, a second reads P.
+    ``points_row_splits`` / ``queries_row_splits``: the batched search, as in :func:`fixed_radius_search` (both or neither,
+    validated on the host before a device is touched; dmcf_radius_search_*_batched)."""
+    batched = points_row_splits is not None or queries_row_splits is not None
+    if batched:
+        (p_host, p_dev), (q_host, q_dev) = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
     L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     queries = _dev_f32(queries, "queries", 3)
@@ -504,18 +655,32 @@ def radius_search(points, queries, radii, ignore_query_point=False, return_dista
     if bad:
         raise ValueError("radii must be finite and non-negative")
     max_radius = float(np.float32(max_radius)) if max_radius > 0 else 1.0  # (all zero: any grid serves, the rows are coincident points)
-    table = build_spatial_hash_table(points, max_radius, n_queries=m)
-    ws = table.workspace
-    nbytes = L.dmcf_frs_workspace_bytes(n, m)
     flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
-    t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_radius_search_count(_ptr(queries), m, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
-                                          _stream()), "dmcf_radius_search_count")
+    if batched:
+        batch = len(p_host) - 1
+        table = build_spatial_hash_table(points, max_radius, n_queries=m, points_row_splits=p_host if p_dev is None else p_dev)
+        ws = table.workspace
+        nbytes = L.dmcf_frs_workspace_bytes_batched(n, m, batch)
+        q_rs = _row_splits_on(q_host, q_dev, dev)
+        t0 = timer.begin() if timer is not None else None
+        _lib.check(L.dmcf_radius_search_count_batched(_ptr(queries), m, _ptr(q_rs), batch, n, _ptr(radii), max_radius, flags, _ptr(ws),
+                                                      nbytes, _ptr(row_splits), _stream()), "dmcf_radius_search_count_batched")
+    else:
+        table = build_spatial_hash_table(points, max_radius, n_queries=m)
+        ws = table.workspace
+        nbytes = L.dmcf_frs_workspace_bytes(n, m)
+        t0 = timer.begin() if timer is not None else None
+        _lib.check(L.dmcf_radius_search_count(_ptr(queries), m, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
+                                              _stream()), "dmcf_radius_search_count")
     total = int(row_splits[-1].item())  # the one host round trip of the two-phase search, as in fixed_radius_search
     capacity = pair_capacity(total) if total else 0
     index = torch.empty(capacity, dtype=torch.int32, device=dev)
     dist = torch.empty(capacity if return_distances else 0, dtype=torch.float32, device=dev)
-    if capacity > 0:
+    if capacity > 0 and batched:
+        _lib.check(L.dmcf_radius_search_write_batched(_ptr(queries), m, _ptr(q_rs), batch, n, _ptr(radii), max_radius, flags, _ptr(ws),
+                                                      nbytes, _ptr(row_splits), _ptr(index), _ptr(dist) if return_distances else None,
+                                                      capacity, _stream()), "dmcf_radius_search_write_batched")
+    elif capacity > 0:
         _lib.check(L.dmcf_radius_search_write(_ptr(queries), m, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
                                               _ptr(index), _ptr(dist) if return_distances else None, capacity, _stream()),
                    "dmcf_radius_search_write")
@@ -544,9 +709,9 @@ class RadiusSearch:
         self.normalize_distances = normalize_distances
 
     def __call__(self, points, queries, radii, points_row_splits=None, queries_row_splits=None):
-        if points_row_splits is not None or queries_row_splits is not None:
-            raise NotImplementedError("batched row_splits are not used by DMCF (batch items are looped, "
-                                      "pipelines/simulator.py:68-70)")
+        if points_row_splits is not None or queries_row_splits is not None:  # Open3D's batched search (both or neither)
+            return radius_search(points, queries, radii, self.ignore_query_point, self.return_distances, self.normalize_distances,
+                                 points_row_splits=points_row_splits, queries_row_splits=queries_row_splits)
         return radius_search(points, queries, radii, self.ignore_query_point, self.return_distances, self.normalize_distances)
 
     call = __call__

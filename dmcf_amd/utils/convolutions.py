@@ -574,7 +574,14 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
 
     def forward(self, inp_features, inp_positions, out_positions, extents, inp_importance=None,
                 fixed_radius_search_hash_table=None, user_neighbors_index=None, user_neighbors_row_splits=None,
-                user_neighbors_importance=None):
+                user_neighbors_importance=None, inp_positions_row_splits=None, out_positions_row_splits=None):
+        """The reference's arguments, and after them ``inp_positions_row_splits`` / ``out_positions_row_splits`` (both or
+        neither): a BATCH of point sets in one call -- item b is inp_positions[irs[b]:irs[b+1]] and
+        out_positions[ors[b]:ors[b+1]], an output point gathers from input points of its own item only (see _batched_lists)."""
+        if inp_positions_row_splits is not None or out_positions_row_splits is not None:
+            user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance = self._batched_lists(
+                inp_positions, out_positions, extents, inp_positions_row_splits, out_positions_row_splits,
+                user_neighbors_index, user_neighbors_row_splits)
         if self.kernel is None:
             with torch.no_grad():
                 self.build(inp_features.shape[-1], inp_features.device)
@@ -585,6 +592,39 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         return self._forward_infer(inp_features, inp_positions, out_positions, extents, inp_importance,
                                    fixed_radius_search_hash_table, user_neighbors_index, user_neighbors_row_splits,
                                    user_neighbors_importance)
+
+    @torch.no_grad()
+    def _batched_lists(self, inp_positions, out_positions, extents, inp_row_splits, out_row_splits, user_neighbors_index,
+                       user_neighbors_row_splits):
+        """The neighbour list of a batched call, handed to the layer's user-list path (:341-349): (neighbors_index,
+        neighbors_row_splits, neighbors_importance).  The batched search -- FixedRadiusSearch at 0.5 * extent for a scalar
+        extent, RadiusSearch at 0.5 * extents for extents of rank 1 -- then the layer's window function on the normalised
+        distances d^2 / r^2 as the importance (None without a window).  The list is an arbitrary CSR list over the
+        concatenated points, which every neighbour-list kernel takes, forward and backward; the lattice, scatter and direct
+        forms and the step's list cache do not apply."""
+        if inp_row_splits is None or out_row_splits is None:
+            raise NotImplementedError("a batched call needs both inp_positions_row_splits and out_positions_row_splits")
+        if user_neighbors_index is not None or user_neighbors_row_splits is not None:
+            raise ValueError("row splits and a user neighbour list exclude each other: the list already says who is whose neighbour")
+        if self.symmetric:
+            raise NotImplementedError("symmetric=True (ASCC) with row splits is not implemented")
+        splits = dict(points_row_splits=inp_row_splits, queries_row_splits=out_row_splits)
+        if _rank1_extents(extents, out_positions):
+            if extents.shape[0] != out_positions.shape[0]:
+                raise ValueError(f"extents of rank 1 must hold one value per output point ({out_positions.shape[0]}), "
+                                 f"got {extents.shape[0]}")
+            nns = self.radius_search(inp_positions, out_positions, 0.5 * extents.detach(), **splits)  # :367, normalised by the search
+            q = nns.neighbors_distance
+        else:
+            if isinstance(extents, torch.Tensor) and extents.dim() > 0 and extents.numel() != 1:
+                raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:352-372)")
+            extent = float(extents) if isinstance(extents, torch.Tensor) else float(np.float32(extents))
+            radius = float(np.float32(0.5) * np.float32(extent))  # :353
+            nns = self.fixed_radius_search(inp_positions, out_positions, radius, **splits)
+            q = nns.neighbors_distance / (np.float32(radius) * np.float32(radius)) if self.window_function is not None else None
+        self.__dict__["nns"] = nns
+        importance = None if self.window_function is None else self.window_function(q).to(torch.float32)
+        return nns.neighbors_index, nns.neighbors_row_splits, importance
 
     def recording(self, inp_features=None):
         """Does a call now record autograd history: grad mode on and a weight (``requires_grad_(True)``) or the input features

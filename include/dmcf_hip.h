@@ -15,6 +15,8 @@
  *   ASCC: mirror :410-412 + second continuous_conv :433-458      dmcf_cconv_forward(DMCF_FLAG_SYMMETRIC)
  *   ml3d.layers.RadiusSearch (utils/convolutions.py:212-216,     dmcf_frs_build / dmcf_radius_search_count /
  *     366-370, 1006-1010: extents of rank 1)                      dmcf_radius_search_write
+ *   both searches with points_row_splits / queries_row_splits    dmcf_frs_build_batched / dmcf_frs_count_batched /
+ *     (a batch of point sets in one call; ABI 2.20)               dmcf_frs_write_batched, dmcf_radius_search_*_batched
  *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
  *                                                                 dmcf_cconv_backward_extents)
  *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
@@ -193,6 +195,45 @@ int dmcf_radius_search_write(const float* queries, int64_t n_queries, int64_t n_
                              float max_radius, int flags, const void* workspace, size_t workspace_bytes,
                              const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance,
                              int64_t pair_capacity, dmcf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Batched search (ABI 2.20): the points_row_splits / queries_row_splits arguments of ml3d.layers.FixedRadiusSearch and
+ * ml3d.layers.RadiusSearch.  `points` holds the point sets of `batch` items one after the other, item b being
+ * points[points_row_splits[b] .. points_row_splits[b + 1]); `queries` likewise with queries_row_splits.  Both row-splits
+ * arrays are DEVICE int64 [batch + 1], start at 0, do not decrease and end at n_points / n_queries; the caller vouches for
+ * that (they cannot be read here without a host round trip).  Arrays that break the promise give wrong rows, never an access
+ * outside the workspace.  Items may be empty.
+ * Result contract: a query of item b finds exactly the points j of item b with ((dx*dx + dy*dy) + dz*dz) <= r*r -- the value
+ * and the test of the un-batched searches -- wherever the items lie: they may overlap or coincide.  neighbors_index indexes
+ * the concatenated `points`, row_splits runs over all queries, DMCF_FRS_IGNORE_QUERY_POINT is decided by position equality,
+ * rows are deterministic (ascending grid cell of the item's slab, then ascending point index).
+ * One grid geometry serves the whole call -- its box and cell edge come from all points together -- with the item as the
+ * outermost digit of the cell index (dmcf_amd/csrc/frs.hip); no host round trip in the build.  A structure built here is
+ * searched with the *_batched entry points only, with the same n_points, batch and radius, and a workspace of
+ * dmcf_frs_workspace_bytes_batched (0 for a negative size or a batch outside [1, 2^26]).
+ * flags: DMCF_FRS_IGNORE_QUERY_POINT only.  The DMCF_FRS_OPEN3D_* flags are DMCF_EINVAL, DMCF_FRS_METRIC_LINF is
+ * DMCF_EUNSUPPORTED (DMCF_EINVAL in the radius search, as in dmcf_radius_search_count).  Null row splits and a batch outside
+ * [1, 2^26] are DMCF_EINVAL.  Arguments are validated before anything is enqueued.  Otherwise every argument is the one of
+ * the un-batched entry point of the same name.
+ * ---------------------------------------------------------------------------------------------- */
+size_t dmcf_frs_workspace_bytes_batched(int64_t n_points, int64_t n_queries, int64_t batch);
+int dmcf_frs_build_batched(const float* points, int64_t n_points, const int64_t* points_row_splits, int64_t batch, float radius,
+                           void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+int dmcf_frs_count_batched(const float* queries, int64_t n_queries, const int64_t* queries_row_splits, int64_t batch,
+                           int64_t n_points, float radius, int flags, void* workspace, size_t workspace_bytes,
+                           int64_t* row_splits, dmcf_stream_t stream);
+int dmcf_frs_write_batched(const float* queries, int64_t n_queries, const int64_t* queries_row_splits, int64_t batch,
+                           int64_t n_points, float radius, int flags, const void* workspace, size_t workspace_bytes,
+                           const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance,
+                           int64_t pair_capacity, dmcf_stream_t stream);
+/* a radius per query on the structure of dmcf_frs_build_batched(points, ..., max_radius) */
+int dmcf_radius_search_count_batched(const float* queries, int64_t n_queries, const int64_t* queries_row_splits, int64_t batch,
+                                     int64_t n_points, const float* radii, float max_radius, int flags, void* workspace,
+                                     size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream);
+int dmcf_radius_search_write_batched(const float* queries, int64_t n_queries, const int64_t* queries_row_splits, int64_t batch,
+                                     int64_t n_points, const float* radii, float max_radius, int flags, const void* workspace,
+                                     size_t workspace_bytes, const int64_t* row_splits, int32_t* neighbors_index,
+                                     float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Continuous convolution (CConv) and its antisymmetric variant (ASCC).
