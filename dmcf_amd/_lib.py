@@ -284,6 +284,8 @@ SYMBOLS = [
     "dmcf_sparse_conv_kernel_names",
     "dmcf_frs_workspace_bytes_batched", "dmcf_frs_build_batched", "dmcf_frs_count_batched", "dmcf_frs_write_batched",
     "dmcf_radius_search_count_batched", "dmcf_radius_search_write_batched",
+    "dmcf_grid_pos_workspace_bytes_batched", "dmcf_grid_pos_bounds_batched", "dmcf_grid_pos_count_batched",
+    "dmcf_grid_pos_write_batched", "dmcf_points_aabb_batched",
 ]
 
 
@@ -520,6 +522,20 @@ def lib():
     L.dmcf_radius_search_write_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float,
                                                    c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
                                                    c.c_void_p]
+    # grid_pos and the fluid box with row splits (ABI 2.21)
+    L.dmcf_grid_pos_workspace_bytes_batched.restype = c.c_size_t
+    L.dmcf_grid_pos_workspace_bytes_batched.argtypes = [c.c_int64, c.c_int64]
+    L.dmcf_grid_pos_bounds_batched.restype = c.c_int
+    L.dmcf_grid_pos_bounds_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, f3, c.c_int, c.c_void_p, c.c_int,
+                                               c.c_float, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_grid_pos_count_batched.restype = c.c_int
+    L.dmcf_grid_pos_count_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, f3, c.c_int, c.c_int, c.c_float,
+                                              c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
+    L.dmcf_grid_pos_write_batched.restype = c.c_int
+    L.dmcf_grid_pos_write_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, f3, c.c_int, c.c_int, c.c_float,
+                                              c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p]
+    L.dmcf_points_aabb_batched.restype = c.c_int
+    L.dmcf_points_aabb_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
     _lib = L
     return L
 

@@ -22,8 +22,9 @@ struct GridHeader {  // 64 bytes, written by the device
     int64_t cells;   // dims product (0 when n == 0)
     int64_t total;   // number of lattice points (valid after count)
     float center[3];
-    int32_t pad_;
+    int32_t pad_[3];
 };
+static_assert(sizeof(GridHeader) == 64, "the batched entry points keep one 64-byte header per item");
 
 struct GridParams {
     const float* pos;
@@ -304,6 +305,275 @@ static int grid_params(GridParams& p, const float* pos, int64_t n, const float* 
     return DMCF_OK;
 }
 
+// ---- grid_pos with row splits (ABI 2.21) ------------------------------------------------------------------------------------
+// A batch of point sets in one call: item b is positions[rs[b] .. rs[b + 1]) and the result is the concatenation, item after item,
+// of what the three phases above return for each slice -- bit for bit, in the same order.  What makes that so:
+//   centre : blockIdx.y = item.  Each item runs grid_sum / grid_center's sums over its LOCAL index with the block count the
+//            un-batched call would launch for n_b points (grid_item_blocks), so every partial sum has the same addends in the same order
+//   bounds : one GridHeader per item; a cell index is local to the item's own box and offset by the cells of the items before it
+//            (cell_off, the item as the outermost digit): two items at the same coordinates never share a cell
+//   rows   : item b owns rows [2 rs[b], 2 rs[b + 1]): its first-half rows, then its second-half rows -- (item, half, local point).
+//            The candidate rank row * n_off + off keeps an item's candidates in their un-batched relative order, and the scan over
+//            the rows gives item-grouped output; out_row_splits[b] = row_off[2 rs[b]]
+__device__ __forceinline__ int grid_item_blocks(int64_t n) {  // the nb of dmcf_grid_pos_bounds
+    const int64_t want = (n + 255) / 256;
+    return (int)(want < 1 ? 1 : (want > kGridBlocks ? kGridBlocks : want));
+}
+
+// the item that holds global point i: the last b with rs[b] <= i (empty items are stepped over)
+__device__ __forceinline__ int grid_item_of(const int64_t* __restrict__ rs, int batch, int64_t i) {
+    int lo = 0, hi = batch;  // invariant: rs[lo] <= i < rs[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rs[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// grid_sum per item; part[(item * nbx + block) * 3 + axis], nbx = gridDim.x
+__global__ __launch_bounds__(256) void grid_sum_batched(const float* __restrict__ pos, const int64_t* __restrict__ rs,
+                                                        double* __restrict__ part) {
+    const int64_t b0 = rs[blockIdx.y], n = rs[blockIdx.y + 1] - b0;
+    const int nb = grid_item_blocks(n);
+    if ((int)blockIdx.x >= nb) return;
+    const float* __restrict__ q = pos + 3 * b0;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)nb * 256) {
+        s[0] += (double)q[3 * i];
+        s[1] += (double)q[3 * i + 1];
+        s[2] += (double)q[3 * i + 2];
+    }
+    __shared__ double red[3][4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s[a] += __shfl_xor(s[a], d, kWave);
+        if (lane_id() == 0) red[a][threadIdx.x >> 6] = s[a];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + a] = (red[a][0] + red[a][1]) + (red[a][2] + red[a][3]);
+    }
+}
+
+// grid_center per item: one wavefront per item (blockIdx.x = item); given: [batch, 3] or NULL
+__global__ void grid_center_batched(const double* __restrict__ part, int nbx, const int64_t* __restrict__ rs,
+                                    const float* __restrict__ given, GridHeader* hs) {
+    const int lane = lane_id();
+    GridHeader* h = hs + blockIdx.x;
+    if (given) {
+        if (lane < 3) h->center[lane] = given[3 * blockIdx.x + lane];
+        return;
+    }
+    const int64_t n = rs[blockIdx.x + 1] - rs[blockIdx.x];
+    const int nblocks = grid_item_blocks(n);
+    part += (size_t)blockIdx.x * nbx * 3;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        double s = 0.0;
+        for (int b = lane; b < nblocks; b += kWave) s += part[b * 3 + a];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, kWave);
+        if (lane == 0) h->center[a] = n > 0 ? (float)(s / (double)n) : 0.0f;
+    }
+}
+
+// grid_extrema per item (min / max: any order gives the same bits, the block count only has to cover the item)
+__global__ __launch_bounds__(256) void grid_extrema_batched(const GridParams p, const GridHeader* hs,
+                                                            const int64_t* __restrict__ rs, float* __restrict__ part) {
+    const int64_t b0 = rs[blockIdx.y], e0 = rs[blockIdx.y + 1];
+    const GridHeader* h = hs + blockIdx.y;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t i = b0 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < e0; i += (int64_t)gridDim.x * 256) {
+        float s[3];
+        grid_scaled(p, h, i, s);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const bool ok = fabsf(s[a]) < INFINITY;
+            mn[a] = ok ? fminf(mn[a], s[a]) : -INFINITY;
+            mx[a] = ok ? fmaxf(mx[a], s[a]) : INFINITY;
+        }
+    }
+    __shared__ float red[2][3][4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            mn[a] = fminf(mn[a], __shfl_xor(mn[a], d, kWave));
+            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d, kWave));
+        }
+        if (lane_id() == 0) {
+            red[0][a][threadIdx.x >> 6] = mn[a];
+            red[1][a][threadIdx.x >> 6] = mx[a];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        float* o = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 6;
+        o[a] = fminf(fminf(red[0][a][0], red[0][a][1]), fminf(red[0][a][2], red[0][a][3]));
+        o[3 + a] = fmaxf(fmaxf(red[1][a][0], red[1][a][1]), fmaxf(red[1][a][2], red[1][a][3]));
+    }
+}
+
+// grid_finish_bounds per item: one wavefront per item
+__global__ void grid_finish_bounds_batched(const GridParams p, const float* __restrict__ part, int nbx,
+                                           const int64_t* __restrict__ rs, GridHeader* hs) {
+    const int lane = lane_id();
+    GridHeader* h = hs + blockIdx.x;
+    const int64_t n = rs[blockIdx.x + 1] - rs[blockIdx.x];
+    part += (size_t)blockIdx.x * nbx * 6;
+    float mns[3], mxs[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float mn = INFINITY, mx = -INFINITY;
+        for (int b = lane; b < nbx; b += kWave) {
+            mn = fminf(mn, part[b * 6 + a]);
+            mx = fmaxf(mx, part[b * 6 + 3 + a]);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, d, kWave));
+            mx = fmaxf(mx, __shfl_xor(mx, d, kWave));
+        }
+        mns[a] = mn;
+        mxs[a] = mx;
+    }
+    if (lane != 0) return;
+    int64_t cells = n > 0 ? 1 : 0;
+    for (int a = 0; a < 3; ++a) {
+        const float mn = mns[a], mx = mxs[a];
+        int lo = 0, d = 0;
+        if (n > 0 && isfinite(mn) && isfinite(mx)) {
+            lo = (int)floorf(__fsub_rn(mn, p.h[a])) + p.lo[a];
+            const int hi = (int)floorf(__fadd_rn(mx, p.h[a])) + p.lo[a] + p.len[a] - 1;
+            d = hi - lo + 1;
+        } else if (n > 0) {
+            cells = -1;
+        }
+        h->minp[a] = lo;
+        h->dims[a] = d;
+        if (cells > 0) cells *= d;
+    }
+    h->cells = cells;
+    h->total = 0;
+}
+
+// cell_off[b] = cells of the items before b (an item with non-finite positions counts as empty: the caller reports the error).
+// One thread: a batch is tens of items, and this runs once per call behind the per-item wavefronts above.
+__global__ void grid_cell_offsets(const GridHeader* __restrict__ hs, int64_t batch, int64_t* __restrict__ cell_off) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int64_t acc = 0;
+    for (int64_t b = 0; b < batch; ++b) {
+        cell_off[b] = acc;
+        const int64_t c = hs[b].cells;
+        acc += c > 0 ? c : 0;
+    }
+    cell_off[batch] = acc;
+}
+
+// grid_pass with items: row r of [0, 2 n) belongs to the item that holds point r / 2's slot (rows [2 rs[b], 2 rs[b + 1])).
+// The dense table index and the hashed key are cell_off[item] + the cell index in the item's own box.
+template <int MODE>
+__global__ __launch_bounds__(256) void grid_pass_batched(const GridParams p, const GridHeader* __restrict__ hs,
+                                                         const int64_t* __restrict__ rs, int batch,
+                                                         const int64_t* __restrict__ cell_off, uint32_t* __restrict__ first,
+                                                         int32_t* __restrict__ counts, const int64_t* __restrict__ row_off,
+                                                         float* __restrict__ out, int64_t out_capacity, int64_t table_cells) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = row < 2 * p.n;
+    const int item = live ? grid_item_of(rs, batch, row >> 1) : 0;
+    const int64_t b0 = rs[item], nb = rs[item + 1] - b0;
+    const int64_t lrow = live ? row - 2 * b0 : 0;
+    const bool second = lrow >= nb;
+    const int64_t i = live ? b0 + (second ? lrow - nb : lrow) : 0;
+    const GridHeader* h = hs + item;
+    int c0[3] = {0, 0, 0}, c1[3] = {0, 0, 0};
+    const bool diff = live && grid_bases(p, h, i, c0, c1);
+    const int* c = second ? c1 : c0;
+    const int64_t d0 = h->dims[0], d01 = d0 * h->dims[1];
+    const int64_t cells = h->cells, base = cell_off[item];
+    const bool active = live && (!second || diff);
+    if (MODE == 0) {
+        // (see grid_pass: the row in the lane below with the same base cell -- of the same item: `base` makes the key global)
+        const int64_t key = active ? base + c[0] + c[1] * d0 + c[2] * d01 : -1 - (int64_t)(threadIdx.x & 63);
+        const int64_t below = __shfl_up(key, 1, 64);
+        if (!active || ((threadIdx.x & 63) != 0 && below == key)) return;
+    } else if (!active) {
+        if (MODE == 1 && live) counts[row] = 0;
+        return;
+    }
+    const int noff = p.len[0] * p.len[1] * p.len[2];
+    const uint32_t k0 = (uint32_t)row * (uint32_t)noff;
+    int cnt = 0;
+    int64_t w = MODE == 2 ? row_off[row] : 0;
+    int o = 0;
+    for (int i0 = 0; i0 < p.len[0]; ++i0)
+        for (int i1 = 0; i1 < p.len[1]; ++i1)
+            for (int i2 = 0; i2 < p.len[2]; ++i2, ++o) {
+                const int g0 = c[0] + p.lo[0] + i0, g1 = c[1] + p.lo[1] + i1, g2 = c[2] + p.lo[2] + i2;
+                int64_t cell = g0 + g1 * d0 + g2 * d01;
+                if (cell < 0 || cell >= cells) continue;  // outside the item's own box: never into another item's cells
+                cell += base;
+                if (table_cells < 0) {
+                    const uint32_t mask = (uint32_t)(-table_cells) - 1u;
+                    unsigned long long* keys = (unsigned long long*)(first + (-table_cells));
+                    cell = MODE == 0 ? grid_slot<true>(keys, mask, cell) : grid_slot<false>(keys, mask, cell);
+                    if (cell < 0) continue;
+                } else if (cell >= table_cells) continue;  // table smaller than the headers say: never out of bounds
+                const uint32_t k = k0 + (uint32_t)o;
+                if (MODE == 0) {
+                    atomicMin(first + cell, k);
+                } else if (first[cell] == k) {
+                    if (MODE == 1) {
+                        ++cnt;
+                    } else if (w < out_capacity) {
+                        const int g[3] = {g0 + h->minp[0], g1 + h->minp[1], g2 + h->minp[2]};
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) {
+                            const float t = __fmul_rn((float)g[a], p.voxel[a]);
+                            out[3 * w + a] = p.centralize ? __fadd_rn(t, h->center[a]) : __fadd_rn(t, __fdiv_rn(p.voxel[a], 2.0f));
+                        }
+                        ++w;
+                    }
+                }
+            }
+    if (MODE == 1) counts[row] = cnt;
+}
+
+// out_row_splits[b] = first output row of item b (b = batch: the number of lattice points); header b's total = item b's points
+__global__ void grid_store_totals_batched(const int64_t* __restrict__ row_off, const int64_t* __restrict__ rs, int64_t batch,
+                                          GridHeader* hs, int64_t* __restrict__ out_row_splits) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b > batch) return;
+    const int64_t lo = row_off[2 * rs[b]];
+    out_row_splits[b] = lo;
+    if (b < batch) hs[b].total = row_off[2 * rs[b + 1]] - lo;
+}
+
+struct GridBatchLayout {
+    size_t off_headers, off_celloff, off_part, off_counts, off_rowoff, off_scan, total;
+    int nbx;  // blocks per item of the two reductions: what the largest possible item (all n points) would get
+};
+
+static GridBatchLayout grid_batch_layout(int64_t n, int64_t batch) {
+    GridBatchLayout L;
+    const int64_t want = (n + 255) / 256;
+    L.nbx = (int)(want < 1 ? 1 : (want > kGridBlocks ? kGridBlocks : want));
+    size_t o = 0;
+    L.off_headers = o; o += align_up((size_t)batch * sizeof(GridHeader), 256);
+    L.off_celloff = o; o += align_up((size_t)(batch + 1) * 8, 256);
+    L.off_part = o; o += align_up((size_t)batch * L.nbx * 6 * sizeof(double), 256);
+    L.off_counts = o; o += align_up((size_t)(2 * n + 1) * 4, 256);
+    L.off_rowoff = o; o += align_up((size_t)(2 * n + 2) * 8, 256);
+    L.off_scan = o; o += align_up(scan_tmp_bytes(2 * n + 1), 256);
+    L.total = o;
+    return L;
+}
+
+constexpr int64_t kGridMaxBatch = 65535;  // the item is blockIdx.y of the two reductions
+
 }  // namespace dmcf
 
 using namespace dmcf;
@@ -390,6 +660,100 @@ int dmcf_grid_pos_write(const float* positions, int64_t n_points, const float* v
     if (rows > 0 && out_capacity > 0) {
         const unsigned g = (unsigned)((rows + 255) / 256);
         hipLaunchKernelGGL((grid_pass<2>), dim3(g), dim3(256), 0, stream, p, h, (uint32_t*)cell_table,
+                           (int32_t*)(ws + L.off_counts), (const int64_t*)(ws + L.off_rowoff), out, out_capacity, table_cells);
+    }
+    return check_launch();
+}
+
+size_t dmcf_grid_pos_workspace_bytes_batched(int64_t n_points, int64_t batch) {
+    if (n_points < 0 || batch < 1 || batch > kGridMaxBatch) return 0;
+    return grid_batch_layout(n_points, batch).total;
+}
+
+int dmcf_grid_pos_bounds_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
+                                 const float* voxel_size, int centralize, const float* centers, int pad, float hyst,
+                                 void* workspace, size_t workspace_bytes, dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GridParams p;
+    if (batch < 1 || !row_splits) return DMCF_EINVAL;
+    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
+    if (rc != DMCF_OK) return rc;
+    if (batch > kGridMaxBatch) return DMCF_EUNSUPPORTED;
+    if (!workspace || ((uintptr_t)workspace & 255)) return DMCF_EINVAL;
+    const GridBatchLayout L = grid_batch_layout(n_points, batch);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    char* ws = (char*)workspace;
+    GridHeader* hs = (GridHeader*)(ws + L.off_headers);
+    if (p.centralize) {
+        double* part = (double*)(ws + L.off_part);
+        if (!centers)
+            hipLaunchKernelGGL(grid_sum_batched, dim3(L.nbx, (unsigned)batch), dim3(256), 0, stream, positions, row_splits, part);
+        hipLaunchKernelGGL(grid_center_batched, dim3((unsigned)batch), dim3(64), 0, stream, part, L.nbx, row_splits, centers, hs);
+    }
+    float* fpart = (float*)(ws + L.off_part);
+    hipLaunchKernelGGL(grid_extrema_batched, dim3(L.nbx, (unsigned)batch), dim3(256), 0, stream, p, hs, row_splits, fpart);
+    hipLaunchKernelGGL(grid_finish_bounds_batched, dim3((unsigned)batch), dim3(64), 0, stream, p, fpart, L.nbx, row_splits, hs);
+    hipLaunchKernelGGL(grid_cell_offsets, dim3(1), dim3(64), 0, stream, hs, batch, (int64_t*)(ws + L.off_celloff));
+    return check_launch();
+}
+
+int dmcf_grid_pos_count_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
+                                const float* voxel_size, int centralize, int pad, float hyst, void* workspace,
+                                size_t workspace_bytes, void* cell_table, int64_t table_cells, int64_t* out_row_splits,
+                                dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GridParams p;
+    if (batch < 1 || !row_splits || !out_row_splits) return DMCF_EINVAL;
+    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
+    if (rc != DMCF_OK) return rc;
+    if (batch > kGridMaxBatch) return DMCF_EUNSUPPORTED;
+    if (!workspace || ((uintptr_t)workspace & 255) || (table_cells != 0 && !cell_table)) return DMCF_EINVAL;
+    if (table_cells < 0 && ((-table_cells) & (-table_cells - 1))) return DMCF_EINVAL;  // hashed: a power of two of slots
+    const GridBatchLayout L = grid_batch_layout(n_points, batch);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    char* ws = (char*)workspace;
+    GridHeader* hs = (GridHeader*)(ws + L.off_headers);
+    const int64_t* cell_off = (const int64_t*)(ws + L.off_celloff);
+    uint32_t* first = (uint32_t*)cell_table;
+    int32_t* counts = (int32_t*)(ws + L.off_counts);
+    int64_t* row_off = (int64_t*)(ws + L.off_rowoff);
+    const int64_t rows = 2 * n_points;
+    const size_t table_bytes = table_cells >= 0 ? (size_t)table_cells * 4 : (size_t)(-table_cells) * 12;
+    if (table_bytes > 0 && hipMemsetAsync(first, 0xff, table_bytes, stream) != hipSuccess) return DMCF_ELAUNCH;
+    if (rows > 0) {
+        const unsigned g = (unsigned)((rows + 255) / 256);
+        hipLaunchKernelGGL((grid_pass_batched<0>), dim3(g), dim3(256), 0, stream, p, hs, row_splits, (int)batch, cell_off, first,
+                           counts, (const int64_t*)nullptr, (float*)nullptr, (int64_t)0, table_cells);
+        hipLaunchKernelGGL((grid_pass_batched<1>), dim3(g), dim3(256), 0, stream, p, hs, row_splits, (int)batch, cell_off, first,
+                           counts, (const int64_t*)nullptr, (float*)nullptr, (int64_t)0, table_cells);
+    }
+    rc = scan_counts_to_row_splits(counts, row_off, rows, ws + L.off_scan, L.total - L.off_scan, stream);
+    if (rc != DMCF_OK) return rc;
+    hipLaunchKernelGGL(grid_store_totals_batched, dim3((unsigned)((batch + 256) / 256)), dim3(256), 0, stream, row_off, row_splits,
+                       batch, hs, out_row_splits);
+    return check_launch();
+}
+
+int dmcf_grid_pos_write_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
+                                const float* voxel_size, int centralize, int pad, float hyst, void* workspace,
+                                size_t workspace_bytes, const void* cell_table, int64_t table_cells, float* out,
+                                int64_t out_capacity, dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GridParams p;
+    if (batch < 1 || !row_splits) return DMCF_EINVAL;
+    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
+    if (rc != DMCF_OK) return rc;
+    if (batch > kGridMaxBatch) return DMCF_EUNSUPPORTED;
+    if (!workspace || ((uintptr_t)workspace & 255) || out_capacity < 0 || (out_capacity > 0 && (!out || !cell_table)))
+        return DMCF_EINVAL;
+    const GridBatchLayout L = grid_batch_layout(n_points, batch);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    char* ws = (char*)workspace;
+    const int64_t rows = 2 * n_points;
+    if (rows > 0 && out_capacity > 0) {
+        const unsigned g = (unsigned)((rows + 255) / 256);
+        hipLaunchKernelGGL((grid_pass_batched<2>), dim3(g), dim3(256), 0, stream, p, (const GridHeader*)(ws + L.off_headers),
+                           row_splits, (int)batch, (const int64_t*)(ws + L.off_celloff), (uint32_t*)cell_table,
                            (int32_t*)(ws + L.off_counts), (const int64_t*)(ws + L.off_rowoff), out, out_capacity, table_cells);
     }
     return check_launch();

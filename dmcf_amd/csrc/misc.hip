@@ -259,6 +259,52 @@ __global__ void aabb_finish(const float* __restrict__ part, int nblocks, float* 
     }
 }
 
+// dmcf_points_aabb_batched: one workgroup per item of a batch (blockIdx.x = item), out[item * 6 ..] as aabb_finish writes them.
+// min / max do not depend on the order, so an item's bounds are those of dmcf_points_aabb on its slice, bit for bit; an EMPTY
+// item gives +3.0e38 / -3.0e38, the model's "no fluid" box (models/pbf_model.py), not +-inf.  Meant for the items of a
+// training batch (up to ~1e5 points each): a larger item is one workgroup's strided loop where dmcf_points_aabb spreads
+// it over up to 1024 blocks.
+__global__ __launch_bounds__(256) void aabb_batched(const float* __restrict__ pts, const int64_t* __restrict__ rs,
+                                                    float* __restrict__ out) {
+    const int64_t b0 = rs[blockIdx.x], e0 = rs[blockIdx.x + 1];
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool bad[3] = {false, false, false};
+    for (int64_t i = b0 + threadIdx.x; i < e0; i += 256) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float v = pts[3 * i + a];
+            mn[a] = fminf(mn[a], v);
+            mx[a] = fmaxf(mx[a], v);
+            bad[a] |= v != v;
+        }
+    }
+    __shared__ float red[3][3][4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float b = bad[a] ? 1.0f : 0.0f;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            mn[a] = fminf(mn[a], __shfl_xor(mn[a], d, kWave));
+            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d, kWave));
+            b = fmaxf(b, __shfl_xor(b, d, kWave));
+        }
+        if (lane_id() == 0) {
+            red[0][a][threadIdx.x >> 6] = mn[a];
+            red[1][a][threadIdx.x >> 6] = mx[a];
+            red[2][a][threadIdx.x >> 6] = b;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        float* o = out + (size_t)blockIdx.x * 6;
+        const bool b = fmaxf(fmaxf(red[2][a][0], red[2][a][1]), fmaxf(red[2][a][2], red[2][a][3])) > 0.0f;
+        const bool empty = e0 <= b0;
+        o[a] = b ? NAN : empty ? 3.0e38f : fminf(fminf(red[0][a][0], red[0][a][1]), fminf(red[0][a][2], red[0][a][3]));
+        o[3 + a] = b ? NAN : empty ? -3.0e38f : fmaxf(fmaxf(red[1][a][0], red[1][a][1]), fmaxf(red[1][a][2], red[1][a][3]));
+    }
+}
+
 __global__ __launch_bounds__(256) void reduce_subarrays_sum_kernel(const float* __restrict__ values,
                                                                    const int64_t* __restrict__ row_splits,
                                                                    int64_t n_rows, float* __restrict__ out) {
@@ -281,7 +327,7 @@ __global__ __launch_bounds__(256) void reduce_subarrays_sum_kernel(const float* 
 
 extern "C" {
 
-int dmcf_version(void) { return 22000; }  // 2.0.0: round 2 removed dmcf_cconv_geometry and the geometry field of dmcf_cconv_args; 2.1.0: filter_tile_mask; 2.2.0: DMCF_FLAG_SKIP_SELF; 2.3.0: row_length_hint (splat F); 2.4.0: dmcf_points_aabb; 2.5.0: DMCF_FLAG_FILTER_PACKED, row_length_hint = 1 (splat H); 2.6.0: dmcf_cconv_scatter_* (splat S), hashed grid_pos table (table_cells < 0); 2.7.0: dmcf_radius_search_count / _write (a radius per query), dmcf_cconv_forward_extents / dmcf_cconv_extents_kernel_name (individual extents); 2.8.0: dmcf_invert_neighbors_list, dmcf_cconv_backward (training); 2.9.0: dmcf_nn_distance, dmcf_approx_match, dmcf_match_cost, dmcf_emd (validation metrics); 2.10.0: dmcf_neighbor_dense_forward / _backward / _kernel_names (PointNet); 2.11.0: dmcf_adam_step (training loop); 2.12.0: dmcf_raster_workspace_bytes / _count / dmcf_raster_discs (renderer); 2.13.0: dmcf_nn_distance_backward, dmcf_match_cost_backward, dmcf_emd_with_levels, dmcf_emd_backward, dmcf_gather_point_backward (metric gradients); 2.14.0: dmcf_frs_window_sum_backward (differentiable density); 2.15.0: dmcf_cconv_backward_extents, dmcf_cconv_backward_extents_kernel_names (training through per-point extents); 2.16.0: dmcf_lattice_conv_backward, dmcf_lattice_conv_backward_workspace_bytes (training through the lattice form); 2.17.0: dmcf_sph1d_rollout (the column datasets' 1-D SPH solver); 2.18.0: DMCF_FRS_METRIC_LINF, dmcf_sparse_conv_forward / _backward / _backward_workspace_bytes / _kernel_names (SparseConv, SparseConvTranspose); 2.19.0: dmcf_cconv_scatter_backward, dmcf_cconv_scatter_backward_workspace_bytes (training through the particles -> lattice layers); 2.20.0: dmcf_frs_workspace_bytes_batched, dmcf_frs_build_batched, dmcf_frs_count_batched / _write_batched, dmcf_radius_search_count_batched / _write_batched (points_row_splits / queries_row_splits in both searches)
+int dmcf_version(void) { return 22100; }  // 2.0.0: round 2 removed dmcf_cconv_geometry and the geometry field of dmcf_cconv_args; 2.1.0: filter_tile_mask; 2.2.0: DMCF_FLAG_SKIP_SELF; 2.3.0: row_length_hint (splat F); 2.4.0: dmcf_points_aabb; 2.5.0: DMCF_FLAG_FILTER_PACKED, row_length_hint = 1 (splat H); 2.6.0: dmcf_cconv_scatter_* (splat S), hashed grid_pos table (table_cells < 0); 2.7.0: dmcf_radius_search_count / _write (a radius per query), dmcf_cconv_forward_extents / dmcf_cconv_extents_kernel_name (individual extents); 2.8.0: dmcf_invert_neighbors_list, dmcf_cconv_backward (training); 2.9.0: dmcf_nn_distance, dmcf_approx_match, dmcf_match_cost, dmcf_emd (validation metrics); 2.10.0: dmcf_neighbor_dense_forward / _backward / _kernel_names (PointNet); 2.11.0: dmcf_adam_step (training loop); 2.12.0: dmcf_raster_workspace_bytes / _count / dmcf_raster_discs (renderer); 2.13.0: dmcf_nn_distance_backward, dmcf_match_cost_backward, dmcf_emd_with_levels, dmcf_emd_backward, dmcf_gather_point_backward (metric gradients); 2.14.0: dmcf_frs_window_sum_backward (differentiable density); 2.15.0: dmcf_cconv_backward_extents, dmcf_cconv_backward_extents_kernel_names (training through per-point extents); 2.16.0: dmcf_lattice_conv_backward, dmcf_lattice_conv_backward_workspace_bytes (training through the lattice form); 2.17.0: dmcf_sph1d_rollout (the column datasets' 1-D SPH solver); 2.18.0: DMCF_FRS_METRIC_LINF, dmcf_sparse_conv_forward / _backward / _backward_workspace_bytes / _kernel_names (SparseConv, SparseConvTranspose); 2.19.0: dmcf_cconv_scatter_backward, dmcf_cconv_scatter_backward_workspace_bytes (training through the particles -> lattice layers); 2.20.0: dmcf_frs_workspace_bytes_batched, dmcf_frs_build_batched, dmcf_frs_count_batched / _write_batched, dmcf_radius_search_count_batched / _write_batched (points_row_splits / queries_row_splits in both searches); 2.21.0: dmcf_grid_pos_workspace_bytes_batched, dmcf_grid_pos_bounds_batched / _count_batched / _write_batched, dmcf_points_aabb_batched (grid_pos and the fluid box of a batch of point sets)
 
 const char* dmcf_error_string(int code) {
     switch (code) {
@@ -326,6 +372,14 @@ int dmcf_points_aabb(const float* points, int64_t n, float* out, void* workspace
     const int nb = (int)(want < 1 ? 1 : (want > dmcf::kAabbBlocks ? dmcf::kAabbBlocks : want));
     hipLaunchKernelGGL(dmcf::aabb_partial, dim3(nb), dim3(256), 0, (hipStream_t)stream, points, n, (float*)workspace);
     hipLaunchKernelGGL(dmcf::aabb_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)workspace, nb, out);
+    return dmcf::check_launch();
+}
+
+int dmcf_points_aabb_batched(const float* points, int64_t n, const int64_t* row_splits, int64_t batch, float* out,
+                             dmcf_stream_t stream) {
+    if (batch < 1 || n < 0 || !out || !row_splits || (n > 0 && !points)) return DMCF_EINVAL;
+    if (batch > 0x7fffffffLL) return DMCF_EUNSUPPORTED;
+    hipLaunchKernelGGL(dmcf::aabb_batched, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, points, row_splits, out);
     return dmcf::check_launch();
 }
 

@@ -101,7 +101,10 @@ class BaseModel(PlainAttributes, torch.nn.Module):
     def recording(self):
         """Does a call now record autograd history (grad mode on and some weight requires grad)?  Weights are built with
         requires_grad=False; ``model.requires_grad_(True)`` enables training.  While recording, the models take their unfused,
-        out-of-place forms (the fused epilogues and paired launches have no backward)."""
+        out-of-place forms (the fused epilogues and paired launches have no backward).  A batched step (PBFNet.step_batched)
+        takes the same forms whether it records or not: the fused forms know nothing of items."""
+        if getattr(self, "_batch", None) is not None:
+            return True
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
     def record_lattice_form(self, on=True):

@@ -18,6 +18,8 @@ _FUSE_EPILOGUE = os.environ.get("DMCF_FUSE_EPILOGUE", "1") != "0"
 
 
 class HRNet(PBFNet):
+    batched_step_supported = True
+
     def __init__(self, name="HRNet", layer_channels=[[16], [32], [32], [3]], window=None, window_dens=None,
                  circular=False, add_merge=False, out_activation=None, **kwargs):
         self.layer_channels = layer_channels

@@ -41,6 +41,52 @@ def align_vector(v0, v1):
     return torch.eye(3, device=v0.device) + vx + (vx @ vx) / (1 + c)
 
 
+def _row_splits_of(counts, device):
+    host = [0]
+    for c in counts:
+        host.append(host[-1] + int(c))
+    return ops.RowSplits(host, torch.tensor(host, dtype=torch.int64, device=device))
+
+
+def _item_of_row(rs):
+    """int64 [n]: the item of every row of a set with row splits ``rs`` (sizes known on the host: no round trip)."""
+    counts = rs.dev[1:] - rs.dev[:-1]
+    return torch.repeat_interleave(torch.arange(counts.shape[0], device=rs.dev.device), counts, output_size=rs.host[-1])
+
+
+def _rotate_rows(x, R, item):
+    """Row i of ``x`` [n, 3] times R[item[i]] (R: [batch, 3, 3]): ``x_b @ R_b`` for every item's rows."""
+    return (x.unsqueeze(2) * R.index_select(0, item)).sum(dim=1)
+
+
+class _BatchStep:
+    """What one step_batched knows about its point sets: the row splits of every position tensor of the step, by tensor
+    identity (the entry keeps the tensor alive, so an id is not reused within the step), and one batched search structure
+    per (point set, radius), built when a layer first searches that set and handed to every later one."""
+
+    def __init__(self):
+        self._splits = {}
+        self._tables = {}
+
+    def register(self, tensor, rs):
+        self._splits[id(tensor)] = (tensor, rs)
+
+    def splits_of(self, tensor):
+        entry = self._splits.get(id(tensor))
+        return entry[1] if entry is not None else None
+
+    def table(self, points, radius, n_queries):
+        """The batched search structure of a registered point set for ``radius``, sized for the largest point set registered
+        so far as queries (built again only if a later, larger query set asks)."""
+        key = (id(points), float(radius))
+        table = self._tables.get(key)
+        if table is None or table.n_queries_capacity < n_queries:
+            m = max([n_queries] + [t.shape[0] for t, _ in self._splits.values()])
+            table = self._tables[key] = ops.build_spatial_hash_table(points.detach(), radius, n_queries=m,
+                                                                     points_row_splits=self.splits_of(points))
+        return table
+
+
 class PBFNet(BaseModel):
     def __init__(self, name="PBFNet", kernel_size=[4, 4, 4], channels=16, strides=[1], particle_radii=[0.05],
                  coordinate_mapping="ball_to_cube_volume_preserving", interpolation="linear", window=None,
@@ -149,6 +195,8 @@ class PBFNet(BaseModel):
         return conv
 
     conv_hook = None
+    _batch = None  # the _BatchStep of a running step_batched (apply_conv and recording() read it); None otherwise
+    batched_step_supported = False  # (HRNet and SymNet: the trunks whose every convolution goes through apply_conv)
     ghost_prefetch = None  # set together with conv_hook by the sharded driver: see HRNet.forward
     # The sharded driver (dmcf_amd/parallel.py: ShardedSimulator) installs itself here for the duration of a step; preprocess asks
     # it for the three things that need other ranks -- fluid_bounds(mn, mx), begin(all_pos, pos, box), dilated_pos(base) -- and
@@ -162,6 +210,17 @@ class PBFNet(BaseModel):
         ``widest_extent``: the largest extent of the calls that read the same ``feats`` (a hint for that hook)."""
         if self.conv_hook is not None:
             return self.conv_hook(conv, feats, inp_pos, out_pos, extent, widest_extent)
+        if self._batch is not None:
+            # a batched step: the row splits of the two point sets, looked up by tensor identity in the step's table
+            irs, ors = self._batch.splits_of(inp_pos), self._batch.splits_of(out_pos)
+            if irs is None or ors is None:
+                # (an un-batched call on the concatenated rows would gather across items: plausible and wrong)
+                raise RuntimeError("step_batched: a convolution between position tensors the step did not register "
+                                   "(a copy of a point set? the table is keyed by tensor identity)")
+            radius = float(np.float32(0.5) * np.float32(extent))
+            return conv(feats, inp_pos, out_pos, extent, None,
+                        fixed_radius_search_hash_table=self._batch.table(inp_pos, radius, out_pos.shape[0]),
+                        inp_positions_row_splits=irs, out_positions_row_splits=ors)
         return conv(feats, inp_pos, out_pos, extent, None)
 
     def integrate_pos_vel(self, pos1, vel1, acc1=None):
@@ -398,6 +457,187 @@ class PBFNet(BaseModel):
                 return ops.reduce_subarrays_sum((idx < n).to(torch.float32), rs)[:n]
         self._fluid_counts = count
         return out[:, :co].contiguous(), out[:, co:].contiguous()
+
+    # -- a batch of samples in one step ---------------------------------------------------------------------------------------
+    def _check_batched_step(self, vel_corr=None):
+        """NotImplementedError for everything a batched step does not do -- before anything is launched."""
+        def no(what):
+            raise NotImplementedError(f"step_batched: {what}")
+        if not self.batched_step_supported:
+            no(f"{type(self).__name__} (HRNet and SymNet have a batched step)")
+        if self.shard is not None or self.conv_hook is not None:
+            no("a sharded model")
+        if vel_corr is not None:
+            no("vel_corr")
+        if not self.use_bnds:
+            no("use_bnds=False")
+        if self.dens_feats or self.pres_feats or self.dens_norm:
+            no("dens_feats / pres_feats / dens_norm (window_sum has no batched form)")
+        if self.equivar:
+            no("equivar")
+        if self.use_pre_adv:
+            no("use_pre_adv")
+        if self.voxel_size is None and any(s != 1 for s in self.strides):
+            no("farthest-point-sampled levels (strides without voxel_size)")
+
+    def step_batched(self, items, training=True, vel_corr=None, **kwargs):
+        """One model step for a BATCH of samples in one pass of the network: ``items`` is a list of the per-sample inputs
+        ``[pos, vel, acc, feats, box, bfeats]`` of :meth:`call`.  -> (pos2, vel2, fluid_row_splits): the samples' new fluid
+        positions and velocities one after the other, and where each sample's rows are (a list of ints).
+
+        Every point set of the step holds the items one after the other -- the fluid rows, the cropped boundary rows, all_pos
+        = [fluid_0, box_0, fluid_1, box_1, ...] and every grid_pos level -- and every convolution runs with the row splits of
+        its two sets (apply_conv), so a point gathers from points of its own item only: item b's rows are what :meth:`call`
+        computes for item b alone, up to the order of float32 additions in the kernels.  After the call ``pos_correction``,
+        ``num_fluid_neighbors`` (fluid rows, item after item; ``fluid_row_splits``) and ``all_pos`` (``all_row_splits``) hold
+        the batch.  The step's list cache, the fused input convolutions, the paired launches and the epilogue fusions are not
+        taken (as while autograd records), and the grid_pos lattices are not registered: no lattice or scatter form."""
+        self._check_batched_step(vel_corr)
+        if not items:
+            raise ValueError("step_batched: no items")
+        step = _BatchStep()
+        self._batch = step
+        try:
+            d = self._transform_batched(items, step)
+            x = self._preprocess_batched(d, step)
+            x = self.run_forward(x, d, training=training)
+            pos2, vel2 = self._postprocess_batched(x, d, step)
+            pos2, vel2 = self._inv_transform_batched(pos2, vel2, step)
+        finally:
+            self._batch = None
+        self.fluid_row_splits, self.all_row_splits = list(step.fluid.host), list(step.all.host)
+        return pos2, vel2, list(step.fluid.host)
+
+    def _transform_batched(self, items, step):
+        """:meth:`transform` for every item, on the concatenated rows; the rotation of grav_eqvar is one R per item, applied
+        to a row by gathering the R of the row's item."""
+        dev = items[0][0].device
+        cat = lambda k: torch.cat([it[k] for it in items], dim=0)  # noqa: E731
+        some = lambda k: all(it[k] is not None for it in items)  # noqa: E731
+        pos, vel, box, bfeats = cat(0), cat(1), cat(4), cat(5)
+        acc = cat(2) if some(2) else None
+        feats = cat(3) if some(3) else None
+        step.fluid = _row_splits_of([it[0].shape[0] for it in items], dev)
+        step.box_in = _row_splits_of([it[4].shape[0] for it in items], dev)
+        step.item_of_fluid = _item_of_row(step.fluid)
+        step.item_of_box_in = _item_of_row(step.box_in)
+        if "translate" in self.transformation:
+            translate = ops.const_tensor(self.transformation["translate"], torch.float32, dev)
+            pos = pos + translate
+            box = box + translate
+        if "scale" in self.transformation:
+            scale = ops.const_tensor(self.transformation["scale"], torch.float32, dev)
+            pos = pos * scale
+            box = box * scale
+            vel = vel * scale
+            if acc is not None:
+                acc = acc * scale
+        if "grav_eqvar" in self.transformation:
+            grav_eqvar = ops.const_tensor(self.transformation["grav_eqvar"], torch.float32, dev)
+            first = step.fluid.host  # (an item without fluid has no acceleration to align with: its rows do not exist either)
+            step.R = torch.stack([align_vector(grav_eqvar, acc[first[b]]) if first[b + 1] > first[b]
+                                  else torch.eye(3, device=dev) for b in range(len(items))])
+            rot = lambda x, item: _rotate_rows(x, step.R, item)  # noqa: E731
+            pos, vel, acc = rot(pos, step.item_of_fluid), rot(vel, step.item_of_fluid), rot(acc, step.item_of_fluid)
+            box, bfeats = rot(box, step.item_of_box_in), rot(bfeats, step.item_of_box_in)
+        return [pos, vel, acc, feats, box, bfeats]
+
+    def _preprocess_batched(self, data, step):
+        """:meth:`preprocess` with every item's rows in one tensor per point set."""
+        _pos, _vel, acc, feats, box, bfeats = data
+        batch = len(step.fluid.host) - 1
+        pos, vel = self.integrate_pos_vel(_pos, _vel, acc)
+        filter_extent = [float(np.float32(r) * np.float32(2)) for r in self.particle_radii]
+        # the boundary crop, per item: the item's fluid box (an empty item: +3e38 / -3e38, nothing kept) +- 2 r_max
+        mn, mx = ops.points_aabb(pos.detach(), row_splits=step.fluid)
+        lo = (mn - filter_extent[-1]).index_select(0, step.item_of_box_in)
+        hi = (mx + filter_extent[-1]).index_select(0, step.item_of_box_in)
+        fltr = ((box >= lo) & (box <= hi)).all(dim=1)
+        keep = fltr.nonzero().flatten()  # (one nonzero for the whole batch; its rows are in item order)
+        kept = torch.searchsorted(keep, step.box_in.dev)  # the items' row splits in the kept rows
+        step.box = ops.RowSplits(kept.tolist(), kept)
+        box = box.index_select(0, keep)
+        bfeats = bfeats.index_select(0, keep)
+        step.item_of_box = step.item_of_box_in.index_select(0, keep)
+
+        fluid_feats = [torch.ones_like(pos[:, :1])]
+        if self.use_vel:
+            fluid_feats.append(vel)
+        if self.use_acc:
+            if acc is None:
+                raise ValueError("use_acc=True needs per-particle accelerations (pbf_model.py:341-342)")
+            fluid_feats.append(acc)
+        if self.use_feats:
+            fluid_feats.append(feats)
+        box_feats = [torch.ones_like(box[:, :1])]
+        if self.use_box_feats:
+            box_feats.append(bfeats)
+        fluid_feats = torch.cat(fluid_feats, dim=-1)
+        box_feats = torch.cat(box_feats, dim=-1)
+        self.inp_feats = fluid_feats
+        self.inp_bfeats = box_feats
+
+        # all_pos = [fluid_0, box_0, fluid_1, box_1, ...]: row of item b's fluid point i = all[b] + i, of its boundary point j =
+        # all[b] + n_fluid_b + j.  Fluid and boundary rows are reached through these index tensors, never as a prefix.
+        n_f, n_b = pos.shape[0], box.shape[0]
+        all_host = [f + k for f, k in zip(step.fluid.host, step.box.host)]
+        step.all = ops.RowSplits(all_host, step.fluid.dev + step.box.dev)
+        step.fluid_rows = torch.arange(n_f, device=pos.device) + step.box.dev.index_select(0, step.item_of_fluid)
+        step.box_rows = torch.arange(n_b, device=pos.device) + step.fluid.dev.index_select(0, step.item_of_box + 1)
+        perm = torch.empty(n_f + n_b, dtype=torch.int64, device=pos.device)  # all row -> row of cat([fluid, box])
+        perm[torch.cat([step.fluid_rows, step.box_rows])] = torch.arange(n_f + n_b, device=pos.device)
+        interleave = lambda f, b: torch.cat([f, b], dim=0).index_select(0, perm)  # noqa: E731
+        all_pos = interleave(pos, box)
+        self.all_pos = all_pos
+        step.register(pos, step.fluid)
+        step.register(box, step.box)
+        step.register(all_pos, step.all)
+
+        ans_conv = self.apply_conv(self.fluid_convs, fluid_feats * self.part_scale, pos, all_pos, filter_extent[0])
+        step.fluid_nns = self.fluid_convs.nns
+        ans_obs = self.apply_conv(self.obs_convs, box_feats * self.part_scale, box, all_pos, filter_extent[0])
+        ans_dense = interleave(self.fluid_dense(fluid_feats), self.obs_dense(box_feats))
+        fluid_feats = torch.cat([ans_conv, ans_obs, ans_dense], dim=-1)
+
+        dilated_pos, _, idx, level_rs = get_dilated_pos(all_pos, self.strides, voxel_size=self.voxel_size,
+                                                        centralize=self.centralize, pad=self.sample_pad, hyst=self.sample_hyst,
+                                                        row_splits=step.all)
+        for p, rs in zip(dilated_pos, level_rs):
+            step.register(p, rs)
+        self.dilated_pos = dilated_pos
+        self.dilated_row_splits = [list(rs.host) for rs in level_rs]
+        return [dilated_pos, fluid_feats, idx, None]
+
+    def _postprocess_batched(self, prev, data, step):
+        """:meth:`postprocess` with the fluid and boundary rows of the network's output gathered by index."""
+        pos, vel, acc = data[:3]
+        # fluid neighbours per fluid particle: the fluid -> all list at the fluid rows
+        self.num_fluid_neighbors = ops.neighbor_counts(step.fluid_nns).index_select(0, step.fluid_rows)
+        out = prev
+        if out.shape[-1] == 1:
+            out = out.repeat(1, 3)
+        elif out.shape[-1] == 2:
+            out = torch.cat([out, out[:, :1]], dim=-1)
+        out_scale = ops.const_tensor(self.out_scale, torch.float32, pos.device)
+        self.net_output = out
+        self.pos_correction = out_scale * out.index_select(0, step.fluid_rows)
+        self.obs = out_scale * out.index_select(0, step.box_rows)
+        pos2, vel2 = self.integrate_pos_vel(pos, vel, acc)
+        return self.compute_new_pos_vel(pos, vel, pos2, vel2, self.pos_correction)
+
+    def _inv_transform_batched(self, pos, vel, step):
+        dev = pos.device
+        if "grav_eqvar" in self.transformation:
+            Rt = step.R.transpose(1, 2)
+            pos = _rotate_rows(pos, Rt, step.item_of_fluid)
+            vel = _rotate_rows(vel, Rt, step.item_of_fluid)
+        if "scale" in self.transformation:
+            scale = ops.const_tensor([max(float(v), 1e-5) for v in self.transformation["scale"]], torch.float32, dev)
+            pos = pos / scale
+            vel = vel / scale
+        if "translate" in self.transformation:
+            pos = pos - ops.const_tensor(self.transformation["translate"], torch.float32, dev)
+        return pos, vel
 
     def loss_keys(self):
         return self.loss_fn.keys()

@@ -40,5 +40,22 @@ class SymNet(HRNet):
         for conv in self.sym_convs:  # sym_net.py:63-67
             ans = torch.relu(ans)
             conv_in = ans if self.part_scale == 1.0 else ans * self.part_scale
-            ans = self.apply_conv(conv, conv_in, self.all_pos, self.all_pos, ext)
+            if self._batch is not None:
+                ans = self._ascc_batched(conv, conv_in, ext)
+            else:
+                ans = self.apply_conv(conv, conv_in, self.all_pos, self.all_pos, ext)
         return self.act(ans)
+
+    def _ascc_batched(self, conv, feats, extent):
+        """The ASCC layer in a batched step.  The layer itself takes no row splits (symmetric=True raises there), so the step
+        runs the batched search -- the layer's own FixedRadiusSearch, its radius, ignore_query_points -- forms the importance
+        from window_sym and calls the layer on its user-list path, which serves symmetric=True.  A point's neighbours are
+        points of its own item and the list is symmetric within the item, so the antisymmetric filter cancels pair by pair
+        inside every item: the output summed over ONE item's fluid and boundary rows vanishes, as it does for the step of
+        that item alone."""
+        step, pos = self._batch, self.all_pos
+        radius = float(np.float32(0.5) * np.float32(extent))
+        index, row_splits, importance = conv._batched_search(pos, pos, extent, step.all, step.all,
+                                                             step.table(pos, radius, pos.shape[0]))
+        return conv(feats, pos, pos, extent, None, user_neighbors_index=index, user_neighbors_row_splits=row_splits,
+                    user_neighbors_importance=importance)

@@ -246,6 +246,8 @@ def _host_row_splits(row_splits, name):
     """Row splits as given (a sequence, a CPU int64 tensor or a device int64 tensor) -> (tuple of ints, the device tensor or
     None).  A device tensor is read back here: one small synchronising copy."""
     dev = None
+    if isinstance(row_splits, RowSplits):  # (both forms at hand: no copy in either direction)
+        return tuple(row_splits.host), row_splits.dev
     if isinstance(row_splits, torch.Tensor):
         if row_splits.dtype != torch.int64:
             raise TypeError(f"{name} must be int64, got {row_splits.dtype}")
@@ -2070,9 +2072,25 @@ def dense_forward(x, kernel, bias=None, residual=None):
     return out
 
 
-def points_aabb(points):
+def points_aabb(points, row_splits=None):
     """(min, max) over axis 0 of [n, 3] float32 points, two [3] device tensors: the fluid bounds of the boundary crop
-    (models/pbf_model.py:330-336) in two small launches (a torch reduction over the strided columns was 0.2 ms + a transpose)."""
+    (models/pbf_model.py:330-336) in two small launches (a torch reduction over the strided columns was 0.2 ms + a transpose).
+
+    ``row_splits`` (a sequence, a CPU or a device int64 tensor): the bounds of every item of a batch in one launch
+    (dmcf_points_aabb_batched) -> two [batch, 3] tensors; an item's bounds are those of the call on its slice, except that an
+    empty item gives +3.0e38 / -3.0e38 (the model's box of "no fluid") where the un-batched call gives +inf / -inf."""
+    if row_splits is not None:
+        host, dev = _host_row_splits(row_splits, "row_splits")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be [n, 3]")
+        _check_row_splits(host, points.shape[0], "row_splits")
+        L = _lib.lib()
+        points = _dev_f32(points, "points")
+        batch = len(host) - 1
+        out = torch.empty((batch, 6), dtype=torch.float32, device=points.device)
+        _lib.check(L.dmcf_points_aabb_batched(_ptr(points), points.shape[0], _ptr(_row_splits_on(host, dev, points.device)), batch,
+                                              _ptr(out), _stream()), "dmcf_points_aabb_batched")
+        return out[:, :3], out[:, 3:]
     L = _lib.lib()
     points = _dev_f32(points, "points")
     if points.dim() != 2 or points.shape[1] != 3:
@@ -2130,11 +2148,68 @@ class GridTooSparse(RuntimeError):
     the caller uses the sort-based device formulation instead."""
 
 
-def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=None):
+def _grid_too_sparse(cells, n):
+    """Too sparse for the dense cell table (a few particles far from the rest): the hashed table (include/dmcf_hip.h)."""
+    return cells > min(GRID_MAX_CELLS, max(GRID_MIN_CELLS, GRID_MAX_CELLS_PER_POINT * n))
+
+
+def _grid_hash_slots(n, voxel, pad):
+    """Slots of the hashed table: a power of two of at least twice the 2 n n_off candidates."""
+    import numpy as np
+    noff = 1
+    for x in np.asarray(voxel, dtype=np.float32).reshape(3):
+        noff *= (2 + 2 * int(pad)) if x >= 1e-5 else 1
+    return 1 << max(int(4 * n * noff - 1).bit_length(), 10)
+
+
+def _grid_cell_table(capacity, device):
+    if capacity < 0:  # hashed: 4 + 8 bytes per slot
+        return torch.empty(3 * (-capacity), dtype=torch.int32, device=device)
+    return torch.empty(max(capacity, 1), dtype=torch.int32, device=device)
+
+
+def _grid_count_levels(levels, key, count, read_headers, hash_slots):
+    """The count passes of all levels of one grid_pos_many call, with or without row splits, and their host round trips.
+    ``count(lv, capacity)`` enqueues a level's count pass on a table of ``capacity`` cells (< 0: hashed slots);
+    ``read_headers()`` brings every level's "cells", "sparse" and totals to the host.
+
+    A rollout asks for the same levels step after step and their boxes move slowly: with the cell count of the last call as an
+    estimate (+ 1/4, in size classes) the count pass runs BEFORE anything is read, and ONE host round trip brings header and point
+    count of every level; a level whose box outgrew its table is counted again with the exact size (a second round trip, rare)."""
+    est = _GRID_CELLS.get(key)
+    if est is not None and len(est) == len(levels):
+        for lv, c in zip(levels, est):  # (c < 0: the level was sparse at the last call)
+            count(lv, -hash_slots if c < 0 else _size_class(c + c // 4))
+        read_headers()
+        again = [lv for lv in levels if lv["capacity"] >= 0 and (lv["sparse"] or lv["cells"] > lv["capacity"])]
+        for lv in again:
+            count(lv, -hash_slots if lv["sparse"] else lv["cells"])
+        if again:
+            read_headers()
+    else:
+        read_headers()  # (host round trip 1 of 2: every level's header)
+        for lv in levels:
+            count(lv, -hash_slots if lv["sparse"] else lv["cells"])
+        read_headers()  # (host round trip 2 of 2: every level's point count)
+    while len(_GRID_CELLS) > 32:  # (virtual ranks are threads sharing this dict: evict without iterating a dict another thread resizes)
+        try:
+            _GRID_CELLS.pop(next(iter(_GRID_CELLS)), None)
+        except (RuntimeError, StopIteration):
+            break
+    _GRID_CELLS[key] = [-1 if lv["sparse"] else lv["cells"] for lv in levels]
+
+
+def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=None, row_splits=None):
     """``grid_pos`` (utils/tools/losses.py:136-181) for SEVERAL voxel sizes over the same positions -- the coarse levels of one step
     (losses.py:266-272) -- via dmcf_grid_pos_bounds/_count/_write with TWO host round trips for all of them (cells of every level,
     then points of every level) instead of two per level.  -> [(points, (minp, dims) | None), ...].  A level whose box is too sparse
-    for the dense cell table (GRID_MAX_CELLS_PER_POINT) takes the hashed table; GridTooSparse is no longer raised (round 6)."""
+    for the dense cell table (GRID_MAX_CELLS_PER_POINT) takes the hashed table; GridTooSparse is no longer raised (round 6).
+
+    ``row_splits`` (a sequence, a CPU or a device int64 tensor): ``pos`` is a BATCH of point sets, item b = pos[rs[b]:rs[b+1]]
+    (dmcf_grid_pos_*_batched) -> [(points, RowSplits), ...]: every level's points are the concatenation, item after item, of
+    what the un-batched call returns for each slice, bit for bit; ``center``, if given, is [batch, 3]."""
+    if row_splits is not None:
+        return _grid_pos_many_batched(pos, voxel_sizes, centralize, pad, hyst, center, row_splits)
     import numpy as np
     L = _lib.lib()
     pos = _dev_f32(pos, "pos", 3)
@@ -2159,47 +2234,15 @@ def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=No
             if lv["cells"] < 0:
                 raise _lib.DmcfError("grid_pos: positions are not finite")
             # too sparse for the dense cell table (a few particles far from the rest): the hashed table (include/dmcf_hip.h)
-            lv["sparse"] = lv["cells"] > min(GRID_MAX_CELLS, max(GRID_MIN_CELLS, GRID_MAX_CELLS_PER_POINT * n))
-
-    noff = 1
-    for x in np.asarray(voxel_sizes[0], dtype=np.float32).reshape(3):
-        noff *= (2 + 2 * int(pad)) if x >= 1e-5 else 1
-    hash_slots = 1 << max(int(4 * n * noff - 1).bit_length(), 10)  # >= twice the 2 n noff candidates
+            lv["sparse"] = _grid_too_sparse(lv["cells"], n)
 
     def count(lv, capacity):
-        if capacity < 0:  # hashed: 4 + 8 bytes per slot
-            lv["table"] = torch.empty(3 * (-capacity), dtype=torch.int32, device=pos.device)
-        else:
-            lv["table"] = torch.empty(max(capacity, 1), dtype=torch.int32, device=pos.device)
-        lv["capacity"] = capacity
+        lv["table"], lv["capacity"] = _grid_cell_table(capacity, pos.device), capacity
         _lib.check(L.dmcf_grid_pos_count(_ptr(pos), n, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
                                          _ptr(lv["table"]), capacity, _stream()), "dmcf_grid_pos_count")
 
-    # A rollout asks for the same levels step after step and their boxes move slowly: with the cell count of the last call as an
-    # estimate (+ 1/4, in size classes) the count pass runs BEFORE anything is read, and ONE host round trip brings header and point
-    # count of every level; a level whose box outgrew its table is counted again with the exact size (a second round trip, rare).
     key = (tuple(tuple(float(x) for x in lv["vs"]) for lv in levels), bool(centralize), int(pad), float(hyst))
-    est = _GRID_CELLS.get(key)
-    if est is not None and len(est) == len(levels):
-        for lv, c in zip(levels, est):  # (c < 0: the level was sparse at the last call)
-            count(lv, -hash_slots if c < 0 else _size_class(c + c // 4))
-        read_headers()
-        again = [lv for lv in levels if lv["capacity"] >= 0 and (lv["sparse"] or lv["cells"] > lv["capacity"])]
-        for lv in again:
-            count(lv, -hash_slots if lv["sparse"] else lv["cells"])
-        if again:
-            read_headers()
-    else:
-        read_headers()  # (host round trip 1 of 2: every level's header)
-        for lv in levels:
-            count(lv, -hash_slots if lv["sparse"] else lv["cells"])
-        read_headers()  # (host round trip 2 of 2: every level's point count)
-    while len(_GRID_CELLS) > 32:  # (virtual ranks are threads sharing this dict: evict without iterating a dict another thread resizes)
-        try:
-            _GRID_CELLS.pop(next(iter(_GRID_CELLS)), None)
-        except (RuntimeError, StopIteration):
-            break
-    _GRID_CELLS[key] = [-1 if lv["sparse"] else lv["cells"] for lv in levels]
+    _grid_count_levels(levels, key, count, read_headers, _grid_hash_slots(n, voxel_sizes[0], pad))
     totals = [lv["total"] for lv in levels]
     res = []
     for lv, total in zip(levels, totals):
@@ -2219,10 +2262,89 @@ def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=No
     return res
 
 
-def grid_pos(pos, voxel_size, centralize=False, pad=0, hyst=0.1, center=None, return_box=False):
+class RowSplits:
+    """Row splits in both forms: ``host`` a tuple of batch + 1 ints, ``dev`` the same as an int64 device tensor.  Every
+    ``row_splits`` argument takes one, and then copies nothing to validate it.  A batched ``grid_pos`` returns its output row
+    splits as one (``dev``: what the count pass wrote; ``sparse``: whether the call took the hashed cell table)."""
+
+    def __init__(self, host, dev, sparse=False):
+        self.host, self.dev, self.sparse = tuple(host), dev, sparse
+
+
+def _grid_pos_many_batched(pos, voxel_sizes, centralize, pad, hyst, center, row_splits):
+    """grid_pos_many with row splits: the same two host round trips for all levels and all items -- the first brings every
+    item's header (its cells), the second every item's point count, which IS the output row splits.  The lattices are not
+    registered with dmcf_amd/lattice.py: the lattice and scatter forms of ContinuousConv know nothing of items."""
+    import numpy as np
+    host, dev = _host_row_splits(row_splits, "row_splits")  # (every host-side check before a device is touched)
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pos must be [n, 3]")
+    _check_row_splits(host, pos.shape[0], "row_splits")
+    batch = len(host) - 1
+    if center is not None and tuple(center.shape) != (batch, 3):
+        raise ValueError(f"center must be [batch, 3] = [{batch}, 3] with row_splits, got {tuple(center.shape)}")
+    L = _lib.lib()
+    pos = _dev_f32(pos, "pos", 3)
+    n = pos.shape[0]
+    rs = _row_splits_on(host, dev, pos.device)
+    cen = _dev_f32(center, "center") if center is not None else None
+    cflag = 1 if centralize else 0
+    ws_bytes = L.dmcf_grid_pos_workspace_bytes_batched(n, batch)
+    if ws_bytes == 0:
+        raise _lib.DmcfError(f"grid_pos: a batch of {batch} items is not supported")
+    levels = []
+    for v in voxel_sizes:
+        vs = (ctypes.c_float * 3)(*[float(x) for x in np.asarray(v, dtype=np.float32).reshape(3)])
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
+        _lib.check(L.dmcf_grid_pos_bounds_batched(_ptr(pos), n, _ptr(rs), batch, vs, cflag, _ptr(cen) if cen is not None else None,
+                                                  int(pad), float(hyst), _ptr(ws), ws_bytes, _stream()),
+                   "dmcf_grid_pos_bounds_batched")
+        levels.append(dict(vs=vs, ws=ws, ors=torch.empty(batch + 1, dtype=torch.int64, device=pos.device)))
+
+    def read_headers():
+        hdrs = torch.stack([lv["ws"][0:64 * batch] for lv in levels]).cpu().view(torch.int64).reshape(len(levels), batch, 8)
+        for lv, hdr in zip(levels, hdrs):
+            cells, totals = hdr[:, 3].tolist(), hdr[:, 4].tolist()
+            if any(c < 0 for c in cells):
+                raise _lib.DmcfError("grid_pos: positions are not finite")
+            lv["cells"] = sum(cells)  # the dense table holds every item's own box, one after the other
+            lv["totals"] = totals
+            # (the sparse rule of the un-batched call, applied to the call: all cells against all points)
+            lv["sparse"] = _grid_too_sparse(lv["cells"], n)
+
+    def count(lv, capacity):
+        lv["table"], lv["capacity"] = _grid_cell_table(capacity, pos.device), capacity
+        _lib.check(L.dmcf_grid_pos_count_batched(_ptr(pos), n, _ptr(rs), batch, lv["vs"], cflag, int(pad), float(hyst),
+                                                 _ptr(lv["ws"]), ws_bytes, _ptr(lv["table"]), capacity, _ptr(lv["ors"]), _stream()),
+                   "dmcf_grid_pos_count_batched")
+
+    # (the estimate path of grid_pos_many, keyed with the batch size: a training loop asks for the same batch step after step)
+    key = (tuple(tuple(float(x) for x in lv["vs"]) for lv in levels), bool(centralize), int(pad), float(hyst), batch)
+    _grid_count_levels(levels, key, count, read_headers, _grid_hash_slots(n, voxel_sizes[0], pad))
+    res = []
+    for lv in levels:
+        out_host = [0]
+        for t in lv["totals"]:
+            out_host.append(out_host[-1] + t)
+        total = out_host[-1]
+        out = torch.empty((total, 3), dtype=torch.float32, device=pos.device)
+        if total:
+            _lib.check(L.dmcf_grid_pos_write_batched(_ptr(pos), n, _ptr(rs), batch, lv["vs"], cflag, int(pad), float(hyst),
+                                                     _ptr(lv["ws"]), ws_bytes, _ptr(lv["table"]), lv["capacity"], _ptr(out), total,
+                                                     _stream()), "dmcf_grid_pos_write_batched")
+        res.append((out, RowSplits(tuple(out_host), lv["ors"], lv["capacity"] < 0)))
+    return res
+
+
+def grid_pos(pos, voxel_size, centralize=False, pad=0, hyst=0.1, center=None, return_box=False, row_splits=None):
     """Lattice points of ``grid_pos`` (utils/tools/losses.py:136-181) via dmcf_grid_pos_bounds/_count/_write.
     ``voxel_size``: 3 host floats; ``center``: optional [3] GPU tensor (lattice origin instead of the mean).
-    ``return_box``: -> (points, (minp, dims) | None): the integer box of cells of THIS call (None for an empty result)."""
+    ``return_box``: -> (points, (minp, dims) | None): the integer box of cells of THIS call (None for an empty result).
+    ``row_splits``: a batch of point sets (see grid_pos_many) -> (points, RowSplits); ``center`` is then [batch, 3]."""
+    if row_splits is not None:
+        if return_box:
+            raise NotImplementedError("grid_pos: return_box with row_splits (a batch has one box per item)")
+        return grid_pos_many(pos, [voxel_size], centralize, pad, hyst, center, row_splits=row_splits)[0]
     out, box = grid_pos_many(pos, [voxel_size], centralize, pad, hyst, center)[0]
     return (out, box) if return_box else out
 

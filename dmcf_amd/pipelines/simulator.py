@@ -456,31 +456,68 @@ class Simulator:
         gradients through all of them; the step-t losses against target frame t + pre + 1 (previous frame t + pre), weighted
         by time_w[t]; summed over the samples and divided by sum(time_w) * batch; plus ``w_decay`` sum w^2.  -> the loss
         vector (one entry per model.loss_keys())."""
-        from ..utils.evaluation_helper import merge_dicts
         model = self.model
         if it > 1:
             # simulator.py:386-391 calls model(inputs, vel, training=True): Keras rejects the second positional argument next
             # to training=..., so the reference cannot run it either (every shipped config has iterations: [0])
             raise NotImplementedError("iterations > 1 (the reference's inner iteration loop cannot run)")
         model.requires_grad_(True)
-        rows = []
         tw = torch.as_tensor(np.asarray(time_w, dtype=np.float32), device=self.device)
-        for bi in range(len(data["pos"])):
-            s = self._sample_tensors(data, bi)
-            pos, vel, pre = in_pos[bi], in_vel[bi], int(pres[bi])
-            for t in range(len(time_w)):
-                inputs = [pos, vel, s["grav0"], None, s["box0"], s["boxn0"]]
-                pos, vel = model(inputs, training=True)
-                target = s["pos"]
-                ls = [model.loss([pos, vel], [inputs, self._to_device(target[t + pre + 1]), self._to_device(target[t + pre]), pre])]
-                ls = merge_dicts(ls, lambda x, y: x + y / len(ls))
-                rows.append(torch.stack([torch.as_tensor(v, device=self.device).reshape(()) for v in ls.values()]) * tw[t])
+        if self.cfg.get("train_batched", False):  # pipeline key train_batched (default false): one batched step per window step
+            rows = self._window_rows_batched(data, tw, in_pos, in_vel, pres)
+        else:
+            rows = self._window_rows(data, tw, in_pos, in_vel, pres)
         loss_sum = torch.stack(rows).sum(0) / (tw.sum() * len(data["pos"]))
         w_decay = self.cfg.get("w_decay", 0) or 0
         if w_decay > 0:
             # a scalar added to every entry of the loss vector (simulator.py:407-410: w_decay * reduce_sum of the per-weight sums)
             loss_sum = loss_sum + w_decay * torch.stack([torch.sum(w ** 2) for w in self.optimizer.params]).sum()
         return loss_sum
+
+    def _window_rows(self, data, tw, in_pos, in_vel, pres):
+        """The weighted per-step losses of window_loss, sample after sample."""
+        from ..utils.evaluation_helper import merge_dicts
+        model = self.model
+        rows = []
+        for bi in range(len(data["pos"])):
+            s = self._sample_tensors(data, bi)
+            pos, vel, pre = in_pos[bi], in_vel[bi], int(pres[bi])
+            for t in range(tw.shape[0]):
+                inputs = [pos, vel, s["grav0"], None, s["box0"], s["boxn0"]]
+                pos, vel = model(inputs, training=True)
+                target = s["pos"]
+                ls = [model.loss([pos, vel], [inputs, self._to_device(target[t + pre + 1]), self._to_device(target[t + pre]), pre])]
+                ls = merge_dicts(ls, lambda x, y: x + y / len(ls))
+                rows.append(torch.stack([torch.as_tensor(v, device=self.device).reshape(()) for v in ls.values()]) * tw[t])
+        return rows
+
+    def _window_rows_batched(self, data, tw, in_pos, in_vel, pres):
+        """The weighted per-step losses of window_loss with pipeline key ``train_batched``: each of the len(time_w) steps is ONE
+        model.step_batched over all samples, and every sample's loss is formed by model.loss on that sample's rows of pos2,
+        pos_correction and num_fluid_neighbors.  The same terms as the per-sample loop, sample-major order of the rows aside
+        (they are summed)."""
+        from ..utils.evaluation_helper import merge_dicts
+        model = self.model
+        samples = [self._sample_tensors(data, bi) for bi in range(len(data["pos"]))]
+        pos, vel = list(in_pos), list(in_vel)
+        rows = []
+        for t in range(tw.shape[0]):
+            items = [[pos[bi], vel[bi], s["grav0"], None, s["box0"], s["boxn0"]] for bi, s in enumerate(samples)]
+            pos2, vel2, rs = model.step_batched(items, training=True)
+            correction, neighbors = model.pos_correction, model.num_fluid_neighbors
+            try:
+                for bi, s in enumerate(samples):
+                    a, b, pre = rs[bi], rs[bi + 1], int(pres[bi])
+                    pos[bi], vel[bi] = pos2[a:b], vel2[a:b]
+                    model.pos_correction, model.num_fluid_neighbors = correction[a:b], neighbors[a:b]
+                    target = s["pos"]
+                    ls = [model.loss([pos[bi], vel[bi]], [items[bi], self._to_device(target[t + pre + 1]),
+                                                          self._to_device(target[t + pre]), pre])]
+                    ls = merge_dicts(ls, lambda x, y: x + y / len(ls))
+                    rows.append(torch.stack([torch.as_tensor(v, device=self.device).reshape(()) for v in ls.values()]) * tw[t])
+            finally:
+                model.pos_correction, model.num_fluid_neighbors = correction, neighbors
+        return rows
 
     def train_step(self, data, time_w, it=0, max_err=None, max_dens_err=None):
         """The reference's ``train(data, time_w, it, max_err, max_dens_err)`` (simulator.py:318-414): warm-up, the recorded

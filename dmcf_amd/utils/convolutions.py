@@ -581,7 +581,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         if inp_positions_row_splits is not None or out_positions_row_splits is not None:
             user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance = self._batched_lists(
                 inp_positions, out_positions, extents, inp_positions_row_splits, out_positions_row_splits,
-                user_neighbors_index, user_neighbors_row_splits)
+                user_neighbors_index, user_neighbors_row_splits, fixed_radius_search_hash_table)
         if self.kernel is None:
             with torch.no_grad():
                 self.build(inp_features.shape[-1], inp_features.device)
@@ -595,7 +595,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
 
     @torch.no_grad()
     def _batched_lists(self, inp_positions, out_positions, extents, inp_row_splits, out_row_splits, user_neighbors_index,
-                       user_neighbors_row_splits):
+                       user_neighbors_row_splits, hash_table=None):
         """The neighbour list of a batched call, handed to the layer's user-list path (:341-349): (neighbors_index,
         neighbors_row_splits, neighbors_importance).  The batched search -- FixedRadiusSearch at 0.5 * extent for a scalar
         extent, RadiusSearch at 0.5 * extents for extents of rank 1 -- then the layer's window function on the normalised
@@ -608,6 +608,13 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             raise ValueError("row splits and a user neighbour list exclude each other: the list already says who is whose neighbour")
         if self.symmetric:
             raise NotImplementedError("symmetric=True (ASCC) with row splits is not implemented")
+        return self._batched_search(inp_positions, out_positions, extents, inp_row_splits, out_row_splits, hash_table)
+
+    @torch.no_grad()
+    def _batched_search(self, inp_positions, out_positions, extents, inp_row_splits, out_row_splits, hash_table=None):
+        """The search and the importance of _batched_lists.  ``hash_table``: a batched structure of (inp_positions, 0.5 * extent,
+        inp_row_splits) to search in (ops.build_spatial_hash_table with points_row_splits) -- a model's batched step builds
+        one per point set and radius and hands it to every layer that reads that set (models/pbf_model.py)."""
         splits = dict(points_row_splits=inp_row_splits, queries_row_splits=out_row_splits)
         if _rank1_extents(extents, out_positions):
             if extents.shape[0] != out_positions.shape[0]:
@@ -620,6 +627,8 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                 raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:352-372)")
             extent = float(extents) if isinstance(extents, torch.Tensor) else float(np.float32(extents))
             radius = float(np.float32(0.5) * np.float32(extent))  # :353
+            if hash_table is not None:
+                splits["hash_table"] = hash_table
             nns = self.fixed_radius_search(inp_positions, out_positions, radius, **splits)
             q = nns.neighbors_distance / (np.float32(radius) * np.float32(radius)) if self.window_function is not None else None
         self.__dict__["nns"] = nns

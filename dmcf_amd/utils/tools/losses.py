@@ -77,13 +77,45 @@ def _unique_first_occurrence(idx):
     return uniq[torch.argsort(first)]
 
 
-def grid_pos(pos, voxel_size, centralize=False, pad=0, hyst=0.1, center=None, return_box=False):
+def _grid_pos_items(pos, voxel_size, centralize, pad, hyst, center, row_splits):
+    """grid_pos of a batch of point sets: item b = pos[rs[b]:rs[b+1]] -> (points, ops.RowSplits).  On the device one
+    batched call (csrc/grid.hip, dmcf_grid_pos_*_batched); on host tensors the loop over the items of the host formulation."""
+    from ... import ops
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pos must be [n, 3]")
+    if pos.is_cuda:
+        vs_host = np.asarray(voxel_size.detach().cpu() if isinstance(voxel_size, torch.Tensor) else voxel_size,
+                             dtype=np.float32).reshape(3)
+        return ops.grid_pos(pos, vs_host, centralize=centralize, pad=pad, hyst=hyst, center=center, row_splits=row_splits)
+    host, _ = ops._host_row_splits(row_splits, "row_splits")
+    ops._check_row_splits(host, pos.shape[0], "row_splits")
+    batch = len(host) - 1
+    if center is not None and tuple(center.shape) != (batch, 3):
+        raise ValueError(f"center must be [batch, 3] = [{batch}, 3] with row_splits, got {tuple(center.shape)}")
+    parts, out_host = [], [0]
+    for b in range(batch):
+        item = pos[host[b]:host[b + 1]]
+        if item.shape[0]:  # (an empty item contributes no rows)
+            parts.append(grid_pos(item, voxel_size, centralize=centralize, pad=pad, hyst=hyst,
+                                  center=None if center is None else center[b]))
+        out_host.append(out_host[-1] + (parts[-1].shape[0] if item.shape[0] else 0))
+    out = torch.cat(parts, dim=0) if parts else pos.new_zeros((0, 3))
+    return out, ops.RowSplits(tuple(out_host), torch.tensor(out_host, dtype=torch.int64, device=pos.device), False)
+
+
+def grid_pos(pos, voxel_size, centralize=False, pad=0, hyst=0.1, center=None, return_box=False, row_splits=None):
     """losses.py:136-181: lattice corners of the voxels (edge ``voxel_size``) that contain a particle,
     with +-``hyst`` hysteresis; axes with voxel_size < 1e-5 collapse (2-D / 1-D scenes).
     ``center`` (extension used by the sharded path): the lattice origin to use instead of this call's own
     mean when ``centralize`` -- every rank passes the global mean so all ranks build the same lattice.
     ``return_box``: -> (points, (minp, dims) | None), the integer box of cells (x, y, z) that holds every returned point;
-    None when it is not known on the host (empty result, or the sort-based fallback ran)."""
+    None when it is not known on the host (empty result, or the sort-based fallback ran).
+    ``row_splits``: ``pos`` is a batch of point sets, item b = pos[rs[b]:rs[b+1]] -> (points, ops.RowSplits): the items'
+    lattices one after the other, each exactly what this call returns for the item alone; ``center`` is then [batch, 3]."""
+    if row_splits is not None:
+        if return_box:
+            raise NotImplementedError("grid_pos: return_box with row_splits (a batch has one box per item)")
+        return _grid_pos_items(pos, voxel_size, centralize, pad, hyst, center, row_splits)
     # voxel_size is kept on the host (list / numpy float32) so that the axis collapse test does not
     # force a device round trip; values are float32 like the reference's tf.constant
     vs_host = np.asarray(voxel_size.detach().cpu() if isinstance(voxel_size, torch.Tensor) else voxel_size,
@@ -130,11 +162,48 @@ def grid_pos(pos, voxel_size, centralize=False, pad=0, hyst=0.1, center=None, re
     return (out, None) if return_box else out
 
 
-def get_dilated_pos(pos, strides, voxel_size=None, centralize=False, pad=0, hyst=0.1):
+def _get_dilated_pos_items(pos, strides, voxel_size, centralize, pad, hyst, row_splits):
+    """get_dilated_pos of a batch of point sets -> (dilated_pos, pcnt, idx, level_row_splits): every level holds the items'
+    point sets one after the other, level_row_splits[k] (ops.RowSplits) says where."""
+    from ... import ops
+    host, dev = ops._host_row_splits(row_splits, "row_splits")
+    ops._check_row_splits(host, pos.shape[0], "row_splits")
+    coarse = [s for s in strides if s != 1]
+    if coarse and voxel_size is None:
+        raise NotImplementedError("get_dilated_pos: farthest-point-sampled levels (voxel_size=None) with row_splits")
+    rs_dev = dev if dev is not None and dev.device == pos.device else torch.tensor(host, dtype=torch.int64, device=pos.device)
+    own = ops.RowSplits(host, rs_dev, False)
+    lattices = {}
+    if coarse:
+        vs = voxel_size.detach().cpu().numpy() if isinstance(voxel_size, torch.Tensor) else voxel_size
+        sizes = [np.asarray(vs, dtype=np.float32) * np.float32(s) for s in coarse]  # :266
+        if pos.is_cuda:  # all levels in one go: two host round trips for all of them
+            res = ops.grid_pos_many(pos, sizes, centralize=centralize, pad=pad, hyst=hyst, row_splits=own)
+        else:
+            res = [grid_pos(pos, v, centralize=centralize, pad=pad, hyst=hyst, row_splits=host) for v in sizes]
+        lattices = dict(zip(coarse, res))
+    dilated_pos, pcnt, idx, level_rs = [], [], [], []
+    for stride in strides:
+        if stride == 1:
+            dilated_pos.append(pos)
+            idx.append(None)
+            level_rs.append(own)
+        else:
+            dilated_pos.append(lattices[stride][0])
+            level_rs.append(lattices[stride][1])
+        pcnt.append(dilated_pos[-1].shape[0])
+    return dilated_pos, pcnt, idx, level_rs
+
+
+def get_dilated_pos(pos, strides, voxel_size=None, centralize=False, pad=0, hyst=0.1, row_splits=None):
     """losses.py:249-284 -> (dilated_pos, pcnt, idx).  With ``voxel_size`` every coarse level is a lattice computed from
     the full-resolution set (:266-272; no entry is appended to ``idx`` on that branch, as in the reference); without it
     level k is ``n // stride`` farthest-point samples of level k-1 (:274-282) and ``idx[k]`` the [1, m] sample indices
-    HRNet's cross-scale Dense branch uses."""
+    HRNet's cross-scale Dense branch uses.
+    ``row_splits``: ``pos`` is a batch of point sets -> (dilated_pos, pcnt, idx, level_row_splits), see
+    :func:`_get_dilated_pos_items`; farthest-point-sampled levels raise NotImplementedError."""
+    if row_splits is not None:
+        return _get_dilated_pos_items(pos, strides, voxel_size, centralize, pad, hyst, row_splits)
     from ... import ops
     pcnt, dilated_pos, idx = [], [], []
     lattices = {}

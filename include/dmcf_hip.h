@@ -31,6 +31,9 @@
  *   farthest_point_sample / gather_point (utils/tools/sampling.cu) dmcf_farthest_point_sample / dmcf_gather_point
  *   grid_pos: candidate cells + tf.unique + decode               dmcf_grid_pos_bounds / _count / _write
  *     (utils/tools/losses.py:136-181, called from :266-272)
+ *   grid_pos and the fluid box of a BATCH of point sets          dmcf_grid_pos_bounds_batched / _count_batched /
+ *     (row splits; no reference counterpart: the reference         _write_batched, dmcf_points_aabb_batched (ABI 2.21)
+ *     loops over the samples of a training batch)
  *   SPH1D.step in gen_data's time loop                           dmcf_sph1d_rollout (ABI 2.17: the column
  *     (datasets/column_gen.py:159-186, 305-312)                    datasets' generator)
  *   SparseConv / SparseConvTranspose: FixedRadiusSearch('Linf')  DMCF_FRS_METRIC_LINF, dmcf_sparse_conv_forward /
@@ -640,6 +643,14 @@ int dmcf_dense_forward(const float* x, int64_t n, int32_t k, const float* W, int
 size_t dmcf_points_aabb_workspace_bytes(void);
 int dmcf_points_aabb(const float* points, int64_t n, float* out, void* workspace, size_t workspace_bytes,
                      dmcf_stream_t stream);
+/* ABI 2.21: the box of every item of a batch in one launch.  Item b is points[row_splits[b] .. row_splits[b + 1]) (row_splits:
+ * DEVICE int64 [batch + 1], starting at 0, not decreasing, ending at n -- the caller has validated it); out [batch][6] as above.
+ * A non-empty item's bounds are those of dmcf_points_aabb on its slice, bit for bit (NaN rule included); an EMPTY item gives
+ * +3.0e38 / -3.0e38 -- the model's box of "no fluid" (models/pbf_model.py) -- not +-inf.  One workgroup per item, no workspace:
+ * intended for items of up to ~1e5 points (a training batch); a larger item is a serial strided loop of that one workgroup.
+ * batch < 1: DMCF_EINVAL. */
+int dmcf_points_aabb_batched(const float* points, int64_t n, const int64_t* row_splits, int64_t batch, float* out,
+                             dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Ghost selection of the block-sharded rollout (no reference counterpart: tum-pbs/DMCF has no distributed code -- SURVEY.md
@@ -695,6 +706,37 @@ int dmcf_grid_pos_count(const float* positions, int64_t n_points, const float* v
 int dmcf_grid_pos_write(const float* positions, int64_t n_points, const float* voxel_size, int centralize, int pad,
                         float hyst, void* workspace, size_t workspace_bytes, const void* cell_table, int64_t table_cells,
                         float* out, int64_t out_capacity, dmcf_stream_t stream);
+/*
+ * grid_pos with row splits (ABI 2.21): the three phases for a BATCH of point sets.  Item b is positions[row_splits[b] ..
+ * row_splits[b + 1]); `row_splits` is a DEVICE int64 [batch + 1] array (starts at 0, does not decrease, ends at n_points: the
+ * caller has validated it).  The result is the concatenation, item after item, of what the un-batched phases return for each
+ * item's slice: item b's rows are BIT-IDENTICAL to them, values and order (tf.unique order within the item's own candidate
+ * list).  Empty items are legal and contribute no rows.
+ *   bounds : per item the lattice origin (the item's own mean, summed exactly as the un-batched call sums it; or
+ *            centers[b], `centers` a DEVICE [batch][3] array or NULL) and the item's own integer box ->
+ *            `batch` 64-byte headers at the start of `workspace`, each laid out as above.  An item's cell index is local to
+ *            its own box and offset by the cells of the items before it: two items at the same coordinates never share a cell.
+ *            The caller reads the headers: the dense table has sum_b max(cells_b, 0) uint32; cells_b = -1: item b holds a
+ *            position that is not finite.
+ *   count  : fills the table; header b's `total` = lattice points of item b; out_row_splits (DEVICE int64 [batch + 1]) =
+ *            their exclusive prefix sum, the row splits of the output
+ *   write  : out[out_row_splits[batch], 3]
+ * Hashed table: table_cells = -S as above, the key is the offset cell index (item and cell).  The candidate ranks of all items
+ * share the 32 bits: 2 * n_points * (2 + 2 pad)^3 < 2^32 for the whole batch.  batch < 1: DMCF_EINVAL; batch > 65535:
+ * DMCF_EUNSUPPORTED (the workspace size function then returns 0).  Workspace: dmcf_grid_pos_workspace_bytes_batched.
+ */
+size_t dmcf_grid_pos_workspace_bytes_batched(int64_t n_points, int64_t batch);
+int dmcf_grid_pos_bounds_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
+                                 const float* voxel_size, int centralize, const float* centers, int pad, float hyst,
+                                 void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+int dmcf_grid_pos_count_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
+                                const float* voxel_size, int centralize, int pad, float hyst, void* workspace,
+                                size_t workspace_bytes, void* cell_table, int64_t table_cells, int64_t* out_row_splits,
+                                dmcf_stream_t stream);
+int dmcf_grid_pos_write_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
+                                const float* voxel_size, int centralize, int pad, float hyst, void* workspace,
+                                size_t workspace_bytes, const void* cell_table, int64_t table_cells, float* out,
+                                int64_t out_capacity, dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * farthest_point_sample(npoint, inp[1,n,3]) and gather_point(inp, idx) (utils/tools/sampling.py / sampling.cu:125-201):
