@@ -286,6 +286,7 @@ SYMBOLS = [
     "dmcf_radius_search_count_batched", "dmcf_radius_search_write_batched",
     "dmcf_grid_pos_workspace_bytes_batched", "dmcf_grid_pos_bounds_batched", "dmcf_grid_pos_count_batched",
     "dmcf_grid_pos_write_batched", "dmcf_points_aabb_batched",
+    "dmcf_frs_window_sum_batched", "dmcf_frs_window_sum_backward_batched",
 ]
 
 
@@ -536,6 +537,14 @@ def lib():
                                               c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p]
     L.dmcf_points_aabb_batched.restype = c.c_int
     L.dmcf_points_aabb_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
+    # the window sum and its gradient with row splits (ABI 2.22)
+    L.dmcf_frs_window_sum_batched.restype = c.c_int
+    L.dmcf_frs_window_sum_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_int,
+                                              c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.dmcf_frs_window_sum_backward_batched.restype = c.c_int
+    L.dmcf_frs_window_sum_backward_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int,
+                                                       c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p,
+                                                       c.c_void_p]
     _lib = L
     return L
 

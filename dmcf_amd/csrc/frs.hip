@@ -1064,6 +1064,73 @@ __global__ __launch_bounds__(256) void frs_query_batched(const float* __restrict
     if (!WRITE && lane_id() == 0) counts[qi] = cnt;
 }
 
+// frs_window_sum on a batched structure (ABI 2.22): the query's item as frs_query_batched finds it, the sums over the points
+// of that item's slab only.  item_max (may be NULL): item_max[b] becomes the largest out of item b.  The sums are not
+// negative here (the entry point refuses the one window whose sums can be), so the floats order as their bits do and an
+// integer atomicMax serves; as with max_count in frs_query_padded, only a wave that beats the value currently visible tries.
+// The maximum does not depend on the order of the atomics.
+__global__ __launch_bounds__(256) void frs_window_sum_batched(const float* __restrict__ queries, int64_t m,
+                                                              const int64_t* __restrict__ queries_row_splits, int32_t batch,
+                                                              const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
+                                                              const float4* __restrict__ sorted, float radius, int flags, int window,
+                                                              float* __restrict__ out, int32_t* __restrict__ item_max) {
+    __shared__ uint32_t marks[4][kWin * kWave + kWave];
+    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (qi >= m) return;  // whole wave leaves
+    const int64_t qu = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(qi >> 32)) << 32) |
+                       (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)qi);
+    const int32_t item = __builtin_amdgcn_readfirstlane(frs_item_of(queries_row_splits, batch, qu));
+    const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
+    float wsum = 0.0f;
+    bool redo = false;
+    frs_scan<2, false>(qx, qy, qz, h, cell_start, sorted, radius, flags & DMCF_FRS_IGNORE_QUERY_POINT, 0, nullptr, nullptr, window,
+                       1.0f / (radius * radius), wsum, marks[threadIdx.x >> 6], 0x7fffffff, redo, nullptr, item * h->ncells);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) wsum += __shfl_xor(wsum, d, kWave);
+    if (lane_id() == 0) {
+        out[qi] = wsum;
+        if (item_max) {
+            const int32_t bits = __float_as_int(wsum);  // (>= +0: a sum of non-negative terms; a NaN's bits rank above every number)
+            if (bits > __hip_atomic_load(item_max + item, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(item_max + item, bits);
+        }
+    }
+}
+
+// frs_window_sum_grad on a batched structure (ABI 2.22): the same three sums over the slab of the query's item.  No atomics.
+__global__ __launch_bounds__(256) void frs_window_sum_grad_batched(const float* __restrict__ queries, int64_t m,
+                                                                   const int64_t* __restrict__ queries_row_splits, int32_t batch,
+                                                                   const FrsHeader* __restrict__ h,
+                                                                   const uint32_t* __restrict__ cell_start,
+                                                                   const float4* __restrict__ sorted, float radius, int flags,
+                                                                   int window, const float* __restrict__ coef_q,
+                                                                   const float* __restrict__ coef_p, float* __restrict__ grad) {
+    __shared__ uint32_t marks[4][kWin * kWave + kWave];
+    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (qi >= m) return;
+    const int64_t qu = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(qi >> 32)) << 32) |
+                       (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)qi);
+    const int32_t item = __builtin_amdgcn_readfirstlane(frs_item_of(queries_row_splits, batch, qu));
+    const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
+    FrsGradAcc ga;
+    ga.coef_q = coef_q ? coef_q[qi] : 0.0f;
+    ga.coef_p = coef_p;
+    ga.inv_r2 = 1.0 / ((double)radius * (double)radius);
+    ga.g[0] = ga.g[1] = ga.g[2] = 0.0f;
+    float unused = 0.0f;
+    bool redo = false;
+    frs_scan<3, false>(qx, qy, qz, h, cell_start, sorted, radius, flags & DMCF_FRS_IGNORE_QUERY_POINT, 0, nullptr, nullptr, window,
+                       1.0f / (radius * radius), unused, marks[threadIdx.x >> 6], 0x7fffffff, redo, &ga, item * h->ncells);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) ga.g[a] += __shfl_xor(ga.g[a], d, kWave);
+    }
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) grad[3 * qi + a] = 2.0f * ga.g[a];
+    }
+}
+
 }  // namespace dmcf
 
 
@@ -1400,6 +1467,59 @@ int dmcf_radius_search_write_batched(const float* queries, int64_t m, const int6
                                      int64_t pair_capacity, dmcf_stream_t stream) {
     return frs_search_batched<true, true>(queries, m, queries_row_splits, batch, n, radii, max_radius, flags, workspace, workspace_bytes,
                                           row_splits, neighbors_index, neighbors_distance, pair_capacity, (hipStream_t)stream);
+}
+
+// what the two batched window sums share with frs_search_batched: the flags and the row splits
+static int frs_window_batched_args(int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius, int flags,
+                                   int window, const void* workspace) {
+    if (flags & kO3dFlags) return DMCF_EINVAL;  // the walk emulations know nothing of items
+    if (flags & DMCF_FRS_METRIC_LINF) return DMCF_EUNSUPPORTED;
+    if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
+    if (m < 0 || n < 0 || !workspace || !(radius > 0.0f)) return DMCF_EINVAL;
+    if (!queries_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
+    if (window < DMCF_WINDOW_NONE || window > DMCF_WINDOW_CUBIC_GRAD) return DMCF_EINVAL;
+    return DMCF_OK;
+}
+
+int dmcf_frs_window_sum_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                                float radius, int flags, int window, const void* workspace, size_t workspace_bytes, float* out,
+                                float* item_max, dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int rc = frs_window_batched_args(m, queries_row_splits, batch, n, radius, flags, window, workspace);
+    if (rc != DMCF_OK) return rc;
+    if (m > 0 && (!queries || !out)) return DMCF_EINVAL;
+    if (item_max && window == DMCF_WINDOW_CUBIC_GRAD) return DMCF_EUNSUPPORTED;  // its sums can be negative: see the kernel
+    const FrsLayout L = frs_layout(n, m, batch);
+    if (m > 0 && workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    // (+0.0f is all bits zero: an item without queries keeps it)
+    if (item_max && hipMemsetAsync(item_max, 0, (size_t)batch * 4, stream) != hipSuccess) return DMCF_ELAUNCH;
+    if (m == 0) return DMCF_OK;
+    const char* ws = (const char*)workspace;
+    hipLaunchKernelGGL(frs_window_sum_batched, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, queries, m, queries_row_splits,
+                       (int32_t)batch, (const FrsHeader*)(ws + L.off_header), (const uint32_t*)(ws + L.off_cell_start),
+                       (const float4*)(ws + L.off_sorted), radius, flags, window, out, (int32_t*)item_max);
+    return check_launch();
+}
+
+int dmcf_frs_window_sum_backward_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch,
+                                         int64_t n, float radius, int flags, int window, const float* coef_queries,
+                                         const float* coef_points, const void* workspace, size_t workspace_bytes, float* grad,
+                                         dmcf_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int rc = frs_window_batched_args(m, queries_row_splits, batch, n, radius, flags, window, workspace);
+    if (rc != DMCF_OK) return rc;
+    if (m > 0 && (!queries || !grad)) return DMCF_EINVAL;
+    if (!coef_queries && !coef_points) return DMCF_EINVAL;
+    if (window == DMCF_WINDOW_NONE) return DMCF_EUNSUPPORTED;  // the count has no gradient
+    if (m == 0) return DMCF_OK;
+    const FrsLayout L = frs_layout(n, m, batch);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    const char* ws = (const char*)workspace;
+    hipLaunchKernelGGL(frs_window_sum_grad_batched, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, queries, m,
+                       queries_row_splits, (int32_t)batch, (const FrsHeader*)(ws + L.off_header),
+                       (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radius, flags, window,
+                       coef_queries, coef_points, grad);
+    return check_launch();
 }
 
 }  // extern "C"

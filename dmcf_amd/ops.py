@@ -2457,52 +2457,137 @@ def _window_sum_backward_pairs(points, queries, radius, window, ignore_query_poi
     return gp, gq
 
 
+def _window_sum_batched_impl(points, queries, radius, window, ignore_query_point, hash_table, p_splits, q_splits, want_max):
+    """dmcf_frs_window_sum_batched -> (out, item_max or None, the batched structure over ``points``, the queries' device splits)."""
+    L = _lib.lib()
+    (p_host, p_dev), (q_host, q_dev) = p_splits, q_splits
+    n, m, batch = points.shape[0], queries.shape[0], len(p_host) - 1
+    dev = points.device
+    hash_table = _batched_table(points, radius, m, p_host, p_dev, hash_table)
+    nbytes = L.dmcf_frs_workspace_bytes_batched(n, hash_table.n_queries_capacity, batch)
+    q_rs = _row_splits_on(q_host, q_dev, dev)
+    out = torch.empty(m, dtype=torch.float32, device=dev)
+    item_max = torch.empty(batch, dtype=torch.float32, device=dev) if want_max else None
+    flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(L.dmcf_frs_window_sum_batched(_ptr(queries), m, _ptr(q_rs), batch, n, radius, flags, WINDOWS[window],
+                                             _ptr(hash_table.workspace), nbytes, _ptr(out), _ptr(item_max), _stream()),
+               "dmcf_frs_window_sum_batched")
+    if timer is not None:
+        timer.end("frs_window_sum_batched", dict(n_points=n, n_queries=m, batch=batch), t0)
+    return out, item_max, hash_table, q_rs
+
+
+def window_sum_backward_batched(queries, queries_row_splits, hash_table, radius, window, coef_queries=None, coef_points=None,
+                                ignore_query_point=False):
+    """dmcf_frs_window_sum_backward_batched on the batched structure ``hash_table`` of some concatenated point sets:
+    ``window_sum_backward`` with the sums of a query running over the points of its own item.  ``queries_row_splits``: as for
+    the batched search, with as many items as the structure."""
+    L = _lib.lib()
+    if hash_table.row_splits is None:
+        raise ValueError("hash_table is not a batched structure (build_spatial_hash_table(..., points_row_splits=...))")
+    q_host, q_dev = _host_row_splits(queries_row_splits, "queries_row_splits")
+    _check_row_splits(q_host, queries.shape[0], "queries_row_splits")
+    if len(q_host) != len(hash_table.row_splits):
+        raise ValueError("queries_row_splits and the structure's row splits must have equal lengths (batch + 1)")
+    queries = _dev_f32(queries, "queries", 3)
+    radius = float(radius)
+    if window not in WINDOWS:
+        raise NotImplementedError(f"window {window!r}")
+    n, m, batch = hash_table.points.shape[0], queries.shape[0], len(q_host) - 1
+    if hash_table.n_queries_capacity < m or hash_table.radius != radius:
+        raise ValueError("hash_table was built for fewer queries or another radius")
+    dev = queries.device
+    cq = None if coef_queries is None else _dev_exact(coef_queries, "coef_queries", torch.float32, (m,), dev)
+    cp = None if coef_points is None else _dev_exact(coef_points, "coef_points", torch.float32, (n,), dev)
+    q_rs = _row_splits_on(q_host, q_dev, dev)
+    nbytes = L.dmcf_frs_workspace_bytes_batched(n, hash_table.n_queries_capacity, batch)
+    grad = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    _lib.check(L.dmcf_frs_window_sum_backward_batched(_ptr(queries), m, _ptr(q_rs), batch, n, radius,
+                                                      FRS_IGNORE_QUERY_POINT if ignore_query_point else 0, WINDOWS[window],
+                                                      _ptr(cq), _ptr(cp), _ptr(hash_table.workspace), nbytes, _ptr(grad), _stream()),
+               "dmcf_frs_window_sum_backward_batched")
+    return grad
+
+
 class WindowSumFunction(torch.autograd.Function):
     """Autograd node of ``window_sum``: the gradient w.r.t. both position sets through dmcf_frs_window_sum_backward -- the
     forward's structure serves the query side, one built over the queries the point side; ``same``: the two sets are one tensor
-    and one scan with both coefficients gives the whole gradient (returned for ``points``)."""
+    and one scan with both coefficients gives the whole gradient (returned for ``points``).
+
+    ``batched`` (None, or ((points splits), (queries splits), return_item_max) with each splits a (host, dev) pair): the same
+    on batched structures (dmcf_frs_window_sum_batched / _backward_batched); the point side then takes a batched structure
+    over the queries with the roles of the two row splits swapped.  With return_item_max the node returns (out, item_max),
+    item_max non-differentiable."""
 
     @staticmethod
-    def forward(ctx, points, queries, radius, window, ignore_query_point, hash_table, same):
-        out, table = _window_sum_impl(points, queries, radius, window, ignore_query_point, hash_table)
+    def forward(ctx, points, queries, radius, window, ignore_query_point, hash_table, same, batched=None):
+        ctx.batched = batched
+        item_max = None
+        if batched is None:
+            out, table = _window_sum_impl(points, queries, radius, window, ignore_query_point, hash_table)
+            flags = frs_flags(ignore_query_point)
+        else:
+            out, item_max, table, ctx.q_rs = _window_sum_batched_impl(points, queries, radius, window, ignore_query_point, hash_table,
+                                                                      batched[0], batched[1], batched[2])
+            flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
         if window is None:
             ctx.mark_non_differentiable(out)  # (the count)
         ctx.save_for_backward(points, queries)
-        ctx.radius, ctx.window, ctx.ignore, ctx.table, ctx.same, ctx.flags = radius, window, ignore_query_point, table, same, \
-            frs_flags(ignore_query_point)
+        ctx.radius, ctx.window, ctx.ignore, ctx.table, ctx.same, ctx.flags = radius, window, ignore_query_point, table, same, flags
+        if item_max is not None:
+            ctx.mark_non_differentiable(item_max)
+            return out, item_max
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
+    def backward(ctx, grad_out, *_grad_item_max):
         points, queries = ctx.saved_tensors
         need_p, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        none5 = (None,) * 5
+        rest = (None,) * 6
         if ctx.window is None or not (need_p or need_q):
-            return (None, None) + none5
-        if frs_flags(ctx.ignore) != ctx.flags:
-            raise RuntimeError("DMCF_FRS_SET changed between the forward and the backward of window_sum")
+            return (None, None) + rest
         g = grad_out.contiguous()
         n, m = points.shape[0], queries.shape[0]
+        if ctx.batched is not None:
+            if n == 0 or m == 0:  # no pair
+                return (torch.zeros_like(points) if need_p else None, torch.zeros_like(queries) if need_q else None) + rest
+            (p_host, _), (q_host, _), _ = ctx.batched
+            q_splits = RowSplits(q_host, ctx.q_rs)
+            if ctx.same:
+                return (window_sum_backward_batched(queries, q_splits, ctx.table, ctx.radius, ctx.window, g, g, ctx.ignore),
+                        None) + rest
+            gp = gq = None
+            if need_q:
+                gq = window_sum_backward_batched(queries, q_splits, ctx.table, ctx.radius, ctx.window, g, None, ctx.ignore)
+            if need_p:
+                swapped = build_spatial_hash_table(queries, ctx.radius, n_queries=n, points_row_splits=q_splits)
+                gp = window_sum_backward_batched(points, RowSplits(p_host, ctx.table.row_splits_dev), swapped, ctx.radius, ctx.window,
+                                                 None, g, ctx.ignore)
+            return (gp, gq) + rest
+        if frs_flags(ctx.ignore) != ctx.flags:
+            raise RuntimeError("DMCF_FRS_SET changed between the forward and the backward of window_sum")
         if n == 0 or m == 0:  # no pair
-            return (torch.zeros_like(points) if need_p else None, torch.zeros_like(queries) if need_q else None) + none5
+            return (torch.zeros_like(points) if need_p else None, torch.zeros_like(queries) if need_q else None) + rest
         if search_set() != "distance":
             gp, gq = _window_sum_backward_pairs(points, queries, ctx.radius, ctx.window, ctx.ignore, g, need_p, need_q)
             if ctx.same:
                 gp, gq = gp + gq, None
-            return (gp, gq) + none5
+            return (gp, gq) + rest
         if ctx.same:
-            return (window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, g, ctx.ignore), None) + none5
+            return (window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, g, ctx.ignore), None) + rest
         gp = gq = None
         if need_q:
             gq = window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, None, ctx.ignore)
         if need_p:
             swapped = build_spatial_hash_table(queries, ctx.radius, n_queries=n)
             gp = window_sum_backward(points, swapped, ctx.radius, ctx.window, None, g, ctx.ignore)
-        return (gp, gq) + none5
+        return (gp, gq) + rest
 
 
-def window_sum(points, queries, radius, window=None, ignore_query_point=False, hash_table=None):
+def window_sum(points, queries, radius, window=None, ignore_query_point=False, hash_table=None, points_row_splits=None,
+               queries_row_splits=None, return_item_max=False):
     """dmcf_frs_window_sum: out[q] = sum_{|p - q| <= R} window(|p - q|^2 / R^2) (``window``: a WINDOWS key; None counts
     the neighbours, 'explicit' sums the squared distances).  The fused form of ``compute_density``
     (utils/tools/losses.py:285-306): the candidate scan of the search with the sum inside, no pair list.
@@ -2510,7 +2595,37 @@ def window_sum(points, queries, radius, window=None, ignore_query_point=False, h
     Differentiable in ``points`` and ``queries`` (dmcf_frs_window_sum_backward: the same scan with three sums; the count,
     ``window=None``, is marked non-differentiable).  For the sqrt-based windows a coincident pair contributes no gradient, where
     the reference's autodiff gives NaN.  Under DMCF_FRS_SET=open3d / open3d_corners the backward takes the explicit pair list and
-    torch ops instead: correct, but slow.  Without grad mode or an input that requires grad the call is the plain kernel launch."""
+    torch ops instead: correct, but slow.  Without grad mode or an input that requires grad the call is the plain kernel launch.
+
+    ``points_row_splits`` / ``queries_row_splits`` (both or neither; the rules of the batched ``fixed_radius_search``): the sums
+    of a BATCH of point sets in one call (dmcf_frs_window_sum_batched), a query summing over the points of its own item only.
+    A batched ``hash_table`` built with the same splits is reused.  ``return_item_max=True`` returns ``(out, item_max)`` with
+    ``item_max`` [batch] each item's largest sum (0 for an item without queries; not differentiable; not with 'cubic_grad',
+    whose sums can be negative).  It needs row splits: pass ``[0, n]`` and ``[0, m]`` for one item."""
+    if points_row_splits is not None or queries_row_splits is not None:
+        # host checks first, in the order of the batched search: both or neither, no walk emulation, well-formed splits
+        if points_row_splits is None or queries_row_splits is None:
+            raise NotImplementedError("batched window_sum needs both points_row_splits and queries_row_splits")
+        if SEARCH_SETS[search_set()] != 0:
+            raise NotImplementedError(f"DMCF_FRS_SET={search_set()} has no batched form: the open3d walk emulations know nothing of items")
+        if window not in WINDOWS:
+            raise NotImplementedError(f"window {window!r}")
+        p_splits, q_splits = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
+        same = points is queries
+        if same and p_splits[0] != q_splits[0]:
+            raise ValueError("points is queries, but points_row_splits and queries_row_splits differ")
+        points = _dev_f32(points, "points", 3)
+        queries = points if same else _dev_f32(queries, "queries", 3)
+        radius = float(radius)
+        if not radius > 0:
+            raise ValueError("radius must be positive")
+        batched = (p_splits, q_splits, bool(return_item_max))
+        if _wants_grad(points, queries):
+            return WindowSumFunction.apply(points, queries, radius, window, bool(ignore_query_point), hash_table, same, batched)
+        out, item_max = _window_sum_batched_impl(points, queries, radius, window, ignore_query_point, hash_table, *batched)[:2]
+        return (out, item_max) if return_item_max else out
+    if return_item_max:
+        raise NotImplementedError("return_item_max needs points_row_splits and queries_row_splits")
     same = points is queries
     points = _dev_f32(points, "points", 3)
     queries = points if same else _dev_f32(queries, "queries", 3)

@@ -91,6 +91,43 @@ class steady_steps:
         return False
 
 
+class WarmUpExits:
+    """The host side of the batched warm-up (Simulator.warm_up_batched): which samples are still warming up, and the early
+    exits of simulator.py:325-368 decided per sample exactly as the per-sample loop decides them -- ``max_err`` first, its
+    break skipping the density test; ``p > 0 and err > prev and err > limit``; a previous error updated only when its test
+    was reached.  No device, no tensors."""
+
+    def __init__(self, pre, max_err=None, max_dens_err=None):
+        self.pre = [int(k) for k in pre]
+        self.max_err, self.max_dens_err = max_err, max_dens_err
+        self.prev_err = [0.0] * len(self.pre)
+        self.prev_dens_err = [0.0] * len(self.pre)
+        self.left = [None] * len(self.pre)  # the iteration at which the sample broke out
+
+    def active(self, p):
+        """The samples that take step ``p``: ``pre > p`` and not left."""
+        return [bi for bi, k in enumerate(self.pre) if k > p and self.left[bi] is None]
+
+    def accept(self, p, bi, err=None, dens_err=None):
+        """Sample ``bi``'s errors after step ``p`` -> True: the step's state is taken; False: the sample leaves with the
+        state from before the step."""
+        if self.max_err is not None:
+            if p > 0 and err > self.prev_err[bi] and err > self.max_err:
+                self.left[bi] = p
+                return False
+            self.prev_err[bi] = err
+        if self.max_dens_err is not None:
+            if p > 0 and dens_err > self.prev_dens_err[bi] and dens_err > self.max_dens_err:
+                self.left[bi] = p
+                return False
+            self.prev_dens_err[bi] = dens_err
+        return True
+
+    def pres(self):
+        """What the loop hands on: the iteration of the break, else the last loop index pre - 1 (0 for pre == 0)."""
+        return [max(k - 1, 0) if at is None else at for k, at in zip(self.pre, self.left)]
+
+
 class Simulator:
     def __init__(self, model, dataset=None, name="Simulator", main_log_dir="./logs/", device="cuda", split="train",
                  reserve_gib=None, **kwargs):
@@ -451,6 +488,64 @@ class Simulator:
                 in_vel.append(pr_vel)
         return in_pos, in_vel, pres
 
+    def warm_up_batched(self, data, max_err=None, max_dens_err=None):
+        """:meth:`warm_up` with ONE ``model.step_batched`` per iteration over the samples that are still warming up (pipeline key
+        ``warm_up_batched``): at iteration p those with ``pre > p`` that have not left.  The ``max_err`` errors of all items
+        come from one chain of torch ops on the concatenated rows, the ``max_dens_err`` errors from one batched density_loss
+        (two dmcf_frs_window_sum_batched launches with the per-item maxima), and both are read back in one host copy per
+        iteration.  The exits are decided per sample on the host (:class:`WarmUpExits`) as the loop decides them; a sample that
+        left or finished is not in the next iteration's batch.  -> (in_pos, in_vel, pre) lists, the contract of warm_up; item
+        b's state is the loop's up to the order of float32 additions in the batched kernels."""
+        from ..utils.tools.losses import density_loss, get_window_func
+        model = self.model
+        check = getattr(model, "_check_batched_step", None)
+        if check is not None:
+            check()  # (NotImplementedError for a model without a batched step, before any launch)
+        elif not hasattr(model, "step_batched"):
+            raise NotImplementedError(f"step_batched: {type(model).__name__}")
+        n = len(data["pos"])
+        exits = WarmUpExits(data["pre"], max_err, max_dens_err)
+        with torch.no_grad():
+            samples = [self._sample_tensors(data, bi) for bi in range(n)]
+            pr_pos = [self._to_device(data["pos"][bi][0]) for bi in range(n)]
+            pr_vel = [self._to_device(data["vel"][bi][0]) for bi in range(n)]
+            for p in range(max(exits.pre, default=0)):
+                active = exits.active(p)
+                if not active:
+                    break
+                items = [[pr_pos[bi], pr_vel[bi], samples[bi]["grav0"], None, samples[bi]["box0"], samples[bi]["boxn0"]]
+                         for bi in active]
+                pos2, vel2, rs = model.step_batched(items, training=False)
+                errs = []
+                if max_err is not None or max_dens_err is not None:
+                    frames = [self._to_device(samples[bi]["pos"][p]) for bi in active]
+                    frame = torch.cat(frames)
+                if max_err is not None:
+                    counts = torch.tensor([rs[k + 1] - rs[k] for k in range(len(active))], device=pos2.device)
+                    item = torch.repeat_interleave(torch.arange(len(active), device=pos2.device), counts, output_size=rs[-1])
+                    row = torch.sum(torch.abs(pos2 - frame), dim=-1)
+                    errs.append(torch.zeros(len(active), dtype=row.dtype, device=row.device).scatter_reduce(
+                        0, item, row, "amax", include_self=False))
+                if max_dens_err is not None:
+                    # the reference's argument order: the prediction as gt, the frame as pred; per item over [pos_b, box0_b]
+                    # and [frame_b, box0_b]
+                    boxes = [samples[bi]["box0"] for bi in active]
+                    in_rs = [0]
+                    for k, box in enumerate(boxes):
+                        in_rs.append(in_rs[-1] + rs[k + 1] - rs[k] + box.shape[0])
+                    pos_in = torch.cat([t for k, box in enumerate(boxes) for t in (pos2[rs[k]:rs[k + 1]], box)])
+                    frame_in = torch.cat([t for f, box in zip(frames, boxes) for t in (f, box)])
+                    errs.append(density_loss(pos2, frame, pos_in, frame_in, radius=model.particle_radii[0],
+                                             win=get_window_func(model.window_dens), use_max=True, row_splits=list(rs),
+                                             in_row_splits=in_rs))
+                host = torch.stack(errs).tolist() if errs else []  # the iteration's one host copy
+                err = host[0] if max_err is not None else None
+                dens_err = host[-1] if max_dens_err is not None else None
+                for k, bi in enumerate(active):
+                    if exits.accept(p, bi, None if err is None else err[k], None if dens_err is None else dens_err[k]):
+                        pr_pos[bi], pr_vel[bi] = pos2[rs[k]:rs[k + 1]], vel2[rs[k]:rs[k + 1]]
+        return pr_pos, pr_vel, exits.pres()
+
     def window_loss(self, data, time_w, in_pos, in_vel, pres, it=0):
         """simulator.py:370-403 on the recording path: per sample, ``len(time_w)`` model steps from the warmed-up state with
         gradients through all of them; the step-t losses against target frame t + pre + 1 (previous frame t + pre), weighted
@@ -530,7 +625,9 @@ class Simulator:
             raise NotImplementedError("training in the sharded step")
         sync = lambda: torch.cuda.synchronize(self.device)  # noqa: E731
         t0 = time.perf_counter()
-        in_pos, in_vel, pres = self.warm_up(data, max_err, max_dens_err)
+        # pipeline key warm_up_batched (default false): one batched step per warm-up iteration instead of the per-sample loop
+        warm_up = self.warm_up_batched if self.cfg.get("warm_up_batched", False) else self.warm_up
+        in_pos, in_vel, pres = warm_up(data, max_err, max_dens_err)
         sync()
         t1 = time.perf_counter()
         self.optimizer.zero_grad()

@@ -239,13 +239,79 @@ def get_dilated_pos(pos, strides, voxel_size=None, centralize=False, pad=0, hyst
     return dilated_pos, pcnt, idx
 
 
-def compute_density(out_pos, in_pos=None, radius=0.005, win=None):
+def _density_row_splits(out_pos, in_pos, out_row_splits, in_row_splits, names):
+    """The host-side checks of the batched density functions, all before a device is touched: both splits or neither
+    (``in_pos is None`` takes the out splits), well-formed, equal batch.  -> (out splits, in splits) as ops.RowSplits whose
+    device copies live on ``out_pos``'s device when that is a GPU (made once here, shared by every call that follows)."""
+    from ... import ops
+    if in_pos is None and in_row_splits is None:
+        in_row_splits = out_row_splits
+    if out_row_splits is None or in_row_splits is None:
+        raise NotImplementedError(f"the batched density needs both {names[0]} and {names[1]}")
+    if ops.SEARCH_SETS[ops.search_set()] != 0:
+        raise NotImplementedError(f"DMCF_FRS_SET={ops.search_set()} has no batched form: the open3d walk emulations know nothing of items")
+    (o_host, o_dev), (i_host, i_dev) = ops._batched_row_splits(out_pos if in_pos is None else in_pos, out_pos, in_row_splits,
+                                                               out_row_splits)[::-1]
+    if out_pos.is_cuda:
+        same = in_row_splits is out_row_splits
+        o_dev = ops._row_splits_on(o_host, o_dev, out_pos.device)
+        i_dev = o_dev if same else ops._row_splits_on(i_host, i_dev, out_pos.device)
+    return ops.RowSplits(o_host, o_dev), ops.RowSplits(i_host, i_dev)
+
+
+def _item_of_rows(row_splits, device):
+    """[n] int64: the batch item of every row."""
+    counts = torch.diff(row_splits.dev if row_splits.dev is not None else torch.tensor(row_splits.host, device=device))
+    return torch.repeat_interleave(torch.arange(len(row_splits.host) - 1, device=device), counts, output_size=row_splits.host[-1])
+
+
+def _compute_density_batched(out_pos, in_pos, radius, win, out_rs, in_rs, want_max=False):
+    """compute_density with row splits (validated: ops.RowSplits) -> dens, or (dens, item_max [batch]) with ``want_max``."""
+    from ... import ops
+    if in_pos is None:
+        in_pos = out_pos
+    radius = float(radius)
+    batch = len(out_rs.host) - 1
+    if win is None or isinstance(win, WindowFunction):
+        name = "explicit" if win is None else win.name
+        fac = 1.0 / (radius * radius) if win is None else win.fac
+        fused_max = want_max and name != "cubic_grad" and fac > 0  # (the kernel's maximum orders non-negative sums; scaling by fac > 0 keeps the order)
+        res = ops.window_sum(in_pos, out_pos, radius, name, points_row_splits=in_rs, queries_row_splits=out_rs,
+                             return_item_max=fused_max)
+        d, mx = res if fused_max else (res, None)
+        if win is None:
+            d = d / (radius * radius)
+            mx = None if mx is None else mx / (radius * radius)
+        elif fac != 1.0:
+            d = d * fac
+            mx = None if mx is None else mx * fac
+    else:
+        nns = ops.fixed_radius_search(in_pos, out_pos, radius, return_distances=True, points_row_splits=in_rs,
+                                      queries_row_splits=out_rs)
+        d = ops.reduce_subarrays_sum(win(nns.neighbors_distance / (radius * radius)), nns.neighbors_row_splits)
+        mx = None
+    if not want_max:
+        return d
+    if mx is None:
+        mx = torch.zeros(batch, dtype=d.dtype, device=d.device).scatter_reduce(0, _item_of_rows(out_rs, d.device), d.detach(), "amax",
+                                                                               include_self=False)
+    return d, mx
+
+
+def compute_density(out_pos, in_pos=None, radius=0.005, win=None, out_row_splits=None, in_row_splits=None):
     """losses.py:285-306: ``dens[i] = sum_j win(|in_pos[j] - out_pos[i]|^2 / radius^2)`` over the points within
     ``radius`` (the query point itself included).  ``win``: an object from :func:`get_window_func` (evaluated inside
     the search kernel, no pair list), None (the reference warns and uses the identity: sum of q), or any callable
     on a tensor of q values (evaluated with torch on the pair list).  Differentiable in both position sets for a window
-    object and for None (ops.window_sum); a callable is evaluated on the search's distances, which carry no gradient."""
+    object and for None (ops.window_sum); a callable is evaluated on the search's distances, which carry no gradient.
+
+    ``out_row_splits`` / ``in_row_splits`` (both or neither; ``in_pos=None`` takes the out splits): the densities of a BATCH of
+    point sets in one call, a point summing over the ``in_pos`` of its own item only (the batched ops.window_sum /
+    ops.fixed_radius_search)."""
     from ... import ops
+    if out_row_splits is not None or in_row_splits is not None:
+        out_rs, in_rs = _density_row_splits(out_pos, in_pos, out_row_splits, in_row_splits, ("out_row_splits", "in_row_splits"))
+        return _compute_density_batched(out_pos, in_pos, radius, win, out_rs, in_rs)
     if in_pos is None:
         in_pos = out_pos
     radius = float(radius)
@@ -287,8 +353,33 @@ def compute_pressure(out_pts, inp_pts=None, dens=None, rest_dens=3.5, stiffness=
     return torch.relu(stiffness * ((dens / rest_dens) ** 7 - 1))
 
 
-def density_loss(gt, pred, gt_in=None, pred_in=None, radius=0.005, eps=0.01, win=None, use_max=False, **kwargs):
-    """losses.py:380-398.  Differentiable in ``pred`` and ``pred_in`` (compute_density); not wired into get_loss."""
+def density_loss(gt, pred, gt_in=None, pred_in=None, radius=0.005, eps=0.01, win=None, use_max=False, row_splits=None,
+                 in_row_splits=None, **kwargs):
+    """losses.py:380-398.  Differentiable in ``pred`` and ``pred_in`` (compute_density); not wired into get_loss.
+
+    ``row_splits`` (shared by ``gt`` and ``pred``) / ``in_row_splits`` (shared by ``gt_in`` and ``pred_in``; without the in sets
+    the row splits serve): a BATCH of items in one call -> [batch], entry b what the un-batched call returns on item b's slices.
+    ``use_max=True`` takes both maxima per item from the window-sum kernel (which carry no gradient: the batched form is the
+    warm-up's check, not a training loss); otherwise the mean of the relu term per item, differentiable as before.  An
+    item without rows is a ValueError (the un-batched call cannot take the maximum of nothing either)."""
+    if row_splits is not None or in_row_splits is not None:
+        if (gt_in is None) != (pred_in is None):
+            raise NotImplementedError("the batched density_loss needs gt_in and pred_in both or neither: they share in_row_splits")
+        if gt.shape[0] != pred.shape[0] or (gt_in is not None and gt_in.shape[0] != pred_in.shape[0]):
+            raise ValueError("gt and pred (and gt_in and pred_in) must have equal numbers of rows: they share their row splits")
+        out_rs, in_rs = _density_row_splits(gt, gt_in, row_splits, in_row_splits, ("row_splits", "in_row_splits"))
+        batch = len(out_rs.host) - 1
+        empty = [b for b in range(batch) if out_rs.host[b + 1] == out_rs.host[b]]
+        if empty:
+            raise ValueError(f"density_loss: items {empty} have no rows (the maximum of nothing)")
+        pred_dens, pred_max = _compute_density_batched(pred, pred_in, radius, win, out_rs, in_rs, want_max=True)
+        _, rest_dens = _compute_density_batched(gt, gt_in, radius, win, out_rs, in_rs, want_max=True)
+        if use_max:
+            return torch.abs(pred_max - rest_dens) / rest_dens
+        item = _item_of_rows(out_rs, pred_dens.device)
+        term = torch.relu(pred_dens - rest_dens[item] - eps)
+        counts = torch.diff(out_rs.dev).to(term.dtype)
+        return torch.zeros(batch, dtype=term.dtype, device=term.device).index_add(0, item, term) / counts
     pred_dens = compute_density(pred, pred_in, radius, win=win)
     gt_dens = compute_density(gt, gt_in, radius, win=win)
     rest_dens = gt_dens.max()

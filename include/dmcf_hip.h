@@ -17,6 +17,8 @@
  *     366-370, 1006-1010: extents of rank 1)                      dmcf_radius_search_write
  *   both searches with points_row_splits / queries_row_splits    dmcf_frs_build_batched / dmcf_frs_count_batched /
  *     (a batch of point sets in one call; ABI 2.20)               dmcf_frs_write_batched, dmcf_radius_search_*_batched
+ *   compute_density per sample of a training batch               dmcf_frs_window_sum_batched /
+ *     (pipelines/simulator.py:227-243 inside the warm-up loop)    dmcf_frs_window_sum_backward_batched (ABI 2.22)
  *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
  *                                                                 dmcf_cconv_backward_extents)
  *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
@@ -237,6 +239,29 @@ int dmcf_radius_search_write_batched(const float* queries, int64_t n_queries, co
                                      int64_t n_points, const float* radii, float max_radius, int flags, const void* workspace,
                                      size_t workspace_bytes, const int64_t* row_splits, int32_t* neighbors_index,
                                      float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream);
+
+/* The window sum and its gradient on the structure of dmcf_frs_build_batched (ABI 2.22): dmcf_frs_window_sum and
+ * dmcf_frs_window_sum_backward with the sums of a query running over the points of the query's OWN item only.  The arguments
+ * are the un-batched ones with (queries_row_splits, batch) after n_queries; coef_points is indexed by the point's index in
+ * the concatenated array.  For the gradient w.r.t. the points, build the batched structure over the QUERIES (with the
+ * queries' row splits) and scan it from the points with the points' row splits.
+ * item_max (forward only; may be NULL): DEVICE float [batch], receives the largest out[q] of every item; the entry point
+ * clears it first, so an item without queries gives 0.  Lane 0 of a query's wave raises it with an integer atomic max on the
+ * float's bits, which orders non-negative floats only: with DMCF_WINDOW_CUBIC_GRAD, whose sums can be negative, a non-NULL
+ * item_max is DMCF_EUNSUPPORTED.  A maximum does not depend on the order of the atomics: identical calls give identical bits.
+ * The backward uses no atomics at all.
+ * flags: DMCF_FRS_IGNORE_QUERY_POINT only; DMCF_FRS_OPEN3D_* are DMCF_EINVAL, DMCF_FRS_METRIC_LINF is DMCF_EUNSUPPORTED.
+ * batch outside [1, 2^26], NULL row splits and a window id out of range are DMCF_EINVAL; in the backward both coefficient
+ * arrays NULL are DMCF_EINVAL and DMCF_WINDOW_NONE is DMCF_EUNSUPPORTED; a workspace below
+ * dmcf_frs_workspace_bytes_batched(n_points, n_queries, batch) is DMCF_EWORKSPACE; n_queries == 0 is DMCF_OK without a
+ * kernel launch.  Arguments are validated before anything is enqueued. */
+int dmcf_frs_window_sum_batched(const float* queries, int64_t n_queries, const int64_t* queries_row_splits, int64_t batch,
+                                int64_t n_points, float radius, int flags, int window, const void* workspace,
+                                size_t workspace_bytes, float* out, float* item_max, dmcf_stream_t stream);
+int dmcf_frs_window_sum_backward_batched(const float* queries, int64_t n_queries, const int64_t* queries_row_splits,
+                                         int64_t batch, int64_t n_points, float radius, int flags, int window,
+                                         const float* coef_queries, const float* coef_points, const void* workspace,
+                                         size_t workspace_bytes, float* grad, dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Continuous convolution (CConv) and its antisymmetric variant (ASCC).
