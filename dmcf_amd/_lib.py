@@ -287,6 +287,7 @@ SYMBOLS = [
     "dmcf_grid_pos_workspace_bytes_batched", "dmcf_grid_pos_bounds_batched", "dmcf_grid_pos_count_batched",
     "dmcf_grid_pos_write_batched", "dmcf_points_aabb_batched",
     "dmcf_frs_window_sum_batched", "dmcf_frs_window_sum_backward_batched",
+    "dmcf_nn_distance_ragged_workspace_bytes", "dmcf_nn_distance_ragged",
 ]
 
 
@@ -545,6 +546,13 @@ def lib():
     L.dmcf_frs_window_sum_backward_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int,
                                                        c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p,
                                                        c.c_void_p]
+    # nn_distance over a ragged batch (ABI 2.23): HOST row splits
+    L.dmcf_nn_distance_ragged_workspace_bytes.restype = c.c_size_t
+    L.dmcf_nn_distance_ragged_workspace_bytes.argtypes = [c.c_int64, c.c_int64, c.c_int64]
+    i64p = c.POINTER(c.c_int64)
+    L.dmcf_nn_distance_ragged.restype = c.c_int
+    L.dmcf_nn_distance_ragged.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p,
+                                          c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
     _lib = L
     return L
 

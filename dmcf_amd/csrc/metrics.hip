@@ -20,6 +20,8 @@
 // reusing the same workspace.
 #include <math.h>
 
+#include <vector>
+
 #include "common.h"
 #include "metrics_plan.h"
 
@@ -85,6 +87,73 @@ __global__ __launch_bounds__(kMtThreads) void nn_combine_kernel(const float* __r
     }
     dist[i] = best;
     if (idx != nullptr) idx[i] = bi;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// nearest neighbour over a ragged batch (ABI 2.23): many items of tens to a few thousand rows.  Every item's rows are cut into
+// tiles of one wavefront; a workgroup IS one wavefront, takes one tile and walks its own item's other set through LDS from the
+// first column to the last with the dense kernel's distance and strict <, so a row's result has the dense call's bits without a
+// combine pass.  The tile table is written by the host from the row splits it has validated: the kernel reads no row splits,
+// and every index it forms lies inside the arrays by construction.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int kNrRows = 64;   // rows per tile = lanes of a wavefront
+constexpr int kNrTile = 256;  // points of the other set per LDS tile
+constexpr int64_t kNrMaxBatch = (int64_t)1 << 26;  // (the limit of the batched searches)
+
+struct NrTile {
+    int32_t row0, rows;  // the tile's rows [row0, row0 + rows) of the concatenated set, 1 <= rows <= kNrRows
+    int32_t c0, c1;      // its item's other set [c0, c1) of the concatenated other set, c0 < c1
+};
+static_assert(sizeof(NrTile) == 16, "NrTile is read as one 16-byte load");
+
+__global__ __launch_bounds__(kNrRows) void nn_ragged_kernel(const float* __restrict__ q, const float* __restrict__ r,
+                                                            const NrTile* __restrict__ tiles, float* __restrict__ dist,
+                                                            int32_t* __restrict__ idx) {
+    __shared__ float4 tile[kNrTile];
+    const NrTile t = tiles[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    const bool live = lane < t.rows;
+    const int64_t row = (int64_t)t.row0 + lane;
+    float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+    if (live) {
+        qx = q[3 * row];
+        qy = q[3 * row + 1];
+        qz = q[3 * row + 2];
+    }
+    float best = INFINITY;
+    int32_t bi = t.c0;
+    for (int32_t t0 = t.c0; t0 < t.c1; t0 += kNrTile) {  // (c1 < 2^31 - 1 - kNrTile is checked by the host)
+        const int cnt = t.c1 - t0 < kNrTile ? t.c1 - t0 : kNrTile;
+        __syncthreads();
+        for (int k = lane; k < cnt; k += kNrRows) {
+            const int64_t c = (int64_t)t0 + k;
+            tile[k] = make_float4(r[3 * c], r[3 * c + 1], r[3 * c + 2], 0.0f);
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int j = 0; j < cnt; ++j) {
+            const float4 p = tile[j];
+            const float d = dist2_unfused(qx, qy, qz, p.x, p.y, p.z);
+            if (d < best) {  // strict, columns ascending: the lowest index of equal distances stays
+                best = d;
+                bi = t0 + j;
+            }
+        }
+    }
+    if (live) {
+        dist[row] = best;
+        idx[row] = bi;
+    }
+}
+
+inline int64_t nr_tile_bound(int64_t rows, int64_t batch) { return rows / kNrRows + batch; }  // every item adds <= 1 partial tile
+
+// host row splits of `batch` items over `total` rows: start at 0, do not decrease, end at total
+bool valid_row_splits(const int64_t* rs, int64_t batch, int64_t total) {
+    if (rs[0] != 0 || rs[batch] != total) return false;
+    for (int64_t b = 0; b < batch; ++b)
+        if (rs[b + 1] < rs[b]) return false;
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -359,6 +428,53 @@ int dmcf_nn_distance(const float* xyz1, const float* xyz2, int64_t b, int64_t n,
         }
         ws += bytes;
     }
+    return check_launch();
+}
+
+size_t dmcf_nn_distance_ragged_workspace_bytes(int64_t n_total, int64_t m_total, int64_t batch) {
+    if (n_total < 0 || m_total < 0 || batch < 1 || batch > kNrMaxBatch) return 0;
+    return align_up((size_t)(nr_tile_bound(n_total, batch) + nr_tile_bound(m_total, batch)) * sizeof(NrTile), 256);
+}
+
+int dmcf_nn_distance_ragged(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                            const int64_t* row_splits2, int64_t batch, float* dist1, int32_t* idx1, float* dist2, int32_t* idx2,
+                            void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    if (batch < 0 || batch > kNrMaxBatch || n_total < 0 || m_total < 0) return DMCF_EINVAL;
+    if (n_total >= INT32_MAX - kNrTile || m_total >= INT32_MAX - kNrTile) return DMCF_EINVAL;  // (int32 indices)
+    if ((dist1 == nullptr) != (idx1 == nullptr) || (dist2 == nullptr) != (idx2 == nullptr)) return DMCF_EINVAL;
+    if (dist1 == nullptr && dist2 == nullptr) return DMCF_EINVAL;
+    if (batch == 0) return n_total == 0 && m_total == 0 ? DMCF_OK : DMCF_EINVAL;
+    if (row_splits1 == nullptr || row_splits2 == nullptr) return DMCF_EINVAL;
+    if (!valid_row_splits(row_splits1, batch, n_total) || !valid_row_splits(row_splits2, batch, m_total)) return DMCF_EINVAL;
+    for (int64_t b = 0; b < batch; ++b)  // a point without a set to search has no nearest neighbour
+        if ((row_splits1[b + 1] == row_splits1[b]) != (row_splits2[b + 1] == row_splits2[b])) return DMCF_EINVAL;
+    if (n_total == 0) return DMCF_OK;  // (every item empty on both sides)
+    if (xyz1 == nullptr || xyz2 == nullptr || workspace == nullptr) return DMCF_EINVAL;
+    if (workspace_bytes < dmcf_nn_distance_ragged_workspace_bytes(n_total, m_total, batch)) return DMCF_EWORKSPACE;
+    // the tile tables of the wanted directions, one after the other, in one copy
+    std::vector<NrTile> tiles;
+    tiles.reserve((size_t)((dist1 != nullptr ? nr_tile_bound(n_total, batch) : 0) + (dist2 != nullptr ? nr_tile_bound(m_total, batch) : 0)));
+    size_t count[2] = {0, 0};
+    for (int dir = 0; dir < 2; ++dir) {
+        if ((dir == 0 ? dist1 : dist2) == nullptr) continue;
+        const int64_t* qs = dir == 0 ? row_splits1 : row_splits2;
+        const int64_t* cs = dir == 0 ? row_splits2 : row_splits1;
+        for (int64_t b = 0; b < batch; ++b)
+            for (int64_t row0 = qs[b]; row0 < qs[b + 1]; row0 += kNrRows) {
+                const int64_t rows = qs[b + 1] - row0 < kNrRows ? qs[b + 1] - row0 : kNrRows;
+                tiles.push_back(NrTile{(int32_t)row0, (int32_t)rows, (int32_t)cs[b], (int32_t)cs[b + 1]});
+            }
+        count[dir] = tiles.size() - count[0] * (size_t)dir;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // (pageable host memory: the call returns once the table has left `tiles`)
+    if (hipMemcpyAsync(workspace, tiles.data(), tiles.size() * sizeof(NrTile), hipMemcpyHostToDevice, st) != hipSuccess)
+        return check_launch();
+    const NrTile* table = (const NrTile*)workspace;
+    if (dist1 != nullptr)
+        nn_ragged_kernel<<<(unsigned)count[0], kNrRows, 0, st>>>(xyz1, xyz2, table, dist1, idx1);
+    if (dist2 != nullptr)
+        nn_ragged_kernel<<<(unsigned)count[1], kNrRows, 0, st>>>(xyz2, xyz1, table + count[0], dist2, idx2);
     return check_launch();
 }
 

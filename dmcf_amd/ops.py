@@ -2858,11 +2858,73 @@ class NnDistanceFunction(torch.autograd.Function):
         return nn_distance_backward(a, b, i1, i2, gd1, gd2, need1, need2)
 
 
-def nn_distance(xyz1, xyz2):
+def nn_distance_row_splits(shape1, shape2, row_splits1, row_splits2, wants_grad=False):
+    """The host-side checks of nn_distance with row splits on the shapes of the two point sets, all of them before a device is
+    touched, in the order of the other batched ops: both or neither and no gradient (NotImplementedError), then well-formed
+    splits, equal batch sizes and no item with exactly one empty set (ValueError).  -> (host splits 1, host splits 2)."""
+    if row_splits1 is None or row_splits2 is None:
+        raise NotImplementedError("batched nn_distance needs both row_splits1 and row_splits2")
+    for shape, name in ((shape1, "xyz1"), (shape2, "xyz2")):
+        if len(shape) != 2 or shape[-1] not in (2, 3):
+            raise ValueError(f"{name} must have shape [n_total, 3] or [n_total, 2] with row splits, got {tuple(shape)}")
+    if wants_grad:
+        raise NotImplementedError("batched nn_distance has no backward: call it under no_grad, or per item without row splits")
+    s1 = _host_row_splits(row_splits1, "row_splits1")[0]
+    s2 = _host_row_splits(row_splits2, "row_splits2")[0]
+    _check_row_splits(s1, shape1[0], "row_splits1")
+    _check_row_splits(s2, shape2[0], "row_splits2")
+    if len(s1) != len(s2):
+        raise ValueError(f"row_splits1 and row_splits2 must have equal lengths (batch + 1), got {len(s1)} and {len(s2)}")
+    for k in range(len(s1) - 1):
+        if (s1[k + 1] == s1[k]) != (s2[k + 1] == s2[k]):
+            raise ValueError(f"nn_distance needs two non-empty point sets: item {k} has {s1[k + 1] - s1[k]} and "
+                             f"{s2[k + 1] - s2[k]} points")
+    return s1, s2
+
+
+def nn_distance_ragged(xyz1, xyz2, row_splits1, row_splits2, want1=True, want2=True):
+    """nn_distance with row splits (dmcf_nn_distance_ragged: one launch per wanted direction).  ``want1`` / ``want2``: a
+    direction that is not wanted is not computed and returns (None, None)."""
+    for t, name in ((xyz1, "xyz1"), (xyz2, "xyz2")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor")
+    s1, s2 = nn_distance_row_splits(xyz1.shape, xyz2.shape, row_splits1, row_splits2, _wants_grad(xyz1, xyz2))
+    if not (want1 or want2):
+        raise ValueError("nn_distance: no direction wanted")
+    batch = len(s1) - 1
+    a, _ = _point_batch(xyz1, "xyz1")
+    b, _ = _point_batch(xyz2, "xyz2")
+    if a.device != b.device:
+        raise ValueError("xyz1 and xyz2 must be on the same device")
+    L = _lib.lib()
+    n, m, dev = a.shape[1], b.shape[1], a.device
+    d1 = torch.empty(n, dtype=torch.float32, device=dev) if want1 else None
+    i1 = torch.empty(n, dtype=torch.int32, device=dev) if want1 else None
+    d2 = torch.empty(m, dtype=torch.float32, device=dev) if want2 else None
+    i2 = torch.empty(m, dtype=torch.int32, device=dev) if want2 else None
+    if n > 0:
+        nbytes = int(L.dmcf_nn_distance_ragged_workspace_bytes(n, m, batch))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        h1, h2 = (ctypes.c_int64 * (batch + 1))(*s1), (ctypes.c_int64 * (batch + 1))(*s2)
+        _lib.check(L.dmcf_nn_distance_ragged(_ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(d1), _ptr(i1), _ptr(d2), _ptr(i2),
+                                             _ptr(ws), nbytes, _stream()), "dmcf_nn_distance_ragged")
+    return d1, i1, d2, i2
+
+
+def nn_distance(xyz1, xyz2, row_splits1=None, row_splits2=None):
     """Mirror of ``utils/tools/nn_distance.py: nn_distance(xyz1, xyz2)`` -> ``(dist1, idx1, dist2, idx2)``: for each point of
     xyz1 [b, n, 3] the squared distance to its nearest point of xyz2 [b, m, 3] and that point's int32 index ([b, n]), and the
     same from xyz2 to xyz1 ([b, m]).  Equal distances go to the lowest index (dmcf_nn_distance).  dist1 and dist2 are
-    differentiable in both point sets (dmcf_nn_distance_backward)."""
+    differentiable in both point sets (dmcf_nn_distance_backward).
+
+    ``row_splits1`` / ``row_splits2`` (both or neither; a sequence, a CPU or device int64 tensor or a :class:`RowSplits`): a
+    RAGGED batch in one call (dmcf_nn_distance_ragged).  xyz1 is then [n_total, 3] and xyz2 [m_total, 3], item b being
+    xyz1[rs1[b]:rs1[b + 1]] against xyz2[rs2[b]:rs2[b + 1]]; the results run over the concatenated rows ([n_total] and
+    [m_total]) and equal the un-batched call on every item alone bit for bit, the indices offset by the item's first row of
+    the other set.  An item with both sets empty is legal, one with exactly one empty set a ValueError.  No gradient: inputs
+    that require grad raise NotImplementedError.  :func:`nn_distance_ragged` computes one direction alone."""
+    if row_splits1 is not None or row_splits2 is not None:
+        return nn_distance_ragged(xyz1, xyz2, row_splits1, row_splits2)
     a, b, batched = _pair_batch(xyz1, xyz2)
     nb, n, m = a.shape[0], a.shape[1], b.shape[1]
     if nb > 0 and (n == 0 or m == 0):

@@ -12,7 +12,10 @@ training loop: ``train_step`` (the reference's ``train(data, time_w, it, max_err
 on the inference path, records the time-weighted window, back-propagates and applies utils/tools/losses.KerasAdam
 (dmcf_adam_step); the outer loop follows the window / warm-up / iteration schedules, writes checkpoints with their Adam
 state (utils/tf_checkpoint.CheckpointManager) and validates and tests after every epoch.  The number of particles may
-change between steps (run_sample.py:173-177 adds inflow), so nothing here assumes a fixed N.
+change between steps (run_sample.py:173-177 adds inflow), so nothing here assumes a fixed N.  Opt-in batched forms (pipeline
+keys, all default false): ``train_batched`` and ``warm_up_batched`` for the training window and its warm-up, ``valid_batched``
+for run_valid -- ``run_rollout_batched`` advances all scenes with one ``model.step_batched`` per time step and
+``valid_losses_batched`` evaluates a frame of all scenes at once (one dmcf_nn_distance_ragged call for the Chamfer metric).
 """
 import logging
 import os
@@ -128,6 +131,19 @@ class WarmUpExits:
         return [max(k - 1, 0) if at is None else at for k, at in zip(self.pre, self.left)]
 
 
+def valid_frames(lengths, eval_stride=1):
+    """The host bookkeeping of the batched validation (Simulator.valid_losses_batched): scene i has ``lengths[i]`` frames and
+    run_valid evaluates its frames t = 1 .. lengths[i] - 1 with ``t % eval_stride == 0``.  -> [(t, [the scenes that have an
+    evaluated frame t, ascending])] in ascending t, frames nobody has left out.  No device, no tensors."""
+    eval_stride = int(eval_stride)
+    if eval_stride < 1:
+        raise ValueError(f"eval_stride must be >= 1, got {eval_stride}")
+    frames = []
+    for t in range(eval_stride, max((int(k) for k in lengths), default=0), eval_stride):
+        frames.append((t, [i for i, k in enumerate(lengths) if t < int(k)]))
+    return frames
+
+
 class Simulator:
     def __init__(self, model, dataset=None, name="Simulator", main_log_dir="./logs/", device="cuda", split="train",
                  reserve_gib=None, **kwargs):
@@ -231,6 +247,47 @@ class Simulator:
             log.info("Average runtime: %.05f" % (np.mean(timing) / len(inputs)))
         return results
 
+    def _require_batched_step(self):
+        """NotImplementedError naming the model unless it has a batched step -- before anything is launched."""
+        check = getattr(self.model, "_check_batched_step", None)
+        if check is not None:
+            check()
+        elif not hasattr(self.model, "step_batched"):
+            raise NotImplementedError(f"step_batched: {type(self.model).__name__}")
+
+    @torch.no_grad()
+    def run_rollout_batched(self, inputs, timesteps=2):
+        """:meth:`run_rollout` with ONE ``model.step_batched`` over all scenes per time step (pipeline key ``valid_batched``)
+        instead of one ``run_inference`` per scene: the same inputs, the same ``results[i][t] = [pos, vel, acc, None, box,
+        bfeats]`` (scene i's rows of the batched result, sliced by its fluid row splits), ``self.timing`` and the "Average
+        runtime" line.  Scene i's frames are the loop's up to the order of float32 additions in the batched kernels.  A model
+        without a batched step is a NotImplementedError before anything is launched."""
+        self._require_batched_step()
+        inputs = [[self._to_device(data["pos"][0]), self._to_device(data["vel"][0]),
+                   self._to_device(data["grav"][0]) if data.get("grav") is not None and data["grav"][0] is not None
+                   else None, None, self._to_device(data["box"][0]), self._to_device(data["box_normals"][0])]
+                  for data in inputs]
+        results = [[] for _ in range(len(inputs))]
+        self.run_inference(inputs[:1])  # "dummy init": builds the lazily created weights (simulator.py:94)
+        timing = []
+        for i in range(len(inputs)):
+            results[i].append(inputs[i])
+        with steady_steps() as steady:
+            for _ in range(timesteps - 1):
+                torch.cuda.synchronize(self.device)
+                start = time.time()
+                pos2, vel2, rs = self.model.step_batched(inputs, training=False)
+                inputs = [[pos2[rs[i]:rs[i + 1]], vel2[rs[i]:rs[i + 1]]] + list(inputs[i][2:]) for i in range(len(inputs))]
+                torch.cuda.synchronize(self.device)
+                timing.append(time.time() - start)
+                for i in range(len(inputs)):
+                    results[i].append(inputs[i])
+                steady.tick()
+        self.timing = timing
+        if timing:
+            log.info("Average runtime: %.05f" % (np.mean(timing) / len(inputs)))
+        return results
+
     def load_ckpt(self, ckpt_path):
         """base_pipeline.py:155-187 for inference: read a TensorFlow tensor-bundle checkpoint (``<dir>/ckpt`` prefix, or
         the newest ``ckpt-<n>`` in a directory) into the model; returns the epoch (0 without a checkpoint: the model then
@@ -311,6 +368,10 @@ class Simulator:
         from ..utils.evaluation_helper import chamfer_distance, compare_dist, distance, merge_dicts
         from ..utils.tools.losses import density_loss, emd_loss, get_window_func
         cfg, model = self.cfg, self.model
+        # pipeline key valid_batched (default false): one batched step per rollout step and per-frame metrics over all scenes
+        valid_batched = bool(cfg.get("valid_batched", False))
+        if valid_batched:
+            self._require_batched_step()  # (NotImplementedError for a model without a batched step, before any launch)
         os.makedirs(cfg.logs_dir, exist_ok=True)
         timestamp = datetime.now().strftime("%Y-%m-%d_%H:%M:%S")
         log_file_path = os.path.join(cfg.logs_dir, "log_valid_" + timestamp + ".txt")
@@ -326,9 +387,11 @@ class Simulator:
             if epoch is None:
                 epoch = self.load_ckpt(model.cfg.get("ckpt_path"))
             log.info("Started validation")
-            results = self.run_rollout(valid_data, valid_data[0]["pos"].shape[0])
+            rollout = self.run_rollout_batched if valid_batched else self.run_rollout
+            results = rollout(valid_data, valid_data[0]["pos"].shape[0])
             eval_stride = valid_kw.get("eval_stride", 1)
             dev = lambda a: self._to_device(a)  # noqa: E731
+            batched = self.valid_losses_batched(valid_data, results, eval_stride) if valid_batched else None
             losses = []
             for i in range(len(valid_data)):
                 data = valid_data[i]
@@ -339,6 +402,10 @@ class Simulator:
                 for t in range(1, target_pos.shape[0]):
                     pos, vel = results[i][t][:2]
                     if t % eval_stride != 0:
+                        continue
+                    if batched is not None:  # (evaluated above, frame by frame over all scenes: the same dict, key for key)
+                        losses.append(batched[i][t])
+                        loss_seq.append(batched[i][t])
                         continue
                     loss = {}
                     if box.shape[0] > 0:
@@ -383,6 +450,84 @@ class Simulator:
             log.setLevel(level)
         self.valid_loss = loss
         return loss
+
+    @torch.no_grad()
+    def valid_losses_batched(self, valid_data, results, eval_stride=1):
+        """The metrics of :meth:`run_valid` with pipeline key ``valid_batched``: every evaluated frame t for ALL scenes that
+        have a frame t at once (:func:`valid_frames`).  -> ``losses[i][t]``, the dict the loop builds for scene i's frame t,
+        key for key in the loop's order.
+
+        Per frame: the clamp to every scene's box with per-row bounds; ONE dmcf_nn_distance_ragged call for ``chamfer_val``
+        and (unless the split is "train") ``chamfer_val_2`` -- the two directions of nn_distance(pos, target); two batched
+        density_loss calls for ``dens_val`` / ``max_dens_val`` (the reference's argument orders kept); ONE model.step_batched
+        from the targets' frames t - 1 for ``mse_single_val``.  The per-point arrays reach the host in one copy per frame, and
+        the per-scene means are np.mean over the same float32 arrays as in the loop: they equal the loop's bit for bit
+        wherever the device arrays do.  ``emd`` and the two ``vel_diff_val*`` stay per scene on the loop's code (the dense
+        EMD's split plan depends on the batch size)."""
+        from ..utils.evaluation_helper import compare_dist, distance
+        from ..utils.tools.losses import density_loss, emd_loss, get_window_func
+        cfg, model, dev = self.cfg, self.model, self._to_device
+        full = cfg.get("split") != "train"
+        boxes = [data["box"][0] for data in valid_data]
+        boxes_d = [dev(box) for box in boxes]
+        # per-scene clamp bounds (the loop's np.min / np.max of the box; a scene without a box is not clamped)
+        inf = np.float32(np.inf)
+        bounds = np.stack([np.concatenate([np.min(box, axis=0), np.max(box, axis=0)]).astype(np.float32) if box.shape[0] > 0
+                           else np.array([-inf] * 3 + [inf] * 3, dtype=np.float32) for box in boxes])
+        losses = [dict() for _ in valid_data]
+        for t, scenes in valid_frames([data["pos"].shape[0] for data in valid_data], eval_stride):
+            counts = [int(results[i][t][0].shape[0]) for i in scenes]
+            rs = [0]
+            for c in counts:
+                rs.append(rs[-1] + c)
+            tcounts = [int(valid_data[i]["pos"][t].shape[0]) for i in scenes]
+            trs = [0]
+            for c in tcounts:
+                trs.append(trs[-1] + c)
+            n = rs[-1]
+            lohi = dev(np.repeat(bounds[scenes], counts, axis=0))
+            pos = torch.clamp(torch.cat([results[i][t][0] for i in scenes]), lohi[:, :3], lohi[:, 3:])
+            tgt = dev(np.concatenate([valid_data[i]["pos"][t] for i in scenes]))
+            d_pos, _, d_tgt, _ = ops.nn_distance_ragged(pos, tgt, rs, trs, want2=full)
+            parts = [pos.reshape(-1), torch.sqrt(d_pos)]
+            if full:
+                # the reference's argument order, kept as it is (see the loop in run_valid)
+                in_rs = [0]
+                for k, i in enumerate(scenes):
+                    in_rs.append(in_rs[-1] + counts[k] + boxes_d[i].shape[0])
+                pos_in = torch.cat([x for k, i in enumerate(scenes) for x in (pos[rs[k]:rs[k + 1]], boxes_d[i])])
+                tgt_in = torch.cat([x for k, i in enumerate(scenes) for x in (tgt[trs[k]:trs[k + 1]], boxes_d[i])])
+                dens = density_loss(tgt, pos, pos_in, tgt_in, win=get_window_func("poly6"), row_splits=rs, in_row_splits=in_rs)
+                max_dens = density_loss(pos, tgt, pos_in, tgt_in, radius=model.particle_radii[0],
+                                        win=get_window_func(model.window_dens), use_max=True, row_splits=rs, in_row_splits=in_rs)
+                parts += [torch.sqrt(d_tgt), dens, max_dens]
+            # mse for a single step only: one batched model step from the targets' previous frames
+            items = [[dev(valid_data[i]["pos"][t - 1]), dev(valid_data[i]["vel"][t - 1])] + list(results[i][t][2:]) for i in scenes]
+            pos_sub, _, srs = model.step_batched(items, training=False)
+            parts.append(pos_sub.reshape(-1))
+            host = torch.cat(parts).cpu().numpy()  # the frame's one host copy of the per-point arrays
+            chunks = np.split(host, np.cumsum([int(x.numel()) for x in parts])[:-1])
+            pos_h, cham, sub_h = chunks[0].reshape(n, 3), chunks[1], chunks[-1].reshape(srs[-1], 3)
+            if full:
+                cham2, dens_h, max_dens_h = chunks[2:5]
+            for k, i in enumerate(scenes):
+                data = valid_data[i]
+                a, b = rs[k], rs[k + 1]
+                loss = {}
+                loss["mse_val"] = float(np.mean(distance(data["pos"][t], pos_h[a:b])))
+                loss["chamfer_val"] = float(np.mean(cham[a:b].astype(np.float32)))
+                if full:
+                    loss["dens_val"] = float(dens_h[k])
+                    loss["max_dens_val"] = float(max_dens_h[k])
+                    loss["chamfer_val_2"] = float(np.mean(cham2[trs[k]:trs[k + 1]].astype(np.float32)))
+                    loss["emd"] = float(np.mean(emd_loss(tgt[trs[k]:trs[k + 1]].unsqueeze(0), pos[a:b].unsqueeze(0))
+                                                .cpu().numpy().astype(np.float32)))
+                    vel = results[i][t][1]
+                    loss["vel_diff_val"] = compare_dist(data["vel"][t], vel)
+                    loss["vel_diff_val_2"] = compare_dist(vel, data["vel"][t])
+                loss["mse_single_val"] = float(np.mean(distance(data["pos"][t], sub_h[srs[k]:srs[k + 1]])))
+                losses[i][t] = loss
+        return losses
 
 
     def train_loader(self, schedule):
@@ -498,11 +643,7 @@ class Simulator:
         b's state is the loop's up to the order of float32 additions in the batched kernels."""
         from ..utils.tools.losses import density_loss, get_window_func
         model = self.model
-        check = getattr(model, "_check_batched_step", None)
-        if check is not None:
-            check()  # (NotImplementedError for a model without a batched step, before any launch)
-        elif not hasattr(model, "step_batched"):
-            raise NotImplementedError(f"step_batched: {type(model).__name__}")
+        self._require_batched_step()  # (NotImplementedError for a model without a batched step, before any launch)
         n = len(data["pos"])
         exits = WarmUpExits(data["pre"], max_err, max_dens_err)
         with torch.no_grad():

@@ -3,7 +3,8 @@ arguments):
 
   distance          :14-16  per-point Euclidean distance (host numpy)
   chamfer_distance  :25-28  for each point of ``gt`` the distance to its nearest point of ``pred``; on the GPU through
-                            ops.nn_distance (dmcf_nn_distance) instead of a host cKDTree
+                            ops.nn_distance (dmcf_nn_distance) instead of a host cKDTree; with row splits, a
+                            batch of scenes of different sizes in one call (dmcf_nn_distance_ragged)
   compare_dist      :43-75  KL divergence of two histograms (one bin per ``bin_size`` points, 1e-5 prior); host numpy,
                             vectorised, the same value as the reference's per-point loop
   merge_dicts       :78-85
@@ -23,11 +24,18 @@ def distance(x, y):
     return np.linalg.norm(_host(x) - _host(y), axis=-1)
 
 
-def chamfer_distance(pred, gt):
+def chamfer_distance(pred, gt, pred_row_splits=None, gt_row_splits=None):
     """:25-28: for each point of ``gt`` [n, 3] the Euclidean distance to its nearest point of ``pred`` [m, 3], as a float32
     numpy array [n].  Numpy arrays or device tensors; the nearest neighbours come from ops.nn_distance on the GPU (float32
-    squared distances, then the square root), where the reference queries a cKDTree in float64."""
+    squared distances, then the square root), where the reference queries a cKDTree in float64.
+
+    ``pred_row_splits`` / ``gt_row_splits`` (both or neither, the rules of ops.nn_distance): a batch of scenes of different
+    sizes, ``pred`` [m_total, 3] and ``gt`` [n_total, 3] holding them one after the other.  One kernel call
+    (dmcf_nn_distance_ragged, the gt -> pred direction only) and one host copy for the whole batch; returns the concatenated
+    distances [n_total], which the caller slices by ``gt_row_splits``: every slice has the bits of the per-scene call."""
     from .. import ops
+    if pred_row_splits is not None or gt_row_splits is not None:  # (host checks before anything goes to the device)
+        ops.nn_distance_row_splits(tuple(gt.shape), tuple(pred.shape), gt_row_splits, pred_row_splits)
     dev = next((t.device for t in (pred, gt) if isinstance(t, torch.Tensor) and t.is_cuda), torch.device("cuda"))
 
     def to_dev(x):
@@ -35,7 +43,10 @@ def chamfer_distance(pred, gt):
             return x.detach().to(dev, dtype=torch.float32)
         return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
 
-    d_gt, _, _, _ = ops.nn_distance(to_dev(gt), to_dev(pred))
+    if pred_row_splits is not None:
+        d_gt = ops.nn_distance_ragged(to_dev(gt), to_dev(pred), gt_row_splits, pred_row_splits, want2=False)[0]
+    else:
+        d_gt, _, _, _ = ops.nn_distance(to_dev(gt), to_dev(pred))
     return torch.sqrt(d_gt).cpu().numpy()
 
 

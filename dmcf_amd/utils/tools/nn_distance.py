@@ -1,5 +1,6 @@
 """Mirror of the reference's ``utils/tools/nn_distance.py``: the custom op on dmcf_nn_distance, differentiable in both point
-sets (dmcf_nn_distance_backward), and the Chamfer loss built on it (nn_distance.py:141-148)."""
+sets (dmcf_nn_distance_backward), and the Chamfer loss built on it (nn_distance.py:141-148).  ``nn_distance`` also takes
+``row_splits1`` / ``row_splits2``: a batch of point sets of different sizes in one call (dmcf_nn_distance_ragged, no gradient)."""
 import torch
 
 from ... import ops

@@ -19,6 +19,8 @@
  *     (a batch of point sets in one call; ABI 2.20)               dmcf_frs_write_batched, dmcf_radius_search_*_batched
  *   compute_density per sample of a training batch               dmcf_frs_window_sum_batched /
  *     (pipelines/simulator.py:227-243 inside the warm-up loop)    dmcf_frs_window_sum_backward_batched (ABI 2.22)
+ *   nn_distance per scene of a validation split                  dmcf_nn_distance_ragged (ABI 2.23: one call for
+ *     (pipelines/simulator.py:222-248, utils/evaluation_helper.py)  scenes of different particle counts)
  *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
  *                                                                 dmcf_cconv_backward_extents)
  *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
@@ -794,6 +796,28 @@ int dmcf_gather_point(const float* inp, const int32_t* index, int64_t n_index, i
 size_t dmcf_nn_distance_workspace_bytes(int64_t b, int64_t n, int64_t m);
 int dmcf_nn_distance(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, float* dist1, int32_t* idx1,
                      float* dist2, int32_t* idx2, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* nn_distance over a RAGGED batch (ABI 2.23): `batch` items of different sizes in one call.  xyz1 [n_total, 3] and xyz2
+ * [m_total, 3] hold the items' point sets one after the other; item b is xyz1[row_splits1[b] .. row_splits1[b + 1]) against
+ * xyz2[row_splits2[b] .. row_splits2[b + 1]).  Both row-splits arrays are HOST int64 [batch + 1] and are validated here, before
+ * anything is enqueued: they start at 0, do not decrease and end at n_total / m_total.  (The *_batched searches take DEVICE row
+ * splits the caller vouches for.  Here the kernel reads no row splits at all: the entry point cuts every item's rows into
+ * tiles of 64, writes one 16-byte record per tile -- its rows and its item's range of the other set -- from the validated
+ * splits and copies that table into the workspace, so nothing on the device can disagree with what was checked.)
+ * Result contract: dist1 [n_total] / idx1 [n_total] hold, for every row, what dmcf_nn_distance gives for its item alone, bit
+ * for bit -- (dx*dx + dy*dy) + dz*dz un-fused, a strict < over the columns in ascending order, so equal distances go to the
+ * lowest index -- with idx1 = the per-item index + row_splits2[b], the row in the concatenated xyz2; dist2 / idx2 [m_total]
+ * the same from xyz2 to xyz1.  A direction is skipped when both its pointers are NULL (one NULL of a pair, or both directions
+ * skipped: DMCF_EINVAL).  One launch per wanted direction, one wavefront per tile walking its item's other set through LDS: no
+ * combine pass, no atomics, nothing that depends on the device, so identical calls give identical bits.  Sized for many items
+ * of tens to a few thousand rows; an item of any size is correct, but one large set is dmcf_nn_distance's case.
+ * An item with both sets empty contributes nothing; an item with exactly ONE empty set is DMCF_EINVAL (as n == 0 || m == 0
+ * is above).  batch == 0 with n_total == m_total == 0, or every item empty: DMCF_OK, nothing enqueued.  batch < 0 or > 2^26,
+ * NULL row splits, n_total or m_total >= 2^31 - 257: DMCF_EINVAL.  Workspace: dmcf_nn_distance_ragged_workspace_bytes (0 for a
+ * negative size or a batch outside [1, 2^26]); the table reaches it by one asynchronous copy from pageable host memory. */
+size_t dmcf_nn_distance_ragged_workspace_bytes(int64_t n_total, int64_t m_total, int64_t batch);
+int dmcf_nn_distance_ragged(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                            const int64_t* row_splits2, int64_t batch, float* dist1, int32_t* idx1, float* dist2, int32_t* idx2,
+                            void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
 /* approx_match(xyz1, xyz2, n, m) (tf_approxmatch.py:40-54): match [b, m, n] of the approximate EMD assignment (the algorithm
  * is restated in dmcf_amd/csrc/metrics.hip: ten levels of three all-pairs passes, __expf weights, the reference's 1e-9 terms,
  * clamps and integer division).  count1 / count2: HOST arrays of b int32 point counts (n_i <= n, m_i <= m; NULL = all
