@@ -2242,7 +2242,7 @@ def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=No
                                          _ptr(lv["table"]), capacity, _stream()), "dmcf_grid_pos_count")
 
     key = (tuple(tuple(float(x) for x in lv["vs"]) for lv in levels), bool(centralize), int(pad), float(hyst))
-    _grid_count_levels(levels, key, count, read_headers, _grid_hash_slots(n, voxel_sizes[0], pad))
+    _grid_count_levels(levels, key, count, read_headers, max(_grid_hash_slots(n, v, pad) for v in voxel_sizes))
     totals = [lv["total"] for lv in levels]
     res = []
     for lv, total in zip(levels, totals):
@@ -2320,7 +2320,7 @@ def _grid_pos_many_batched(pos, voxel_sizes, centralize, pad, hyst, center, row_
 
     # (the estimate path of grid_pos_many, keyed with the batch size: a training loop asks for the same batch step after step)
     key = (tuple(tuple(float(x) for x in lv["vs"]) for lv in levels), bool(centralize), int(pad), float(hyst), batch)
-    _grid_count_levels(levels, key, count, read_headers, _grid_hash_slots(n, voxel_sizes[0], pad))
+    _grid_count_levels(levels, key, count, read_headers, max(_grid_hash_slots(n, v, pad) for v in voxel_sizes))
     res = []
     for lv in levels:
         out_host = [0]

@@ -52,6 +52,40 @@ def test_workspace_queries_and_host_validation(hip_lib):
     assert hip_lib.dmcf_cconv_forward(ctypes.byref(a), None, 0, None) == -1  # zero filter dims
 
 
+def test_grid_pos_refuses_more_than_2_32_candidates(hip_lib):
+    """Candidate ranks are 32-bit: 2 n n_off >= 2^32 is DMCF_EUNSUPPORTED from every grid_pos entry point, before anything is
+    enqueued.  Counts only: n = 400000 at pad = 8 (18^3 offsets) is 4.67e9 candidates; the workspace has the right size and
+    nothing in it or in the positions is touched (a word each would do: the call returns from its argument checks)."""
+    import torch
+    L = hip_lib
+    n, pad = 400000, 8
+    assert 2 * n * 18 ** 3 >= 1 << 32
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    nb = L.dmcf_grid_pos_workspace_bytes(n)
+    nbb = L.dmcf_grid_pos_workspace_bytes_batched(n, 2)
+    assert 0 < nb < 64 << 20 and 0 < nbb < 64 << 20  # (rows, not candidates: tens of megabytes)
+    buf = torch.zeros(max(nb, nbb) + 256, dtype=torch.uint8, device=dev)
+    ws = (buf.data_ptr() + 255) // 256 * 256
+    pos = torch.zeros(16, dtype=torch.float32, device=dev).data_ptr()
+    rs = torch.tensor([0, n // 2, n], dtype=torch.int64, device=dev).data_ptr()
+    vs = (ctypes.c_float * 3)(0.1, 0.1, 0.1)
+    EUNSUPPORTED = -4
+    assert L.dmcf_grid_pos_bounds(pos, n, vs, 1, None, pad, 0.1, ws, nb, None) == EUNSUPPORTED
+    assert L.dmcf_grid_pos_count(pos, n, vs, 1, pad, 0.1, ws, nb, pos, 4, None) == EUNSUPPORTED
+    assert L.dmcf_grid_pos_write(pos, n, vs, 1, pad, 0.1, ws, nb, pos, 4, pos, 1, None) == EUNSUPPORTED
+    assert L.dmcf_grid_pos_bounds_batched(pos, n, rs, 2, vs, 1, None, pad, 0.1, ws, nbb, None) == EUNSUPPORTED
+    assert L.dmcf_grid_pos_count_batched(pos, n, rs, 2, vs, 1, pad, 0.1, ws, nbb, pos, 4, rs, None) == EUNSUPPORTED
+    assert L.dmcf_grid_pos_write_batched(pos, n, rs, 2, vs, 1, pad, 0.1, ws, nbb, pos, 4, pos, 1, None) == EUNSUPPORTED
+    # just under the limit the same arguments pass that check: the next one (no workspace) answers
+    under = ((1 << 32) - 2) // (2 * 18 ** 3)
+    assert 2 * under * 18 ** 3 < (1 << 32) - 1 <= 2 * (under + 1) * 18 ** 3
+    assert L.dmcf_grid_pos_bounds(pos, under, vs, 1, None, pad, 0.1, None, 0, None) == -1
+    assert L.dmcf_grid_pos_bounds(pos, under + 1, vs, 1, None, pad, 0.1, None, 0, None) == EUNSUPPORTED
+    # the fewer offsets of a 2-D lattice move the limit: 18^2 offsets at the same n are fine
+    flat = (ctypes.c_float * 3)(0.1, 0.1, 0.0)
+    assert L.dmcf_grid_pos_bounds(pos, n, flat, 1, None, pad, 0.1, None, 0, None) == -1
+
+
 def test_struct_layout_matches_header():
     # field order of struct dmcf_cconv_args in the header == ctypes mirror
     from dmcf_amd._lib import CconvArgs
