@@ -47,13 +47,59 @@ __device__ __forceinline__ void grid_scaled(const GridParams& p, const GridHeade
     }
 }
 
-// stage 1 of the mean: per-block double sums
-__global__ __launch_bounds__(256) void grid_sum(const float* __restrict__ pos, int64_t n, double* __restrict__ part) {
+// ---- items --------------------------------------------------------------------------------------------------------------------
+// A call works on a BATCH of point sets (the _batched entry points, ABI 2.21): item b is positions[rs[b] .. rs[b + 1]) and the
+// result is the concatenation, item after item, of what the call returns for each slice alone -- bit for bit, in the same order.
+// The un-batched entry points are the case of ONE item: every kernel but the pass is instantiated twice, and ITEMS = false takes
+// the item's size from n and never reads rs (NULL) -- no load.  The pass alone stays two kernels, grid_pass for one item and
+// grid_pass_batched (see there).  What makes the identity so:
+//   centre : blockIdx.y = item.  Each item sums over its LOCAL index with the block count a call on n_b points alone launches
+//            (grid_item_blocks), so every partial sum has the same addends in the same order
+//   bounds : one GridHeader per item; a cell index is local to the item's own box and offset by the cells of the items before it
+//            (cell_off, the item as the outermost digit): two items at the same coordinates never share a cell
+//   rows   : item b owns rows [2 rs[b], 2 rs[b + 1]): its first-half rows, then its second-half rows -- (item, half, local point).
+//            The candidate rank row * n_off + off keeps an item's candidates in the relative order they have alone, and the scan
+//            over the rows gives item-grouped output; out_row_splits[b] = row_off[2 rs[b]]
+struct GridItems {
+    const int64_t* rs;        // [batch + 1] row splits
+    const int64_t* cell_off;  // [batch + 1] exclusive sum of the items' cells (grid_cell_offsets)
+    int batch;
+};
+template <bool ITEMS>
+__device__ __forceinline__ int64_t grid_item_begin(const GridItems& it, int b) { return ITEMS ? it.rs[b] : 0; }
+template <bool ITEMS>
+__device__ __forceinline__ int64_t grid_item_end(const GridItems& it, int b, int64_t n) { return ITEMS ? it.rs[b + 1] : n; }
+
+// blocks of the two reductions over an item of n points (the summation order of the mean depends on it)
+__host__ __device__ __forceinline__ int grid_item_blocks(int64_t n) {
+    const int64_t want = (n + 255) / 256;
+    return (int)(want < 1 ? 1 : (want > kGridBlocks ? kGridBlocks : want));
+}
+
+// the item that holds global point i: the last b with rs[b] <= i (empty items are stepped over)
+__device__ __forceinline__ int grid_item_of(const int64_t* __restrict__ rs, int batch, int64_t i) {
+    int lo = 0, hi = batch;  // invariant: rs[lo] <= i < rs[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rs[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// stage 1 of the mean: per-block double sums of item blockIdx.y; part[(item * gridDim.x + block) * 3 + axis].  The grid has the
+// blocks of the largest possible item (all n points): the surplus blocks of a smaller one return
+template <bool ITEMS>
+__global__ __launch_bounds__(256) void grid_sum(const float* __restrict__ pos, int64_t n_all, const GridItems it,
+                                                double* __restrict__ part) {
+    const int64_t b0 = grid_item_begin<ITEMS>(it, blockIdx.y), n = grid_item_end<ITEMS>(it, blockIdx.y, n_all) - b0;
+    const int nb = grid_item_blocks(n);
+    if ((int)blockIdx.x >= nb) return;
+    const float* __restrict__ q = pos + 3 * b0;
     double s[3] = {0.0, 0.0, 0.0};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        s[0] += (double)pos[3 * i];
-        s[1] += (double)pos[3 * i + 1];
-        s[2] += (double)pos[3 * i + 2];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)nb * 256) {
+        s[0] += (double)q[3 * i];
+        s[1] += (double)q[3 * i + 1];
+        s[2] += (double)q[3 * i + 2];
     }
     __shared__ double red[3][4];
 #pragma unroll
@@ -65,19 +111,25 @@ __global__ __launch_bounds__(256) void grid_sum(const float* __restrict__ pos, i
     __syncthreads();
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        part[blockIdx.x * 3 + a] = (red[a][0] + red[a][1]) + (red[a][2] + red[a][3]);
+        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + a] = (red[a][0] + red[a][1]) + (red[a][2] + red[a][3]);
     }
 }
 
-// one wavefront: lane l sums the blocks l, l + 64, ... in rising order, the 64 partial sums meet in a fixed butterfly --
-// deterministic (a serial loop over the blocks was 54 us of dependent double adds behind dependent loads)
-__global__ void grid_center(const double* __restrict__ part, int nblocks, int64_t n, const float* __restrict__ given,
-                            GridHeader* h) {
+// one wavefront per item (blockIdx.x): lane l sums the item's blocks l, l + 64, ... in rising order, the 64 partial sums meet in a
+// fixed butterfly -- deterministic (a serial loop over the blocks was 54 us of dependent double adds behind dependent loads).
+// given: [batch, 3] or NULL
+template <bool ITEMS>
+__global__ void grid_center(const double* __restrict__ part, int nbx, int64_t n_all, const GridItems it,
+                            const float* __restrict__ given, GridHeader* hs) {
     const int lane = lane_id();
+    GridHeader* h = hs + blockIdx.x;
     if (given) {
-        if (lane < 3) h->center[lane] = given[lane];
+        if (lane < 3) h->center[lane] = given[3 * blockIdx.x + lane];
         return;
     }
+    const int64_t n = grid_item_end<ITEMS>(it, blockIdx.x, n_all) - grid_item_begin<ITEMS>(it, blockIdx.x);
+    const int nblocks = grid_item_blocks(n);
+    part += (size_t)blockIdx.x * nbx * 3;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         double s = 0.0;
@@ -88,10 +140,15 @@ __global__ void grid_center(const double* __restrict__ part, int nblocks, int64_
     }
 }
 
-// extrema of the scaled positions, per block
-__global__ __launch_bounds__(256) void grid_extrema(const GridParams p, const GridHeader* h, float* __restrict__ part) {
+// extrema of the scaled positions of item blockIdx.y, per block (min / max: any order gives the same bits, the block count only
+// has to cover the item)
+template <bool ITEMS>
+__global__ __launch_bounds__(256) void grid_extrema(const GridParams p, const GridHeader* hs, const GridItems it,
+                                                    float* __restrict__ part) {
+    const int64_t b0 = grid_item_begin<ITEMS>(it, blockIdx.y), e0 = grid_item_end<ITEMS>(it, blockIdx.y, p.n);
+    const GridHeader* h = hs + blockIdx.y;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * 256) {
+    for (int64_t i = b0 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < e0; i += (int64_t)gridDim.x * 256) {
         float s[3];
         grid_scaled(p, h, i, s);
 #pragma unroll
@@ -118,19 +175,25 @@ __global__ __launch_bounds__(256) void grid_extrema(const GridParams p, const Gr
     __syncthreads();
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        part[blockIdx.x * 6 + a] = fminf(fminf(red[0][a][0], red[0][a][1]), fminf(red[0][a][2], red[0][a][3]));
-        part[blockIdx.x * 6 + 3 + a] = fmaxf(fmaxf(red[1][a][0], red[1][a][1]), fmaxf(red[1][a][2], red[1][a][3]));
+        float* o = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 6;
+        o[a] = fminf(fminf(red[0][a][0], red[0][a][1]), fminf(red[0][a][2], red[0][a][3]));
+        o[3 + a] = fmaxf(fmaxf(red[1][a][0], red[1][a][1]), fmaxf(red[1][a][2], red[1][a][3]));
     }
 }
 
-__global__ void grid_finish_bounds(const GridParams p, const float* __restrict__ part, int nblocks, GridHeader* h) {
-    // one wavefront: the blocks' extrema by lanes, then a butterfly (min / max: any order gives the same bits)
+// one wavefront per item (blockIdx.x): the blocks' extrema by lanes, then a butterfly -> the item's header
+template <bool ITEMS>
+__global__ void grid_finish_bounds(const GridParams p, const float* __restrict__ part, int nbx, const GridItems it,
+                                   GridHeader* hs) {
     const int lane = lane_id();
+    GridHeader* h = hs + blockIdx.x;
+    const int64_t n = grid_item_end<ITEMS>(it, blockIdx.x, p.n) - grid_item_begin<ITEMS>(it, blockIdx.x);
+    part += (size_t)blockIdx.x * nbx * 6;
     float mns[3], mxs[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         float mn = INFINITY, mx = -INFINITY;
-        for (int b = lane; b < nblocks; b += kWave) {
+        for (int b = lane; b < nbx; b += kWave) {
             mn = fminf(mn, part[b * 6 + a]);
             mx = fmaxf(mx, part[b * 6 + 3 + a]);
         }
@@ -143,16 +206,16 @@ __global__ void grid_finish_bounds(const GridParams p, const float* __restrict__
         mxs[a] = mx;
     }
     if (lane != 0) return;
-    int64_t cells = p.n > 0 ? 1 : 0;
+    int64_t cells = n > 0 ? 1 : 0;
     for (int a = 0; a < 3; ++a) {
         const float mn = mns[a], mx = mxs[a];
         int lo = 0, d = 0;
-        if (p.n > 0 && isfinite(mn) && isfinite(mx)) {
+        if (n > 0 && isfinite(mn) && isfinite(mx)) {
             // :167-170 -- floor is monotone: the extrema of the candidates follow from the extrema of the positions
             lo = (int)floorf(__fsub_rn(mn, p.h[a])) + p.lo[a];
             const int hi = (int)floorf(__fadd_rn(mx, p.h[a])) + p.lo[a] + p.len[a] - 1;
             d = hi - lo + 1;
-        } else if (p.n > 0) {
+        } else if (n > 0) {
             cells = -1;  // non-finite positions: the caller reports an error
         }
         h->minp[a] = lo;
@@ -161,6 +224,19 @@ __global__ void grid_finish_bounds(const GridParams p, const float* __restrict__
     }
     h->cells = cells;
     h->total = 0;
+}
+
+// cell_off[b] = cells of the items before b (an item with non-finite positions counts as empty: the caller reports the error).
+// One thread: a batch is tens of items, and this runs once per call behind the per-item wavefronts above.  (One item: base 0.)
+__global__ void grid_cell_offsets(const GridHeader* __restrict__ hs, int64_t batch, int64_t* __restrict__ cell_off) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int64_t acc = 0;
+    for (int64_t b = 0; b < batch; ++b) {
+        cell_off[b] = acc;
+        const int64_t c = hs[b].cells;
+        acc += c > 0 ? c : 0;
+    }
+    cell_off[batch] = acc;
 }
 
 // the two candidate base cells of particle i (relative to minp); returns whether the "+h" cell differs from the "-h" one
@@ -202,6 +278,9 @@ __device__ __forceinline__ int64_t grid_slot(unsigned long long* keys, uint32_t 
     return -1;  // (table full: the caller sized it for every candidate, so this does not happen)
 }
 
+// The pass is the one step that stays two kernels, this one for one item and grid_pass_batched below: folded into one template,
+// the one-item instantiation measured 0.4 us of 44 slower per call of MODE 1 on a million points and 0.4 of 50 in MODE 2
+// (profiles/grid_pos_unified.md).  A fix to the candidate ranks, the hashed table or the lane-below rule goes into both.
 // MODE 0: atomicMin pass; MODE 1: count owners per row; MODE 2: write owners
 template <int MODE>
 __global__ __launch_bounds__(256) void grid_pass(const GridParams p, const GridHeader* __restrict__ h,
@@ -263,214 +342,6 @@ __global__ __launch_bounds__(256) void grid_pass(const GridParams p, const GridH
                 }
             }
     if (MODE == 1) counts[row] = cnt;
-}
-
-__global__ void grid_store_total(const int64_t* __restrict__ row_off, int64_t rows, GridHeader* h) {
-    if (threadIdx.x == 0) h->total = row_off[rows];
-}
-
-struct GridLayout {
-    size_t off_header, off_part, off_counts, off_rowoff, off_scan, total;
-};
-
-static GridLayout grid_layout(int64_t n) {
-    GridLayout L;
-    size_t o = 0;
-    L.off_header = o; o += 256;
-    L.off_part = o; o += align_up((size_t)kGridBlocks * 6 * sizeof(double), 256);
-    L.off_counts = o; o += align_up((size_t)(2 * n + 1) * 4, 256);
-    L.off_rowoff = o; o += align_up((size_t)(2 * n + 2) * 8, 256);
-    L.off_scan = o; o += align_up(scan_tmp_bytes(2 * n + 1), 256);
-    L.total = o;
-    return L;
-}
-
-static int grid_params(GridParams& p, const float* pos, int64_t n, const float* voxel, int centralize, int pad,
-                       float hyst) {
-    if (n < 0 || (n > 0 && !pos) || !voxel || pad < 0 || pad > 8) return DMCF_EINVAL;
-    p.pos = pos;
-    p.n = n;
-    p.centralize = centralize ? 1 : 0;
-    int64_t noff = 1;
-    for (int a = 0; a < 3; ++a) {
-        const bool active = voxel[a] >= 1e-5f;
-        p.voxel[a] = voxel[a];
-        p.vs[a] = active ? voxel[a] : 1e-5f;
-        p.h[a] = active ? hyst : 0.0f;
-        p.lo[a] = active ? -pad : 0;           // :151-161
-        p.len[a] = active ? 2 + 2 * pad : 1;
-        noff *= p.len[a];
-    }
-    if (2 * n * noff >= (int64_t)0xffffffffLL) return DMCF_EUNSUPPORTED;  // candidate ranks are 32-bit
-    return DMCF_OK;
-}
-
-// ---- grid_pos with row splits (ABI 2.21) ------------------------------------------------------------------------------------
-// A batch of point sets in one call: item b is positions[rs[b] .. rs[b + 1]) and the result is the concatenation, item after item,
-// of what the three phases above return for each slice -- bit for bit, in the same order.  What makes that so:
-//   centre : blockIdx.y = item.  Each item runs grid_sum / grid_center's sums over its LOCAL index with the block count the
-//            un-batched call would launch for n_b points (grid_item_blocks), so every partial sum has the same addends in the same order
-//   bounds : one GridHeader per item; a cell index is local to the item's own box and offset by the cells of the items before it
-//            (cell_off, the item as the outermost digit): two items at the same coordinates never share a cell
-//   rows   : item b owns rows [2 rs[b], 2 rs[b + 1]): its first-half rows, then its second-half rows -- (item, half, local point).
-//            The candidate rank row * n_off + off keeps an item's candidates in their un-batched relative order, and the scan over
-//            the rows gives item-grouped output; out_row_splits[b] = row_off[2 rs[b]]
-__device__ __forceinline__ int grid_item_blocks(int64_t n) {  // the nb of dmcf_grid_pos_bounds
-    const int64_t want = (n + 255) / 256;
-    return (int)(want < 1 ? 1 : (want > kGridBlocks ? kGridBlocks : want));
-}
-
-// the item that holds global point i: the last b with rs[b] <= i (empty items are stepped over)
-__device__ __forceinline__ int grid_item_of(const int64_t* __restrict__ rs, int batch, int64_t i) {
-    int lo = 0, hi = batch;  // invariant: rs[lo] <= i < rs[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (rs[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// grid_sum per item; part[(item * nbx + block) * 3 + axis], nbx = gridDim.x
-__global__ __launch_bounds__(256) void grid_sum_batched(const float* __restrict__ pos, const int64_t* __restrict__ rs,
-                                                        double* __restrict__ part) {
-    const int64_t b0 = rs[blockIdx.y], n = rs[blockIdx.y + 1] - b0;
-    const int nb = grid_item_blocks(n);
-    if ((int)blockIdx.x >= nb) return;
-    const float* __restrict__ q = pos + 3 * b0;
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)nb * 256) {
-        s[0] += (double)q[3 * i];
-        s[1] += (double)q[3 * i + 1];
-        s[2] += (double)q[3 * i + 2];
-    }
-    __shared__ double red[3][4];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s[a] += __shfl_xor(s[a], d, kWave);
-        if (lane_id() == 0) red[a][threadIdx.x >> 6] = s[a];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + a] = (red[a][0] + red[a][1]) + (red[a][2] + red[a][3]);
-    }
-}
-
-// grid_center per item: one wavefront per item (blockIdx.x = item); given: [batch, 3] or NULL
-__global__ void grid_center_batched(const double* __restrict__ part, int nbx, const int64_t* __restrict__ rs,
-                                    const float* __restrict__ given, GridHeader* hs) {
-    const int lane = lane_id();
-    GridHeader* h = hs + blockIdx.x;
-    if (given) {
-        if (lane < 3) h->center[lane] = given[3 * blockIdx.x + lane];
-        return;
-    }
-    const int64_t n = rs[blockIdx.x + 1] - rs[blockIdx.x];
-    const int nblocks = grid_item_blocks(n);
-    part += (size_t)blockIdx.x * nbx * 3;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        double s = 0.0;
-        for (int b = lane; b < nblocks; b += kWave) s += part[b * 3 + a];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, kWave);
-        if (lane == 0) h->center[a] = n > 0 ? (float)(s / (double)n) : 0.0f;
-    }
-}
-
-// grid_extrema per item (min / max: any order gives the same bits, the block count only has to cover the item)
-__global__ __launch_bounds__(256) void grid_extrema_batched(const GridParams p, const GridHeader* hs,
-                                                            const int64_t* __restrict__ rs, float* __restrict__ part) {
-    const int64_t b0 = rs[blockIdx.y], e0 = rs[blockIdx.y + 1];
-    const GridHeader* h = hs + blockIdx.y;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int64_t i = b0 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < e0; i += (int64_t)gridDim.x * 256) {
-        float s[3];
-        grid_scaled(p, h, i, s);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const bool ok = fabsf(s[a]) < INFINITY;
-            mn[a] = ok ? fminf(mn[a], s[a]) : -INFINITY;
-            mx[a] = ok ? fmaxf(mx[a], s[a]) : INFINITY;
-        }
-    }
-    __shared__ float red[2][3][4];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], d, kWave));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d, kWave));
-        }
-        if (lane_id() == 0) {
-            red[0][a][threadIdx.x >> 6] = mn[a];
-            red[1][a][threadIdx.x >> 6] = mx[a];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        float* o = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 6;
-        o[a] = fminf(fminf(red[0][a][0], red[0][a][1]), fminf(red[0][a][2], red[0][a][3]));
-        o[3 + a] = fmaxf(fmaxf(red[1][a][0], red[1][a][1]), fmaxf(red[1][a][2], red[1][a][3]));
-    }
-}
-
-// grid_finish_bounds per item: one wavefront per item
-__global__ void grid_finish_bounds_batched(const GridParams p, const float* __restrict__ part, int nbx,
-                                           const int64_t* __restrict__ rs, GridHeader* hs) {
-    const int lane = lane_id();
-    GridHeader* h = hs + blockIdx.x;
-    const int64_t n = rs[blockIdx.x + 1] - rs[blockIdx.x];
-    part += (size_t)blockIdx.x * nbx * 6;
-    float mns[3], mxs[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float mn = INFINITY, mx = -INFINITY;
-        for (int b = lane; b < nbx; b += kWave) {
-            mn = fminf(mn, part[b * 6 + a]);
-            mx = fmaxf(mx, part[b * 6 + 3 + a]);
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            mn = fminf(mn, __shfl_xor(mn, d, kWave));
-            mx = fmaxf(mx, __shfl_xor(mx, d, kWave));
-        }
-        mns[a] = mn;
-        mxs[a] = mx;
-    }
-    if (lane != 0) return;
-    int64_t cells = n > 0 ? 1 : 0;
-    for (int a = 0; a < 3; ++a) {
-        const float mn = mns[a], mx = mxs[a];
-        int lo = 0, d = 0;
-        if (n > 0 && isfinite(mn) && isfinite(mx)) {
-            lo = (int)floorf(__fsub_rn(mn, p.h[a])) + p.lo[a];
-            const int hi = (int)floorf(__fadd_rn(mx, p.h[a])) + p.lo[a] + p.len[a] - 1;
-            d = hi - lo + 1;
-        } else if (n > 0) {
-            cells = -1;
-        }
-        h->minp[a] = lo;
-        h->dims[a] = d;
-        if (cells > 0) cells *= d;
-    }
-    h->cells = cells;
-    h->total = 0;
-}
-
-// cell_off[b] = cells of the items before b (an item with non-finite positions counts as empty: the caller reports the error).
-// One thread: a batch is tens of items, and this runs once per call behind the per-item wavefronts above.
-__global__ void grid_cell_offsets(const GridHeader* __restrict__ hs, int64_t batch, int64_t* __restrict__ cell_off) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    int64_t acc = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        cell_off[b] = acc;
-        const int64_t c = hs[b].cells;
-        acc += c > 0 ? c : 0;
-    }
-    cell_off[batch] = acc;
 }
 
 // grid_pass with items: row r of [0, 2 n) belongs to the item that holds point r / 2's slot (rows [2 rs[b], 2 rs[b + 1])).
@@ -542,25 +413,31 @@ __global__ __launch_bounds__(256) void grid_pass_batched(const GridParams p, con
     if (MODE == 1) counts[row] = cnt;
 }
 
-// out_row_splits[b] = first output row of item b (b = batch: the number of lattice points); header b's total = item b's points
-__global__ void grid_store_totals_batched(const int64_t* __restrict__ row_off, const int64_t* __restrict__ rs, int64_t batch,
-                                          GridHeader* hs, int64_t* __restrict__ out_row_splits) {
+// out_row_splits[b] = first output row of item b (b = batch: the number of lattice points; not written where NULL);
+// header b's total = item b's points
+template <bool ITEMS>
+__global__ void grid_store_totals(const int64_t* __restrict__ row_off, int64_t n_all, const GridItems it, GridHeader* hs,
+                                  int64_t* __restrict__ out_row_splits) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b > batch) return;
-    const int64_t lo = row_off[2 * rs[b]];
-    out_row_splits[b] = lo;
-    if (b < batch) hs[b].total = row_off[2 * rs[b + 1]] - lo;
+    if (b > it.batch) return;
+    // (b = batch is past the last item: its "begin" is the end of the call, n_all -- rs[batch] for the validated row splits the
+    // header asks of the caller)
+    const int64_t lo = row_off[2 * (b < it.batch ? grid_item_begin<ITEMS>(it, (int)b) : n_all)];
+    if (out_row_splits) out_row_splits[b] = lo;
+    if (b < it.batch) hs[b].total = row_off[2 * grid_item_end<ITEMS>(it, (int)b, n_all)] - lo;
 }
 
-struct GridBatchLayout {
+constexpr int64_t kGridMaxBatch = 65535;  // the item is blockIdx.y of the two reductions
+
+// the workspace of a call of `batch` items (the un-batched entry points: 1); header 0 is at offset 0
+struct GridLayout {
     size_t off_headers, off_celloff, off_part, off_counts, off_rowoff, off_scan, total;
-    int nbx;  // blocks per item of the two reductions: what the largest possible item (all n points) would get
+    int nbx;  // blocks per item of the two reductions: what the largest possible item (all n points) gets
 };
 
-static GridBatchLayout grid_batch_layout(int64_t n, int64_t batch) {
-    GridBatchLayout L;
-    const int64_t want = (n + 255) / 256;
-    L.nbx = (int)(want < 1 ? 1 : (want > kGridBlocks ? kGridBlocks : want));
+static GridLayout grid_layout(int64_t n, int64_t batch) {
+    GridLayout L;
+    L.nbx = grid_item_blocks(n);
     size_t o = 0;
     L.off_headers = o; o += align_up((size_t)batch * sizeof(GridHeader), 256);
     L.off_celloff = o; o += align_up((size_t)(batch + 1) * 8, 256);
@@ -572,7 +449,129 @@ static GridBatchLayout grid_batch_layout(int64_t n, int64_t batch) {
     return L;
 }
 
-constexpr int64_t kGridMaxBatch = 65535;  // the item is blockIdx.y of the two reductions
+static int grid_params(GridParams& p, const float* pos, int64_t n, const float* voxel, int centralize, int pad,
+                       float hyst) {
+    if (n < 0 || (n > 0 && !pos) || !voxel || pad < 0 || pad > 8) return DMCF_EINVAL;
+    p.pos = pos;
+    p.n = n;
+    p.centralize = centralize ? 1 : 0;
+    int64_t noff = 1;
+    for (int a = 0; a < 3; ++a) {
+        const bool active = voxel[a] >= 1e-5f;
+        p.voxel[a] = voxel[a];
+        p.vs[a] = active ? voxel[a] : 1e-5f;
+        p.h[a] = active ? hyst : 0.0f;
+        p.lo[a] = active ? -pad : 0;           // :151-161
+        p.len[a] = active ? 2 + 2 * pad : 1;
+        noff *= p.len[a];
+    }
+    if (2 * n * noff >= (int64_t)0xffffffffLL) return DMCF_EUNSUPPORTED;  // candidate ranks are 32-bit
+    return DMCF_OK;
+}
+
+// What the three phases share: the argument checks, in the order of precedence the ABI tests pin, and the carved workspace.
+// ITEMS = false is an un-batched entry point: rs = NULL, batch = 1.  bad_items / bad_args: the phase's own DMCF_EINVAL
+// conditions, checked before grid_params with the row splits and after it with the workspace.
+struct GridCall {
+    GridParams p;
+    GridLayout L;
+    GridItems it;
+    char* ws;
+    GridHeader* hs;
+};
+
+template <bool ITEMS>
+static int grid_call(GridCall& c, const float* pos, int64_t n, const int64_t* rs, int64_t batch, const float* voxel,
+                     int centralize, int pad, float hyst, void* workspace, size_t workspace_bytes, bool bad_items,
+                     bool bad_args) {
+    if (ITEMS && (batch < 1 || !rs || bad_items)) return DMCF_EINVAL;
+    const int rc = grid_params(c.p, pos, n, voxel, centralize, pad, hyst);
+    if (rc != DMCF_OK) return rc;
+    if (batch > kGridMaxBatch) return DMCF_EUNSUPPORTED;
+    if (!workspace || ((uintptr_t)workspace & 255) || bad_args) return DMCF_EINVAL;
+    c.L = grid_layout(n, batch);
+    if (workspace_bytes < c.L.total) return DMCF_EWORKSPACE;
+    c.ws = (char*)workspace;
+    c.hs = (GridHeader*)(c.ws + c.L.off_headers);
+    c.it = GridItems{rs, ITEMS ? (const int64_t*)(c.ws + c.L.off_celloff) : nullptr, (int)batch};
+    return DMCF_OK;
+}
+
+// pass MODE over the 2 n rows of the call (n > 0): the one-item kernel or the items kernel
+template <int MODE, bool ITEMS>
+static void grid_launch_pass(const GridCall& c, uint32_t* first, int32_t* counts, const int64_t* row_off, float* out,
+                             int64_t out_capacity, int64_t table_cells, hipStream_t stream) {
+    const dim3 g((unsigned)((2 * c.p.n + 255) / 256));
+    const GridHeader* hs = c.hs;
+    if (ITEMS)
+        hipLaunchKernelGGL((grid_pass_batched<MODE>), g, dim3(256), 0, stream, c.p, hs, c.it.rs, c.it.batch, c.it.cell_off, first,
+                           counts, row_off, out, out_capacity, table_cells);
+    else
+        hipLaunchKernelGGL((grid_pass<MODE>), g, dim3(256), 0, stream, c.p, hs, first, counts, row_off, out, out_capacity,
+                           table_cells);
+}
+
+template <bool ITEMS>
+static int grid_bounds(const float* pos, int64_t n, const int64_t* rs, int64_t batch, const float* voxel, int centralize,
+                       const float* centers, int pad, float hyst, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    GridCall c;
+    const int rc = grid_call<ITEMS>(c, pos, n, rs, batch, voxel, centralize, pad, hyst, workspace, workspace_bytes, false, false);
+    if (rc != DMCF_OK) return rc;
+    const dim3 blocks(c.L.nbx, (unsigned)batch), waves((unsigned)batch);
+    if (c.p.centralize) {
+        double* part = (double*)(c.ws + c.L.off_part);
+        if (!centers) hipLaunchKernelGGL(grid_sum<ITEMS>, blocks, dim3(256), 0, stream, pos, n, c.it, part);
+        hipLaunchKernelGGL(grid_center<ITEMS>, waves, dim3(64), 0, stream, part, c.L.nbx, n, c.it, centers, c.hs);
+    }
+    float* fpart = (float*)(c.ws + c.L.off_part);
+    hipLaunchKernelGGL(grid_extrema<ITEMS>, blocks, dim3(256), 0, stream, c.p, c.hs, c.it, fpart);
+    hipLaunchKernelGGL(grid_finish_bounds<ITEMS>, waves, dim3(64), 0, stream, c.p, fpart, c.L.nbx, c.it, c.hs);
+    if (ITEMS)
+        hipLaunchKernelGGL(grid_cell_offsets, dim3(1), dim3(64), 0, stream, c.hs, batch, (int64_t*)(c.ws + c.L.off_celloff));
+    return check_launch();
+}
+
+template <bool ITEMS>
+static int grid_count(const float* pos, int64_t n, const int64_t* rs, int64_t batch, const float* voxel, int centralize, int pad,
+                      float hyst, void* workspace, size_t workspace_bytes, void* cell_table, int64_t table_cells,
+                      int64_t* out_row_splits, hipStream_t stream) {
+    GridCall c;
+    const bool hashed_bad = table_cells < 0 && ((-table_cells) & (-table_cells - 1));  // hashed: a power of two of slots
+    int rc = grid_call<ITEMS>(c, pos, n, rs, batch, voxel, centralize, pad, hyst, workspace, workspace_bytes, !out_row_splits,
+                              (table_cells != 0 && !cell_table) || hashed_bad);
+    if (rc != DMCF_OK) return rc;
+    uint32_t* first = (uint32_t*)cell_table;
+    int32_t* counts = (int32_t*)(c.ws + c.L.off_counts);
+    int64_t* row_off = (int64_t*)(c.ws + c.L.off_rowoff);
+    const int64_t rows = 2 * n;
+    // (hashed: 4 bytes of `first` + 8 bytes of key per slot, all ones = empty)
+    const size_t table_bytes = table_cells >= 0 ? (size_t)table_cells * 4 : (size_t)(-table_cells) * 12;
+    if (table_bytes > 0 && hipMemsetAsync(first, 0xff, table_bytes, stream) != hipSuccess) return DMCF_ELAUNCH;
+    if (rows > 0) {
+        grid_launch_pass<0, ITEMS>(c, first, counts, nullptr, nullptr, 0, table_cells, stream);
+        grid_launch_pass<1, ITEMS>(c, first, counts, nullptr, nullptr, 0, table_cells, stream);
+    }
+    rc = scan_counts_to_row_splits(counts, row_off, rows, c.ws + c.L.off_scan, c.L.total - c.L.off_scan, stream);
+    if (rc != DMCF_OK) return rc;
+    hipLaunchKernelGGL(grid_store_totals<ITEMS>, dim3((unsigned)((batch + 256) / 256)), dim3(256), 0, stream, row_off, n, c.it,
+                       c.hs, out_row_splits);
+    return check_launch();
+}
+
+template <bool ITEMS>
+static int grid_write(const float* pos, int64_t n, const int64_t* rs, int64_t batch, const float* voxel, int centralize, int pad,
+                      float hyst, void* workspace, size_t workspace_bytes, const void* cell_table, int64_t table_cells, float* out,
+                      int64_t out_capacity, hipStream_t stream) {
+    GridCall c;
+    const int rc = grid_call<ITEMS>(c, pos, n, rs, batch, voxel, centralize, pad, hyst, workspace, workspace_bytes, false,
+                                    out_capacity < 0 || (out_capacity > 0 && (!out || !cell_table)));
+    if (rc != DMCF_OK) return rc;
+    const int64_t rows = 2 * n;
+    if (rows > 0 && out_capacity > 0)
+        grid_launch_pass<2, ITEMS>(c, (uint32_t*)cell_table, (int32_t*)(c.ws + c.L.off_counts),
+                                   (const int64_t*)(c.ws + c.L.off_rowoff), out, out_capacity, table_cells, stream);
+    return check_launch();
+}
 
 }  // namespace dmcf
 
@@ -582,181 +581,56 @@ extern "C" {
 
 size_t dmcf_grid_pos_workspace_bytes(int64_t n_points) {
     if (n_points < 0) return 0;
-    return grid_layout(n_points).total;
+    return grid_layout(n_points, 1).total;
 }
 
 int dmcf_grid_pos_bounds(const float* positions, int64_t n_points, const float* voxel_size, int centralize,
                          const float* center, int pad, float hyst, void* workspace, size_t workspace_bytes,
-                         dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GridParams p;
-    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
-    if (rc != DMCF_OK) return rc;
-    if (!workspace || ((uintptr_t)workspace & 255)) return DMCF_EINVAL;
-    const GridLayout L = grid_layout(n_points);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    GridHeader* h = (GridHeader*)(ws + L.off_header);
-    const int64_t want = (n_points + 255) / 256;
-    const int nb = (int)(want < 1 ? 1 : (want > kGridBlocks ? kGridBlocks : want));
-    if (p.centralize) {
-        double* part = (double*)(ws + L.off_part);
-        if (!center) hipLaunchKernelGGL(grid_sum, dim3(nb), dim3(256), 0, stream, positions, n_points, part);
-        hipLaunchKernelGGL(grid_center, dim3(1), dim3(64), 0, stream, part, nb, n_points, center, h);
-    }
-    float* fpart = (float*)(ws + L.off_part);
-    hipLaunchKernelGGL(grid_extrema, dim3(nb), dim3(256), 0, stream, p, h, fpart);
-    hipLaunchKernelGGL(grid_finish_bounds, dim3(1), dim3(64), 0, stream, p, fpart, nb, h);
-    return check_launch();
+                         dmcf_stream_t stream) {
+    return grid_bounds<false>(positions, n_points, nullptr, 1, voxel_size, centralize, center, pad, hyst, workspace,
+                              workspace_bytes, (hipStream_t)stream);
 }
 
 int dmcf_grid_pos_count(const float* positions, int64_t n_points, const float* voxel_size, int centralize, int pad,
                         float hyst, void* workspace, size_t workspace_bytes, void* cell_table, int64_t table_cells,
-                        dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GridParams p;
-    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
-    if (rc != DMCF_OK) return rc;
-    if (!workspace || ((uintptr_t)workspace & 255) || (table_cells != 0 && !cell_table)) return DMCF_EINVAL;
-    if (table_cells < 0 && ((-table_cells) & (-table_cells - 1))) return DMCF_EINVAL;  // hashed: a power of two of slots
-    const GridLayout L = grid_layout(n_points);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    GridHeader* h = (GridHeader*)(ws + L.off_header);
-    uint32_t* first = (uint32_t*)cell_table;
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    int64_t* row_off = (int64_t*)(ws + L.off_rowoff);
-    const int64_t rows = 2 * n_points;
-    // (hashed: 4 bytes of `first` + 8 bytes of key per slot, all ones = empty)
-    const size_t table_bytes = table_cells >= 0 ? (size_t)table_cells * 4 : (size_t)(-table_cells) * 12;
-    if (table_bytes > 0 && hipMemsetAsync(first, 0xff, table_bytes, stream) != hipSuccess) return DMCF_ELAUNCH;
-    if (rows > 0) {
-        const unsigned g = (unsigned)((rows + 255) / 256);
-        hipLaunchKernelGGL((grid_pass<0>), dim3(g), dim3(256), 0, stream, p, h, first, counts, (const int64_t*)nullptr,
-                           (float*)nullptr, (int64_t)0, table_cells);
-        hipLaunchKernelGGL((grid_pass<1>), dim3(g), dim3(256), 0, stream, p, h, first, counts, (const int64_t*)nullptr,
-                           (float*)nullptr, (int64_t)0, table_cells);
-    }
-    rc = scan_counts_to_row_splits(counts, row_off, rows, ws + L.off_scan, L.total - L.off_scan, stream);
-    if (rc != DMCF_OK) return rc;
-    hipLaunchKernelGGL(grid_store_total, dim3(1), dim3(64), 0, stream, row_off, rows, h);
-    return check_launch();
+                        dmcf_stream_t stream) {
+    return grid_count<false>(positions, n_points, nullptr, 1, voxel_size, centralize, pad, hyst, workspace, workspace_bytes,
+                             cell_table, table_cells, nullptr, (hipStream_t)stream);
 }
 
 int dmcf_grid_pos_write(const float* positions, int64_t n_points, const float* voxel_size, int centralize, int pad,
                         float hyst, void* workspace, size_t workspace_bytes, const void* cell_table, int64_t table_cells,
-                        float* out, int64_t out_capacity, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GridParams p;
-    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
-    if (rc != DMCF_OK) return rc;
-    if (!workspace || ((uintptr_t)workspace & 255) || out_capacity < 0 || (out_capacity > 0 && (!out || !cell_table)))
-        return DMCF_EINVAL;
-    const GridLayout L = grid_layout(n_points);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    const GridHeader* h = (const GridHeader*)(ws + L.off_header);
-    const int64_t rows = 2 * n_points;
-    if (rows > 0 && out_capacity > 0) {
-        const unsigned g = (unsigned)((rows + 255) / 256);
-        hipLaunchKernelGGL((grid_pass<2>), dim3(g), dim3(256), 0, stream, p, h, (uint32_t*)cell_table,
-                           (int32_t*)(ws + L.off_counts), (const int64_t*)(ws + L.off_rowoff), out, out_capacity, table_cells);
-    }
-    return check_launch();
+                        float* out, int64_t out_capacity, dmcf_stream_t stream) {
+    return grid_write<false>(positions, n_points, nullptr, 1, voxel_size, centralize, pad, hyst, workspace, workspace_bytes,
+                             cell_table, table_cells, out, out_capacity, (hipStream_t)stream);
 }
 
 size_t dmcf_grid_pos_workspace_bytes_batched(int64_t n_points, int64_t batch) {
     if (n_points < 0 || batch < 1 || batch > kGridMaxBatch) return 0;
-    return grid_batch_layout(n_points, batch).total;
+    return grid_layout(n_points, batch).total;
 }
 
 int dmcf_grid_pos_bounds_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
                                  const float* voxel_size, int centralize, const float* centers, int pad, float hyst,
-                                 void* workspace, size_t workspace_bytes, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GridParams p;
-    if (batch < 1 || !row_splits) return DMCF_EINVAL;
-    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
-    if (rc != DMCF_OK) return rc;
-    if (batch > kGridMaxBatch) return DMCF_EUNSUPPORTED;
-    if (!workspace || ((uintptr_t)workspace & 255)) return DMCF_EINVAL;
-    const GridBatchLayout L = grid_batch_layout(n_points, batch);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    GridHeader* hs = (GridHeader*)(ws + L.off_headers);
-    if (p.centralize) {
-        double* part = (double*)(ws + L.off_part);
-        if (!centers)
-            hipLaunchKernelGGL(grid_sum_batched, dim3(L.nbx, (unsigned)batch), dim3(256), 0, stream, positions, row_splits, part);
-        hipLaunchKernelGGL(grid_center_batched, dim3((unsigned)batch), dim3(64), 0, stream, part, L.nbx, row_splits, centers, hs);
-    }
-    float* fpart = (float*)(ws + L.off_part);
-    hipLaunchKernelGGL(grid_extrema_batched, dim3(L.nbx, (unsigned)batch), dim3(256), 0, stream, p, hs, row_splits, fpart);
-    hipLaunchKernelGGL(grid_finish_bounds_batched, dim3((unsigned)batch), dim3(64), 0, stream, p, fpart, L.nbx, row_splits, hs);
-    hipLaunchKernelGGL(grid_cell_offsets, dim3(1), dim3(64), 0, stream, hs, batch, (int64_t*)(ws + L.off_celloff));
-    return check_launch();
+                                 void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    return grid_bounds<true>(positions, n_points, row_splits, batch, voxel_size, centralize, centers, pad, hyst, workspace,
+                             workspace_bytes, (hipStream_t)stream);
 }
 
 int dmcf_grid_pos_count_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
                                 const float* voxel_size, int centralize, int pad, float hyst, void* workspace,
                                 size_t workspace_bytes, void* cell_table, int64_t table_cells, int64_t* out_row_splits,
-                                dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GridParams p;
-    if (batch < 1 || !row_splits || !out_row_splits) return DMCF_EINVAL;
-    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
-    if (rc != DMCF_OK) return rc;
-    if (batch > kGridMaxBatch) return DMCF_EUNSUPPORTED;
-    if (!workspace || ((uintptr_t)workspace & 255) || (table_cells != 0 && !cell_table)) return DMCF_EINVAL;
-    if (table_cells < 0 && ((-table_cells) & (-table_cells - 1))) return DMCF_EINVAL;  // hashed: a power of two of slots
-    const GridBatchLayout L = grid_batch_layout(n_points, batch);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    GridHeader* hs = (GridHeader*)(ws + L.off_headers);
-    const int64_t* cell_off = (const int64_t*)(ws + L.off_celloff);
-    uint32_t* first = (uint32_t*)cell_table;
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    int64_t* row_off = (int64_t*)(ws + L.off_rowoff);
-    const int64_t rows = 2 * n_points;
-    const size_t table_bytes = table_cells >= 0 ? (size_t)table_cells * 4 : (size_t)(-table_cells) * 12;
-    if (table_bytes > 0 && hipMemsetAsync(first, 0xff, table_bytes, stream) != hipSuccess) return DMCF_ELAUNCH;
-    if (rows > 0) {
-        const unsigned g = (unsigned)((rows + 255) / 256);
-        hipLaunchKernelGGL((grid_pass_batched<0>), dim3(g), dim3(256), 0, stream, p, hs, row_splits, (int)batch, cell_off, first,
-                           counts, (const int64_t*)nullptr, (float*)nullptr, (int64_t)0, table_cells);
-        hipLaunchKernelGGL((grid_pass_batched<1>), dim3(g), dim3(256), 0, stream, p, hs, row_splits, (int)batch, cell_off, first,
-                           counts, (const int64_t*)nullptr, (float*)nullptr, (int64_t)0, table_cells);
-    }
-    rc = scan_counts_to_row_splits(counts, row_off, rows, ws + L.off_scan, L.total - L.off_scan, stream);
-    if (rc != DMCF_OK) return rc;
-    hipLaunchKernelGGL(grid_store_totals_batched, dim3((unsigned)((batch + 256) / 256)), dim3(256), 0, stream, row_off, row_splits,
-                       batch, hs, out_row_splits);
-    return check_launch();
+                                dmcf_stream_t stream) {
+    return grid_count<true>(positions, n_points, row_splits, batch, voxel_size, centralize, pad, hyst, workspace, workspace_bytes,
+                            cell_table, table_cells, out_row_splits, (hipStream_t)stream);
 }
 
 int dmcf_grid_pos_write_batched(const float* positions, int64_t n_points, const int64_t* row_splits, int64_t batch,
                                 const float* voxel_size, int centralize, int pad, float hyst, void* workspace,
                                 size_t workspace_bytes, const void* cell_table, int64_t table_cells, float* out,
-                                int64_t out_capacity, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GridParams p;
-    if (batch < 1 || !row_splits) return DMCF_EINVAL;
-    int rc = grid_params(p, positions, n_points, voxel_size, centralize, pad, hyst);
-    if (rc != DMCF_OK) return rc;
-    if (batch > kGridMaxBatch) return DMCF_EUNSUPPORTED;
-    if (!workspace || ((uintptr_t)workspace & 255) || out_capacity < 0 || (out_capacity > 0 && (!out || !cell_table)))
-        return DMCF_EINVAL;
-    const GridBatchLayout L = grid_batch_layout(n_points, batch);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    const int64_t rows = 2 * n_points;
-    if (rows > 0 && out_capacity > 0) {
-        const unsigned g = (unsigned)((rows + 255) / 256);
-        hipLaunchKernelGGL((grid_pass_batched<2>), dim3(g), dim3(256), 0, stream, p, (const GridHeader*)(ws + L.off_headers),
-                           row_splits, (int)batch, (const int64_t*)(ws + L.off_celloff), (uint32_t*)cell_table,
-                           (int32_t*)(ws + L.off_counts), (const int64_t*)(ws + L.off_rowoff), out, out_capacity, table_cells);
-    }
-    return check_launch();
+                                int64_t out_capacity, dmcf_stream_t stream) {
+    return grid_write<true>(positions, n_points, row_splits, batch, voxel_size, centralize, pad, hyst, workspace, workspace_bytes,
+                            cell_table, table_cells, out, out_capacity, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -2199,69 +2199,6 @@ def _grid_count_levels(levels, key, count, read_headers, hash_slots):
     _GRID_CELLS[key] = [-1 if lv["sparse"] else lv["cells"] for lv in levels]
 
 
-def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=None, row_splits=None):
-    """``grid_pos`` (utils/tools/losses.py:136-181) for SEVERAL voxel sizes over the same positions -- the coarse levels of one step
-    (losses.py:266-272) -- via dmcf_grid_pos_bounds/_count/_write with TWO host round trips for all of them (cells of every level,
-    then points of every level) instead of two per level.  -> [(points, (minp, dims) | None), ...].  A level whose box is too sparse
-    for the dense cell table (GRID_MAX_CELLS_PER_POINT) takes the hashed table; GridTooSparse is no longer raised (round 6).
-
-    ``row_splits`` (a sequence, a CPU or a device int64 tensor): ``pos`` is a BATCH of point sets, item b = pos[rs[b]:rs[b+1]]
-    (dmcf_grid_pos_*_batched) -> [(points, RowSplits), ...]: every level's points are the concatenation, item after item, of
-    what the un-batched call returns for each slice, bit for bit; ``center``, if given, is [batch, 3]."""
-    if row_splits is not None:
-        return _grid_pos_many_batched(pos, voxel_sizes, centralize, pad, hyst, center, row_splits)
-    import numpy as np
-    L = _lib.lib()
-    pos = _dev_f32(pos, "pos", 3)
-    n = pos.shape[0]
-    cen = _dev_f32(center.reshape(3), "center") if center is not None else None
-    cflag = 1 if centralize else 0
-    ws_bytes = L.dmcf_grid_pos_workspace_bytes(n)
-    levels = []
-    for v in voxel_sizes:
-        vs = (ctypes.c_float * 3)(*[float(x) for x in np.asarray(v, dtype=np.float32).reshape(3)])
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
-        _lib.check(L.dmcf_grid_pos_bounds(_ptr(pos), n, vs, cflag, _ptr(cen) if cen is not None else None, int(pad),
-                                          float(hyst), _ptr(ws), ws_bytes, _stream()), "dmcf_grid_pos_bounds")
-        levels.append(dict(vs=vs, ws=ws))
-    def read_headers():
-        hdrs = torch.stack([lv["ws"][0:64] for lv in levels]).cpu()
-        for lv, hdr in zip(levels, hdrs):
-            lv["center_host"] = hdr[40:52].view(torch.float32).tolist()
-            lv["minp"], lv["dims"] = hdr[0:12].view(torch.int32).tolist(), hdr[12:24].view(torch.int32).tolist()
-            lv["cells"] = int(hdr[24:32].view(torch.int64).item())
-            lv["total"] = int(hdr[32:40].view(torch.int64).item())
-            if lv["cells"] < 0:
-                raise _lib.DmcfError("grid_pos: positions are not finite")
-            # too sparse for the dense cell table (a few particles far from the rest): the hashed table (include/dmcf_hip.h)
-            lv["sparse"] = _grid_too_sparse(lv["cells"], n)
-
-    def count(lv, capacity):
-        lv["table"], lv["capacity"] = _grid_cell_table(capacity, pos.device), capacity
-        _lib.check(L.dmcf_grid_pos_count(_ptr(pos), n, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
-                                         _ptr(lv["table"]), capacity, _stream()), "dmcf_grid_pos_count")
-
-    key = (tuple(tuple(float(x) for x in lv["vs"]) for lv in levels), bool(centralize), int(pad), float(hyst))
-    _grid_count_levels(levels, key, count, read_headers, max(_grid_hash_slots(n, v, pad) for v in voxel_sizes))
-    totals = [lv["total"] for lv in levels]
-    res = []
-    for lv, total in zip(levels, totals):
-        out = torch.empty((total, 3), dtype=torch.float32, device=pos.device)
-        if total:
-            _lib.check(L.dmcf_grid_pos_write(_ptr(pos), n, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
-                                             _ptr(lv["table"]), lv["capacity"], _ptr(out), total, _stream()), "dmcf_grid_pos_write")
-            if centralize and center is None:
-                # out = float(cell) * voxel + mean(pos): every lattice built from these positions shares the centre exactly
-                # (dmcf_amd/lattice.py; the lattice form of ContinuousConv uses it)
-                from . import lattice
-                # (the entry keeps ``pos`` alive: its address + version identify the family for as long as the entry exists)
-                lattice.register(out, lv["ws"][40:52].view(torch.float32).clone(), [float(v) for v in lv["vs"]],
-                                 ("mean", pos.data_ptr(), pos.shape[0], pos._version), lv["minp"], lv["dims"], keep=pos,
-                                 center_host=lv["center_host"])
-        res.append((out, (lv["minp"], lv["dims"]) if total else None))
-    return res
-
-
 class RowSplits:
     """Row splits in both forms: ``host`` a tuple of batch + 1 ints, ``dev`` the same as an int64 device tensor.  Every
     ``row_splits`` argument takes one, and then copies nothing to validate it.  A batched ``grid_pos`` returns its output row
@@ -2271,68 +2208,102 @@ class RowSplits:
         self.host, self.dev, self.sparse = tuple(host), dev, sparse
 
 
-def _grid_pos_many_batched(pos, voxel_sizes, centralize, pad, hyst, center, row_splits):
-    """grid_pos_many with row splits: the same two host round trips for all levels and all items -- the first brings every
-    item's header (its cells), the second every item's point count, which IS the output row splits.  The lattices are not
-    registered with dmcf_amd/lattice.py: the lattice and scatter forms of ContinuousConv know nothing of items."""
+def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=None, row_splits=None):
+    """``grid_pos`` (utils/tools/losses.py:136-181) for SEVERAL voxel sizes over the same positions -- the coarse levels of one step
+    (losses.py:266-272) -- via dmcf_grid_pos_bounds/_count/_write with TWO host round trips for all of them (cells of every level,
+    then points of every level) instead of two per level.  -> [(points, (minp, dims) | None), ...].  A level whose box is too sparse
+    for the dense cell table (GRID_MAX_CELLS_PER_POINT) takes the hashed table; GridTooSparse is no longer raised (round 6).
+
+    ``row_splits`` (a sequence, a CPU or a device int64 tensor): ``pos`` is a BATCH of point sets, item b = pos[rs[b]:rs[b+1]]
+    (dmcf_grid_pos_*_batched) -> [(points, RowSplits), ...]: every level's points are the concatenation, item after item, of
+    what the un-batched call returns for each slice, bit for bit; ``center``, if given, is [batch, 3].  The same two round trips
+    bring every item's header (its cells), then every item's point count, which IS the output row splits.  These lattices are
+    not registered with dmcf_amd/lattice.py: the lattice and scatter forms of ContinuousConv know nothing of items."""
     import numpy as np
-    host, dev = _host_row_splits(row_splits, "row_splits")  # (every host-side check before a device is touched)
-    if pos.dim() != 2 or pos.shape[1] != 3:
-        raise ValueError("pos must be [n, 3]")
-    _check_row_splits(host, pos.shape[0], "row_splits")
-    batch = len(host) - 1
-    if center is not None and tuple(center.shape) != (batch, 3):
-        raise ValueError(f"center must be [batch, 3] = [{batch}, 3] with row_splits, got {tuple(center.shape)}")
+    batched = row_splits is not None
+    if batched:
+        host, dev = _host_row_splits(row_splits, "row_splits")  # (every host-side check before a device is touched)
+        if pos.dim() != 2 or pos.shape[1] != 3:
+            raise ValueError("pos must be [n, 3]")
+        _check_row_splits(host, pos.shape[0], "row_splits")
+        batch = len(host) - 1
+        if center is not None and tuple(center.shape) != (batch, 3):
+            raise ValueError(f"center must be [batch, 3] = [{batch}, 3] with row_splits, got {tuple(center.shape)}")
     L = _lib.lib()
     pos = _dev_f32(pos, "pos", 3)
     n = pos.shape[0]
-    rs = _row_splits_on(host, dev, pos.device)
-    cen = _dev_f32(center, "center") if center is not None else None
     cflag = 1 if centralize else 0
-    ws_bytes = L.dmcf_grid_pos_workspace_bytes_batched(n, batch)
-    if ws_bytes == 0:
-        raise _lib.DmcfError(f"grid_pos: a batch of {batch} items is not supported")
+    # the entry points of the call and what the batched ones take after (positions, n): the un-batched ones take no row splits
+    if batched:
+        names = ["dmcf_grid_pos_bounds_batched", "dmcf_grid_pos_count_batched", "dmcf_grid_pos_write_batched"]
+        rs = _row_splits_on(host, dev, pos.device)
+        items = (_ptr(rs), batch)
+        cen = _dev_f32(center, "center") if center is not None else None
+        ws_bytes = L.dmcf_grid_pos_workspace_bytes_batched(n, batch)
+        if ws_bytes == 0:
+            raise _lib.DmcfError(f"grid_pos: a batch of {batch} items is not supported")
+    else:
+        names = ["dmcf_grid_pos_bounds", "dmcf_grid_pos_count", "dmcf_grid_pos_write"]
+        items, batch = (), 1
+        cen = _dev_f32(center.reshape(3), "center") if center is not None else None
+        ws_bytes = L.dmcf_grid_pos_workspace_bytes(n)
+    bounds_fn, count_fn, write_fn = (getattr(L, name) for name in names)
     levels = []
     for v in voxel_sizes:
         vs = (ctypes.c_float * 3)(*[float(x) for x in np.asarray(v, dtype=np.float32).reshape(3)])
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
-        _lib.check(L.dmcf_grid_pos_bounds_batched(_ptr(pos), n, _ptr(rs), batch, vs, cflag, _ptr(cen) if cen is not None else None,
-                                                  int(pad), float(hyst), _ptr(ws), ws_bytes, _stream()),
-                   "dmcf_grid_pos_bounds_batched")
-        levels.append(dict(vs=vs, ws=ws, ors=torch.empty(batch + 1, dtype=torch.int64, device=pos.device)))
+        _lib.check(bounds_fn(_ptr(pos), n, *items, vs, cflag, _ptr(cen) if cen is not None else None, int(pad), float(hyst),
+                             _ptr(ws), ws_bytes, _stream()), names[0])
+        # (ors: the output row splits, the batched count pass's extra argument)
+        levels.append(dict(vs=vs, ws=ws, ors=torch.empty(batch + 1, dtype=torch.int64, device=pos.device) if batched else None))
 
     def read_headers():
-        hdrs = torch.stack([lv["ws"][0:64 * batch] for lv in levels]).cpu().view(torch.int64).reshape(len(levels), batch, 8)
+        hdrs = torch.stack([lv["ws"][0:64 * batch] for lv in levels]).cpu()
         for lv, hdr in zip(levels, hdrs):
-            cells, totals = hdr[:, 3].tolist(), hdr[:, 4].tolist()
+            words = hdr.view(torch.int64).reshape(batch, 8)
+            cells, lv["totals"] = words[:, 3].tolist(), words[:, 4].tolist()
             if any(c < 0 for c in cells):
                 raise _lib.DmcfError("grid_pos: positions are not finite")
             lv["cells"] = sum(cells)  # the dense table holds every item's own box, one after the other
-            lv["totals"] = totals
-            # (the sparse rule of the un-batched call, applied to the call: all cells against all points)
+            if not batched:
+                lv["center_host"] = hdr[40:52].view(torch.float32).tolist()
+                lv["minp"], lv["dims"] = hdr[0:12].view(torch.int32).tolist(), hdr[12:24].view(torch.int32).tolist()
+            # too sparse for the dense cell table (a few particles far from the rest): the hashed table (include/dmcf_hip.h).
+            # The rule is applied to the call: all cells against all points
             lv["sparse"] = _grid_too_sparse(lv["cells"], n)
 
     def count(lv, capacity):
         lv["table"], lv["capacity"] = _grid_cell_table(capacity, pos.device), capacity
-        _lib.check(L.dmcf_grid_pos_count_batched(_ptr(pos), n, _ptr(rs), batch, lv["vs"], cflag, int(pad), float(hyst),
-                                                 _ptr(lv["ws"]), ws_bytes, _ptr(lv["table"]), capacity, _ptr(lv["ors"]), _stream()),
-                   "dmcf_grid_pos_count_batched")
+        _lib.check(count_fn(_ptr(pos), n, *items, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
+                            _ptr(lv["table"]), capacity, *([_ptr(lv["ors"])] if batched else []), _stream()), names[1])
 
-    # (the estimate path of grid_pos_many, keyed with the batch size: a training loop asks for the same batch step after step)
-    key = (tuple(tuple(float(x) for x in lv["vs"]) for lv in levels), bool(centralize), int(pad), float(hyst), batch)
+    # (the estimates are keyed with the batch size: a training loop asks for the same batch step after step)
+    key = (tuple(tuple(float(x) for x in lv["vs"]) for lv in levels), bool(centralize), int(pad), float(hyst))
+    if batched:
+        key += (batch,)
     _grid_count_levels(levels, key, count, read_headers, max(_grid_hash_slots(n, v, pad) for v in voxel_sizes))
     res = []
     for lv in levels:
-        out_host = [0]
-        for t in lv["totals"]:
-            out_host.append(out_host[-1] + t)
-        total = out_host[-1]
+        total = sum(lv["totals"])
         out = torch.empty((total, 3), dtype=torch.float32, device=pos.device)
         if total:
-            _lib.check(L.dmcf_grid_pos_write_batched(_ptr(pos), n, _ptr(rs), batch, lv["vs"], cflag, int(pad), float(hyst),
-                                                     _ptr(lv["ws"]), ws_bytes, _ptr(lv["table"]), lv["capacity"], _ptr(out), total,
-                                                     _stream()), "dmcf_grid_pos_write_batched")
-        res.append((out, RowSplits(tuple(out_host), lv["ors"], lv["capacity"] < 0)))
+            _lib.check(write_fn(_ptr(pos), n, *items, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
+                                _ptr(lv["table"]), lv["capacity"], _ptr(out), total, _stream()), names[2])
+        if batched:
+            out_host = [0]
+            for t in lv["totals"]:
+                out_host.append(out_host[-1] + t)
+            res.append((out, RowSplits(tuple(out_host), lv["ors"], lv["capacity"] < 0)))
+            continue
+        if total and centralize and center is None:
+            # out = float(cell) * voxel + mean(pos): every lattice built from these positions shares the centre exactly
+            # (dmcf_amd/lattice.py; the lattice form of ContinuousConv uses it)
+            from . import lattice
+            # (the entry keeps ``pos`` alive: its address + version identify the family for as long as the entry exists)
+            lattice.register(out, lv["ws"][40:52].view(torch.float32).clone(), [float(v) for v in lv["vs"]],
+                             ("mean", pos.data_ptr(), pos.shape[0], pos._version), lv["minp"], lv["dims"], keep=pos,
+                             center_host=lv["center_host"])
+        res.append((out, (lv["minp"], lv["dims"]) if total else None))
     return res
 
 

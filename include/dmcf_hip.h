@@ -722,6 +722,10 @@ int dmcf_ghost_write(const float* points, int64_t n, const float* boxes, int32_t
  * table_cells = -S to count / write, S a power of two >= twice the number of candidates 2 * n_points * (2 + 2 pad)^3 at most
  * occupied, and a table of 12 * S bytes: the kernels then hash the cell index into S slots (open addressing) instead of
  * indexing a dense table.  Same points, same order.
+ * Workspace: dmcf_grid_pos_workspace_bytes(n_points), always queried, never assumed: it is the layout of the batched
+ * phases below for ONE item, dmcf_grid_pos_workspace_bytes_batched(n_points, 1) -- since the two families share their
+ * kernels and their layout the value is no longer what earlier builds of ABI 2.x returned (the header is still at
+ * offset 0, its fields where they were).
  * ---------------------------------------------------------------------------------------------- */
 size_t dmcf_grid_pos_workspace_bytes(int64_t n_points);
 int dmcf_grid_pos_bounds(const float* positions, int64_t n_points, const float* voxel_size, int centralize,
@@ -738,8 +742,11 @@ int dmcf_grid_pos_write(const float* positions, int64_t n_points, const float* v
  * row_splits[b + 1]); `row_splits` is a DEVICE int64 [batch + 1] array (starts at 0, does not decrease, ends at n_points: the
  * caller has validated it).  The result is the concatenation, item after item, of what the un-batched phases return for each
  * item's slice: item b's rows are BIT-IDENTICAL to them, values and order (tf.unique order within the item's own candidate
- * list).  Empty items are legal and contribute no rows.
- *   bounds : per item the lattice origin (the item's own mean, summed exactly as the un-batched call sums it; or
+ * list).  Empty items are legal and contribute no rows.  The un-batched phases ARE these phases for one item: the same reduction
+ * kernels (instantiated without the row-split loads for the un-batched entry points), one workspace layout, one host function
+ * per phase; only the pass over the candidates is a kernel of its own for one item.
+ *   bounds : per item the lattice origin (the item's own mean, summed over the item's local index with the block count a call
+ *            on the item alone launches; or
  *            centers[b], `centers` a DEVICE [batch][3] array or NULL) and the item's own integer box ->
  *            `batch` 64-byte headers at the start of `workspace`, each laid out as above.  An item's cell index is local to
  *            its own box and offset by the cells of the items before it: two items at the same coordinates never share a cell.

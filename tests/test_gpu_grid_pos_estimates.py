@@ -1,5 +1,6 @@
 """grid_pos on the cell tables a rollout sizes from its last step: ops._grid_count_levels with the estimates of ``_GRID_CELLS``
-on the device, un-batched and with row splits, and the C ABI on tables and outputs smaller than the header says.
+on the device, un-batched and with row splits, the C ABI on tables and outputs smaller than the header says, and both entry-point
+families on a workspace of exactly the reported size (they share one layout).
 
 Every comparison is bit for bit against ``oracle.grid_pos`` (numpy) on the positions of that call -- per item and concatenated
 for a batch -- never against a second run of the product.  Every step asserts how many count passes it made: the number says
@@ -395,6 +396,105 @@ def test_abi_hashed_table_of_the_right_size(oracle, form, monkeypatch):
     _guarded_out(abi, big.data_ptr() + 4 * G, -slots, ref, ref.shape[0] // 2)
     words = big.cpu()
     assert bool((words[:G] == WORD).all()) and bool((words[G + 3 * slots:] == WORD).all())
+
+
+# ---- A4b: both families share one workspace layout: a workspace of EXACTLY the reported size, between guard bytes --------------------
+
+HDR = np.dtype([("minp", "<i4", 3), ("dims", "<i4", 3), ("cells", "<i8"), ("total", "<i8"), ("center", "<u4", 3), ("pad_", "<i4", 3)])
+EXACT_N = [0, 1, 255, 256, 257, 513]  # the block-count edges of the two reductions (256 points per block) and the empty call
+BYTE = 0x5A
+
+
+def raster_points(n, seed):
+    """n points of [-1, 1]^3 on a raster of 2^-12: a double sum of them is exact in any order, so the device's mean is numpy's."""
+    return (np.round(np.random.RandomState(seed).uniform(-1.0, 1.0, size=(n, 3)) * 4096.0) / 4096.0).astype(np.float32)
+
+
+def _fenced(inner, dtype, fill):
+    return torch.full((G + inner + G,), fill, dtype=dtype, device=DEV)
+
+
+def _fences_whole(t, inner, fill):
+    """Every element of ``t`` outside [G, G + inner) still holds ``fill``."""
+    host = t.cpu().numpy()
+    rest = np.concatenate([host[:G], host[G + inner:]])
+    return rest.size >= 2 * G and rest.tobytes() == np.full(rest.shape, fill, dtype=rest.dtype).tobytes()
+
+
+def _phases_exact(pos, rs, centralize, pad, slots):
+    """bounds, count and write of one family (``rs`` None: the un-batched one) at voxel 0.1, every buffer between guards and the
+    workspace as long as the size function says, not a byte more.  ``slots``: the hashed table, None: a dense one of exactly the
+    headers' cells.  -> (points, the item headers, the output row splits | None)."""
+    import ctypes
+    from dmcf_amd import ops, _lib
+    L, stream = _lib.lib(), ops._stream
+    n, batch, sfx = pos.shape[0], 1 if rs is None else len(rs) - 1, "" if rs is None else "_batched"
+    rs_dev = None if rs is None else torch.tensor(rs, dtype=torch.int64, device=DEV)
+    nb = L.dmcf_grid_pos_workspace_bytes(n) if rs is None else L.dmcf_grid_pos_workspace_bytes_batched(n, batch)
+    assert nb >= 64 * batch
+    ws = _fenced(nb, torch.uint8, BYTE)
+    w = ws.data_ptr() + G
+    assert w % 256 == 0
+    head = (pos.data_ptr(), n) + (() if rs is None else (rs_dev.data_ptr(), batch)) + ((ctypes.c_float * 3)(0.1, 0.1, 0.1), centralize)
+    assert getattr(L, "dmcf_grid_pos_bounds" + sfx)(*head, None, pad, 0.1, w, nb, stream()) == 0
+
+    def headers():
+        return np.frombuffer(ws[G:G + 64 * batch].cpu().numpy().tobytes(), dtype=HDR)
+
+    cells = int(np.maximum(headers()["cells"], 0).sum())
+    words, table_cells = (cells, cells) if slots is None else (3 * slots, -slots)
+    table = _fenced(words, torch.int32, WORD)
+    ors = _fenced(batch + 1, torch.int64, WORD)
+    assert getattr(L, "dmcf_grid_pos_count" + sfx)(*head, pad, 0.1, w, nb, table.data_ptr() + 4 * G, table_cells,
+                                                   *(() if rs is None else (ors.data_ptr() + 8 * G,)), stream()) == 0
+    total = int(headers()["total"].sum())
+    out = _fenced(3 * total, torch.float32, FSENT)
+    assert getattr(L, "dmcf_grid_pos_write" + sfx)(*head, pad, 0.1, w, nb, table.data_ptr() + 4 * G, table_cells,
+                                                   out.data_ptr() + 4 * G, total, stream()) == 0
+    torch.cuda.synchronize()
+    assert _fences_whole(ws, nb, BYTE), "workspace"
+    assert _fences_whole(table, words, WORD), "cell table"
+    assert _fences_whole(out, 3 * total, FSENT), "points"
+    assert _fences_whole(ors, 0 if rs is None else batch + 1, WORD), "output row splits"
+    return (out[G:G + 3 * total].cpu().numpy().reshape(-1, 3), headers(),
+            None if rs is None else ors[G:G + batch + 1].tolist())
+
+
+@pytest.mark.parametrize("n", EXACT_N)
+def test_abi_both_families_on_a_workspace_of_exactly_the_reported_size(oracle, n):
+    """The un-batched and the batched entry points carve one workspace layout.  Every phase of both, on ``n`` points as one
+    item, behind an empty item and as three items with an empty one in the middle, with a dense table of exactly the headers'
+    cells and with a hashed one: no byte outside any buffer changes, every item's points and header are the oracle's for its
+    slice, and the un-batched call and the call with row splits [0, n] leave the same bytes in points and header."""
+    from dmcf_amd import ops
+    p = raster_points(n, seed=100 + n)
+    pos = torch.from_numpy(p).to(DEV)
+    forms = [None, [0, n], [0, 0, n], [0, n // 3, n // 3, n]]
+    for centralize in (0, 1):
+        for pad in (0, 1):
+            o = dict(centralize=bool(centralize), pad=pad, hyst=0.1, center=None)
+            refs = {}
+            for slots in (None, ops._grid_hash_slots(n, [0.1] * 3, pad)):
+                got = []
+                for rs in forms:
+                    tag = (n, centralize, pad, slots, rs)
+                    pts, hdr, ors = _phases_exact(pos, rs, centralize, pad, slots)
+                    splits = [0, n] if rs is None else rs
+                    host = [0]
+                    for b, (lo, hi) in enumerate(zip(splits[:-1], splits[1:])):
+                        if (lo, hi) not in refs:
+                            refs[(lo, hi)] = reference(oracle, p[lo:hi], [0.1] * 3, o)
+                        ref, box, cells = refs[(lo, hi)]
+                        assert same_bits(pts[host[b]:host[b] + ref.shape[0]], ref), (tag, b)
+                        assert (int(hdr["cells"][b]), int(hdr["total"][b])) == (cells, ref.shape[0]), (tag, b)
+                        assert box is None or (hdr["minp"][b].tolist(), hdr["dims"][b].tolist()) == box, (tag, b)
+                        host.append(host[b] + ref.shape[0])
+                    assert pts.shape[0] == host[-1] and (ors is None or ors == host), (tag, ors, host)
+                    got.append((pts, hdr))
+                (one, one_hdr), (many, many_hdr) = got[0], got[1]
+                assert one.tobytes() == many.tobytes(), (n, centralize, pad, slots)
+                for field in ("minp", "dims", "cells", "total", "center"):
+                    assert one_hdr[field].tobytes() == many_hdr[field].tobytes(), (n, centralize, pad, slots, field)
 
 
 # ---- A5: levels with different numbers of active axes share one call, hashed ---------------------------------------------------------
