@@ -15,6 +15,7 @@ torch = pytest.importorskip("torch")
 import batched_search_ref as bs  # noqa: E402
 import cconv_backward_ref as ref  # noqa: E402
 import cconv_forward_ref as fr  # noqa: E402
+import frs_regimes as fg  # noqa: E402
 from test_gpu_cconv_backward_sets import _kbars  # noqa: E402
 from test_gpu_radius_search import _canonical, _check_rows, brute_force  # noqa: E402
 
@@ -41,12 +42,22 @@ def _search(s, dev, ignore=False, form="list", **kw):
                                    points_row_splits=conv(s["prs"]), queries_row_splits=conv(s["qrs"]), **kw)
 
 
+def _header(s, dev):
+    """The header of the batched structure of scene ``s``, read back from the device (frs_regimes.decode)."""
+    from dmcf_amd import ops
+    table = ops.build_spatial_hash_table(_t(s["points"], dev), s["radius"], n_queries=s["queries"].shape[0],
+                                         points_row_splits=[int(v) for v in s["prs"]])
+    return fg.decode(table)
+
+
 def _check_scene(name, dev, ignore=False, dim=3, form="list", **kw):
     s = bs.scene(name, dim)
     res = _search(s, dev, ignore, form, **kw)
     assert res.neighbors_index.dtype == torch.int32 and res.neighbors_row_splits.dtype == torch.int64
     assert res.neighbors_row_splits.shape[0] == s["queries"].shape[0] + 1
     _check_rows(res, bs.reference(name, ignore, dim), None, normalized=False)
+    h = _header(s, dev)
+    assert h["ncells"] * (len(s["prs"]) - 1) <= h["table"], "the slabs of the batch do not fit the cell table"
     return s, res
 
 
@@ -113,6 +124,8 @@ def test_strays_and_far_items(dev):
         assert p in idx[rs[q]:rs[q + 1]]
     for q in s["foreign_queries"]:
         assert rs[q] == rs[q + 1], "a query found the stray point of another item"
+    # the one grid of the call is coarse: asserted from the device's header
+    assert fg.cells_per_radius(_header(s, dev)) < 0.95
 
 
 def test_many_items(dev):
@@ -121,8 +134,10 @@ def test_many_items(dev):
 
 
 def test_table_bound(dev):
-    _check_scene("table_bound", dev)
+    s, _ = _check_scene("table_bound", dev)
     _check_scene("table_bound", dev, ignore=True)
+    # the build had to take cells coarser than R / 3 (tests/test_batched_search_ref_cpu.py predicts it): the device's header
+    assert fg.cells_per_radius(_header(s, dev)) < 2.9
 
 
 def test_one_item_is_the_unbatched_search(dev):
