@@ -1,7 +1,7 @@
 // Fixed-radius neighbour search for gfx950: cell-sorted uniform grid + one wavefront per query.
 //
 // Replaces ml3d.layers.FixedRadiusSearch (reference call sites utils/convolutions.py:207-210,354-358,
-// utils/tools/losses.py:296-298) and, with a radius per query, ml3d.layers.RadiusSearch (:212-216, 366-370; frs_query_radii).
+// utils/tools/losses.py:296-298) and, with a radius per query, ml3d.layers.RadiusSearch (:212-216, 366-370; frs_query<.., RADII>).
 // The Open3D structure behind that layer (spatial hash with ~64
 // points per bin, 8 corner bins per query) is NOT what is built here; only its result contract is
 // kept (see include/dmcf_hip.h).  MI355X-first choices:
@@ -15,7 +15,7 @@
 //   * everything that sizes the grid (bounding box, cell edge, dims) is computed on the device into a
 //     header inside the workspace, so the build needs no host round trip;
 //   * a batch of point sets (Open3D's points_row_splits / queries_row_splits, ABI 2.20) shares one grid geometry, with the
-//     batch item as the outermost digit of the cell index: see frs_query_batched.
+//     batch item as the outermost digit of the cell index: see frs_item_of and frs_query<WRITE, RADII, ITEMS>.
 #include "cconv_common.h"  // window_value
 
 namespace dmcf {
@@ -154,7 +154,8 @@ __global__ __launch_bounds__(256) void frs_bbox(const float* __restrict__ pts, i
 // batch > 1 (dmcf_frs_build_batched): the table holds `batch` copies of the grid, one slab per item, so the grid gets
 // table / batch cells and is filled by n_points / batch points.
 __device__ void frs_finish_header_one(FrsHeader* h, int64_t table, int64_t batch = 1) {
-    const double slab_table = (double)(table / batch), fill = (double)batch;
+    // (table and batch are at most 2^26: a 32-bit division, a fifth of the instructions of the 64-bit one in this one thread)
+    const double slab_table = (double)((uint32_t)table / (uint32_t)batch), fill = (double)batch;
     float lo[3], ext[3];
     for (int a = 0; a < 3; ++a) {
         lo[a] = ord2f(h->bb_min[a]);
@@ -215,8 +216,50 @@ __device__ void frs_finish_header_one(FrsHeader* h, int64_t table, int64_t batch
     h->ncells = d[0] * d[1] * d[2];
 }
 
-__global__ void frs_finish_header(FrsHeader* h, int64_t table) {
-    if (threadIdx.x == 0) frs_finish_header_one(h, table);
+// A guard, never seen to trigger: if the 64 rounds of coarsening did not get the grid into its share of the table, one cell
+// per item still serves every query, and no cell index lies beyond the table.
+__global__ void frs_finish_header(FrsHeader* h, int64_t table, int64_t batch) {
+    if (threadIdx.x == 0) {
+        frs_finish_header_one(h, table, batch);
+        if ((double)h->dims[0] * (double)h->dims[1] * (double)h->dims[2] * (double)batch > (double)table || h->ncells < 1) {
+            h->dims[0] = h->dims[1] = h->dims[2] = 1;
+            h->ncells = 1;
+        }
+    }
+}
+
+// ---- batches of point sets (ABI 2.20): Open3D's points_row_splits / queries_row_splits ------------------------------------------
+// One structure for a whole batch of point sets that were concatenated into one array: ONE grid geometry (box, cell edge, dims:
+// the header, sized from all points together), and the batch item as the outermost digit of the cell index,
+//   cell = ((b * dims[2] + cz) * dims[1] + cy) * dims[0] + cx,
+// so the table holds `batch` slabs of ncells cells and the cell-sorted array holds the items one after the other.  A point is
+// clamped into the grid of ITS slab (the border cells hold what was binned from beyond the box, per item), a query walks the
+// cells of ITS slab only: the scan is frs_scan with the slab's first cell added to every row of cells, nothing else.  Points of
+// different items never meet, wherever they lie -- the items may overlap or coincide.  The header's ncells stays the cells of
+// ONE slab.  A single point set is a batch of one item: every kernel below is a template on ITEMS, and ITEMS = false makes the
+// item a compile-time 0 and reads no row splits.  What only ITEMS (or RADII) reads stands LAST among a kernel's arguments, so the
+// other instantiations load the arguments their un-batched kernels always loaded, from the same offsets.
+
+// The batch item of element i: the b with splits[b] <= i < splits[b + 1] (empty items are stepped over).  The result always
+// lies in [0, batch): row splits that are not what the caller promised give wrong neighbours, never an index beyond the table.
+__device__ __forceinline__ int32_t frs_item_of(const int64_t* __restrict__ splits, int32_t batch, int64_t i) {
+    int32_t lo = 0, hi = batch - 1;
+    while (lo < hi) {  // the first b with splits[b + 1] > i
+        const int32_t mid = (lo + hi) >> 1;
+        if (splits[mid + 1] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The item of a wave's query (one query per wave): a search over queries_row_splits on the wave-uniform query index, so that
+// the walk -- and the slab base made from the item -- stays scalar.
+template <bool ITEMS>
+__device__ __forceinline__ int32_t frs_wave_item(const int64_t* __restrict__ queries_row_splits, int32_t batch, int64_t qi) {
+    if (!ITEMS) return 0;
+    const int64_t qu = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(qi >> 32)) << 32) |
+                       (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)qi);
+    return __builtin_amdgcn_readfirstlane(frs_item_of(queries_row_splits, batch, qu));
 }
 
 // cell coordinate along one axis; the SAME function is used for points and for the ends of a query's
@@ -227,19 +270,22 @@ __device__ __forceinline__ int cell_coord(float x, float origin, float inv, int 
     return (int)c;
 }
 
+template <bool ITEMS>
 __global__ __launch_bounds__(256) void frs_count_cells(const float* __restrict__ pts, int64_t n,
                                                        const FrsHeader* __restrict__ h,
                                                        int32_t* __restrict__ point_cell,
-                                                       uint32_t* __restrict__ cell_count, uint32_t* __restrict__ slot_of) {
+                                                       uint32_t* __restrict__ cell_count, uint32_t* __restrict__ slot_of,
+                                                       const int64_t* __restrict__ points_row_splits, int32_t batch) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     int c[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         c[a] = cell_coord(pts[3 * i + a], h->origin[a], h->inv_cell[a], h->dims[a]);
-        c[a] = min(max(c[a], 0), h->dims[a] - 1);
+        c[a] = min(max(c[a], 0), h->dims[a] - 1);  // (into the grid of the point's OWN slab: a stray never lands in a neighbouring item)
     }
-    const int32_t cell = (c[2] * h->dims[1] + c[1]) * h->dims[0] + c[0];
+    int32_t cell = (c[2] * h->dims[1] + c[1]) * h->dims[0] + c[0];
+    if (ITEMS) cell += frs_item_of(points_row_splits, batch, i) * h->ncells;
     point_cell[i] = cell;
     // (the counter's old value is the point's place among its cell's members: the scatter needs no second round of atomics)
     slot_of[i] = atomicAdd(&cell_count[cell], 1u);
@@ -528,7 +574,7 @@ struct FrsGradAcc {
 // out_base; MODE 2: add window(d^2 / R^2) of every hit to `wsum` (per lane; the caller reduces over the wave); MODE 3: add the
 // hit's term of the window sum's gradient to `ga` (per lane, see frs_window_sum_grad).
 // Returns the number of hits.  Hits come out in a fixed order (cell rows, then position in the cell-sorted array).
-// slab_base: see frs_query_batched.
+// slab_base: the first cell of the query's item (frs_wave_item), 0 for a single point set.
 // EXACT (open3d visibility flags only): every hit that could lie outside the reference's 8 bins takes the exact
 // visibility test -- the form of the FIXUP kernel (frs_fix), which re-scans the few queries the hot kernels flag.  !EXACT is the
 // hot form: it only NOTICES such a hit (d^2 above r2_inner: one compare per window) and reports it through `redo`.  The test
@@ -708,63 +754,55 @@ __device__ __forceinline__ int32_t frs_scan(float qx, float qy, float qz, const 
     return cnt;
 }
 
-// One wavefront per query.  WRITE=false: counts[q] = number of hits.  WRITE=true: fill the CSR row.  qflags (with an
-// open3d visibility flag): EACH pass marks the queries whose row may hold a point the reference cannot see and leaves them to
-// the frs_fix launch behind it -- the write pass does not rely on the count pass's marks (another search on the same
-// structure may have run in between); it never writes beyond the row's exact length, which the count pass put in row_splits.
-template <bool WRITE>
+// One wavefront per query.  WRITE=false: counts[q] = number of hits.  WRITE=true: fill the CSR row.
+// RADII (dmcf_radius_search_*): the radius of the query, on the grid built for `radius` = max_radius.  The scan range and the
+// chord trimming follow r_i; the cells stay sized for max_radius, so a small radius still visits whole cells of that size
+// (DESIGN.md section 2).  A radius outside [0, max_radius] (NaN included) gives an empty row.
+// ITEMS (the *_batched entry points): the scan stays inside the slab of the query's item.
+// Only the plain search (neither RADII nor ITEMS) knows the open3d visibility flags -- the entry points of the others refuse
+// them, so their flags are masked to DMCF_FRS_IGNORE_QUERY_POINT and the visibility code folds away.  qflags (plain search with
+// such a flag): EACH pass marks the queries whose row may hold a point the reference cannot see and leaves them to the frs_fix
+// launch behind it -- the write pass does not rely on the count pass's marks (another search on the same structure may have
+// run in between); it never writes beyond the row's exact length, which the count pass put in row_splits.
+template <bool WRITE, bool RADII, bool ITEMS>
 __global__ __launch_bounds__(256) void frs_query(const float* __restrict__ queries, int64_t m,
-                                                 const FrsHeader* __restrict__ h,
-                                                 const uint32_t* __restrict__ cell_start,
+                                                 const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
                                                  const float4* __restrict__ sorted, float radius, int flags,
                                                  int32_t* __restrict__ counts, const int64_t* __restrict__ row_splits,
-                                                 int32_t* __restrict__ nbr_index, float* __restrict__ nbr_dist,
-                                                 int64_t capacity, uint8_t* __restrict__ qflags) {
+                                                 int32_t* __restrict__ nbr_index, float* __restrict__ nbr_dist, int64_t capacity,
+                                                 uint8_t* __restrict__ qflags, const float* __restrict__ radii,
+                                                 const int64_t* __restrict__ queries_row_splits, int32_t batch) {
     __shared__ uint32_t marks[4][kWin * kWave + kWave];
     const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (qi >= m) return;  // whole wave leaves
     // a row that does not fit the caller's buffers is skipped as a whole (the caller detects the overflow from
     // row_splits[m] > capacity and repeats the search with exact buffers)
     if (WRITE && row_splits[qi + 1] > capacity) return;
+    if (RADII || ITEMS) flags &= DMCF_FRS_IGNORE_QUERY_POINT;
     const bool o3d = (flags & kO3dFlags) != 0;
-    const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
-    float unused = 0.0f;
+    float r = radius;
+    bool live = true;
+    if (RADII) {
+        r = radii[qi];
+        live = r >= 0.0f && r <= radius;  // (wave uniform: one query per wave)
+    }
+    int32_t cnt = 0;
     bool redo = false;
-    // (a row the reference sees less of than the distance test holds fewer entries than this scan finds: capped here, rewritten
-    // by frs_fix)
-    const int32_t cap = WRITE && o3d ? (int32_t)(row_splits[qi + 1] - row_splits[qi]) : 0x7fffffff;
-    const int32_t cnt = frs_scan<WRITE ? 1 : 0, false>(qx, qy, qz, h, cell_start, sorted, radius, flags, WRITE ? row_splits[qi] : 0,
-                                                       nbr_index, nbr_dist, 0, 0.0f, unused, marks[threadIdx.x >> 6], cap, redo);
+    if (live) {
+        const int32_t item = frs_wave_item<ITEMS>(queries_row_splits, batch, qi);
+        const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
+        float unused = 0.0f;
+        // (a row the reference sees less of than the distance test holds fewer entries than this scan finds: capped here,
+        // rewritten by frs_fix)
+        const int32_t cap = WRITE && o3d ? (int32_t)(row_splits[qi + 1] - row_splits[qi]) : 0x7fffffff;
+        cnt = frs_scan<WRITE ? 1 : 0, false>(qx, qy, qz, h, cell_start, sorted, r, flags, WRITE ? row_splits[qi] : 0, nbr_index,
+                                             nbr_dist, 0, 0.0f, unused, marks[threadIdx.x >> 6], cap, redo, nullptr,
+                                             ITEMS ? item * h->ncells : 0);
+    }
     if (lane_id() == 0) {
         if (!WRITE) counts[qi] = cnt;
         if (o3d) qflags[qi] = redo ? 1 : 0;
     }
-}
-
-// Radius search (dmcf_radius_search_count / _write): the same wave-per-query scan with the radius of the query, on the grid
-// built for max_radius.  The scan range and the chord trimming follow r_i; the cells stay sized for max_radius, so a small
-// radius still visits whole cells of that size.  A radius outside [0, max_radius] (NaN included) gives
-// an empty row.  No open3d visibility flags here: the validation rejects them, so the scan never needs its fixup.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void frs_query_radii(const float* __restrict__ queries, int64_t m, const FrsHeader* __restrict__ h,
-                                                       const uint32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
-                                                       const float* __restrict__ radii, float max_radius, int flags,
-                                                       int32_t* __restrict__ counts, const int64_t* __restrict__ row_splits,
-                                                       int32_t* __restrict__ nbr_index, float* __restrict__ nbr_dist, int64_t capacity) {
-    __shared__ uint32_t marks[4][kWin * kWave + kWave];
-    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (qi >= m) return;  // whole wave leaves
-    if (WRITE && row_splits[qi + 1] > capacity) return;  // (as frs_query: the caller sees the overflow in row_splits[m])
-    const float radius = radii[qi];
-    int32_t cnt = 0;
-    if (radius >= 0.0f && radius <= max_radius) {  // (wave uniform: one query per wave)
-        const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
-        float unused = 0.0f;
-        bool redo = false;
-        cnt = frs_scan<WRITE ? 1 : 0, false>(qx, qy, qz, h, cell_start, sorted, radius, flags, WRITE ? row_splits[qi] : 0, nbr_index,
-                                             nbr_dist, 0, 0.0f, unused, marks[threadIdx.x >> 6], 0x7fffffff, redo);
-    }
-    if (!WRITE && lane_id() == 0) counts[qi] = cnt;
 }
 
 // Single pass into padded rows (see dmcf_frs_search_padded): row qi starts at qi * stride.
@@ -797,38 +835,57 @@ __global__ __launch_bounds__(256) void frs_query_padded(const float* __restrict_
 
 // compute_density (utils/tools/losses.py:285-306) without the pair list: out[q] = sum over the points within R of
 // window(|x - q|^2 / R^2).  Same candidate scan as the search; nothing but the sums leaves the kernel.
+// ITEMS (dmcf_frs_window_sum_batched, ABI 2.22): the sums over the points of the slab of the query's item only; no open3d
+// visibility flags (the entry point refuses them).  item_max (ITEMS only; may be NULL): item_max[b] becomes the largest out of
+// item b.  The sums are not negative there (the entry point refuses the one window whose sums can be), so the floats order as
+// their bits do and an integer atomicMax serves; as with max_count in frs_query_padded, only a wave that beats the value
+// currently visible tries.  The maximum does not depend on the order of the atomics.
+template <bool ITEMS>
 __global__ __launch_bounds__(256) void frs_window_sum(const float* __restrict__ queries, int64_t m,
                                                       const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
                                                       const float4* __restrict__ sorted, float radius, int flags, int window,
-                                                      float* __restrict__ out, uint8_t* __restrict__ qflags) {
+                                                      float* __restrict__ out, uint8_t* __restrict__ qflags,
+                                                      const int64_t* __restrict__ queries_row_splits, int32_t batch,
+                                                      int32_t* __restrict__ item_max) {
     __shared__ uint32_t marks[4][kWin * kWave + kWave];
     const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (qi >= m) return;
+    if (qi >= m) return;  // whole wave leaves
+    if (ITEMS) flags &= DMCF_FRS_IGNORE_QUERY_POINT;
+    const int32_t item = frs_wave_item<ITEMS>(queries_row_splits, batch, qi);
     const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
     float wsum = 0.0f;
     bool redo = false;
     frs_scan<2, false>(qx, qy, qz, h, cell_start, sorted, radius, flags, 0, nullptr, nullptr, window, 1.0f / (radius * radius), wsum,
-                       marks[threadIdx.x >> 6], 0x7fffffff, redo);
+                       marks[threadIdx.x >> 6], 0x7fffffff, redo, nullptr, ITEMS ? item * h->ncells : 0);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) wsum += __shfl_xor(wsum, d, kWave);
     if (lane_id() == 0) {
         out[qi] = wsum;
         if (flags & kO3dFlags) qflags[qi] = redo ? 1 : 0;
+        if (ITEMS && item_max) {
+            const int32_t bits = __float_as_int(wsum);  // (>= +0: a sum of non-negative terms; a NaN's bits rank above every number)
+            if (bits > __hip_atomic_load(item_max + item, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(item_max + item, bits);
+        }
     }
 }
 
 // Gradient of the window sum w.r.t. the positions (dmcf_frs_window_sum_backward): the scan of frs_window_sum with three sums,
 //   grad[q] = 2 * sum over the hits p of (coef_q[q] + coef_p[p]) * dw/d(d^2) * (q - p).
 // Every term is added by the lane that tested the candidate, in the scan's fixed order, then the wave is reduced: no atomics,
-// identical calls give identical bits.  No open3d visibility flags here (the entry point refuses them).
+// identical calls give identical bits.  No open3d visibility flags here (the entry points refuse them).  ITEMS
+// (dmcf_frs_window_sum_backward_batched): the same three sums over the slab of the query's item.
+template <bool ITEMS>
 __global__ __launch_bounds__(256) void frs_window_sum_grad(const float* __restrict__ queries, int64_t m,
                                                            const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
                                                            const float4* __restrict__ sorted, float radius, int flags, int window,
                                                            const float* __restrict__ coef_q, const float* __restrict__ coef_p,
-                                                           float* __restrict__ grad) {
+                                                           float* __restrict__ grad,
+                                                           const int64_t* __restrict__ queries_row_splits, int32_t batch) {
     __shared__ uint32_t marks[4][kWin * kWave + kWave];
     const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (qi >= m) return;
+    if (ITEMS) flags &= DMCF_FRS_IGNORE_QUERY_POINT;
+    const int32_t item = frs_wave_item<ITEMS>(queries_row_splits, batch, qi);
     const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
     FrsGradAcc ga;
     ga.coef_q = coef_q ? coef_q[qi] : 0.0f;
@@ -838,7 +895,7 @@ __global__ __launch_bounds__(256) void frs_window_sum_grad(const float* __restri
     float unused = 0.0f;
     bool redo = false;
     frs_scan<3, false>(qx, qy, qz, h, cell_start, sorted, radius, flags, 0, nullptr, nullptr, window, 1.0f / (radius * radius), unused,
-                       marks[threadIdx.x >> 6], 0x7fffffff, redo, &ga);
+                       marks[threadIdx.x >> 6], 0x7fffffff, redo, &ga, ITEMS ? item * h->ncells : 0);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -976,161 +1033,6 @@ __global__ __launch_bounds__(256) void frs_query_linf(const float* __restrict__ 
     if (!WRITE && lane == 0) counts[qi] = cnt;
 }
 
-// ---- batched search (ABI 2.20): Open3D's points_row_splits / queries_row_splits ------------------------------------------------
-// One structure for a whole batch of point sets that were concatenated into one array: ONE grid geometry (box, cell edge, dims:
-// the header, sized from all points together), and the batch item as the outermost digit of the cell index,
-//   cell = ((b * dims[2] + cz) * dims[1] + cy) * dims[0] + cx,
-// so the table holds `batch` slabs of ncells cells and the cell-sorted array holds the items one after the other.  A point is
-// clamped into the grid of ITS slab (the border cells hold what was binned from beyond the box, per item), a query walks the
-// cells of ITS slab only: the scan is frs_scan with the slab's first cell added to every row of cells, nothing else.  Points of
-// different items never meet, wherever they lie -- the items may overlap or coincide.  The header's ncells stays the cells of
-// ONE slab.
-
-// The batch item of element i: the b with splits[b] <= i < splits[b + 1] (empty items are stepped over).  The result always
-// lies in [0, batch): row splits that are not what the caller promised give wrong neighbours, never an index beyond the table.
-__device__ __forceinline__ int32_t frs_item_of(const int64_t* __restrict__ splits, int32_t batch, int64_t i) {
-    int32_t lo = 0, hi = batch - 1;
-    while (lo < hi) {  // the first b with splits[b + 1] > i
-        const int32_t mid = (lo + hi) >> 1;
-        if (splits[mid + 1] <= i) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// (if the coarsening of frs_finish_header_one did not get the grid into its share of the table -- its 64 rounds always have so
-// far -- one cell per item still serves every query)
-__global__ void frs_finish_header_batched(FrsHeader* h, int64_t table, int64_t batch) {
-    if (threadIdx.x == 0) {
-        frs_finish_header_one(h, table, batch);
-        if ((double)h->dims[0] * (double)h->dims[1] * (double)h->dims[2] * (double)batch > (double)table || h->ncells < 1) {
-            h->dims[0] = h->dims[1] = h->dims[2] = 1;
-            h->ncells = 1;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void frs_count_cells_batched(const float* __restrict__ pts, int64_t n,
-                                                               const int64_t* __restrict__ points_row_splits, int32_t batch,
-                                                               const FrsHeader* __restrict__ h, int32_t* __restrict__ point_cell,
-                                                               uint32_t* __restrict__ cell_count, uint32_t* __restrict__ slot_of) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        c[a] = cell_coord(pts[3 * i + a], h->origin[a], h->inv_cell[a], h->dims[a]);
-        c[a] = min(max(c[a], 0), h->dims[a] - 1);  // (into the grid of the point's OWN slab: a stray never lands in a neighbouring item)
-    }
-    const int32_t b = frs_item_of(points_row_splits, batch, i);
-    const int32_t cell = b * h->ncells + (c[2] * h->dims[1] + c[1]) * h->dims[0] + c[0];
-    point_cell[i] = cell;
-    slot_of[i] = atomicAdd(&cell_count[cell], 1u);
-}
-
-// frs_query / frs_query_radii (RADII: a radius per query, `radius` is the build's max_radius) on a batched structure.  The
-// query's item -- and with it the slab -- is the same for the whole wave (one query per wave): found by a search over
-// queries_row_splits on the wave-uniform query index, so that the walk stays scalar.  DMCF_FRS_IGNORE_QUERY_POINT is the only flag.
-template <bool WRITE, bool RADII>
-__global__ __launch_bounds__(256) void frs_query_batched(const float* __restrict__ queries, int64_t m,
-                                                         const int64_t* __restrict__ queries_row_splits, int32_t batch,
-                                                         const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
-                                                         const float4* __restrict__ sorted, float radius,
-                                                         const float* __restrict__ radii, int flags, int32_t* __restrict__ counts,
-                                                         const int64_t* __restrict__ row_splits, int32_t* __restrict__ nbr_index,
-                                                         float* __restrict__ nbr_dist, int64_t capacity) {
-    __shared__ uint32_t marks[4][kWin * kWave + kWave];
-    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (qi >= m) return;  // whole wave leaves
-    if (WRITE && row_splits[qi + 1] > capacity) return;  // (as frs_query: the caller sees the overflow in row_splits[m])
-    float r = radius;
-    bool live = true;
-    if (RADII) {
-        r = radii[qi];
-        live = r >= 0.0f && r <= radius;  // (as frs_query_radii; wave uniform)
-    }
-    int32_t cnt = 0;
-    if (live) {
-        const int64_t qu = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(qi >> 32)) << 32) |
-                           (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)qi);
-        const int32_t item = __builtin_amdgcn_readfirstlane(frs_item_of(queries_row_splits, batch, qu));
-        const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
-        float unused = 0.0f;
-        bool redo = false;
-        cnt = frs_scan<WRITE ? 1 : 0, false>(qx, qy, qz, h, cell_start, sorted, r, flags & DMCF_FRS_IGNORE_QUERY_POINT,
-                                             WRITE ? row_splits[qi] : 0, nbr_index, nbr_dist, 0, 0.0f, unused, marks[threadIdx.x >> 6],
-                                             0x7fffffff, redo, nullptr, item * h->ncells);
-    }
-    if (!WRITE && lane_id() == 0) counts[qi] = cnt;
-}
-
-// frs_window_sum on a batched structure (ABI 2.22): the query's item as frs_query_batched finds it, the sums over the points
-// of that item's slab only.  item_max (may be NULL): item_max[b] becomes the largest out of item b.  The sums are not
-// negative here (the entry point refuses the one window whose sums can be), so the floats order as their bits do and an
-// integer atomicMax serves; as with max_count in frs_query_padded, only a wave that beats the value currently visible tries.
-// The maximum does not depend on the order of the atomics.
-__global__ __launch_bounds__(256) void frs_window_sum_batched(const float* __restrict__ queries, int64_t m,
-                                                              const int64_t* __restrict__ queries_row_splits, int32_t batch,
-                                                              const FrsHeader* __restrict__ h, const uint32_t* __restrict__ cell_start,
-                                                              const float4* __restrict__ sorted, float radius, int flags, int window,
-                                                              float* __restrict__ out, int32_t* __restrict__ item_max) {
-    __shared__ uint32_t marks[4][kWin * kWave + kWave];
-    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (qi >= m) return;  // whole wave leaves
-    const int64_t qu = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(qi >> 32)) << 32) |
-                       (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)qi);
-    const int32_t item = __builtin_amdgcn_readfirstlane(frs_item_of(queries_row_splits, batch, qu));
-    const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
-    float wsum = 0.0f;
-    bool redo = false;
-    frs_scan<2, false>(qx, qy, qz, h, cell_start, sorted, radius, flags & DMCF_FRS_IGNORE_QUERY_POINT, 0, nullptr, nullptr, window,
-                       1.0f / (radius * radius), wsum, marks[threadIdx.x >> 6], 0x7fffffff, redo, nullptr, item * h->ncells);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wsum += __shfl_xor(wsum, d, kWave);
-    if (lane_id() == 0) {
-        out[qi] = wsum;
-        if (item_max) {
-            const int32_t bits = __float_as_int(wsum);  // (>= +0: a sum of non-negative terms; a NaN's bits rank above every number)
-            if (bits > __hip_atomic_load(item_max + item, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(item_max + item, bits);
-        }
-    }
-}
-
-// frs_window_sum_grad on a batched structure (ABI 2.22): the same three sums over the slab of the query's item.  No atomics.
-__global__ __launch_bounds__(256) void frs_window_sum_grad_batched(const float* __restrict__ queries, int64_t m,
-                                                                   const int64_t* __restrict__ queries_row_splits, int32_t batch,
-                                                                   const FrsHeader* __restrict__ h,
-                                                                   const uint32_t* __restrict__ cell_start,
-                                                                   const float4* __restrict__ sorted, float radius, int flags,
-                                                                   int window, const float* __restrict__ coef_q,
-                                                                   const float* __restrict__ coef_p, float* __restrict__ grad) {
-    __shared__ uint32_t marks[4][kWin * kWave + kWave];
-    const int64_t qi = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (qi >= m) return;
-    const int64_t qu = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(qi >> 32)) << 32) |
-                       (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)qi);
-    const int32_t item = __builtin_amdgcn_readfirstlane(frs_item_of(queries_row_splits, batch, qu));
-    const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
-    FrsGradAcc ga;
-    ga.coef_q = coef_q ? coef_q[qi] : 0.0f;
-    ga.coef_p = coef_p;
-    ga.inv_r2 = 1.0 / ((double)radius * (double)radius);
-    ga.g[0] = ga.g[1] = ga.g[2] = 0.0f;
-    float unused = 0.0f;
-    bool redo = false;
-    frs_scan<3, false>(qx, qy, qz, h, cell_start, sorted, radius, flags & DMCF_FRS_IGNORE_QUERY_POINT, 0, nullptr, nullptr, window,
-                       1.0f / (radius * radius), unused, marks[threadIdx.x >> 6], 0x7fffffff, redo, &ga, item * h->ncells);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) ga.g[a] += __shfl_xor(ga.g[a], d, kWave);
-    }
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) grad[3 * qi + a] = 2.0f * ga.g[a];
-    }
-}
-
 }  // namespace dmcf
 
 
@@ -1144,36 +1046,167 @@ static bool frs_linf(int flags) { return (flags & DMCF_FRS_METRIC_LINF) != 0; }
 
 static constexpr unsigned kFixGrid = 1024;  // 4096 waves walk the query flags (frs_fix)
 
-// ---- batched entry points (ABI 2.20) ---------------------------------------------------------------------------------------------
 static constexpr int64_t kFrsMaxBatch = (int64_t)1 << 26;  // the largest cell table: one cell per item at least
 
 static bool frs_batch_ok(int64_t batch) { return batch >= 1 && batch <= kFrsMaxBatch; }
 
-// what the four batched searches share: validation, then one launch of frs_query_batched
+// the arrays of a workspace (frs_layout), typed
+struct FrsViews {
+    FrsHeader* h;
+    uint32_t *cell_start, *cell_fill;
+    int32_t *point_cell, *tmp_idx;
+    float4* sorted;
+    int32_t* counts;
+    char* scan;
+    uint8_t* qflags;  // (the query flags live in the workspace: see frs_layout)
+    FrsViews(const void* workspace, const FrsLayout& L) {
+        char* ws = (char*)workspace;
+        h = (FrsHeader*)(ws + L.off_header);
+        cell_start = (uint32_t*)(ws + L.off_cell_start);
+        cell_fill = (uint32_t*)(ws + L.off_cell_fill);
+        point_cell = (int32_t*)(ws + L.off_point_cell);
+        tmp_idx = (int32_t*)(ws + L.off_tmp_idx);
+        sorted = (float4*)(ws + L.off_sorted);
+        counts = (int32_t*)(ws + L.off_counts);
+        scan = ws + L.off_scan;
+        qflags = (uint8_t*)(ws + L.off_flags);
+    }
+};
+
+static unsigned frs_wave_grid(int64_t m) { return (unsigned)((m + 3) / 4); }  // one wave per query, four per workgroup
+
+// Every phase below serves both families of entry points, which validate their own arguments first: a single point set comes
+// with NULL row splits and batch 1 (and takes the ITEMS = false kernels), a batch with its row splits.
+
+// The general path of the build.  The box and the sums are those of all items together.
+static int frs_build_general(const float* points, int64_t n, const int64_t* points_row_splits, int64_t batch, float radius,
+                             const FrsLayout& L, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    // the scan scratch sits after the (query-count dependent) counts array; during the build nothing
+    // else lives there, so use the tail of the workspace the caller actually gave us
+    const size_t scan_need = scan_tmp_bytes(L.table + 1);
+    if (workspace_bytes < L.off_counts + scan_need) return DMCF_EWORKSPACE;
+    const FrsViews v(workspace, L);
+    const unsigned g = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(frs_init_header, dim3(1), dim3(64), 0, stream, v.h, radius, (int32_t)n);
+    if (n > 0) hipLaunchKernelGGL(frs_bbox, dim3(g < 512u ? g : 512u), dim3(256), 0, stream, points, n, v.h);
+    hipLaunchKernelGGL(frs_finish_header, dim3(1), dim3(64), 0, stream, v.h, L.table, batch);
+    // cell_fill is the histogram: count (each point keeps the counter's old value) -> scan into cell_start -> scatter
+    if (hipMemsetAsync(v.cell_fill, 0, (size_t)(L.table + 1) * 4, stream) != hipSuccess) return DMCF_ELAUNCH;
+    if (n > 0) {
+        // (the places inside the cells wait in the sorted array's memory, which is written last)
+        auto count = points_row_splits ? frs_count_cells<true> : frs_count_cells<false>;
+        hipLaunchKernelGGL(count, dim3(g), dim3(256), 0, stream, points, n, (const FrsHeader*)v.h, v.point_cell, v.cell_fill,
+                           (uint32_t*)v.sorted, points_row_splits, (int32_t)batch);
+    }
+    int rc = scan_exclusive_u32(v.cell_fill, v.cell_start, L.table + 1, (char*)workspace + workspace_bytes - scan_need, scan_need, stream);
+    if (rc != DMCF_OK) return rc;
+    if (n > 0) {
+        hipLaunchKernelGGL(frs_scatter, dim3(g), dim3(256), 0, stream, n, (const int32_t*)v.point_cell, (const uint32_t*)v.cell_start,
+                           (const uint32_t*)v.sorted, v.tmp_idx);
+        hipLaunchKernelGGL(frs_rank_and_place, dim3(g), dim3(256), 0, stream, points, n, (const int32_t*)v.point_cell,
+                           (const uint32_t*)v.cell_start, (const int32_t*)v.tmp_idx, v.sorted);
+    }
+    return check_launch();
+}
+
+// One pass of a two-pass search, count (then the scan into row_splits) or write: frs_query, the max-norm kernel under
+// DMCF_FRS_METRIC_LINF, and the fixup launch behind an open3d visibility flag (both of the plain un-batched search only).
 template <bool WRITE, bool RADII>
-static int frs_search_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
-                              const float* radii, float radius, int flags, const void* workspace, size_t workspace_bytes,
-                              const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance, int64_t pair_capacity,
-                              hipStream_t stream) {
-    if (!RADII && (flags & kO3dFlags)) return DMCF_EINVAL;               // the walk emulations know nothing of items
-    if (!RADII && (flags & DMCF_FRS_METRIC_LINF)) return DMCF_EUNSUPPORTED;
-    if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
-    if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || !row_splits || (m > 0 && (!queries || (RADII && !radii)))) return DMCF_EINVAL;
-    if (!queries_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
+static int frs_search(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                      const float* radii, float radius, int flags, const void* workspace, size_t workspace_bytes,
+                      const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance, int64_t pair_capacity,
+                      hipStream_t stream) {
     if (WRITE && m == 0) return DMCF_OK;
     if (WRITE && (!neighbors_index || pair_capacity < 0)) return DMCF_EINVAL;
     const FrsLayout L = frs_layout(n, m, batch);
     if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    if (m > 0)
-        hipLaunchKernelGGL((frs_query_batched<WRITE, RADII>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, queries, m,
-                           queries_row_splits, (int32_t)batch, (const FrsHeader*)(ws + L.off_header),
-                           (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radius, radii, flags,
-                           WRITE ? (int32_t*)nullptr : counts, WRITE ? row_splits : (const int64_t*)nullptr, neighbors_index,
-                           neighbors_distance, pair_capacity);
+    const FrsViews v(workspace, L);
+    int32_t* counts = WRITE ? nullptr : v.counts;
+    const int64_t* splits = WRITE ? row_splits : nullptr;
+    if (m > 0 && frs_linf(flags)) {
+        hipLaunchKernelGGL((frs_query_linf<WRITE>), dim3(frs_wave_grid(m)), dim3(256), 0, stream, queries, m, (const FrsHeader*)v.h,
+                           (const uint32_t*)v.cell_start, (const float4*)v.sorted, radius, flags, counts, splits, neighbors_index,
+                           pair_capacity);
+    } else if (m > 0) {
+        auto query = queries_row_splits ? frs_query<WRITE, RADII, true> : frs_query<WRITE, RADII, false>;
+        hipLaunchKernelGGL(query, dim3(frs_wave_grid(m)), dim3(256), 0, stream, queries, m, (const FrsHeader*)v.h,
+                           (const uint32_t*)v.cell_start, (const float4*)v.sorted, radius, flags, counts, splits, neighbors_index,
+                           neighbors_distance, pair_capacity, v.qflags, radii, queries_row_splits, (int32_t)batch);
+        if (flags & kO3dFlags)
+            hipLaunchKernelGGL((frs_fix<WRITE ? 1 : 0>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, (const FrsHeader*)v.h,
+                               (const uint32_t*)v.cell_start, (const float4*)v.sorted, radius, flags, (const uint8_t*)v.qflags, counts,
+                               splits, (int64_t)0, neighbors_index, neighbors_distance, pair_capacity, 0, (float*)nullptr);
+    }
     if (WRITE) return check_launch();
-    return scan_counts_to_row_splits(counts, (int64_t*)row_splits, m, ws + L.off_scan, L.scan_bytes, stream);
+    return scan_counts_to_row_splits(v.counts, (int64_t*)row_splits, m, v.scan, L.scan_bytes, stream);
+}
+
+// item_max: of the batched form only (NULL otherwise); zeroed even when there is no query, and the workspace is looked at only
+// when there is one
+static int frs_window_sum_run(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                              float radius, int flags, int window, const void* workspace, size_t workspace_bytes, float* out,
+                              float* item_max, hipStream_t stream) {
+    const FrsLayout L = frs_layout(n, m, batch);
+    if (m > 0 && workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    // (+0.0f is all bits zero: an item without queries keeps it)
+    if (item_max && hipMemsetAsync(item_max, 0, (size_t)batch * 4, stream) != hipSuccess) return DMCF_ELAUNCH;
+    if (m == 0) return DMCF_OK;
+    const FrsViews v(workspace, L);
+    auto sum = queries_row_splits ? frs_window_sum<true> : frs_window_sum<false>;
+    hipLaunchKernelGGL(sum, dim3(frs_wave_grid(m)), dim3(256), 0, stream, queries, m, (const FrsHeader*)v.h,
+                       (const uint32_t*)v.cell_start, (const float4*)v.sorted, radius, flags, window, out, v.qflags, queries_row_splits,
+                       (int32_t)batch, (int32_t*)item_max);
+    if (flags & kO3dFlags)
+        hipLaunchKernelGGL((frs_fix<3>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, (const FrsHeader*)v.h,
+                           (const uint32_t*)v.cell_start, (const float4*)v.sorted, radius, flags, (const uint8_t*)v.qflags,
+                           (int32_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, (int32_t*)nullptr, (float*)nullptr, (int64_t)0, window,
+                           out);
+    return check_launch();
+}
+
+static int frs_window_sum_backward_run(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                                       float radius, int flags, int window, const float* coef_queries, const float* coef_points,
+                                       const void* workspace, size_t workspace_bytes, float* grad, hipStream_t stream) {
+    if (m == 0) return DMCF_OK;
+    const FrsLayout L = frs_layout(n, m, batch);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    const FrsViews v(workspace, L);
+    auto sums = queries_row_splits ? frs_window_sum_grad<true> : frs_window_sum_grad<false>;
+    hipLaunchKernelGGL(sums, dim3(frs_wave_grid(m)), dim3(256), 0, stream, queries, m, (const FrsHeader*)v.h,
+                       (const uint32_t*)v.cell_start, (const float4*)v.sorted, radius, flags, window, coef_queries, coef_points, grad,
+                       queries_row_splits, (int32_t)batch);
+    return check_launch();
+}
+
+// what the batched searches and window sums refuse or require beyond their un-batched forms: the flags and the row splits
+static int frs_batched_flags(int flags, bool radii) {
+    if (!radii && (flags & kO3dFlags)) return DMCF_EINVAL;  // the walk emulations know nothing of items
+    if (!radii && (flags & DMCF_FRS_METRIC_LINF)) return DMCF_EUNSUPPORTED;
+    if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
+    return DMCF_OK;
+}
+
+template <bool WRITE, bool RADII>
+static int frs_search_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                              const float* radii, float radius, int flags, const void* workspace, size_t workspace_bytes,
+                              const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance, int64_t pair_capacity,
+                              dmcf_stream_t stream) {
+    const int rc = frs_batched_flags(flags, RADII);
+    if (rc != DMCF_OK) return rc;
+    if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || !row_splits || (m > 0 && (!queries || (RADII && !radii)))) return DMCF_EINVAL;
+    if (!queries_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
+    return frs_search<WRITE, RADII>(queries, m, queries_row_splits, batch, n, radii, radius, flags, workspace, workspace_bytes, row_splits,
+                                    neighbors_index, neighbors_distance, pair_capacity, (hipStream_t)stream);
+}
+
+static int frs_window_batched_args(int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius, int flags,
+                                   int window, const void* workspace) {
+    const int rc = frs_batched_flags(flags, false);
+    if (rc != DMCF_OK) return rc;
+    if (m < 0 || n < 0 || !workspace || !(radius > 0.0f)) return DMCF_EINVAL;
+    if (!queries_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
+    if (window < DMCF_WINDOW_NONE || window > DMCF_WINDOW_CUBIC_GRAD) return DMCF_EINVAL;
+    return DMCF_OK;
 }
 
 extern "C" {
@@ -1181,6 +1214,11 @@ extern "C" {
 size_t dmcf_frs_workspace_bytes(int64_t n_points, int64_t n_queries) {
     if (n_points < 0 || n_queries < 0) return 0;
     return frs_layout(n_points, n_queries).total;
+}
+
+size_t dmcf_frs_workspace_bytes_batched(int64_t n_points, int64_t n_queries, int64_t batch) {
+    if (n_points < 0 || n_queries < 0 || !frs_batch_ok(batch)) return 0;
+    return frs_layout(n_points, n_queries, batch).total;
 }
 
 int dmcf_frs_build(const float* points, int64_t n, float radius, void* workspace, size_t workspace_bytes,
@@ -1191,141 +1229,88 @@ int dmcf_frs_build(const float* points, int64_t n, float radius, void* workspace
     // the layout does not depend on the number of queries up to off_counts; validate with m = 0
     const FrsLayout L = frs_layout(n, 0);
     if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    FrsHeader* h = (FrsHeader*)(ws + L.off_header);
-    uint32_t* cell_start = (uint32_t*)(ws + L.off_cell_start);
-    uint32_t* cell_fill = (uint32_t*)(ws + L.off_cell_fill);
-    int32_t* point_cell = (int32_t*)(ws + L.off_point_cell);
-    int32_t* tmp_idx = (int32_t*)(ws + L.off_tmp_idx);
-    float4* sorted = (float4*)(ws + L.off_sorted);
-
     if (n <= kSmallBuildMax && !getenv("DMCF_FRS_NO_SMALL_BUILD")) {
-        hipLaunchKernelGGL(frs_build_small, dim3(1), dim3(kSmallThreads), 0, stream, points, n, radius, h, L.table, cell_start, cell_fill,
-                           point_cell, tmp_idx, sorted);
+        const FrsViews v(workspace, L);
+        hipLaunchKernelGGL(frs_build_small, dim3(1), dim3(kSmallThreads), 0, stream, points, n, radius, v.h, L.table, v.cell_start,
+                           v.cell_fill, v.point_cell, v.tmp_idx, v.sorted);
         return check_launch();
     }
-    hipLaunchKernelGGL(frs_init_header, dim3(1), dim3(64), 0, stream, h, radius, (int32_t)n);
-    if (n > 0) {
-        const unsigned g = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(frs_bbox, dim3(g < 512u ? g : 512u), dim3(256), 0, stream, points, n, h);
-    }
-    hipLaunchKernelGGL(frs_finish_header, dim3(1), dim3(64), 0, stream, h, L.table);
-    // cell_fill is the histogram: count (each point keeps the counter's old value) -> scan into cell_start -> scatter
-    if (hipMemsetAsync(cell_fill, 0, (size_t)(L.table + 1) * 4, stream) != hipSuccess) return DMCF_ELAUNCH;
-    if (n > 0) {
-        const unsigned g = (unsigned)((n + 255) / 256);
-        // (the places inside the cells wait in the sorted array's memory, which is written last)
-        hipLaunchKernelGGL(frs_count_cells, dim3(g), dim3(256), 0, stream, points, n, h, point_cell, cell_fill, (uint32_t*)sorted);
-    }
-    // the scan scratch sits after the (query-count dependent) counts array; during the build nothing
-    // else lives there, so use the tail of the workspace the caller actually gave us
-    const size_t scan_need = scan_tmp_bytes(L.table + 1);
-    if (workspace_bytes < L.off_counts + scan_need) return DMCF_EWORKSPACE;
-    int rc = scan_exclusive_u32(cell_fill, cell_start, L.table + 1, ws + workspace_bytes - scan_need, scan_need, stream);
-    if (rc != DMCF_OK) return rc;
-    if (n > 0) {
-        const unsigned g = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(frs_scatter, dim3(g), dim3(256), 0, stream, n, point_cell, cell_start, (const uint32_t*)sorted, tmp_idx);
-        hipLaunchKernelGGL(frs_rank_and_place, dim3(g), dim3(256), 0, stream, points, n, point_cell, cell_start,
-                           tmp_idx, sorted);
-    }
-    return check_launch();
+    return frs_build_general(points, n, nullptr, 1, radius, L, workspace, workspace_bytes, stream);
+}
+
+// (the single-workgroup build is not taken: it has no slabs)
+int dmcf_frs_build_batched(const float* points, int64_t n, const int64_t* points_row_splits, int64_t batch, float radius,
+                           void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    if (n < 0 || n > 0x7fffffff || !workspace || !(radius > 0.0f) || (n > 0 && !points)) return DMCF_EINVAL;
+    if (!points_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
+    if (((uintptr_t)workspace & 255) != 0) return DMCF_EINVAL;
+    const FrsLayout L = frs_layout(n, 0, batch);
+    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
+    return frs_build_general(points, n, points_row_splits, batch, radius, L, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int dmcf_frs_count(const float* queries, int64_t m, int64_t n, float radius, int flags, void* workspace,
-                   size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                   size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream) {
     if (!frs_flags_ok(flags)) return DMCF_EINVAL;
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || !row_splits || (m > 0 && !queries)) return DMCF_EINVAL;
     if (frs_linf(flags) && (flags & kO3dFlags)) return DMCF_EUNSUPPORTED;
-    const FrsLayout L = frs_layout(n, m);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    const FrsHeader* h = (const FrsHeader*)(ws + L.off_header);
-    const uint32_t* cell_start = (const uint32_t*)(ws + L.off_cell_start);
-    const float4* sorted = (const float4*)(ws + L.off_sorted);
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    if (m > 0 && frs_linf(flags)) {
-        hipLaunchKernelGGL((frs_query_linf<false>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, queries, m, h, cell_start, sorted,
-                           radius, flags, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0);
-    } else if (m > 0) {
-        const unsigned g = (unsigned)((m + 3) / 4);
-        uint8_t* qflags = (uint8_t*)(ws + L.off_flags);
-        hipLaunchKernelGGL((frs_query<false>), dim3(g), dim3(256), 0, stream, queries, m, h, cell_start, sorted,
-                           radius, flags, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int64_t)0, qflags);
-        if (flags & kO3dFlags)
-            hipLaunchKernelGGL((frs_fix<0>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags,
-                               (const uint8_t*)qflags, counts, (const int64_t*)nullptr, (int64_t)0, (int32_t*)nullptr, (float*)nullptr,
-                               (int64_t)0, 0, (float*)nullptr);
-    }
-    return scan_counts_to_row_splits(counts, row_splits, m, ws + L.off_scan, L.scan_bytes, stream);
+    return frs_search<false, false>(queries, m, nullptr, 1, n, nullptr, radius, flags, workspace, workspace_bytes, row_splits, nullptr,
+                                    nullptr, 0, (hipStream_t)stream);
 }
 
 int dmcf_frs_write(const float* queries, int64_t m, int64_t n, float radius, int flags, const void* workspace,
                    size_t workspace_bytes, const int64_t* row_splits, int32_t* neighbors_index,
-                   float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                   float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream) {
     if (!frs_flags_ok(flags)) return DMCF_EINVAL;
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || !row_splits || (m > 0 && !queries)) return DMCF_EINVAL;
     if (frs_linf(flags) && ((flags & kO3dFlags) || neighbors_distance)) return DMCF_EUNSUPPORTED;
-    if (m == 0) return DMCF_OK;
-    if (!neighbors_index || pair_capacity < 0) return DMCF_EINVAL;
-    const FrsLayout L = frs_layout(n, m);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;  // (the query flags live in it: see frs_layout)
-    const FrsHeader* h = (const FrsHeader*)(ws + L.off_header);
-    const uint32_t* cell_start = (const uint32_t*)(ws + L.off_cell_start);
-    const float4* sorted = (const float4*)(ws + L.off_sorted);
-    const unsigned g = (unsigned)((m + 3) / 4);
-    if (frs_linf(flags)) {
-        hipLaunchKernelGGL((frs_query_linf<true>), dim3(g), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags,
-                           (int32_t*)nullptr, row_splits, neighbors_index, pair_capacity);
-        return check_launch();
-    }
-    uint8_t* qflags = (uint8_t*)(ws + L.off_flags);  // (written by the count pass of this search)
-    hipLaunchKernelGGL((frs_query<true>), dim3(g), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius,
-                       flags, (int32_t*)nullptr, row_splits, neighbors_index, neighbors_distance, pair_capacity, qflags);
-    if (flags & kO3dFlags)
-        hipLaunchKernelGGL((frs_fix<1>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags,
-                           (const uint8_t*)qflags, (int32_t*)nullptr, row_splits, (int64_t)0, neighbors_index, neighbors_distance,
-                           pair_capacity, 0, (float*)nullptr);
-    return check_launch();
+    return frs_search<true, false>(queries, m, nullptr, 1, n, nullptr, radius, flags, workspace, workspace_bytes, row_splits,
+                                   neighbors_index, neighbors_distance, pair_capacity, (hipStream_t)stream);
 }
 
 int dmcf_radius_search_count(const float* queries, int64_t m, int64_t n, const float* radii, float max_radius, int flags,
-                             void* workspace, size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                             void* workspace, size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream) {
     if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
     if (m < 0 || n < 0 || !workspace || !(max_radius > 0.0f) || !row_splits || (m > 0 && (!queries || !radii))) return DMCF_EINVAL;
-    const FrsLayout L = frs_layout(n, m);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    if (m > 0) {
-        const unsigned g = (unsigned)((m + 3) / 4);
-        hipLaunchKernelGGL((frs_query_radii<false>), dim3(g), dim3(256), 0, stream, queries, m, (const FrsHeader*)(ws + L.off_header),
-                           (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radii, max_radius, flags, counts,
-                           (const int64_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int64_t)0);
-    }
-    return scan_counts_to_row_splits(counts, row_splits, m, ws + L.off_scan, L.scan_bytes, stream);
+    return frs_search<false, true>(queries, m, nullptr, 1, n, radii, max_radius, flags, workspace, workspace_bytes, row_splits, nullptr,
+                                   nullptr, 0, (hipStream_t)stream);
 }
 
 int dmcf_radius_search_write(const float* queries, int64_t m, int64_t n, const float* radii, float max_radius, int flags,
                              const void* workspace, size_t workspace_bytes, const int64_t* row_splits, int32_t* neighbors_index,
-                             float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                             float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream) {
     if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
     if (m < 0 || n < 0 || !workspace || !(max_radius > 0.0f) || !row_splits || (m > 0 && (!queries || !radii))) return DMCF_EINVAL;
-    if (m == 0) return DMCF_OK;
-    if (!neighbors_index || pair_capacity < 0) return DMCF_EINVAL;
-    const FrsLayout L = frs_layout(n, m);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    const char* ws = (const char*)workspace;
-    const unsigned g = (unsigned)((m + 3) / 4);
-    hipLaunchKernelGGL((frs_query_radii<true>), dim3(g), dim3(256), 0, stream, queries, m, (const FrsHeader*)(ws + L.off_header),
-                       (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radii, max_radius, flags,
-                       (int32_t*)nullptr, row_splits, neighbors_index, neighbors_distance, pair_capacity);
-    return check_launch();
+    return frs_search<true, true>(queries, m, nullptr, 1, n, radii, max_radius, flags, workspace, workspace_bytes, row_splits,
+                                  neighbors_index, neighbors_distance, pair_capacity, (hipStream_t)stream);
+}
+
+int dmcf_frs_count_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius,
+                           int flags, void* workspace, size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream) {
+    return frs_search_batched<false, false>(queries, m, queries_row_splits, batch, n, nullptr, radius, flags, workspace, workspace_bytes,
+                                            row_splits, nullptr, nullptr, 0, stream);
+}
+
+int dmcf_frs_write_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius,
+                           int flags, const void* workspace, size_t workspace_bytes, const int64_t* row_splits,
+                           int32_t* neighbors_index, float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream) {
+    return frs_search_batched<true, false>(queries, m, queries_row_splits, batch, n, nullptr, radius, flags, workspace, workspace_bytes,
+                                           row_splits, neighbors_index, neighbors_distance, pair_capacity, stream);
+}
+
+int dmcf_radius_search_count_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                                     const float* radii, float max_radius, int flags, void* workspace, size_t workspace_bytes,
+                                     int64_t* row_splits, dmcf_stream_t stream) {
+    return frs_search_batched<false, true>(queries, m, queries_row_splits, batch, n, radii, max_radius, flags, workspace,
+                                           workspace_bytes, row_splits, nullptr, nullptr, 0, stream);
+}
+
+int dmcf_radius_search_write_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                                     const float* radii, float max_radius, int flags, const void* workspace, size_t workspace_bytes,
+                                     const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance,
+                                     int64_t pair_capacity, dmcf_stream_t stream) {
+    return frs_search_batched<true, true>(queries, m, queries_row_splits, batch, n, radii, max_radius, flags, workspace, workspace_bytes,
+                                          row_splits, neighbors_index, neighbors_distance, pair_capacity, stream);
 }
 
 int dmcf_frs_search_padded(const float* queries, int64_t m, int64_t n, float radius, int flags, const void* workspace,
@@ -1340,186 +1325,62 @@ int dmcf_frs_search_padded(const float* queries, int64_t m, int64_t n, float rad
     const FrsLayout L = frs_layout(n, m);
     if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
     if (m == 0) return hipMemsetAsync(row_begin, 0, 8, stream) == hipSuccess ? DMCF_OK : DMCF_ELAUNCH;
-    char* ws = (char*)workspace;  // (the query flags live in it: see frs_layout)
-    const unsigned g = (unsigned)((m + 3) / 4);
-    uint8_t* qflags = (uint8_t*)(ws + L.off_flags);
-    const FrsHeader* h = (const FrsHeader*)(ws + L.off_header);
-    const uint32_t* cell_start = (const uint32_t*)(ws + L.off_cell_start);
-    const float4* sorted = (const float4*)(ws + L.off_sorted);
-    hipLaunchKernelGGL(frs_query_padded, dim3(g), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags, row_stride,
-                       row_begin, row_count, neighbors_index, neighbors_distance, max_count, qflags);
+    const FrsViews v(workspace, L);
+    hipLaunchKernelGGL(frs_query_padded, dim3(frs_wave_grid(m)), dim3(256), 0, stream, queries, m, (const FrsHeader*)v.h,
+                       (const uint32_t*)v.cell_start, (const float4*)v.sorted, radius, flags, row_stride, row_begin, row_count,
+                       neighbors_index, neighbors_distance, max_count, v.qflags);
     if (flags & kO3dFlags)
-        hipLaunchKernelGGL((frs_fix<2>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags,
-                           (const uint8_t*)qflags, row_count, (const int64_t*)nullptr, row_stride, neighbors_index, neighbors_distance,
-                           (int64_t)0, 0, (float*)nullptr);
+        hipLaunchKernelGGL((frs_fix<2>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, (const FrsHeader*)v.h,
+                           (const uint32_t*)v.cell_start, (const float4*)v.sorted, radius, flags, (const uint8_t*)v.qflags, row_count,
+                           (const int64_t*)nullptr, row_stride, neighbors_index, neighbors_distance, (int64_t)0, 0, (float*)nullptr);
     return check_launch();
 }
 
 int dmcf_frs_window_sum(const float* queries, int64_t m, int64_t n, float radius, int flags, int window,
-                        const void* workspace, size_t workspace_bytes, float* out, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                        const void* workspace, size_t workspace_bytes, float* out, dmcf_stream_t stream) {
     if (!frs_flags_ok(flags)) return DMCF_EINVAL;
     if (frs_linf(flags)) return DMCF_EUNSUPPORTED;  // the max-norm search returns index lists only
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || (m > 0 && (!queries || !out))) return DMCF_EINVAL;
     if (window < DMCF_WINDOW_NONE || window > DMCF_WINDOW_CUBIC_GRAD) return DMCF_EINVAL;
-    if (m == 0) return DMCF_OK;
-    const FrsLayout L = frs_layout(n, m);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;  // (the query flags live in it: see frs_layout)
-    const unsigned g = (unsigned)((m + 3) / 4);
-    uint8_t* qflags = (uint8_t*)(ws + L.off_flags);
-    const FrsHeader* h = (const FrsHeader*)(ws + L.off_header);
-    const uint32_t* cell_start = (const uint32_t*)(ws + L.off_cell_start);
-    const float4* sorted = (const float4*)(ws + L.off_sorted);
-    hipLaunchKernelGGL(frs_window_sum, dim3(g), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags, window, out, qflags);
-    if (flags & kO3dFlags)
-        hipLaunchKernelGGL((frs_fix<3>), dim3(kFixGrid), dim3(256), 0, stream, queries, m, h, cell_start, sorted, radius, flags,
-                           (const uint8_t*)qflags, (int32_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, (int32_t*)nullptr,
-                           (float*)nullptr, (int64_t)0, window, out);
-    return check_launch();
+    return frs_window_sum_run(queries, m, nullptr, 1, n, radius, flags, window, workspace, workspace_bytes, out, nullptr,
+                              (hipStream_t)stream);
+}
+
+int dmcf_frs_window_sum_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
+                                float radius, int flags, int window, const void* workspace, size_t workspace_bytes, float* out,
+                                float* item_max, dmcf_stream_t stream) {
+    const int rc = frs_window_batched_args(m, queries_row_splits, batch, n, radius, flags, window, workspace);
+    if (rc != DMCF_OK) return rc;
+    if (m > 0 && (!queries || !out)) return DMCF_EINVAL;
+    if (item_max && window == DMCF_WINDOW_CUBIC_GRAD) return DMCF_EUNSUPPORTED;  // its sums can be negative: see the kernel
+    return frs_window_sum_run(queries, m, queries_row_splits, batch, n, radius, flags, window, workspace, workspace_bytes, out, item_max,
+                              (hipStream_t)stream);
 }
 
 int dmcf_frs_window_sum_backward(const float* queries, int64_t m, int64_t n, float radius, int flags, int window,
                                  const float* coef_queries, const float* coef_points, const void* workspace,
-                                 size_t workspace_bytes, float* grad, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                                 size_t workspace_bytes, float* grad, dmcf_stream_t stream) {
     if (!frs_flags_ok(flags) || frs_linf(flags)) return DMCF_EINVAL;  // (the metric flag was never a flag of this entry point)
     if (m < 0 || n < 0 || !workspace || !(radius > 0.0f) || (m > 0 && (!queries || !grad))) return DMCF_EINVAL;
     if (window < DMCF_WINDOW_NONE || window > DMCF_WINDOW_CUBIC_GRAD) return DMCF_EINVAL;
     if (!coef_queries && !coef_points) return DMCF_EINVAL;
     if (window == DMCF_WINDOW_NONE) return DMCF_EUNSUPPORTED;  // the count has no gradient
     if (flags & kO3dFlags) return DMCF_EUNSUPPORTED;           // asymmetric pair sets: the caller differentiates on the pair list
-    if (m == 0) return DMCF_OK;
-    const FrsLayout L = frs_layout(n, m);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    const char* ws = (const char*)workspace;
-    const unsigned g = (unsigned)((m + 3) / 4);
-    hipLaunchKernelGGL(frs_window_sum_grad, dim3(g), dim3(256), 0, stream, queries, m, (const FrsHeader*)(ws + L.off_header),
-                       (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radius, flags, window, coef_queries,
-                       coef_points, grad);
-    return check_launch();
-}
-
-size_t dmcf_frs_workspace_bytes_batched(int64_t n_points, int64_t n_queries, int64_t batch) {
-    if (n_points < 0 || n_queries < 0 || !frs_batch_ok(batch)) return 0;
-    return frs_layout(n_points, n_queries, batch).total;
-}
-
-int dmcf_frs_build_batched(const float* points, int64_t n, const int64_t* points_row_splits, int64_t batch, float radius,
-                           void* workspace, size_t workspace_bytes, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n < 0 || n > 0x7fffffff || !workspace || !(radius > 0.0f) || (n > 0 && !points)) return DMCF_EINVAL;
-    if (!points_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
-    if (((uintptr_t)workspace & 255) != 0) return DMCF_EINVAL;
-    const FrsLayout L = frs_layout(n, 0, batch);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    const size_t scan_need = scan_tmp_bytes(L.table + 1);  // (in the tail of the workspace, as in dmcf_frs_build)
-    if (workspace_bytes < L.off_counts + scan_need) return DMCF_EWORKSPACE;
-    char* ws = (char*)workspace;
-    FrsHeader* h = (FrsHeader*)(ws + L.off_header);
-    uint32_t* cell_start = (uint32_t*)(ws + L.off_cell_start);
-    uint32_t* cell_fill = (uint32_t*)(ws + L.off_cell_fill);
-    int32_t* point_cell = (int32_t*)(ws + L.off_point_cell);
-    int32_t* tmp_idx = (int32_t*)(ws + L.off_tmp_idx);
-    float4* sorted = (float4*)(ws + L.off_sorted);
-    // the phases of dmcf_frs_build's general path (the single-workgroup build is not taken: it has no slabs); the box and the
-    // sums are those of all items together
-    hipLaunchKernelGGL(frs_init_header, dim3(1), dim3(64), 0, stream, h, radius, (int32_t)n);
-    const unsigned g = (unsigned)((n + 255) / 256);
-    if (n > 0) hipLaunchKernelGGL(frs_bbox, dim3(g < 512u ? g : 512u), dim3(256), 0, stream, points, n, h);
-    hipLaunchKernelGGL(frs_finish_header_batched, dim3(1), dim3(64), 0, stream, h, L.table, batch);
-    if (hipMemsetAsync(cell_fill, 0, (size_t)(L.table + 1) * 4, stream) != hipSuccess) return DMCF_ELAUNCH;
-    if (n > 0)
-        hipLaunchKernelGGL(frs_count_cells_batched, dim3(g), dim3(256), 0, stream, points, n, points_row_splits, (int32_t)batch,
-                           (const FrsHeader*)h, point_cell, cell_fill, (uint32_t*)sorted);
-    int rc = scan_exclusive_u32(cell_fill, cell_start, L.table + 1, ws + workspace_bytes - scan_need, scan_need, stream);
-    if (rc != DMCF_OK) return rc;
-    if (n > 0) {
-        hipLaunchKernelGGL(frs_scatter, dim3(g), dim3(256), 0, stream, n, point_cell, cell_start, (const uint32_t*)sorted, tmp_idx);
-        hipLaunchKernelGGL(frs_rank_and_place, dim3(g), dim3(256), 0, stream, points, n, point_cell, cell_start, tmp_idx, sorted);
-    }
-    return check_launch();
-}
-
-int dmcf_frs_count_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius,
-                           int flags, void* workspace, size_t workspace_bytes, int64_t* row_splits, dmcf_stream_t stream) {
-    return frs_search_batched<false, false>(queries, m, queries_row_splits, batch, n, nullptr, radius, flags, workspace, workspace_bytes,
-                                            row_splits, nullptr, nullptr, 0, (hipStream_t)stream);
-}
-
-int dmcf_frs_write_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius,
-                           int flags, const void* workspace, size_t workspace_bytes, const int64_t* row_splits,
-                           int32_t* neighbors_index, float* neighbors_distance, int64_t pair_capacity, dmcf_stream_t stream) {
-    return frs_search_batched<true, false>(queries, m, queries_row_splits, batch, n, nullptr, radius, flags, workspace, workspace_bytes,
-                                           row_splits, neighbors_index, neighbors_distance, pair_capacity, (hipStream_t)stream);
-}
-
-int dmcf_radius_search_count_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
-                                     const float* radii, float max_radius, int flags, void* workspace, size_t workspace_bytes,
-                                     int64_t* row_splits, dmcf_stream_t stream) {
-    return frs_search_batched<false, true>(queries, m, queries_row_splits, batch, n, radii, max_radius, flags, workspace,
-                                           workspace_bytes, row_splits, nullptr, nullptr, 0, (hipStream_t)stream);
-}
-
-int dmcf_radius_search_write_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
-                                     const float* radii, float max_radius, int flags, const void* workspace, size_t workspace_bytes,
-                                     const int64_t* row_splits, int32_t* neighbors_index, float* neighbors_distance,
-                                     int64_t pair_capacity, dmcf_stream_t stream) {
-    return frs_search_batched<true, true>(queries, m, queries_row_splits, batch, n, radii, max_radius, flags, workspace, workspace_bytes,
-                                          row_splits, neighbors_index, neighbors_distance, pair_capacity, (hipStream_t)stream);
-}
-
-// what the two batched window sums share with frs_search_batched: the flags and the row splits
-static int frs_window_batched_args(int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n, float radius, int flags,
-                                   int window, const void* workspace) {
-    if (flags & kO3dFlags) return DMCF_EINVAL;  // the walk emulations know nothing of items
-    if (flags & DMCF_FRS_METRIC_LINF) return DMCF_EUNSUPPORTED;
-    if ((flags & ~DMCF_FRS_IGNORE_QUERY_POINT) != 0) return DMCF_EINVAL;
-    if (m < 0 || n < 0 || !workspace || !(radius > 0.0f)) return DMCF_EINVAL;
-    if (!queries_row_splits || !frs_batch_ok(batch)) return DMCF_EINVAL;
-    if (window < DMCF_WINDOW_NONE || window > DMCF_WINDOW_CUBIC_GRAD) return DMCF_EINVAL;
-    return DMCF_OK;
-}
-
-int dmcf_frs_window_sum_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch, int64_t n,
-                                float radius, int flags, int window, const void* workspace, size_t workspace_bytes, float* out,
-                                float* item_max, dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int rc = frs_window_batched_args(m, queries_row_splits, batch, n, radius, flags, window, workspace);
-    if (rc != DMCF_OK) return rc;
-    if (m > 0 && (!queries || !out)) return DMCF_EINVAL;
-    if (item_max && window == DMCF_WINDOW_CUBIC_GRAD) return DMCF_EUNSUPPORTED;  // its sums can be negative: see the kernel
-    const FrsLayout L = frs_layout(n, m, batch);
-    if (m > 0 && workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    // (+0.0f is all bits zero: an item without queries keeps it)
-    if (item_max && hipMemsetAsync(item_max, 0, (size_t)batch * 4, stream) != hipSuccess) return DMCF_ELAUNCH;
-    if (m == 0) return DMCF_OK;
-    const char* ws = (const char*)workspace;
-    hipLaunchKernelGGL(frs_window_sum_batched, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, queries, m, queries_row_splits,
-                       (int32_t)batch, (const FrsHeader*)(ws + L.off_header), (const uint32_t*)(ws + L.off_cell_start),
-                       (const float4*)(ws + L.off_sorted), radius, flags, window, out, (int32_t*)item_max);
-    return check_launch();
+    return frs_window_sum_backward_run(queries, m, nullptr, 1, n, radius, flags, window, coef_queries, coef_points, workspace,
+                                       workspace_bytes, grad, (hipStream_t)stream);
 }
 
 int dmcf_frs_window_sum_backward_batched(const float* queries, int64_t m, const int64_t* queries_row_splits, int64_t batch,
                                          int64_t n, float radius, int flags, int window, const float* coef_queries,
                                          const float* coef_points, const void* workspace, size_t workspace_bytes, float* grad,
-                                         dmcf_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                                         dmcf_stream_t stream) {
     const int rc = frs_window_batched_args(m, queries_row_splits, batch, n, radius, flags, window, workspace);
     if (rc != DMCF_OK) return rc;
     if (m > 0 && (!queries || !grad)) return DMCF_EINVAL;
     if (!coef_queries && !coef_points) return DMCF_EINVAL;
     if (window == DMCF_WINDOW_NONE) return DMCF_EUNSUPPORTED;  // the count has no gradient
-    if (m == 0) return DMCF_OK;
-    const FrsLayout L = frs_layout(n, m, batch);
-    if (workspace_bytes < L.total) return DMCF_EWORKSPACE;
-    const char* ws = (const char*)workspace;
-    hipLaunchKernelGGL(frs_window_sum_grad_batched, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, queries, m,
-                       queries_row_splits, (int32_t)batch, (const FrsHeader*)(ws + L.off_header),
-                       (const uint32_t*)(ws + L.off_cell_start), (const float4*)(ws + L.off_sorted), radius, flags, window,
-                       coef_queries, coef_points, grad);
-    return check_launch();
+    return frs_window_sum_backward_run(queries, m, queries_row_splits, batch, n, radius, flags, window, coef_queries, coef_points,
+                                       workspace, workspace_bytes, grad, (hipStream_t)stream);
 }
 
 }  // extern "C"

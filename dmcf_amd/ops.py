@@ -300,33 +300,47 @@ def build_spatial_hash_table(points, radius, n_queries=None, points_row_splits=N
     ``points_row_splits`` (a sequence, a CPU or a device int64 tensor; a device tensor costs one small synchronising copy for
     its validation): the structure of a BATCH of point sets (dmcf_frs_build_batched), which remembers its splits and serves
     searches with those splits only."""
+    host = rs_dev = batch = None
     if points_row_splits is not None:
         host, dev = _host_row_splits(points_row_splits, "points_row_splits")
         _check_row_splits(host, points.shape[0], "points_row_splits")
-        L = _lib.lib()
-        points = _dev_f32(points, "points", 3)
-        n, batch = points.shape[0], len(host) - 1
-        m = n if n_queries is None else int(n_queries)
-        nbytes = L.dmcf_frs_workspace_bytes_batched(n, m, batch)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
-        rs_dev = _row_splits_on(host, dev, points.device)
-        t0 = timer.begin() if timer is not None else None
-        _lib.check(L.dmcf_frs_build_batched(_ptr(points), n, _ptr(rs_dev), batch, float(radius), _ptr(ws), nbytes, _stream()),
-                   "dmcf_frs_build_batched")
-        if timer is not None:
-            timer.end("frs_build_batched", dict(n_points=n, batch=batch), t0)
-        return SpatialHashTable(points, radius, ws, m, row_splits=host, row_splits_dev=rs_dev)
+        batch = len(host) - 1
     L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     n = points.shape[0]
     m = n if n_queries is None else int(n_queries)
-    nbytes = L.dmcf_frs_workspace_bytes(n, m)
+    nbytes = _frs_workspace_bytes(n, m, batch)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+    if batch is not None:
+        rs_dev = _row_splits_on(host, dev, points.device)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_frs_build(_ptr(points), n, float(radius), _ptr(ws), nbytes, _stream()), "dmcf_frs_build")
+    if batch is None:
+        _lib.check(L.dmcf_frs_build(_ptr(points), n, float(radius), _ptr(ws), nbytes, _stream()), "dmcf_frs_build")
+        kind, meta = "frs_build", dict(n_points=n)
+    else:
+        _lib.check(L.dmcf_frs_build_batched(_ptr(points), n, _ptr(rs_dev), batch, float(radius), _ptr(ws), nbytes, _stream()),
+                   "dmcf_frs_build_batched")
+        kind, meta = "frs_build_batched", dict(n_points=n, batch=batch)
     if timer is not None:
-        timer.end("frs_build", dict(n_points=n), t0)
-    return SpatialHashTable(points, radius, ws, m)
+        timer.end(kind, meta, t0)
+    return SpatialHashTable(points, radius, ws, m, row_splits=host, row_splits_dev=rs_dev)
+
+
+def _frs_workspace_bytes(n, m, batch=None):
+    """Bytes of the search structure of n points with room for m queries; ``batch``: items of a batched one, else None."""
+    L = _lib.lib()
+    return L.dmcf_frs_workspace_bytes(n, m) if batch is None else L.dmcf_frs_workspace_bytes_batched(n, m, batch)
+
+
+def _serving_table(hash_table, points, radius, m, p_splits=None):
+    """The caller's ``hash_table`` when it is the structure of exactly these points, this radius and these points_row_splits
+    with room for m queries, else a new one.  ``p_splits``: the (host, dev) pair of the points' row splits, None for a single
+    point set -- which a batched structure does not serve, nor the other way round."""
+    host, dev = p_splits if p_splits is not None else (None, None)
+    if (hash_table is None or hash_table.n_queries_capacity < m or hash_table.points.data_ptr() != points.data_ptr()
+            or hash_table.radius != radius or hash_table.row_splits != host):
+        hash_table = build_spatial_hash_table(points, radius, n_queries=m, points_row_splits=host if dev is None else dev)
+    return hash_table
 
 
 def reserve_device_memory(gib, device=None):
@@ -412,71 +426,10 @@ def search_set():
     return name
 
 
-def frs_flags(ignore_query_point):
-    """Flags of the dmcf_frs_* entry points for the neighbour set in force (search_set)."""
-    return (FRS_IGNORE_QUERY_POINT if ignore_query_point else 0) | SEARCH_SETS[search_set()]
-
-
-def _batched_table(points, radius, m, p_host, p_dev, hash_table):
-    """The batched structure of (points, radius, these splits): the caller's when it is one, else a new one."""
-    if (hash_table is None or hash_table.n_queries_capacity < m or hash_table.points.data_ptr() != points.data_ptr()
-            or hash_table.radius != radius or hash_table.row_splits != p_host):
-        hash_table = build_spatial_hash_table(points, radius, n_queries=m, points_row_splits=p_host if p_dev is None else p_dev)
-    return hash_table
-
-
-def _fixed_radius_search_batched(points, queries, radius, ignore_query_point, return_distances, hash_table, capacity_hint, row_stride,
-                                 metric, points_row_splits, queries_row_splits):
-    """fixed_radius_search with row splits (dmcf_frs_*_batched).  Host checks first, in this order: both or neither; the
-    options that have no batched form; well-formed row splits; only then the operands' device."""
-    if points_row_splits is None or queries_row_splits is None:
-        raise NotImplementedError("batched search needs both points_row_splits and queries_row_splits")
-    if row_stride is not None:
-        raise NotImplementedError("row_stride (padded rows) has no batched form: pass row splits or row_stride, not both")
-    if metric != "L2":
-        raise NotImplementedError(f"metric {metric!r} has no batched form: a search with row splits is 'L2'")
-    if SEARCH_SETS[search_set()] != 0:
-        raise NotImplementedError(f"DMCF_FRS_SET={search_set()} has no batched form: the open3d walk emulations know nothing of items")
-    (p_host, p_dev), (q_host, q_dev) = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
-    L = _lib.lib()
-    points = _dev_f32(points, "points", 3)
-    queries = _dev_f32(queries, "queries", 3)
-    radius = float(radius)
-    if not radius > 0:
-        raise ValueError("radius must be positive")
-    n, m, batch = points.shape[0], queries.shape[0], len(p_host) - 1
-    dev = points.device
-    hash_table = _batched_table(points, radius, m, p_host, p_dev, hash_table)
-    ws = hash_table.workspace
-    nbytes = L.dmcf_frs_workspace_bytes_batched(n, hash_table.n_queries_capacity, batch)
-    q_rs = _row_splits_on(q_host, q_dev, dev)
-    flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
-    row_splits = torch.empty(m + 1, dtype=torch.int64, device=dev)
-    t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_frs_count_batched(_ptr(queries), m, _ptr(q_rs), batch, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
-                                        _stream()), "dmcf_frs_count_batched")
-
-    def write(capacity):
-        index = torch.empty(capacity, dtype=torch.int32, device=dev)
-        dist = torch.empty(capacity if return_distances else 0, dtype=torch.float32, device=dev)
-        if capacity > 0 and m > 0:
-            _lib.check(L.dmcf_frs_write_batched(_ptr(queries), m, _ptr(q_rs), batch, n, radius, flags, _ptr(ws), nbytes,
-                                                _ptr(row_splits), _ptr(index), _ptr(dist) if return_distances else None, capacity,
-                                                _stream()), "dmcf_frs_write_batched")
-        return index, dist
-
-    if capacity_hint is None:
-        total = int(row_splits[-1].item())  # the one host round trip of the two-phase search
-        index, dist = write(pair_capacity(total) if total else 0)
-        res = NeighborSearchResult(index, row_splits, dist, total=total)
-    else:
-        index, dist = write(pair_capacity(capacity_hint))
-        keep = (points, queries, ws, q_rs)  # noqa: F841  (the closure keeps the operands alive for a possible redo)
-        res = NeighborSearchResult(index, row_splits, dist, total=None, redo=write)
-    if timer is not None:
-        timer.end("frs_search_batched", dict(n_points=n, n_queries=m, batch=batch, pairs=res.total_ref,
-                                             distances=bool(return_distances)), t0)
-    return res
+def frs_flags(ignore_query_point, batched=False):
+    """Flags of the dmcf_frs_* entry points for the neighbour set in force (search_set); of the ``batched`` ones, which know the
+    distance set only (their callers refuse the other sets on the host), the ignore flag alone."""
+    return (FRS_IGNORE_QUERY_POINT if ignore_query_point else 0) | (0 if batched else SEARCH_SETS[search_set()])
 
 
 def fixed_radius_search(points, queries, radius, ignore_query_point=False, return_distances=True,
@@ -498,9 +451,21 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
     batched search.  Item b of the batch is points[prs[b]:prs[b+1]] and queries[qrs[b]:qrs[b+1]]; a query finds points of its
     own item only, neighbors_index indexes the concatenated points, the row splits of the result run over all queries.  'L2'
     and DMCF_FRS_SET=distance only, no ``row_stride``; ``capacity_hint`` as without row splits."""
-    if points_row_splits is not None or queries_row_splits is not None:
-        return _fixed_radius_search_batched(points, queries, radius, ignore_query_point, return_distances, hash_table, capacity_hint,
-                                            row_stride, metric, points_row_splits, queries_row_splits)
+    batched = points_row_splits is not None or queries_row_splits is not None
+    p_splits = batch = None
+    if batched:
+        # host checks first, in this order: both or neither; the options that have no batched form; well-formed row splits;
+        # only then the operands' device
+        if points_row_splits is None or queries_row_splits is None:
+            raise NotImplementedError("batched search needs both points_row_splits and queries_row_splits")
+        if row_stride is not None:
+            raise NotImplementedError("row_stride (padded rows) has no batched form: pass row splits or row_stride, not both")
+        if metric != "L2":
+            raise NotImplementedError(f"metric {metric!r} has no batched form: a search with row splits is 'L2'")
+        if SEARCH_SETS[search_set()] != 0:
+            raise NotImplementedError(f"DMCF_FRS_SET={search_set()} has no batched form: the open3d walk emulations know nothing of items")
+        p_splits, (q_host, q_dev) = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
+        batch = len(q_host) - 1
     L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     queries = _dev_f32(queries, "queries", 3)
@@ -512,12 +477,10 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
     if metric == "Linf" and (return_distances or row_stride is not None):
         raise NotImplementedError("the 'Linf' search returns index lists only (no distances, no padded rows)")
     n, m = points.shape[0], queries.shape[0]
-    if hash_table is None or hash_table.n_queries_capacity < m or hash_table.points.data_ptr() != points.data_ptr() \
-            or hash_table.radius != radius or hash_table.row_splits is not None:  # (a batched structure does not serve this search)
-        hash_table = build_spatial_hash_table(points, radius, n_queries=m)
+    hash_table = _serving_table(hash_table, points, radius, m, p_splits)
     ws = hash_table.workspace
-    nbytes = L.dmcf_frs_workspace_bytes(n, hash_table.n_queries_capacity)
-    flags = frs_flags(ignore_query_point)
+    nbytes = _frs_workspace_bytes(n, hash_table.n_queries_capacity, batch)
+    flags = frs_flags(ignore_query_point)  # (a batched search runs under DMCF_FRS_SET=distance: the ignore flag alone)
     if metric == "Linf":
         flags = (FRS_IGNORE_QUERY_POINT if ignore_query_point else 0) | FRS_METRIC_LINF
     dev = points.device
@@ -556,33 +519,44 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
         if timer is not None:
             timer.end("frs_search_padded", dict(n_points=n, n_queries=m, pairs=res.total_ref, distances=bool(return_distances)), t0)
         return res
+    # one count / write body for both families: row splits select the entry points and the timer spans (frs_count and
+    # frs_write around the two passes of a single point set, one frs_search_batched around both of a batch)
+    if batched:
+        q_rs = _row_splits_on(q_host, q_dev, dev)
+        item = (_ptr(q_rs), batch)
+        count, write_rows = L.dmcf_frs_count_batched, L.dmcf_frs_write_batched
+        names = ("dmcf_frs_count_batched", "dmcf_frs_write_batched")
+    else:
+        q_rs, item = None, ()
+        count, write_rows, names = L.dmcf_frs_count, L.dmcf_frs_write, ("dmcf_frs_count", "dmcf_frs_write")
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_frs_count(_ptr(queries), m, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _stream()),
-               "dmcf_frs_count")
-    if timer is not None:
+    _lib.check(count(_ptr(queries), m, *item, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _stream()), names[0])
+    if timer is not None and not batched:
         timer.end("frs_count", dict(n_points=n, n_queries=m), t0)
 
     def write(capacity):
         index = torch.empty(capacity, dtype=torch.int32, device=dev)
         dist = torch.empty(capacity if return_distances else 0, dtype=torch.float32, device=dev)
         if capacity > 0 and m > 0:
-            _lib.check(L.dmcf_frs_write(_ptr(queries), m, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
-                                        _ptr(index), _ptr(dist) if return_distances else None, capacity, _stream()),
-                       "dmcf_frs_write")
+            _lib.check(write_rows(_ptr(queries), m, *item, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _ptr(index),
+                                  _ptr(dist) if return_distances else None, capacity, _stream()), names[1])
         return index, dist
 
     if capacity_hint is None:
         total = int(row_splits[-1].item())  # the one host round trip of the two-phase search
-        t1 = timer.begin() if timer is not None else None
+        t1 = timer.begin() if timer is not None and not batched else t0
         index, dist = write(pair_capacity(total) if total else 0)
         res = NeighborSearchResult(index, row_splits, dist, total=total)
     else:
-        t1 = timer.begin() if timer is not None else None
+        t1 = timer.begin() if timer is not None and not batched else t0
         index, dist = write(pair_capacity(capacity_hint))
-        keep = (points, queries, ws)  # noqa: F841  (the closure keeps the operands alive for a possible redo)
+        keep = (points, queries, ws, q_rs)  # noqa: F841  (the closure keeps the operands alive for a possible redo)
         res = NeighborSearchResult(index, row_splits, dist, total=None, redo=write)
     if timer is not None:
-        timer.end("frs_write", dict(n_points=n, n_queries=m, pairs=res.total_ref, distances=bool(return_distances)), t1)
+        meta = dict(n_points=n, n_queries=m, pairs=res.total_ref, distances=bool(return_distances))
+        if batched:
+            meta["batch"] = batch
+        timer.end("frs_search_batched" if batched else "frs_write", meta, t1)
     return res
 
 
@@ -639,8 +613,10 @@ def radius_search(points, queries, radii, ignore_query_point=False, return_dista
     ``points_row_splits`` / ``queries_row_splits``: the batched search, as in :func:`fixed_radius_search` (both or neither,
     validated on the host before a device is touched; dmcf_radius_search_*_batched)."""
     batched = points_row_splits is not None or queries_row_splits is not None
+    p_splits = batch = None
     if batched:
-        (p_host, p_dev), (q_host, q_dev) = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
+        p_splits, (q_host, q_dev) = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
+        batch = len(q_host) - 1
     L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     queries = _dev_f32(queries, "queries", 3)
@@ -658,34 +634,26 @@ def radius_search(points, queries, radii, ignore_query_point=False, return_dista
         raise ValueError("radii must be finite and non-negative")
     max_radius = float(np.float32(max_radius)) if max_radius > 0 else 1.0  # (all zero: any grid serves, the rows are coincident points)
     flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
+    ws = _serving_table(None, points, max_radius, m, p_splits).workspace
+    nbytes = _frs_workspace_bytes(n, m, batch)
     if batched:
-        batch = len(p_host) - 1
-        table = build_spatial_hash_table(points, max_radius, n_queries=m, points_row_splits=p_host if p_dev is None else p_dev)
-        ws = table.workspace
-        nbytes = L.dmcf_frs_workspace_bytes_batched(n, m, batch)
         q_rs = _row_splits_on(q_host, q_dev, dev)
-        t0 = timer.begin() if timer is not None else None
-        _lib.check(L.dmcf_radius_search_count_batched(_ptr(queries), m, _ptr(q_rs), batch, n, _ptr(radii), max_radius, flags, _ptr(ws),
-                                                      nbytes, _ptr(row_splits), _stream()), "dmcf_radius_search_count_batched")
+        item = (_ptr(q_rs), batch)
+        count, write, names = (L.dmcf_radius_search_count_batched, L.dmcf_radius_search_write_batched,
+                               ("dmcf_radius_search_count_batched", "dmcf_radius_search_write_batched"))
     else:
-        table = build_spatial_hash_table(points, max_radius, n_queries=m)
-        ws = table.workspace
-        nbytes = L.dmcf_frs_workspace_bytes(n, m)
-        t0 = timer.begin() if timer is not None else None
-        _lib.check(L.dmcf_radius_search_count(_ptr(queries), m, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
-                                              _stream()), "dmcf_radius_search_count")
+        item = ()
+        count, write, names = (L.dmcf_radius_search_count, L.dmcf_radius_search_write,
+                               ("dmcf_radius_search_count", "dmcf_radius_search_write"))
+    t0 = timer.begin() if timer is not None else None
+    _lib.check(count(_ptr(queries), m, *item, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _stream()), names[0])
     total = int(row_splits[-1].item())  # the one host round trip of the two-phase search, as in fixed_radius_search
     capacity = pair_capacity(total) if total else 0
     index = torch.empty(capacity, dtype=torch.int32, device=dev)
     dist = torch.empty(capacity if return_distances else 0, dtype=torch.float32, device=dev)
-    if capacity > 0 and batched:
-        _lib.check(L.dmcf_radius_search_write_batched(_ptr(queries), m, _ptr(q_rs), batch, n, _ptr(radii), max_radius, flags, _ptr(ws),
-                                                      nbytes, _ptr(row_splits), _ptr(index), _ptr(dist) if return_distances else None,
-                                                      capacity, _stream()), "dmcf_radius_search_write_batched")
-    elif capacity > 0:
-        _lib.check(L.dmcf_radius_search_write(_ptr(queries), m, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits),
-                                              _ptr(index), _ptr(dist) if return_distances else None, capacity, _stream()),
-                   "dmcf_radius_search_write")
+    if capacity > 0:
+        _lib.check(write(_ptr(queries), m, *item, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _ptr(index),
+                         _ptr(dist) if return_distances else None, capacity, _stream()), names[1])
     if timer is not None:
         timer.end("radius_search", dict(n_points=n, n_queries=m, pairs=total, distances=bool(return_distances)), t0)
     if return_distances and normalize_distances and total > 0:
@@ -2363,25 +2331,53 @@ def ghost_select(pos, boxes, widths2):
     return GhostSelection(pos, boxes, widths2, ws, totals)
 
 
-def _window_sum_impl(points, queries, radius, window, ignore_query_point, hash_table):
-    """-> (out, the search structure over ``points`` that served the call)."""
+def _window_sum_impl(points, queries, radius, window, flags, hash_table, batched=None):
+    """dmcf_frs_window_sum, or with ``batched`` (WindowSumFunction's triple) dmcf_frs_window_sum_batched, under the span
+    frs_window_sum_batched -> (out, item_max or None, the search structure over ``points`` that served the call, the queries'
+    device splits or None)."""
     L = _lib.lib()
     n, m = points.shape[0], queries.shape[0]
-    if hash_table is None or hash_table.n_queries_capacity < m or hash_table.points.data_ptr() != points.data_ptr() \
-            or hash_table.radius != radius:
-        hash_table = build_spatial_hash_table(points, radius, n_queries=m)
-    nbytes = L.dmcf_frs_workspace_bytes(n, hash_table.n_queries_capacity)
-    out = torch.empty(m, dtype=torch.float32, device=points.device)
-    _lib.check(L.dmcf_frs_window_sum(_ptr(queries), m, n, radius, frs_flags(ignore_query_point), WINDOWS[window],
-                                     _ptr(hash_table.workspace), nbytes, _ptr(out), _stream()), "dmcf_frs_window_sum")
-    return out, hash_table
+    dev = points.device
+    p_splits, (q_host, q_dev), want_max = batched if batched is not None else (None, (None, None), False)
+    batch = None if batched is None else len(q_host) - 1
+    hash_table = _serving_table(hash_table, points, radius, m, p_splits)
+    nbytes = _frs_workspace_bytes(n, hash_table.n_queries_capacity, batch)
+    out = torch.empty(m, dtype=torch.float32, device=dev)
+    q_rs = item_max = None
+    if batched is None:
+        entry, name, item, tail = L.dmcf_frs_window_sum, "dmcf_frs_window_sum", (), ()
+    else:
+        q_rs = _row_splits_on(q_host, q_dev, dev)
+        item_max = torch.empty(batch, dtype=torch.float32, device=dev) if want_max else None
+        entry, name, item, tail = L.dmcf_frs_window_sum_batched, "dmcf_frs_window_sum_batched", (_ptr(q_rs), batch), (_ptr(item_max),)
+    t0 = timer.begin() if timer is not None and batched is not None else None
+    _lib.check(entry(_ptr(queries), m, *item, n, radius, flags, WINDOWS[window], _ptr(hash_table.workspace), nbytes, _ptr(out), *tail,
+                     _stream()), name)
+    if t0 is not None:
+        timer.end("frs_window_sum_batched", dict(n_points=n, n_queries=m, batch=batch), t0)
+    return out, item_max, hash_table, q_rs
 
 
-def window_sum_backward(queries, hash_table, radius, window, coef_queries=None, coef_points=None, ignore_query_point=False):
+def window_sum_backward(queries, hash_table, radius, window, coef_queries=None, coef_points=None, ignore_query_point=False,
+                        queries_row_splits=None):
     """dmcf_frs_window_sum_backward on the structure ``hash_table`` of some point set: float32 [m, 3],
     ``grad[q] = 2 sum_{|p - q| <= R} (coef_queries[q] + coef_points[p]) dw/d(d^2) (q - p)``.  ``coef_queries`` [m] and
-    ``coef_points`` [n points of the structure] may each be None (0), not both.  Distance set only (DMCF_FRS_SET=distance)."""
+    ``coef_points`` [n points of the structure] may each be None (0), not both.  Distance set only (DMCF_FRS_SET=distance).
+
+    ``queries_row_splits`` (as for the batched search, with as many items as the structure): on the batched structure of some
+    concatenated point sets (dmcf_frs_window_sum_backward_batched), the sums of a query running over the points of its own
+    item.  A batched structure needs them, the structure of a single point set takes none (ValueError either way)."""
     L = _lib.lib()
+    batched = queries_row_splits is not None
+    if batched and hash_table.row_splits is None:
+        raise ValueError("hash_table is not a batched structure (build_spatial_hash_table(..., points_row_splits=...))")
+    if not batched and hash_table.row_splits is not None:
+        raise ValueError("hash_table is a batched structure: pass queries_row_splits")
+    if batched:
+        q_host, q_dev = _host_row_splits(queries_row_splits, "queries_row_splits")
+        _check_row_splits(q_host, queries.shape[0], "queries_row_splits")
+        if len(q_host) != len(hash_table.row_splits):
+            raise ValueError("queries_row_splits and the structure's row splits must have equal lengths (batch + 1)")
     queries = _dev_f32(queries, "queries", 3)
     radius = float(radius)
     if window not in WINDOWS:
@@ -2392,11 +2388,17 @@ def window_sum_backward(queries, hash_table, radius, window, coef_queries=None, 
     dev = queries.device
     cq = None if coef_queries is None else _dev_exact(coef_queries, "coef_queries", torch.float32, (m,), dev)
     cp = None if coef_points is None else _dev_exact(coef_points, "coef_points", torch.float32, (n,), dev)
-    nbytes = L.dmcf_frs_workspace_bytes(n, hash_table.n_queries_capacity)
+    if batched:
+        q_rs = _row_splits_on(q_host, q_dev, dev)
+        batch = len(q_host) - 1
+        entry, name, item = L.dmcf_frs_window_sum_backward_batched, "dmcf_frs_window_sum_backward_batched", (_ptr(q_rs), batch)
+    else:
+        batch = None
+        entry, name, item = L.dmcf_frs_window_sum_backward, "dmcf_frs_window_sum_backward", ()
+    nbytes = _frs_workspace_bytes(n, hash_table.n_queries_capacity, batch)
     grad = torch.empty((m, 3), dtype=torch.float32, device=dev)
-    _lib.check(L.dmcf_frs_window_sum_backward(_ptr(queries), m, n, radius, frs_flags(ignore_query_point), WINDOWS[window], _ptr(cq),
-                                              _ptr(cp), _ptr(hash_table.workspace), nbytes, _ptr(grad), _stream()),
-               "dmcf_frs_window_sum_backward")
+    _lib.check(entry(_ptr(queries), m, *item, n, radius, frs_flags(ignore_query_point, batched), WINDOWS[window], _ptr(cq), _ptr(cp),
+                     _ptr(hash_table.workspace), nbytes, _ptr(grad), _stream()), name)
     return grad
 
 
@@ -2428,80 +2430,21 @@ def _window_sum_backward_pairs(points, queries, radius, window, ignore_query_poi
     return gp, gq
 
 
-def _window_sum_batched_impl(points, queries, radius, window, ignore_query_point, hash_table, p_splits, q_splits, want_max):
-    """dmcf_frs_window_sum_batched -> (out, item_max or None, the batched structure over ``points``, the queries' device splits)."""
-    L = _lib.lib()
-    (p_host, p_dev), (q_host, q_dev) = p_splits, q_splits
-    n, m, batch = points.shape[0], queries.shape[0], len(p_host) - 1
-    dev = points.device
-    hash_table = _batched_table(points, radius, m, p_host, p_dev, hash_table)
-    nbytes = L.dmcf_frs_workspace_bytes_batched(n, hash_table.n_queries_capacity, batch)
-    q_rs = _row_splits_on(q_host, q_dev, dev)
-    out = torch.empty(m, dtype=torch.float32, device=dev)
-    item_max = torch.empty(batch, dtype=torch.float32, device=dev) if want_max else None
-    flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
-    t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_frs_window_sum_batched(_ptr(queries), m, _ptr(q_rs), batch, n, radius, flags, WINDOWS[window],
-                                             _ptr(hash_table.workspace), nbytes, _ptr(out), _ptr(item_max), _stream()),
-               "dmcf_frs_window_sum_batched")
-    if timer is not None:
-        timer.end("frs_window_sum_batched", dict(n_points=n, n_queries=m, batch=batch), t0)
-    return out, item_max, hash_table, q_rs
-
-
-def window_sum_backward_batched(queries, queries_row_splits, hash_table, radius, window, coef_queries=None, coef_points=None,
-                                ignore_query_point=False):
-    """dmcf_frs_window_sum_backward_batched on the batched structure ``hash_table`` of some concatenated point sets:
-    ``window_sum_backward`` with the sums of a query running over the points of its own item.  ``queries_row_splits``: as for
-    the batched search, with as many items as the structure."""
-    L = _lib.lib()
-    if hash_table.row_splits is None:
-        raise ValueError("hash_table is not a batched structure (build_spatial_hash_table(..., points_row_splits=...))")
-    q_host, q_dev = _host_row_splits(queries_row_splits, "queries_row_splits")
-    _check_row_splits(q_host, queries.shape[0], "queries_row_splits")
-    if len(q_host) != len(hash_table.row_splits):
-        raise ValueError("queries_row_splits and the structure's row splits must have equal lengths (batch + 1)")
-    queries = _dev_f32(queries, "queries", 3)
-    radius = float(radius)
-    if window not in WINDOWS:
-        raise NotImplementedError(f"window {window!r}")
-    n, m, batch = hash_table.points.shape[0], queries.shape[0], len(q_host) - 1
-    if hash_table.n_queries_capacity < m or hash_table.radius != radius:
-        raise ValueError("hash_table was built for fewer queries or another radius")
-    dev = queries.device
-    cq = None if coef_queries is None else _dev_exact(coef_queries, "coef_queries", torch.float32, (m,), dev)
-    cp = None if coef_points is None else _dev_exact(coef_points, "coef_points", torch.float32, (n,), dev)
-    q_rs = _row_splits_on(q_host, q_dev, dev)
-    nbytes = L.dmcf_frs_workspace_bytes_batched(n, hash_table.n_queries_capacity, batch)
-    grad = torch.empty((m, 3), dtype=torch.float32, device=dev)
-    _lib.check(L.dmcf_frs_window_sum_backward_batched(_ptr(queries), m, _ptr(q_rs), batch, n, radius,
-                                                      FRS_IGNORE_QUERY_POINT if ignore_query_point else 0, WINDOWS[window],
-                                                      _ptr(cq), _ptr(cp), _ptr(hash_table.workspace), nbytes, _ptr(grad), _stream()),
-               "dmcf_frs_window_sum_backward_batched")
-    return grad
-
-
 class WindowSumFunction(torch.autograd.Function):
     """Autograd node of ``window_sum``: the gradient w.r.t. both position sets through dmcf_frs_window_sum_backward -- the
     forward's structure serves the query side, one built over the queries the point side; ``same``: the two sets are one tensor
     and one scan with both coefficients gives the whole gradient (returned for ``points``).
 
     ``batched`` (None, or ((points splits), (queries splits), return_item_max) with each splits a (host, dev) pair): the same
-    on batched structures (dmcf_frs_window_sum_batched / _backward_batched); the point side then takes a batched structure
-    over the queries with the roles of the two row splits swapped.  With return_item_max the node returns (out, item_max),
-    item_max non-differentiable."""
+    on batched structures (dmcf_frs_window_sum_batched / dmcf_frs_window_sum_backward_batched); the point side then takes a
+    batched structure over the queries with the roles of the two row splits swapped.  With return_item_max the node returns
+    (out, item_max), item_max non-differentiable."""
 
     @staticmethod
     def forward(ctx, points, queries, radius, window, ignore_query_point, hash_table, same, batched=None):
         ctx.batched = batched
-        item_max = None
-        if batched is None:
-            out, table = _window_sum_impl(points, queries, radius, window, ignore_query_point, hash_table)
-            flags = frs_flags(ignore_query_point)
-        else:
-            out, item_max, table, ctx.q_rs = _window_sum_batched_impl(points, queries, radius, window, ignore_query_point, hash_table,
-                                                                      batched[0], batched[1], batched[2])
-            flags = FRS_IGNORE_QUERY_POINT if ignore_query_point else 0
+        flags = frs_flags(ignore_query_point, batched is not None)
+        out, item_max, table, ctx.q_rs = _window_sum_impl(points, queries, radius, window, flags, hash_table, batched)
         if window is None:
             ctx.mark_non_differentiable(out)  # (the count)
         ctx.save_for_backward(points, queries)
@@ -2521,39 +2464,27 @@ class WindowSumFunction(torch.autograd.Function):
             return (None, None) + rest
         g = grad_out.contiguous()
         n, m = points.shape[0], queries.shape[0]
+        p_splits = q_splits = None
         if ctx.batched is not None:
-            if n == 0 or m == 0:  # no pair
-                return (torch.zeros_like(points) if need_p else None, torch.zeros_like(queries) if need_q else None) + rest
             (p_host, _), (q_host, _), _ = ctx.batched
-            q_splits = RowSplits(q_host, ctx.q_rs)
-            if ctx.same:
-                return (window_sum_backward_batched(queries, q_splits, ctx.table, ctx.radius, ctx.window, g, g, ctx.ignore),
-                        None) + rest
-            gp = gq = None
-            if need_q:
-                gq = window_sum_backward_batched(queries, q_splits, ctx.table, ctx.radius, ctx.window, g, None, ctx.ignore)
-            if need_p:
-                swapped = build_spatial_hash_table(queries, ctx.radius, n_queries=n, points_row_splits=q_splits)
-                gp = window_sum_backward_batched(points, RowSplits(p_host, ctx.table.row_splits_dev), swapped, ctx.radius, ctx.window,
-                                                 None, g, ctx.ignore)
-            return (gp, gq) + rest
-        if frs_flags(ctx.ignore) != ctx.flags:
+            p_splits, q_splits = RowSplits(p_host, ctx.table.row_splits_dev), RowSplits(q_host, ctx.q_rs)
+        elif frs_flags(ctx.ignore) != ctx.flags:
             raise RuntimeError("DMCF_FRS_SET changed between the forward and the backward of window_sum")
         if n == 0 or m == 0:  # no pair
             return (torch.zeros_like(points) if need_p else None, torch.zeros_like(queries) if need_q else None) + rest
-        if search_set() != "distance":
+        if ctx.batched is None and search_set() != "distance":
             gp, gq = _window_sum_backward_pairs(points, queries, ctx.radius, ctx.window, ctx.ignore, g, need_p, need_q)
             if ctx.same:
                 gp, gq = gp + gq, None
             return (gp, gq) + rest
         if ctx.same:
-            return (window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, g, ctx.ignore), None) + rest
+            return (window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, g, ctx.ignore, q_splits), None) + rest
         gp = gq = None
         if need_q:
-            gq = window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, None, ctx.ignore)
-        if need_p:
-            swapped = build_spatial_hash_table(queries, ctx.radius, n_queries=n)
-            gp = window_sum_backward(points, swapped, ctx.radius, ctx.window, None, g, ctx.ignore)
+            gq = window_sum_backward(queries, ctx.table, ctx.radius, ctx.window, g, None, ctx.ignore, q_splits)
+        if need_p:  # (the roles swapped: a structure over the queries, with their row splits)
+            swapped = build_spatial_hash_table(queries, ctx.radius, n_queries=n, points_row_splits=q_splits)
+            gp = window_sum_backward(points, swapped, ctx.radius, ctx.window, None, g, ctx.ignore, p_splits)
         return (gp, gq) + rest
 
 
@@ -2570,9 +2501,13 @@ def window_sum(points, queries, radius, window=None, ignore_query_point=False, h
 
     ``points_row_splits`` / ``queries_row_splits`` (both or neither; the rules of the batched ``fixed_radius_search``): the sums
     of a BATCH of point sets in one call (dmcf_frs_window_sum_batched), a query summing over the points of its own item only.
-    A batched ``hash_table`` built with the same splits is reused.  ``return_item_max=True`` returns ``(out, item_max)`` with
+    A batched ``hash_table`` built with the same splits is reused (as everywhere, a table that does not serve the call -- other
+    points, radius or splits, too few queries, a batched one without row splits -- is replaced by a new one).
+    ``return_item_max=True`` returns ``(out, item_max)`` with
     ``item_max`` [batch] each item's largest sum (0 for an item without queries; not differentiable; not with 'cubic_grad',
     whose sums can be negative).  It needs row splits: pass ``[0, n]`` and ``[0, m]`` for one item."""
+    batched = None
+    same = points is queries
     if points_row_splits is not None or queries_row_splits is not None:
         # host checks first, in the order of the batched search: both or neither, no walk emulation, well-formed splits
         if points_row_splits is None or queries_row_splits is None:
@@ -2582,30 +2517,23 @@ def window_sum(points, queries, radius, window=None, ignore_query_point=False, h
         if window not in WINDOWS:
             raise NotImplementedError(f"window {window!r}")
         p_splits, q_splits = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
-        same = points is queries
         if same and p_splits[0] != q_splits[0]:
             raise ValueError("points is queries, but points_row_splits and queries_row_splits differ")
-        points = _dev_f32(points, "points", 3)
-        queries = points if same else _dev_f32(queries, "queries", 3)
-        radius = float(radius)
-        if not radius > 0:
-            raise ValueError("radius must be positive")
         batched = (p_splits, q_splits, bool(return_item_max))
-        if _wants_grad(points, queries):
-            return WindowSumFunction.apply(points, queries, radius, window, bool(ignore_query_point), hash_table, same, batched)
-        out, item_max = _window_sum_batched_impl(points, queries, radius, window, ignore_query_point, hash_table, *batched)[:2]
-        return (out, item_max) if return_item_max else out
-    if return_item_max:
+    elif return_item_max:
         raise NotImplementedError("return_item_max needs points_row_splits and queries_row_splits")
-    same = points is queries
     points = _dev_f32(points, "points", 3)
     queries = points if same else _dev_f32(queries, "queries", 3)
     radius = float(radius)
+    if batched is not None and not radius > 0:
+        raise ValueError("radius must be positive")
     if window not in WINDOWS:
         raise NotImplementedError(f"window {window!r}")
     if _wants_grad(points, queries):
-        return WindowSumFunction.apply(points, queries, radius, window, bool(ignore_query_point), hash_table, same)
-    return _window_sum_impl(points, queries, radius, window, ignore_query_point, hash_table)[0]
+        return WindowSumFunction.apply(points, queries, radius, window, bool(ignore_query_point), hash_table, same, batched)
+    flags = frs_flags(ignore_query_point, batched is not None)
+    out, item_max = _window_sum_impl(points, queries, radius, window, flags, hash_table, batched)[:2]
+    return (out, item_max) if return_item_max else out
 
 
 def farthest_point_sample(npoint, inp):

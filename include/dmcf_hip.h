@@ -218,6 +218,9 @@ int dmcf_radius_search_write(const float* queries, int64_t n_queries, int64_t n_
  * outermost digit of the cell index (dmcf_amd/csrc/frs.hip); no host round trip in the build.  A structure built here is
  * searched with the *_batched entry points only, with the same n_points, batch and radius, and a workspace of
  * dmcf_frs_workspace_bytes_batched (0 for a negative size or a batch outside [1, 2^26]).
+ * A single point set is a batch of one item: the un-batched entry points run the same host code and the same kernels per
+ * phase (the instantiation that takes the item as 0 and reads no row splits), and dmcf_frs_build_batched(points, [0, n])
+ * leaves the bytes of dmcf_frs_build's general path.  The two families keep their own argument validation.
  * flags: DMCF_FRS_IGNORE_QUERY_POINT only.  The DMCF_FRS_OPEN3D_* flags are DMCF_EINVAL, DMCF_FRS_METRIC_LINF is
  * DMCF_EUNSUPPORTED (DMCF_EINVAL in the radius search, as in dmcf_radius_search_count).  Null row splits and a batch outside
  * [1, 2^26] are DMCF_EINVAL.  Arguments are validated before anything is enqueued.  Otherwise every argument is the one of
