@@ -20,6 +20,7 @@ import torch
 
 import oracle
 import cconv_backward_ref as ref
+import primitive_edges_ref as pe
 from cconv_backward_ref import EPS, WORST, PairWeights, conv  # noqa: F401
 
 K_BAR = 256
@@ -484,6 +485,15 @@ def matrix():
                                        ("identity", "linear", False)):
             out.append((f"options-{kernel}-{mapping}-{interp}", kernel, KERNELS[kernel]["name"],
                         dict(shape=shape, cin=cin, cout=cout, mapping=mapping, interp=interp, align=align, n_out=255, seed=3)))
+    # packed filters above the cap of their packer's grid (tests/primitive_edges_ref.py, G): the grid-stride loop of pack_filter /
+    # pack_filter_cls runs a second time.  The smallest 4x4x4 shape each form accepts above 2048 x 256 packed elements; the
+    # antisymmetric form of the same size once (the packers mirror in the same loop)
+    for kernel, shapes in pe.PACKER_CASES.items():
+        for n, (cin, cout) in enumerate(shapes):
+            out.append((f"packer-{kernel}-{cin}", kernel, KERNELS[kernel]["name"],
+                        dict(shape=S444, cin=cin, cout=cout, n_out=33, padded=bool(n % 2), bias=True, seed=2)))
+    out.append(("packer-cls-132-sym", "cls", KERNELS["cls"]["name"],
+                dict(shape=(4, 4, 2), sym_axis=2, cin=132, cout=49, n_out=33, window="peak", dist=True, seed=3)))
     # dmcf_cconv_forward_extents: per-row extents over a factor of 4
     for cin in (3, 9):
         for padded, dist in ((False, False), (True, True)):
@@ -492,7 +502,7 @@ def matrix():
     return out
 
 
-LATTICE_CASES = ("same", "fine_to_coarse", "coarse_same", "coarse_to_fine")
+LATTICE_CASES = ("same", "fine_to_coarse", "coarse_same", "coarse_to_fine", "over_cap")
 
 
 def _lattice(rng, dims, occupancy, voxel, center, step=1):
@@ -524,6 +534,11 @@ def lattice_case(case):
         icell, ipos = _lattice(rng, (12, 11, 10), 0.9, 2 * h, center)
         ocell, opos = icell, ipos
         ivox, ovox = 2 * h, 2 * h
+    elif case == "over_cap":       # R = 10.2 voxels: 4,457 stencil offsets x 256 packed floats, above lat_build_filters' grid cap
+        cin, cout, radius = pe.LAT_OVER_CAP["cin"], pe.LAT_OVER_CAP["cout"], pe.LAT_OVER_CAP["radius"]
+        icell, ipos = _lattice(rng, (14, 12, 13), 0.85, h, center)
+        ocell, opos = icell[:64], ipos[:64]  # (every output sees most of the inputs: few rows keep the float64 reference small)
+        ivox, ovox = h, h
     else:                          # s2 -> s1, R = 0.4: outputs on the finer lattice
         cin, cout, radius = 4, 16, 0.4
         icell, ipos = _lattice(rng, (10, 9, 8), 0.8, h, center, step=2)
