@@ -288,6 +288,7 @@ SYMBOLS = [
     "dmcf_grid_pos_write_batched", "dmcf_points_aabb_batched",
     "dmcf_frs_window_sum_batched", "dmcf_frs_window_sum_backward_batched",
     "dmcf_nn_distance_ragged_workspace_bytes", "dmcf_nn_distance_ragged",
+    "dmcf_emd_ragged_workspace_bytes", "dmcf_emd_ragged",
 ]
 
 
@@ -553,6 +554,12 @@ def lib():
     L.dmcf_nn_distance_ragged.restype = c.c_int
     L.dmcf_nn_distance_ragged.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p,
                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    # the fused EMD over a ragged batch (ABI 2.24): HOST row splits, read by the workspace query too
+    L.dmcf_emd_ragged_workspace_bytes.restype = c.c_size_t
+    L.dmcf_emd_ragged_workspace_bytes.argtypes = [c.c_int64, i64p, c.c_int64, i64p, c.c_int64]
+    L.dmcf_emd_ragged.restype = c.c_int
+    L.dmcf_emd_ragged.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p, c.c_void_p,
+                                  c.c_size_t, c.c_void_p]
     _lib = L
     return L
 

@@ -388,6 +388,212 @@ int approx_match_common(const float* xyz1, const float* xyz2, int64_t b, int64_t
     return check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// the fused EMD over a ragged batch (ABI 2.24): the passes, finish steps and totals of approx_match_item, each ONE launch over
+// the tiles of ALL items, so the number of launches (the 62 of one approx_match_item) does not depend on the batch.  An item keeps the column
+// chunks of its own mt_plan and every sum keeps approx_match_item's order, so cost[b] has dmcf_emd's bits for item b alone.
+// The host writes the tables from the row splits it has validated: a pass tile per (item, row block, column chunk), a row
+// record per (item, row block) for the finish steps, one record per item for the totals.  No kernel reads row splits, and
+// every index lies inside the arrays by construction of the tables.  The state arrays run over the concatenated rows; an
+// item's partials are [nsplit, rows of the item] at its own base.
+// ------------------------------------------------------------------------------------------------------------------
+struct ErTile {          // one workgroup of a pass
+    int32_t row0, rows;  // rows [row0, row0 + rows) of the concatenated row set, 1 <= rows <= kMtThreads
+    int32_t c0, c1;      // the chunk [c0, c1) of the concatenated column set, c0 < c1
+    int64_t pbase;       // part[pbase + lane]: the partial of (this chunk, row0 + lane)
+};
+static_assert(sizeof(ErTile) == 24, "ErTile is packed");
+
+struct ErRows {             // one workgroup of a finish step or of the init
+    int32_t row0, rows;     // as above
+    int32_t stride, nsplit; // the row's partials: part[pbase + j * stride + lane], j < nsplit in split order
+    int64_t pbase;
+    float mult;             // the initial remain of the item's rows on this side (multiL / multiR)
+    int32_t left;           // 1: rows of xyz1 (remainL, costL), 0: rows of xyz2 (remainR)
+};
+static_assert(sizeof(ErRows) == 32, "ErRows is packed");
+
+struct ErItem {
+    int32_t row0, rows;  // the item's rows of xyz1; rows == 0 when either of its sets is empty (cost 0)
+};
+
+template <int MODE>  // kMtSumWeighted (passes A and B) or kMtFused (pass C): the column walk of am_pass_kernel
+__global__ __launch_bounds__(kMtThreads) void er_pass_kernel(const float* __restrict__ rp, const float* __restrict__ cp,
+                                                             const ErTile* __restrict__ tiles, float level,
+                                                             const float* __restrict__ cw, const float* __restrict__ rw,
+                                                             float* __restrict__ part, float* __restrict__ part2) {
+    static_assert(MODE == kMtSumWeighted || MODE == kMtFused, "the ragged form has the fused passes only");
+    __shared__ float4 tile[kMtTile];
+    const ErTile t = tiles[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    const bool live = lane < t.rows;
+    const int64_t row = (int64_t)t.row0 + lane;
+    float x = 0.0f, y = 0.0f, z = 0.0f, rs = 0.0f;
+    if (live) {
+        x = rp[3 * row];
+        y = rp[3 * row + 1];
+        z = rp[3 * row + 2];
+        if (MODE == kMtFused) rs = rw[row];
+    }
+    float sum = 0.0f, sum2 = 0.0f;
+    for (int32_t t0 = t.c0; t0 < t.c1; t0 += kMtTile) {  // (c1 < 2^31 - 1 - kMtTile is checked by the host)
+        const int cnt = t.c1 - t0 < kMtTile ? t.c1 - t0 : kMtTile;
+        __syncthreads();
+        if (lane < cnt) {
+            const int64_t c = (int64_t)t0 + lane;
+            tile[lane] = make_float4(cp[3 * c], cp[3 * c + 1], cp[3 * c + 2], cw[c]);
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < cnt; ++j) {
+            const float4 p = tile[j];
+            const float dx = x - p.x, dy = y - p.y, dz = z - p.z;
+            const float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+            const float e = __expf(level * d2) * p.w;
+            if (MODE == kMtSumWeighted) {
+                sum += e;
+            } else {
+                const float w = e * rs;
+                sum += w;
+                sum2 = fmaf(w, __builtin_amdgcn_sqrtf(d2), sum2);
+            }
+        }
+    }
+    if (live) {
+        part[t.pbase + lane] = sum;
+        if (MODE == kMtFused) part2[t.pbase + lane] = sum2;
+    }
+}
+
+__global__ __launch_bounds__(kMtThreads) void er_init_kernel(const ErRows* __restrict__ recs, float* __restrict__ remainL,
+                                                             float* __restrict__ costL, float* __restrict__ remainR) {
+    const ErRows r = recs[blockIdx.x];
+    if ((int)threadIdx.x >= r.rows) return;
+    const int64_t k = (int64_t)r.row0 + threadIdx.x;
+    if (r.left != 0) {
+        remainL[k] = r.mult;
+        costL[k] = 0.0f;
+    } else {
+        remainR[k] = r.mult;
+    }
+}
+
+// the three finish steps, with the sums and expressions of am_finish_a / b / c_kernel
+__global__ __launch_bounds__(kMtThreads) void er_finish_a_kernel(const ErRows* __restrict__ recs, const float* __restrict__ part,
+                                                                 const float* __restrict__ remainL, float* __restrict__ ratioL) {
+    const ErRows r = recs[blockIdx.x];
+    if ((int)threadIdx.x >= r.rows) return;
+    const int64_t k = (int64_t)r.row0 + threadIdx.x;
+    const float* p = part + r.pbase + threadIdx.x;
+    float s = 1e-9f;
+    for (int32_t j = 0; j < r.nsplit; ++j) s += p[(int64_t)j * r.stride];
+    ratioL[k] = remainL[k] / s;
+}
+
+__global__ __launch_bounds__(kMtThreads) void er_finish_b_kernel(const ErRows* __restrict__ recs, const float* __restrict__ part,
+                                                                 float* __restrict__ remainR, float* __restrict__ ratioR) {
+    const ErRows r = recs[blockIdx.x];
+    if ((int)threadIdx.x >= r.rows) return;
+    const int64_t l = (int64_t)r.row0 + threadIdx.x;
+    const float* p = part + r.pbase + threadIdx.x;
+    float s = 0.0f;
+    for (int32_t j = 0; j < r.nsplit; ++j) s += p[(int64_t)j * r.stride];
+    const float rr = remainR[l];
+    s *= rr;
+    ratioR[l] = fminf(rr / (s + 1e-9f), 1.0f) * rr;
+    remainR[l] = fmaxf(0.0f, rr - s);
+}
+
+__global__ __launch_bounds__(kMtThreads) void er_finish_c_kernel(const ErRows* __restrict__ recs, const float* __restrict__ part,
+                                                                 const float* __restrict__ part2, float* __restrict__ remainL,
+                                                                 float* __restrict__ costL) {
+    const ErRows r = recs[blockIdx.x];
+    if ((int)threadIdx.x >= r.rows) return;
+    const int64_t k = (int64_t)r.row0 + threadIdx.x;
+    const float* p = part + r.pbase + threadIdx.x;
+    const float* p2 = part2 + r.pbase + threadIdx.x;
+    float s = 0.0f, c = 0.0f;
+    for (int32_t j = 0; j < r.nsplit; ++j) s += p[(int64_t)j * r.stride];
+    remainL[k] = fmaxf(0.0f, remainL[k] - s);
+    for (int32_t j = 0; j < r.nsplit; ++j) c += p2[(int64_t)j * r.stride];
+    costL[k] += c;
+}
+
+// cost[b] = the sum of the item's costL in am_total_kernel's order (strided per lane, then a tree); one workgroup per item
+__global__ __launch_bounds__(kMtThreads) void er_total_kernel(const ErItem* __restrict__ items, const float* __restrict__ costL,
+                                                              float* __restrict__ cost) {
+    __shared__ float red[kMtThreads];
+    const ErItem it = items[blockIdx.x];
+    const float* c = costL + it.row0;
+    float s = 0.0f;
+    for (int32_t k = (int32_t)threadIdx.x; k < it.rows; k += kMtThreads) s += c[k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kMtThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) cost[blockIdx.x] = red[0];
+}
+
+// what the validated splits ask of the workspace: the tables' record counts and the partials of every item's plan
+struct ErSizes {
+    int64_t tiles_a = 0, tiles_b = 0;  // pass tiles with rows of xyz1 (passes A and C) / of xyz2 (pass B)
+    int64_t rows_a = 0, rows_b = 0;    // row records of xyz1 / xyz2
+    int64_t part_a = 0, part_b = 0;    // floats of partials: sum of nsplit * rows over the items
+};
+
+inline ErSizes er_sizes(const int64_t* rs1, const int64_t* rs2, int64_t batch) {
+    ErSizes z;
+    for (int64_t b = 0; b < batch; ++b) {
+        const int64_t n = rs1[b + 1] - rs1[b], m = rs2[b + 1] - rs2[b];
+        if (n == 0 || m == 0) continue;
+        const MtPlan pa = mt_plan(n, m), pb = mt_plan(m, n);
+        z.tiles_a += pa.row_blocks * pa.nsplit;
+        z.tiles_b += pb.row_blocks * pb.nsplit;
+        z.rows_a += pa.row_blocks;
+        z.rows_b += pb.row_blocks;
+        z.part_a += pa.nsplit * n;
+        z.part_b += pb.nsplit * m;
+    }
+    return z;
+}
+
+// the tables of dmcf_emd_ragged, one block at the start of its workspace (one copy from the host's block of the same layout)
+struct ErTables {
+    ErTile *ta, *tb;
+    ErRows *ra, *rb;  // (adjacent: the init walks them as one array)
+    ErItem* items;
+};
+
+inline size_t er_tables(const ErSizes& z, int64_t batch, char* base, ErTables* t) {
+    const size_t at_tb = (size_t)z.tiles_a * sizeof(ErTile), at_ra = at_tb + (size_t)z.tiles_b * sizeof(ErTile);
+    const size_t at_rb = at_ra + (size_t)z.rows_a * sizeof(ErRows), at_items = at_rb + (size_t)z.rows_b * sizeof(ErRows);
+    if (base != nullptr) *t = ErTables{(ErTile*)base, (ErTile*)(base + at_tb), (ErRows*)(base + at_ra), (ErRows*)(base + at_rb),
+                                       (ErItem*)(base + at_items)};
+    return at_items + (size_t)batch * sizeof(ErItem);
+}
+
+// the rest of the workspace, from `off` on: the state arrays over the concatenated rows and the partials
+inline size_t er_carve(const ErSizes& z, int64_t n_total, int64_t m_total, size_t off, char* base, AmWork* w) {
+    const int64_t sizes[7] = {n_total, n_total, n_total, m_total, m_total, z.part_a > z.part_b ? z.part_a : z.part_b, z.part_a};
+    float** dst[7] = {&w->remainL, &w->ratioL, &w->costL, &w->remainR, &w->ratioR, &w->part, &w->part2};
+    off = align_up(off, 256);
+    for (int i = 0; i < 7; ++i) {
+        if (base != nullptr) *dst[i] = (float*)(base + off);
+        off += align_up((size_t)(sizes[i] > 0 ? sizes[i] : 1) * sizeof(float), 256);
+    }
+    return off;
+}
+
+// the argument checks dmcf_emd_ragged and its workspace query share (no pointer but the splits is looked at)
+inline bool er_valid(int64_t n_total, const int64_t* rs1, int64_t m_total, const int64_t* rs2, int64_t batch) {
+    if (batch < 1 || batch > kNrMaxBatch || n_total < 0 || m_total < 0) return false;
+    if (n_total >= INT32_MAX - kMtTile || m_total >= INT32_MAX - kMtTile) return false;  // (int32 indices)
+    if (rs1 == nullptr || rs2 == nullptr) return false;
+    return valid_row_splits(rs1, batch, n_total) && valid_row_splits(rs2, batch, m_total);
+}
+
 }  // namespace dmcf
 
 using namespace dmcf;
@@ -496,6 +702,80 @@ int dmcf_emd(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t
              float* cost, void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
     if (cost == nullptr) return DMCF_EINVAL;
     return approx_match_common(xyz1, xyz2, b, n, m, count1, count2, nullptr, cost, workspace, workspace_bytes, stream);
+}
+
+size_t dmcf_emd_ragged_workspace_bytes(int64_t n_total, const int64_t* row_splits1, int64_t m_total, const int64_t* row_splits2,
+                                       int64_t batch) {
+    if (!er_valid(n_total, row_splits1, m_total, row_splits2, batch)) return 0;
+    const ErSizes z = er_sizes(row_splits1, row_splits2, batch);
+    if (z.tiles_a > INT32_MAX || z.tiles_b > INT32_MAX) return 0;
+    AmWork w;
+    return er_carve(z, n_total, m_total, er_tables(z, batch, nullptr, nullptr), nullptr, &w);
+}
+
+int dmcf_emd_ragged(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                    const int64_t* row_splits2, int64_t batch, float* cost, void* workspace, size_t workspace_bytes,
+                    dmcf_stream_t stream) {
+    if (batch == 0) return n_total == 0 && m_total == 0 ? DMCF_OK : DMCF_EINVAL;
+    if (!er_valid(n_total, row_splits1, m_total, row_splits2, batch)) return DMCF_EINVAL;
+    if (n_total == 0 && m_total == 0) return DMCF_OK;  // (every item empty on both sides: nothing enqueued)
+    if (cost == nullptr || workspace == nullptr || (xyz1 == nullptr && n_total > 0) || (xyz2 == nullptr && m_total > 0))
+        return DMCF_EINVAL;
+    const ErSizes z = er_sizes(row_splits1, row_splits2, batch);
+    if (z.tiles_a > INT32_MAX || z.tiles_b > INT32_MAX) return DMCF_EINVAL;  // (one workgroup per tile)
+    ErTables d, h;  // the tables in the workspace and on the host
+    AmWork w;
+    const size_t table_bytes = er_tables(z, batch, (char*)workspace, &d);
+    if (workspace_bytes < er_carve(z, n_total, m_total, table_bytes, (char*)workspace, &w)) return DMCF_EWORKSPACE;
+    std::vector<char> table(table_bytes);
+    er_tables(z, batch, table.data(), &h);
+    int64_t na = 0, nb = 0, ra = 0, rb = 0, off_a = 0, off_b = 0;
+    for (int64_t b = 0; b < batch; ++b) {
+        const int64_t n = row_splits1[b + 1] - row_splits1[b], m = row_splits2[b + 1] - row_splits2[b];
+        if (n == 0 || m == 0) {  // nothing to match: cost 0
+            h.items[b] = ErItem{0, 0};
+            continue;
+        }
+        h.items[b] = ErItem{(int32_t)row_splits1[b], (int32_t)n};
+        for (int side = 0; side < 2; ++side) {  // 0: rows of xyz1 over the item's xyz2 (passes A and C); 1: the reverse (pass B)
+            const int64_t rows = side == 0 ? n : m, cols = side == 0 ? m : n;
+            const int64_t r0 = side == 0 ? row_splits1[b] : row_splits2[b], c0 = side == 0 ? row_splits2[b] : row_splits1[b];
+            const MtPlan p = mt_plan(rows, cols);
+            // the multipliers of approx_match_item: 1 on the larger side, the integer quotient on the smaller
+            const float mult = side == 0 ? (n >= m ? 1.0f : (float)(m / n)) : (n >= m ? (float)(n / m) : 1.0f);
+            int64_t& off = side == 0 ? off_a : off_b;
+            for (int64_t k = 0; k < p.row_blocks; ++k) {
+                const int64_t first = k * kMtThreads, cnt = rows - first < kMtThreads ? rows - first : kMtThreads;
+                (side == 0 ? h.ra[ra++] : h.rb[rb++]) =
+                    ErRows{(int32_t)(r0 + first), (int32_t)cnt, (int32_t)rows, (int32_t)p.nsplit, off + first, mult, side == 0};
+                for (int64_t s = 0; s < p.nsplit; ++s) {
+                    const int64_t a = s * p.chunk, e = a + p.chunk < cols ? a + p.chunk : cols;
+                    (side == 0 ? h.ta[na++] : h.tb[nb++]) =
+                        ErTile{(int32_t)(r0 + first), (int32_t)cnt, (int32_t)(c0 + a), (int32_t)(c0 + e), off + s * rows + first};
+                }
+            }
+            off += p.nsplit * rows;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // (pageable host memory: the call returns once the tables have left `table`)
+    if (hipMemcpyAsync(workspace, table.data(), table.size(), hipMemcpyHostToDevice, st) != hipSuccess) return check_launch();
+    // 2 + 6 kAmLevels launches whatever the batch: each one covers the tiles or rows of every item
+    if (z.tiles_a > 0) {
+        const unsigned ga = (unsigned)z.tiles_a, gb = (unsigned)z.tiles_b, fa = (unsigned)z.rows_a, fb = (unsigned)z.rows_b;
+        er_init_kernel<<<fa + fb, kMtThreads, 0, st>>>(d.ra, w.remainL, w.costL, w.remainR);
+        for (int L = 0; L < kAmLevels; ++L) {
+            const float level = am_level(L);
+            er_pass_kernel<kMtSumWeighted><<<ga, kMtThreads, 0, st>>>(xyz1, xyz2, d.ta, level, w.remainR, nullptr, w.part, nullptr);
+            er_finish_a_kernel<<<fa, kMtThreads, 0, st>>>(d.ra, w.part, w.remainL, w.ratioL);
+            er_pass_kernel<kMtSumWeighted><<<gb, kMtThreads, 0, st>>>(xyz2, xyz1, d.tb, level, w.ratioL, nullptr, w.part, nullptr);
+            er_finish_b_kernel<<<fb, kMtThreads, 0, st>>>(d.rb, w.part, w.remainR, w.ratioR);
+            er_pass_kernel<kMtFused><<<ga, kMtThreads, 0, st>>>(xyz1, xyz2, d.ta, level, w.ratioR, w.ratioL, w.part, w.part2);
+            er_finish_c_kernel<<<fa, kMtThreads, 0, st>>>(d.ra, w.part, w.part2, w.remainL, w.costL);
+        }
+    }
+    er_total_kernel<<<(unsigned)batch, kMtThreads, 0, st>>>(d.items, w.costL, cost);
+    return check_launch();
 }
 
 int dmcf_emd_with_levels(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,

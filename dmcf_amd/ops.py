@@ -2994,11 +2994,66 @@ class EmdFunction(torch.autograd.Function):
         return gx1, gx2, None, None
 
 
-def emd(xyz1, xyz2, n=None, m=None):
+def emd_row_splits(shape1, shape2, row_splits1, row_splits2, wants_grad=False):
+    """The host-side checks of emd with row splits on the shapes of the two point sets, all of them before a device is
+    touched, in the order of the other batched ops: both or neither and no gradient (NotImplementedError), then [n_total, 2|3]
+    sets, well-formed splits and equal batch sizes (ValueError).  Unlike nn_distance, an item with an empty set is legal.
+    -> (host splits 1, host splits 2)."""
+    if row_splits1 is None or row_splits2 is None:
+        raise NotImplementedError("batched emd needs both row_splits1 and row_splits2")
+    if wants_grad:
+        raise NotImplementedError("batched emd has no backward: call it under no_grad, or per item without row splits")
+    for shape, name in ((shape1, "xyz1"), (shape2, "xyz2")):
+        if len(shape) != 2 or shape[-1] not in (2, 3):
+            raise ValueError(f"{name} must have shape [n_total, 3] or [n_total, 2] with row splits, got {tuple(shape)}")
+    s1 = _host_row_splits(row_splits1, "row_splits1")[0]
+    s2 = _host_row_splits(row_splits2, "row_splits2")[0]
+    _check_row_splits(s1, shape1[0], "row_splits1")
+    _check_row_splits(s2, shape2[0], "row_splits2")
+    if len(s1) != len(s2):
+        raise ValueError(f"row_splits1 and row_splits2 must have equal lengths (batch + 1), got {len(s1)} and {len(s2)}")
+    return s1, s2
+
+
+def emd_ragged(xyz1, xyz2, row_splits1, row_splits2):
+    """emd over a RAGGED batch in one call (dmcf_emd_ragged: 62 launches whatever the batch): xyz1 [n_total, 3|2] and xyz2
+    [m_total, 3|2] float32 GPU tensors, item b being xyz1[rs1[b]:rs1[b + 1]] against xyz2[rs2[b]:rs2[b + 1]]; the splits a
+    sequence, a CPU or device int64 tensor or a :class:`RowSplits`.  -> cost [batch], every entry with the bits of
+    ``emd(xyz1_b[None], xyz2_b[None])[0]``; an item with an empty set costs 0.  No gradient."""
+    for t, name in ((xyz1, "xyz1"), (xyz2, "xyz2")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor")
+    s1, s2 = emd_row_splits(xyz1.shape, xyz2.shape, row_splits1, row_splits2, _wants_grad(xyz1, xyz2))
+    batch = len(s1) - 1
+    a, _ = _point_batch(xyz1, "xyz1")
+    b, _ = _point_batch(xyz2, "xyz2")
+    if a.device != b.device:
+        raise ValueError("xyz1 and xyz2 must be on the same device")
+    n, m, dev = a.shape[1], b.shape[1], a.device
+    if n == 0 and m == 0:  # (every item empty: the library enqueues nothing and leaves cost alone)
+        return torch.zeros(batch, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    cost = torch.empty(batch, dtype=torch.float32, device=dev)
+    h1, h2 = (ctypes.c_int64 * (batch + 1))(*s1), (ctypes.c_int64 * (batch + 1))(*s2)
+    nbytes = int(L.dmcf_emd_ragged_workspace_bytes(n, h1, m, h2, batch))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _lib.check(L.dmcf_emd_ragged(_ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(cost), _ptr(ws), nbytes, _stream()), "dmcf_emd_ragged")
+    return cost
+
+
+def emd(xyz1, xyz2, n=None, m=None, row_splits1=None, row_splits2=None):
     """``match_cost(xyz1, xyz2, approx_match(xyz1, xyz2, n, m))`` without forming the match (dmcf_emd): cost [b] in O(n + m)
     memory.  Same arguments as :func:`approx_match`.  Differentiable in xyz1 and xyz2 with the match held constant
     (dmcf_emd_backward); only then, when grad mode is on and an input requires grad, does the forward record the ratios of
-    every level (dmcf_emd_with_levels, 40 (n + m) bytes per item more, same cost bits)."""
+    every level (dmcf_emd_with_levels, 40 (n + m) bytes per item more, same cost bits).
+
+    ``row_splits1`` / ``row_splits2`` (both or neither, and then no ``n`` / ``m``): a RAGGED batch in one call
+    (:func:`emd_ragged`), xyz1 [n_total, 3] and xyz2 [m_total, 3]; cost [batch] equals the call on every item alone bit for
+    bit.  No gradient: inputs that require grad raise NotImplementedError."""
+    if row_splits1 is not None or row_splits2 is not None:
+        if row_splits1 is not None and row_splits2 is not None and (n is not None or m is not None):
+            raise ValueError("emd takes row splits or the point counts n / m of a padded batch, not both")
+        return emd_ragged(xyz1, xyz2, row_splits1, row_splits2)  # (one split alone: its NotImplementedError)
     a, b, batched = _pair_batch(xyz1, xyz2)
     nb, nn_, mm = a.shape[0], a.shape[1], b.shape[1]
     c1, c2 = _host_counts(n, nb, nn_, "n"), _host_counts(m, nb, mm, "m")

@@ -462,8 +462,9 @@ class Simulator:
         density_loss calls for ``dens_val`` / ``max_dens_val`` (the reference's argument orders kept); ONE model.step_batched
         from the targets' frames t - 1 for ``mse_single_val``.  The per-point arrays reach the host in one copy per frame, and
         the per-scene means are np.mean over the same float32 arrays as in the loop: they equal the loop's bit for bit
-        wherever the device arrays do.  ``emd`` and the two ``vel_diff_val*`` stay per scene on the loop's code (the dense
-        EMD's split plan depends on the batch size)."""
+        wherever the device arrays do.  ``emd`` is ONE emd_loss call with row splits (dmcf_emd_ragged: every scene's cost has
+        the bits of the loop's per-scene call), its [scenes] result travelling in the same host copy.  The two
+        ``vel_diff_val*`` stay per scene on the loop's code."""
         from ..utils.evaluation_helper import compare_dist, distance
         from ..utils.tools.losses import density_loss, emd_loss, get_window_func
         cfg, model, dev = self.cfg, self.model, self._to_device
@@ -500,7 +501,7 @@ class Simulator:
                 dens = density_loss(tgt, pos, pos_in, tgt_in, win=get_window_func("poly6"), row_splits=rs, in_row_splits=in_rs)
                 max_dens = density_loss(pos, tgt, pos_in, tgt_in, radius=model.particle_radii[0],
                                         win=get_window_func(model.window_dens), use_max=True, row_splits=rs, in_row_splits=in_rs)
-                parts += [torch.sqrt(d_tgt), dens, max_dens]
+                parts += [torch.sqrt(d_tgt), dens, max_dens, emd_loss(tgt, pos, true_row_splits=trs, pred_row_splits=rs)]
             # mse for a single step only: one batched model step from the targets' previous frames
             items = [[dev(valid_data[i]["pos"][t - 1]), dev(valid_data[i]["vel"][t - 1])] + list(results[i][t][2:]) for i in scenes]
             pos_sub, _, srs = model.step_batched(items, training=False)
@@ -509,7 +510,7 @@ class Simulator:
             chunks = np.split(host, np.cumsum([int(x.numel()) for x in parts])[:-1])
             pos_h, cham, sub_h = chunks[0].reshape(n, 3), chunks[1], chunks[-1].reshape(srs[-1], 3)
             if full:
-                cham2, dens_h, max_dens_h = chunks[2:5]
+                cham2, dens_h, max_dens_h, emd_h = chunks[2:6]
             for k, i in enumerate(scenes):
                 data = valid_data[i]
                 a, b = rs[k], rs[k + 1]
@@ -520,8 +521,7 @@ class Simulator:
                     loss["dens_val"] = float(dens_h[k])
                     loss["max_dens_val"] = float(max_dens_h[k])
                     loss["chamfer_val_2"] = float(np.mean(cham2[trs[k]:trs[k + 1]].astype(np.float32)))
-                    loss["emd"] = float(np.mean(emd_loss(tgt[trs[k]:trs[k + 1]].unsqueeze(0), pos[a:b].unsqueeze(0))
-                                                .cpu().numpy().astype(np.float32)))
+                    loss["emd"] = float(emd_h[k])
                     vel = results[i][t][1]
                     loss["vel_diff_val"] = compare_dist(data["vel"][t], vel)
                     loss["vel_diff_val_2"] = compare_dist(vel, data["vel"][t])

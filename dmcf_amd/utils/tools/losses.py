@@ -9,7 +9,8 @@
   compute_pressure  losses.py:367-377  Tait-style pressure from the density
   density_loss      losses.py:380-398  validation metric of pipelines/simulator.py:227-243
   emd_loss          losses.py:401-409  approximate-match EMD per batch item (ops.emd; differentiable in both sets with the
-                                       match held constant, dmcf_emd_backward)
+                                       match held constant, dmcf_emd_backward; with row splits a ragged batch in one
+                                       call, dmcf_emd_ragged, no gradient)
 
   get_loss          losses.py:47-110   the training losses mse / weighted_mse / vel / weighted_vel / momentum
   get_optimizer     models/pbf_model.py:508-517  Adam (eps 1e-6), piecewise-constant learning rate (torch.optim.Adam)
@@ -388,12 +389,22 @@ def density_loss(gt, pred, gt_in=None, pred_in=None, radius=0.005, eps=0.01, win
     return torch.relu(pred_dens - rest_dens - eps).mean()
 
 
-def emd_loss(y_true, y_pred, n=None, m=None):
+def emd_loss(y_true, y_pred, n=None, m=None, true_row_splits=None, pred_row_splits=None):
     """losses.py:401-409: ``match_cost(approx_match(y_true, y_pred, n, m)) / max(n, m)`` per batch item, [b].  ``y_true``
     [b, n, 3], ``y_pred`` [b, m, 3] (2-D: z = 0); ``n`` / ``m`` per-batch point counts (None: all points).  Runs the fused
     kernel (ops.emd), which never forms the [b, m, n] match.  Differentiable in ``y_true`` and ``y_pred`` with the match held
-    constant (approx_match has no gradient), through dmcf_emd_backward, which does not form the match either."""
+    constant (approx_match has no gradient), through dmcf_emd_backward, which does not form the match either.
+
+    ``true_row_splits`` / ``pred_row_splits`` (both or neither, and then no ``n`` / ``m``): a RAGGED batch in one call
+    (ops.emd with row splits), ``y_true`` [n_total, 3] and ``y_pred`` [m_total, 3]; -> ``cost / max(n_b, m_b)`` per item,
+    [batch], with the bits of the call on every item alone; an item with both sets empty gives 0.  No gradient."""
     from ... import ops
+    if true_row_splits is not None or pred_row_splits is not None:
+        cost = ops.emd(y_true, y_pred, n, m, row_splits1=true_row_splits, row_splits2=pred_row_splits)
+        s1 = np.asarray(ops._host_row_splits(true_row_splits, "true_row_splits")[0])
+        s2 = np.asarray(ops._host_row_splits(pred_row_splits, "pred_row_splits")[0])
+        denom = np.maximum(np.maximum(np.diff(s1), np.diff(s2)), 1)  # (both sets empty: cost 0 over 1)
+        return cost / torch.from_numpy(denom.astype(np.float32)).to(cost.device)
     b = y_true.shape[0]
     nn_ = ops._host_counts(n, b, y_true.shape[1], "n")
     mm = ops._host_counts(m, b, y_pred.shape[1], "m")

@@ -21,6 +21,8 @@
  *     (pipelines/simulator.py:227-243 inside the warm-up loop)    dmcf_frs_window_sum_backward_batched (ABI 2.22)
  *   nn_distance per scene of a validation split                  dmcf_nn_distance_ragged (ABI 2.23: one call for
  *     (pipelines/simulator.py:222-248, utils/evaluation_helper.py)  scenes of different particle counts)
+ *   emd_loss per scene of a validation split                     dmcf_emd_ragged (ABI 2.24: the same, with
+ *     (pipelines/simulator.py:247-249, utils/tools/losses.py:401-409)  dmcf_emd's bits for every scene)
  *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
  *                                                                 dmcf_cconv_backward_extents)
  *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
@@ -846,6 +848,27 @@ int dmcf_match_cost(const float* xyz1, const float* xyz2, int64_t b, int64_t n, 
 size_t dmcf_emd_workspace_bytes(int64_t b, int64_t n, int64_t m);
 int dmcf_emd(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1, const int32_t* count2,
              float* cost, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* dmcf_emd over a RAGGED batch (ABI 2.24): `batch` items of different sizes in one call, laid out as for
+ * dmcf_nn_distance_ragged -- xyz1 [n_total, 3], xyz2 [m_total, 3], item b being xyz1[row_splits1[b] .. row_splits1[b + 1])
+ * against xyz2[row_splits2[b] .. row_splits2[b + 1]), both row-splits arrays HOST int64 [batch + 1], validated here before
+ * anything is enqueued.  Result contract: cost[b] has exactly the bits dmcf_emd gives for item b alone (b = 1, no counts).
+ * Every item keeps the column chunks of its own split plan, the column order inside a chunk, the split-order sums of the
+ * finish steps, the multipliers (integer division included) and the order of the final sum; what changes is that each pass,
+ * each finish step, the init and the totals are ONE launch over the tiles or rows of all items, so the call enqueues one
+ * table copy and 62 launches whatever the batch (dmcf_emd: 62 per item).  The entry point writes the tables -- a record per
+ * (item, 256 rows, column chunk), per (item, 256 rows) and per item -- from the validated splits and copies them into the
+ * workspace in one asynchronous copy from pageable host memory; no kernel reads row splits, and no float atomics are used.
+ * An item with either set empty costs 0 (as a zero count does in dmcf_emd; dmcf_nn_distance_ragged refuses such an item).
+ * batch == 0 with n_total == m_total == 0: DMCF_OK.  Every item empty on both sides (n_total == m_total == 0): DMCF_OK with
+ * nothing enqueued and no pointer but the splits looked at -- cost is NOT written, the caller holds its zeros.  batch < 0 or
+ * > 2^26, NULL or malformed row splits, n_total or m_total >= 2^31 - 257, NULL cost or workspace, NULL points of a non-empty
+ * set: DMCF_EINVAL.  The workspace holds the tables, five state arrays over the concatenated rows and the partials of every
+ * item's plan, which is why its query takes the splits; the query returns 0 for arguments the call refuses. */
+size_t dmcf_emd_ragged_workspace_bytes(int64_t n_total, const int64_t* row_splits1, int64_t m_total, const int64_t* row_splits2,
+                                       int64_t batch);
+int dmcf_emd_ragged(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                    const int64_t* row_splits2, int64_t batch, float* cost, void* workspace, size_t workspace_bytes,
+                    dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Gradients of the point-cloud ops (ABI 2.13; dmcf_amd/csrc/metrics_bwd.hip): nn_distance (NnDistanceGrad,
