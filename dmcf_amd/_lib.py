@@ -289,6 +289,7 @@ SYMBOLS = [
     "dmcf_frs_window_sum_batched", "dmcf_frs_window_sum_backward_batched",
     "dmcf_nn_distance_ragged_workspace_bytes", "dmcf_nn_distance_ragged",
     "dmcf_emd_ragged_workspace_bytes", "dmcf_emd_ragged",
+    "dmcf_emd_ragged_with_levels", "dmcf_emd_ragged_backward_workspace_bytes", "dmcf_emd_ragged_backward",
 ]
 
 
@@ -560,6 +561,15 @@ def lib():
     L.dmcf_emd_ragged.restype = c.c_int
     L.dmcf_emd_ragged.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p, c.c_void_p,
                                   c.c_size_t, c.c_void_p]
+    # the gradient of the ragged EMD (ABI 2.25): the recording forward, and the backward with its own workspace query
+    L.dmcf_emd_ragged_with_levels.restype = c.c_int
+    L.dmcf_emd_ragged_with_levels.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p,
+                                              c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.dmcf_emd_ragged_backward_workspace_bytes.restype = c.c_size_t
+    L.dmcf_emd_ragged_backward_workspace_bytes.argtypes = [c.c_int64, i64p, c.c_int64, i64p, c.c_int64]
+    L.dmcf_emd_ragged_backward.restype = c.c_int
+    L.dmcf_emd_ragged_backward.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p,
+                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
     _lib = L
     return L
 

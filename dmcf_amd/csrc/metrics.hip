@@ -479,19 +479,24 @@ __global__ __launch_bounds__(kMtThreads) void er_init_kernel(const ErRows* __res
 }
 
 // the three finish steps, with the sums and expressions of am_finish_a / b / c_kernel
+// lv (NULL: not wanted): the level's row of dmcf_emd_ragged_with_levels, which takes a copy of the ratio
 __global__ __launch_bounds__(kMtThreads) void er_finish_a_kernel(const ErRows* __restrict__ recs, const float* __restrict__ part,
-                                                                 const float* __restrict__ remainL, float* __restrict__ ratioL) {
+                                                                 const float* __restrict__ remainL, float* __restrict__ ratioL,
+                                                                 float* __restrict__ lv) {
     const ErRows r = recs[blockIdx.x];
     if ((int)threadIdx.x >= r.rows) return;
     const int64_t k = (int64_t)r.row0 + threadIdx.x;
     const float* p = part + r.pbase + threadIdx.x;
     float s = 1e-9f;
     for (int32_t j = 0; j < r.nsplit; ++j) s += p[(int64_t)j * r.stride];
-    ratioL[k] = remainL[k] / s;
+    const float v = remainL[k] / s;
+    ratioL[k] = v;
+    if (lv != nullptr) lv[k] = v;
 }
 
 __global__ __launch_bounds__(kMtThreads) void er_finish_b_kernel(const ErRows* __restrict__ recs, const float* __restrict__ part,
-                                                                 float* __restrict__ remainR, float* __restrict__ ratioR) {
+                                                                 float* __restrict__ remainR, float* __restrict__ ratioR,
+                                                                 float* __restrict__ lv) {
     const ErRows r = recs[blockIdx.x];
     if ((int)threadIdx.x >= r.rows) return;
     const int64_t l = (int64_t)r.row0 + threadIdx.x;
@@ -500,7 +505,9 @@ __global__ __launch_bounds__(kMtThreads) void er_finish_b_kernel(const ErRows* _
     for (int32_t j = 0; j < r.nsplit; ++j) s += p[(int64_t)j * r.stride];
     const float rr = remainR[l];
     s *= rr;
-    ratioR[l] = fminf(rr / (s + 1e-9f), 1.0f) * rr;
+    const float v = fminf(rr / (s + 1e-9f), 1.0f) * rr;
+    ratioR[l] = v;
+    if (lv != nullptr) lv[l] = v;
     remainR[l] = fmaxf(0.0f, rr - s);
 }
 
@@ -586,12 +593,83 @@ inline size_t er_carve(const ErSizes& z, int64_t n_total, int64_t m_total, size_
     return off;
 }
 
-// the argument checks dmcf_emd_ragged and its workspace query share (no pointer but the splits is looked at)
-inline bool er_valid(int64_t n_total, const int64_t* rs1, int64_t m_total, const int64_t* rs2, int64_t batch) {
+// the argument checks the ragged EMD entry points and their workspace queries share (no pointer but the splits is looked at)
+bool er_valid(int64_t n_total, const int64_t* rs1, int64_t m_total, const int64_t* rs2, int64_t batch) {
     if (batch < 1 || batch > kNrMaxBatch || n_total < 0 || m_total < 0) return false;
     if (n_total >= INT32_MAX - kMtTile || m_total >= INT32_MAX - kMtTile) return false;  // (int32 indices)
     if (rs1 == nullptr || rs2 == nullptr) return false;
     return valid_row_splits(rs1, batch, n_total) && valid_row_splits(rs2, batch, m_total);
+}
+
+// dmcf_emd_ragged, and with `record` dmcf_emd_ragged_with_levels: levels [kAmLevels, n_total + m_total] is zeroed, then every
+// level's finish steps A and B write their ratios into its row as well (rows of items without pairs stay zero)
+int emd_ragged_common(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                      const int64_t* row_splits2, int64_t batch, float* cost, bool record, float* levels, void* workspace,
+                      size_t workspace_bytes, dmcf_stream_t stream) {
+    if (batch == 0) return n_total == 0 && m_total == 0 ? DMCF_OK : DMCF_EINVAL;
+    if (!er_valid(n_total, row_splits1, m_total, row_splits2, batch)) return DMCF_EINVAL;
+    if (n_total == 0 && m_total == 0) return DMCF_OK;  // (every item empty on both sides: nothing enqueued)
+    if (record && levels == nullptr) return DMCF_EINVAL;
+    if (cost == nullptr || workspace == nullptr || (xyz1 == nullptr && n_total > 0) || (xyz2 == nullptr && m_total > 0))
+        return DMCF_EINVAL;
+    const ErSizes z = er_sizes(row_splits1, row_splits2, batch);
+    if (z.tiles_a > INT32_MAX || z.tiles_b > INT32_MAX) return DMCF_EINVAL;  // (one workgroup per tile)
+    ErTables d, h;  // the tables in the workspace and on the host
+    AmWork w;
+    const size_t table_bytes = er_tables(z, batch, (char*)workspace, &d);
+    if (workspace_bytes < er_carve(z, n_total, m_total, table_bytes, (char*)workspace, &w)) return DMCF_EWORKSPACE;
+    std::vector<char> table(table_bytes);
+    er_tables(z, batch, table.data(), &h);
+    int64_t na = 0, nb = 0, ra = 0, rb = 0, off_a = 0, off_b = 0;
+    for (int64_t b = 0; b < batch; ++b) {
+        const int64_t n = row_splits1[b + 1] - row_splits1[b], m = row_splits2[b + 1] - row_splits2[b];
+        if (n == 0 || m == 0) {  // nothing to match: cost 0
+            h.items[b] = ErItem{0, 0};
+            continue;
+        }
+        h.items[b] = ErItem{(int32_t)row_splits1[b], (int32_t)n};
+        for (int side = 0; side < 2; ++side) {  // 0: rows of xyz1 over the item's xyz2 (passes A and C); 1: the reverse (pass B)
+            const int64_t rows = side == 0 ? n : m, cols = side == 0 ? m : n;
+            const int64_t r0 = side == 0 ? row_splits1[b] : row_splits2[b], c0 = side == 0 ? row_splits2[b] : row_splits1[b];
+            const MtPlan p = mt_plan(rows, cols);
+            // the multipliers of approx_match_item: 1 on the larger side, the integer quotient on the smaller
+            const float mult = side == 0 ? (n >= m ? 1.0f : (float)(m / n)) : (n >= m ? (float)(n / m) : 1.0f);
+            int64_t& off = side == 0 ? off_a : off_b;
+            for (int64_t k = 0; k < p.row_blocks; ++k) {
+                const int64_t first = k * kMtThreads, cnt = rows - first < kMtThreads ? rows - first : kMtThreads;
+                (side == 0 ? h.ra[ra++] : h.rb[rb++]) =
+                    ErRows{(int32_t)(r0 + first), (int32_t)cnt, (int32_t)rows, (int32_t)p.nsplit, off + first, mult, side == 0};
+                for (int64_t s = 0; s < p.nsplit; ++s) {
+                    const int64_t a = s * p.chunk, e = a + p.chunk < cols ? a + p.chunk : cols;
+                    (side == 0 ? h.ta[na++] : h.tb[nb++]) =
+                        ErTile{(int32_t)(r0 + first), (int32_t)cnt, (int32_t)(c0 + a), (int32_t)(c0 + e), off + s * rows + first};
+                }
+            }
+            off += p.nsplit * rows;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // (pageable host memory: the call returns once the tables have left `table`)
+    if (hipMemcpyAsync(workspace, table.data(), table.size(), hipMemcpyHostToDevice, st) != hipSuccess) return check_launch();
+    const int64_t lvl_ld = n_total + m_total;
+    if (record && hipMemsetAsync(levels, 0, (size_t)kAmLevels * lvl_ld * sizeof(float), st) != hipSuccess) return check_launch();
+    // 2 + 6 kAmLevels launches whatever the batch: each one covers the tiles or rows of every item
+    if (z.tiles_a > 0) {
+        const unsigned ga = (unsigned)z.tiles_a, gb = (unsigned)z.tiles_b, fa = (unsigned)z.rows_a, fb = (unsigned)z.rows_b;
+        er_init_kernel<<<fa + fb, kMtThreads, 0, st>>>(d.ra, w.remainL, w.costL, w.remainR);
+        for (int L = 0; L < kAmLevels; ++L) {
+            const float level = am_level(L);
+            er_pass_kernel<kMtSumWeighted><<<ga, kMtThreads, 0, st>>>(xyz1, xyz2, d.ta, level, w.remainR, nullptr, w.part, nullptr);
+            float* lv = record ? levels + L * lvl_ld : nullptr;
+            er_finish_a_kernel<<<fa, kMtThreads, 0, st>>>(d.ra, w.part, w.remainL, w.ratioL, lv);
+            er_pass_kernel<kMtSumWeighted><<<gb, kMtThreads, 0, st>>>(xyz2, xyz1, d.tb, level, w.ratioL, nullptr, w.part, nullptr);
+            er_finish_b_kernel<<<fb, kMtThreads, 0, st>>>(d.rb, w.part, w.remainR, w.ratioR, lv != nullptr ? lv + n_total : nullptr);
+            er_pass_kernel<kMtFused><<<ga, kMtThreads, 0, st>>>(xyz1, xyz2, d.ta, level, w.ratioR, w.ratioL, w.part, w.part2);
+            er_finish_c_kernel<<<fa, kMtThreads, 0, st>>>(d.ra, w.part, w.part2, w.remainL, w.costL);
+        }
+    }
+    er_total_kernel<<<(unsigned)batch, kMtThreads, 0, st>>>(d.items, w.costL, cost);
+    return check_launch();
 }
 
 }  // namespace dmcf
@@ -716,66 +794,15 @@ size_t dmcf_emd_ragged_workspace_bytes(int64_t n_total, const int64_t* row_split
 int dmcf_emd_ragged(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
                     const int64_t* row_splits2, int64_t batch, float* cost, void* workspace, size_t workspace_bytes,
                     dmcf_stream_t stream) {
-    if (batch == 0) return n_total == 0 && m_total == 0 ? DMCF_OK : DMCF_EINVAL;
-    if (!er_valid(n_total, row_splits1, m_total, row_splits2, batch)) return DMCF_EINVAL;
-    if (n_total == 0 && m_total == 0) return DMCF_OK;  // (every item empty on both sides: nothing enqueued)
-    if (cost == nullptr || workspace == nullptr || (xyz1 == nullptr && n_total > 0) || (xyz2 == nullptr && m_total > 0))
-        return DMCF_EINVAL;
-    const ErSizes z = er_sizes(row_splits1, row_splits2, batch);
-    if (z.tiles_a > INT32_MAX || z.tiles_b > INT32_MAX) return DMCF_EINVAL;  // (one workgroup per tile)
-    ErTables d, h;  // the tables in the workspace and on the host
-    AmWork w;
-    const size_t table_bytes = er_tables(z, batch, (char*)workspace, &d);
-    if (workspace_bytes < er_carve(z, n_total, m_total, table_bytes, (char*)workspace, &w)) return DMCF_EWORKSPACE;
-    std::vector<char> table(table_bytes);
-    er_tables(z, batch, table.data(), &h);
-    int64_t na = 0, nb = 0, ra = 0, rb = 0, off_a = 0, off_b = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        const int64_t n = row_splits1[b + 1] - row_splits1[b], m = row_splits2[b + 1] - row_splits2[b];
-        if (n == 0 || m == 0) {  // nothing to match: cost 0
-            h.items[b] = ErItem{0, 0};
-            continue;
-        }
-        h.items[b] = ErItem{(int32_t)row_splits1[b], (int32_t)n};
-        for (int side = 0; side < 2; ++side) {  // 0: rows of xyz1 over the item's xyz2 (passes A and C); 1: the reverse (pass B)
-            const int64_t rows = side == 0 ? n : m, cols = side == 0 ? m : n;
-            const int64_t r0 = side == 0 ? row_splits1[b] : row_splits2[b], c0 = side == 0 ? row_splits2[b] : row_splits1[b];
-            const MtPlan p = mt_plan(rows, cols);
-            // the multipliers of approx_match_item: 1 on the larger side, the integer quotient on the smaller
-            const float mult = side == 0 ? (n >= m ? 1.0f : (float)(m / n)) : (n >= m ? (float)(n / m) : 1.0f);
-            int64_t& off = side == 0 ? off_a : off_b;
-            for (int64_t k = 0; k < p.row_blocks; ++k) {
-                const int64_t first = k * kMtThreads, cnt = rows - first < kMtThreads ? rows - first : kMtThreads;
-                (side == 0 ? h.ra[ra++] : h.rb[rb++]) =
-                    ErRows{(int32_t)(r0 + first), (int32_t)cnt, (int32_t)rows, (int32_t)p.nsplit, off + first, mult, side == 0};
-                for (int64_t s = 0; s < p.nsplit; ++s) {
-                    const int64_t a = s * p.chunk, e = a + p.chunk < cols ? a + p.chunk : cols;
-                    (side == 0 ? h.ta[na++] : h.tb[nb++]) =
-                        ErTile{(int32_t)(r0 + first), (int32_t)cnt, (int32_t)(c0 + a), (int32_t)(c0 + e), off + s * rows + first};
-                }
-            }
-            off += p.nsplit * rows;
-        }
-    }
-    hipStream_t st = (hipStream_t)stream;
-    // (pageable host memory: the call returns once the tables have left `table`)
-    if (hipMemcpyAsync(workspace, table.data(), table.size(), hipMemcpyHostToDevice, st) != hipSuccess) return check_launch();
-    // 2 + 6 kAmLevels launches whatever the batch: each one covers the tiles or rows of every item
-    if (z.tiles_a > 0) {
-        const unsigned ga = (unsigned)z.tiles_a, gb = (unsigned)z.tiles_b, fa = (unsigned)z.rows_a, fb = (unsigned)z.rows_b;
-        er_init_kernel<<<fa + fb, kMtThreads, 0, st>>>(d.ra, w.remainL, w.costL, w.remainR);
-        for (int L = 0; L < kAmLevels; ++L) {
-            const float level = am_level(L);
-            er_pass_kernel<kMtSumWeighted><<<ga, kMtThreads, 0, st>>>(xyz1, xyz2, d.ta, level, w.remainR, nullptr, w.part, nullptr);
-            er_finish_a_kernel<<<fa, kMtThreads, 0, st>>>(d.ra, w.part, w.remainL, w.ratioL);
-            er_pass_kernel<kMtSumWeighted><<<gb, kMtThreads, 0, st>>>(xyz2, xyz1, d.tb, level, w.ratioL, nullptr, w.part, nullptr);
-            er_finish_b_kernel<<<fb, kMtThreads, 0, st>>>(d.rb, w.part, w.remainR, w.ratioR);
-            er_pass_kernel<kMtFused><<<ga, kMtThreads, 0, st>>>(xyz1, xyz2, d.ta, level, w.ratioR, w.ratioL, w.part, w.part2);
-            er_finish_c_kernel<<<fa, kMtThreads, 0, st>>>(d.ra, w.part, w.part2, w.remainL, w.costL);
-        }
-    }
-    er_total_kernel<<<(unsigned)batch, kMtThreads, 0, st>>>(d.items, w.costL, cost);
-    return check_launch();
+    return emd_ragged_common(xyz1, n_total, row_splits1, xyz2, m_total, row_splits2, batch, cost, false, nullptr, workspace,
+                             workspace_bytes, stream);
+}
+
+int dmcf_emd_ragged_with_levels(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                                const int64_t* row_splits2, int64_t batch, float* cost, float* levels, void* workspace,
+                                size_t workspace_bytes, dmcf_stream_t stream) {
+    return emd_ragged_common(xyz1, n_total, row_splits1, xyz2, m_total, row_splits2, batch, cost, true, levels, workspace,
+                             workspace_bytes, stream);
 }
 
 int dmcf_emd_with_levels(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,

@@ -18,6 +18,8 @@
 // Both sweeps form d2 from (row - column) differences; negation is exact, so d2 has the forward's bits in either sweep.
 #include <math.h>
 
+#include <vector>
+
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
@@ -314,15 +316,14 @@ struct alignas(16) EmdCol {
     float pad2[2];
 };
 
+// the tile walk of both EMD gradient kernels: the columns [c0, c1) of cp in ascending order, in LDS tiles of kMtTile, against
+// the row at rp[3 * row] (live: the lane has one) -> the three sums of the chunk.  rrat / crat: the ten ratios of row r at
+// rrat[L * lvl_ld + r], of column c at crat[L * lvl_ld + c].  Every lane of the workgroup calls it (it synchronises).
 template <bool ROWS1>
-__global__ __launch_bounds__(kMtThreads) void emd_grad_kernel(const float* __restrict__ rp, int64_t nrow, const float* __restrict__ cp,
-                                                              int64_t ncol, int64_t chunk, AmLevels lv, const float* __restrict__ rrat,
-                                                              const float* __restrict__ crat, int64_t lvl_ld,
-                                                              float* __restrict__ part) {
-    __shared__ EmdCol tile[kMtTile];
-    const int64_t s = blockIdx.y;
-    const int64_t row = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
-    const bool live = row < nrow;
+__device__ __forceinline__ void emd_grad_walk(EmdCol* __restrict__ tile, const float* __restrict__ rp, int64_t row, bool live,
+                                              const float* __restrict__ cp, int64_t c0, int64_t c1, const AmLevels& lv,
+                                              const float* __restrict__ rrat, const float* __restrict__ crat, int64_t lvl_ld,
+                                              float& ax, float& ay, float& az) {
     float x = 0.0f, y = 0.0f, z = 0.0f, rr[kAmLevels];
 #pragma unroll
     for (int L = 0; L < kAmLevels; ++L) rr[L] = 0.0f;
@@ -333,8 +334,7 @@ __global__ __launch_bounds__(kMtThreads) void emd_grad_kernel(const float* __res
 #pragma unroll
         for (int L = 0; L < kAmLevels; ++L) rr[L] = rrat[L * lvl_ld + row];
     }
-    const int64_t c0 = s * chunk, c1 = c0 + chunk < ncol ? c0 + chunk : ncol;
-    float ax = 0.0f, ay = 0.0f, az = 0.0f;
+    ax = ay = az = 0.0f;
     for (int64_t t0 = c0; t0 < c1; t0 += kMtTile) {
         const int cnt = (int)(c1 - t0 < kMtTile ? c1 - t0 : kMtTile);
         __syncthreads();
@@ -366,12 +366,33 @@ __global__ __launch_bounds__(kMtThreads) void emd_grad_kernel(const float* __res
             az = fmaf(cf, dz, az);
         }
     }
+}
+
+template <bool ROWS1>
+__global__ __launch_bounds__(kMtThreads) void emd_grad_kernel(const float* __restrict__ rp, int64_t nrow, const float* __restrict__ cp,
+                                                              int64_t ncol, int64_t chunk, AmLevels lv, const float* __restrict__ rrat,
+                                                              const float* __restrict__ crat, int64_t lvl_ld,
+                                                              float* __restrict__ part) {
+    __shared__ EmdCol tile[kMtTile];
+    const int64_t s = blockIdx.y;
+    const int64_t row = (int64_t)blockIdx.x * kMtThreads + threadIdx.x;
+    const bool live = row < nrow;
+    const int64_t c0 = s * chunk, c1 = c0 + chunk < ncol ? c0 + chunk : ncol;
+    float ax, ay, az;
+    emd_grad_walk<ROWS1>(tile, rp, row, live, cp, c0, c1, lv, rrat, crat, lvl_ld, ax, ay, az);
     if (live) {
         float* pp = part + s * 3 * nrow + row;
         pp[0] = ax;
         pp[nrow] = ay;
         pp[2 * nrow] = az;
     }
+}
+
+// the sum of a row's partials of one coordinate, p[j * step] for j < nsplit in split order (both combine kernels)
+__device__ __forceinline__ float grad_split_sum(const float* __restrict__ p, int64_t step, int64_t nsplit) {
+    float s = 0.0f;
+    for (int64_t j = 0; j < nsplit; ++j) s += p[j * step];
+    return s;
 }
 
 // grad[(b * nout + row) * 3 + c] = grad_cost[b] * sum_s part[((s * nb + b) * 3 + c) * nrow + row] for row < nrow, 0 up to nout
@@ -384,15 +405,113 @@ __global__ __launch_bounds__(kMtThreads) void grad_combine_kernel(const float* _
     float a[3] = {0.0f, 0.0f, 0.0f};
     if (row < nrow) {
         const float g = grad_cost[b];
-        for (int c = 0; c < 3; ++c) {
-            float s = 0.0f;
-            for (int64_t j = 0; j < nsplit; ++j) s += part[((j * nb + b) * 3 + c) * nrow + row];
-            a[c] = g * s;
-        }
+        for (int c = 0; c < 3; ++c) a[c] = g * grad_split_sum(part + (b * 3 + c) * nrow + row, nb * 3 * nrow, nsplit);
     }
     grad[3 * i] = a[0];
     grad[3 * i + 1] = a[1];
     grad[3 * i + 2] = a[2];
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// EMD over a ragged batch (ABI 2.25): the gradient launch and the combine launch of dmcf_emd_backward, each ONE launch over the
+// tiles / row blocks of ALL items.  An item keeps the column chunks of its own mt_plan(rows, cols), the walk is emd_grad_walk
+// and the combine sums in split order before g * s, so an item's rows have dmcf_emd_backward's bits for the item alone.  The
+// host writes the tables from the row splits it has validated: no kernel reads row splits and every index lies inside its array
+// by construction.  Points and levels run over the concatenated rows (levels [kAmLevels, n_total + m_total], ratioR from
+// column n_total on); an item's partials are [nsplit, 3, rows of the item] at its own base.
+// ------------------------------------------------------------------------------------------------------------------
+struct EgTile {          // one workgroup of the gradient launch
+    int32_t row0, rows;  // rows [row0, row0 + rows) of the concatenated row set, 1 <= rows <= kMtThreads
+    int32_t c0, c1;      // the chunk [c0, c1) of the concatenated column set, c0 < c1
+    int64_t pbase;       // part[pbase + c * stride + lane]: coordinate c of (this chunk, row0 + lane)
+    int32_t stride, pad; // the item's rows
+};
+static_assert(sizeof(EgTile) == 32, "EgTile is packed");
+
+struct EgRows {             // one workgroup of the combine launch
+    int32_t row0, rows;     // as above
+    int32_t item, nsplit;   // grad_cost[item]; nsplit == 0: an item without pairs, its rows get zeros
+    int64_t pbase;          // part[pbase + (j * 3 + c) * stride + lane], j < nsplit in split order
+    int32_t stride, pad;
+};
+static_assert(sizeof(EgRows) == 32, "EgRows is packed");
+
+template <bool ROWS1>
+__global__ __launch_bounds__(kMtThreads) void emd_ragged_grad_kernel(const float* __restrict__ rp, const float* __restrict__ cp,
+                                                                     const EgTile* __restrict__ tiles, AmLevels lv,
+                                                                     const float* __restrict__ rrat, const float* __restrict__ crat,
+                                                                     int64_t lvl_ld, float* __restrict__ part) {
+    __shared__ EmdCol tile[kMtTile];
+    const EgTile t = tiles[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    const bool live = lane < t.rows;
+    float ax, ay, az;
+    emd_grad_walk<ROWS1>(tile, rp, (int64_t)t.row0 + lane, live, cp, t.c0, t.c1, lv, rrat, crat, lvl_ld, ax, ay, az);
+    if (live) {
+        float* pp = part + t.pbase + lane;
+        pp[0] = ax;
+        pp[t.stride] = ay;
+        pp[2 * (int64_t)t.stride] = az;
+    }
+}
+
+__global__ __launch_bounds__(kMtThreads) void emd_ragged_combine_kernel(const EgRows* __restrict__ recs, const float* __restrict__ part,
+                                                                        const float* __restrict__ grad_cost, float* __restrict__ grad) {
+    const EgRows r = recs[blockIdx.x];
+    if ((int)threadIdx.x >= r.rows) return;
+    const int64_t row = (int64_t)r.row0 + threadIdx.x;
+    float a[3] = {0.0f, 0.0f, 0.0f};
+    if (r.nsplit > 0) {
+        const float g = grad_cost[r.item];
+        for (int c = 0; c < 3; ++c)
+            a[c] = g * grad_split_sum(part + r.pbase + (int64_t)c * r.stride + threadIdx.x, 3 * (int64_t)r.stride, r.nsplit);
+    }
+    grad[3 * row] = a[0];
+    grad[3 * row + 1] = a[1];
+    grad[3 * row + 2] = a[2];
+}
+
+// what the validated splits ask of dmcf_emd_ragged_backward, per side (0: rows of xyz1, 1: rows of xyz2)
+struct EgSizes {
+    int64_t tiles[2] = {0, 0};  // gradient tiles: sum of row_blocks * nsplit over the items with pairs
+    int64_t recs[2] = {0, 0};   // combine records: the row blocks of every item, with pairs or not
+    int64_t part[2] = {0, 0};   // floats of partials: sum of nsplit * 3 * rows over the items with pairs
+};
+
+inline EgSizes eg_sizes(const int64_t* rs1, const int64_t* rs2, int64_t batch) {
+    EgSizes z;
+    for (int64_t b = 0; b < batch; ++b) {
+        const int64_t n = rs1[b + 1] - rs1[b], m = rs2[b + 1] - rs2[b];
+        for (int side = 0; side < 2; ++side) {
+            const int64_t rows = side == 0 ? n : m, cols = side == 0 ? m : n;
+            const int64_t blocks = (rows + kMtThreads - 1) / kMtThreads;
+            z.recs[side] += blocks;
+            if (rows == 0 || cols == 0) continue;
+            const MtPlan p = mt_plan(rows, cols);
+            z.tiles[side] += blocks * p.nsplit;
+            z.part[side] += p.nsplit * 3 * rows;
+        }
+    }
+    return z;
+}
+
+// the workspace: the four tables (tiles of side 0, of side 1, records of side 0, of side 1; one copy from the host's block of the
+// same layout), then the partials, which the two sides use one after the other
+struct EgTables {
+    EgTile* t[2];
+    EgRows* r[2];
+};
+
+inline size_t eg_tables(const EgSizes& z, char* base, EgTables* t) {
+    const size_t at_t1 = (size_t)z.tiles[0] * sizeof(EgTile), at_r0 = at_t1 + (size_t)z.tiles[1] * sizeof(EgTile);
+    const size_t at_r1 = at_r0 + (size_t)z.recs[0] * sizeof(EgRows);
+    if (base != nullptr) *t = EgTables{{(EgTile*)base, (EgTile*)(base + at_t1)}, {(EgRows*)(base + at_r0), (EgRows*)(base + at_r1)}};
+    return at_r1 + (size_t)z.recs[1] * sizeof(EgRows);
+}
+
+inline size_t eg_workspace(const EgSizes& z, size_t table_bytes) {
+    const int64_t part = z.part[0] > z.part[1] ? z.part[0] : z.part[1];
+    return align_up(table_bytes, 256) + align_up((size_t)(part > 0 ? part : 1) * sizeof(float), 256);
 }
 
 inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -535,6 +654,77 @@ int dmcf_emd_backward(const float* xyz1, const float* xyz2, int64_t b, int64_t n
         }
     }
     return DMCF_OK;
+}
+
+size_t dmcf_emd_ragged_backward_workspace_bytes(int64_t n_total, const int64_t* row_splits1, int64_t m_total,
+                                                const int64_t* row_splits2, int64_t batch) {
+    if (!er_valid(n_total, row_splits1, m_total, row_splits2, batch)) return 0;
+    const EgSizes z = eg_sizes(row_splits1, row_splits2, batch);
+    if (z.tiles[0] > INT32_MAX || z.tiles[1] > INT32_MAX) return 0;
+    return eg_workspace(z, eg_tables(z, nullptr, nullptr));
+}
+
+int dmcf_emd_ragged_backward(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                             const int64_t* row_splits2, int64_t batch, const float* levels, const float* grad_cost,
+                             float* grad_xyz1, float* grad_xyz2, void* workspace, size_t workspace_bytes, dmcf_stream_t stream) {
+    if (grad_xyz1 == nullptr && grad_xyz2 == nullptr) return DMCF_EINVAL;
+    if (batch == 0) return n_total == 0 && m_total == 0 ? DMCF_OK : DMCF_EINVAL;
+    if (!er_valid(n_total, row_splits1, m_total, row_splits2, batch)) return DMCF_EINVAL;
+    const EgSizes z = eg_sizes(row_splits1, row_splits2, batch);
+    if (z.tiles[0] > INT32_MAX || z.tiles[1] > INT32_MAX) return DMCF_EINVAL;  // (one workgroup per tile)
+    hipStream_t st = (hipStream_t)stream;
+    if (z.tiles[0] == 0) {  // no item has a pair (then neither side has a tile): zero gradients
+        if (grad_xyz1 != nullptr && n_total > 0 && hipMemsetAsync(grad_xyz1, 0, (size_t)n_total * 3 * sizeof(float), st) != hipSuccess)
+            return check_launch();
+        if (grad_xyz2 != nullptr && m_total > 0 && hipMemsetAsync(grad_xyz2, 0, (size_t)m_total * 3 * sizeof(float), st) != hipSuccess)
+            return check_launch();
+        return DMCF_OK;
+    }
+    if (xyz1 == nullptr || xyz2 == nullptr || levels == nullptr || grad_cost == nullptr || workspace == nullptr) return DMCF_EINVAL;
+    EgTables d, h;  // the tables in the workspace and on the host
+    const size_t table_bytes = eg_tables(z, (char*)workspace, &d);
+    if (workspace_bytes < eg_workspace(z, table_bytes)) return DMCF_EWORKSPACE;
+    float* part = (float*)((char*)workspace + align_up(table_bytes, 256));
+    std::vector<char> table(table_bytes);
+    eg_tables(z, table.data(), &h);
+    for (int side = 0; side < 2; ++side) {  // 0: rows of xyz1 over the item's xyz2; 1: the reverse
+        if ((side == 0 ? grad_xyz1 : grad_xyz2) == nullptr) continue;  // (its tables stay zero and are not read)
+        const int64_t* rrs = side == 0 ? row_splits1 : row_splits2;
+        const int64_t* crs = side == 0 ? row_splits2 : row_splits1;
+        int64_t nt = 0, nr = 0, off = 0;
+        for (int64_t b = 0; b < batch; ++b) {
+            const int64_t rows = rrs[b + 1] - rrs[b], cols = crs[b + 1] - crs[b], r0 = rrs[b], c0 = crs[b];
+            const MtPlan p = rows == 0 || cols == 0 ? MtPlan{0, 0, 0} : mt_plan(rows, cols);  // (no pairs: zeros, no tile)
+            const int64_t nsplit = p.nsplit;
+            for (int64_t first = 0; first < rows; first += kMtThreads) {
+                const int64_t cnt = rows - first < kMtThreads ? rows - first : kMtThreads;
+                h.r[side][nr++] = EgRows{(int32_t)(r0 + first), (int32_t)cnt, (int32_t)b, (int32_t)nsplit, off + first, (int32_t)rows, 0};
+                for (int64_t s = 0; s < nsplit; ++s) {
+                    const int64_t a = s * p.chunk, e = a + p.chunk < cols ? a + p.chunk : cols;
+                    h.t[side][nt++] = EgTile{(int32_t)(r0 + first), (int32_t)cnt, (int32_t)(c0 + a), (int32_t)(c0 + e),
+                                             off + s * 3 * rows + first, (int32_t)rows, 0};
+                }
+            }
+            off += nsplit * 3 * rows;
+        }
+    }
+    // (pageable host memory: the call returns once the tables have left `table`)
+    if (hipMemcpyAsync(workspace, table.data(), table.size(), hipMemcpyHostToDevice, st) != hipSuccess) return check_launch();
+    AmLevels lv;
+    for (int L = 0; L < kAmLevels; ++L) lv.v[L] = am_level(L);
+    const int64_t lvl_ld = n_total + m_total;
+    // at most 4 launches whatever the batch: the gradient and the combine of every wanted side
+    if (grad_xyz1 != nullptr) {
+        emd_ragged_grad_kernel<true><<<(unsigned)z.tiles[0], kMtThreads, 0, st>>>(xyz1, xyz2, d.t[0], lv, levels, levels + n_total,
+                                                                                  lvl_ld, part);
+        emd_ragged_combine_kernel<<<(unsigned)z.recs[0], kMtThreads, 0, st>>>(d.r[0], part, grad_cost, grad_xyz1);
+    }
+    if (grad_xyz2 != nullptr) {
+        emd_ragged_grad_kernel<false><<<(unsigned)z.tiles[1], kMtThreads, 0, st>>>(xyz2, xyz1, d.t[1], lv, levels + n_total, levels,
+                                                                                   lvl_ld, part);
+        emd_ragged_combine_kernel<<<(unsigned)z.recs[1], kMtThreads, 0, st>>>(d.r[1], part, grad_cost, grad_xyz2);
+    }
+    return check_launch();
 }
 
 size_t dmcf_gather_point_backward_workspace_bytes(int64_t n_index, int64_t n_inp) {

@@ -16,6 +16,8 @@ change between steps (run_sample.py:173-177 adds inflow), so nothing here assume
 keys, all default false): ``train_batched`` and ``warm_up_batched`` for the training window and its warm-up, ``valid_batched``
 for run_valid -- ``run_rollout_batched`` advances all scenes with one ``model.step_batched`` per time step and
 ``valid_losses_batched`` evaluates a frame of all scenes at once (one dmcf_nn_distance_ragged call for the Chamfer metric).
+``train_set_losses`` (default none; needs ``train_batched``) adds correspondence-free Chamfer / EMD terms to the training
+window, each ONE recording ragged call per window step over all samples.
 """
 import logging
 import os
@@ -35,6 +37,8 @@ log = logging.getLogger(__name__)
 # 1M fluid + 0.12M boundary particles peak at 16 GB of live buffers and ~45 GB of pool once the lists have grown (DESIGN.md
 # section 4.1): 40 KiB per point
 RESERVE_BYTES_PER_POINT = 40 * 1024
+
+SET_LOSSES = ("chamfer", "emd")  # the names pipeline key train_set_losses takes
 
 
 def reserve_for_scene(reserve_gib, n_points, device):
@@ -180,6 +184,46 @@ class Simulator:
                 if os.path.exists(d):
                     shutil.rmtree(d)
         self.optimizer = None
+        self.set_losses = self._set_losses()
+
+    def _set_losses(self):
+        """Pipeline key ``train_set_losses`` (default none): a mapping from "chamfer" / "emd" to a factor, e.g. ``{chamfer: 1.0,
+        emd: 0.1}`` -> [(name, factor)] in the mapping's order.  Every window step of a ``train_batched`` window then adds
+        ``factor * loss`` of the samples' new positions against their target frames as one more column per name of the loss
+        vector.  An unknown name is a ValueError, the key without ``train_batched`` a NotImplementedError (the per-sample window
+        has no batch to make one call for) -- both here, before anything runs."""
+        conf = self.cfg.get("train_set_losses", None)
+        if not conf:
+            return []
+        terms = [(str(k), float(v)) for k, v in dict(conf).items()]
+        for name, _ in terms:
+            if name not in SET_LOSSES:
+                raise ValueError(f"train_set_losses: unknown loss {name!r} (one of {', '.join(SET_LOSSES)})")
+        if not self.cfg.get("train_batched", False):
+            raise NotImplementedError("train_set_losses needs train_batched: the terms are one ragged call per window step")
+        return terms
+
+    def loss_keys(self):
+        """The names of the entries of the training loss vector: the model's, then those of ``train_set_losses``."""
+        return list(self.model.loss_keys()) + [name for name, _ in self.set_losses]
+
+    def _set_loss_columns(self, pos2, rs, targets):
+        """[batch, len(train_set_losses)]: ``factor * loss`` per sample and configured name, every name ONE recording ragged
+        call over all samples: their rows of ``pos2`` (row splits ``rs``) against ``targets`` (one frame per sample)."""
+        from ..utils.tools.losses import emd_loss_ragged
+        from ..utils.tools.nn_distance import chamfer_loss
+        tgt = torch.cat(targets, dim=0)
+        trs = [0]
+        for x in targets:
+            trs.append(trs[-1] + x.shape[0])
+        cols = []
+        for name, fac in self.set_losses:
+            if name == "chamfer":
+                value = chamfer_loss(tgt, pos2, true_row_splits=trs, pred_row_splits=rs, record=True)
+            else:
+                value = emd_loss_ragged(tgt, pos2, trs, rs, record=True)
+            cols.append(fac * value)
+        return torch.stack(cols, dim=1)
 
     def _to_device(self, x):
         if x is None:
@@ -699,11 +743,15 @@ class Simulator:
             raise NotImplementedError("iterations > 1 (the reference's inner iteration loop cannot run)")
         model.requires_grad_(True)
         tw = torch.as_tensor(np.asarray(time_w, dtype=np.float32), device=self.device)
+        set_rows = []  # (the weighted rows of the train_set_losses columns, when the key is set)
         if self.cfg.get("train_batched", False):  # pipeline key train_batched (default false): one batched step per window step
-            rows = self._window_rows_batched(data, tw, in_pos, in_vel, pres)
+            rows = self._window_rows_batched(data, tw, in_pos, in_vel, pres, set_rows)
         else:
             rows = self._window_rows(data, tw, in_pos, in_vel, pres)
         loss_sum = torch.stack(rows).sum(0) / (tw.sum() * len(data["pos"]))
+        if set_rows:
+            # the columns of train_set_losses, summed apart from the model's: those keep the bits they have without the key
+            loss_sum = torch.cat([loss_sum, torch.stack(set_rows).sum(0) / (tw.sum() * len(data["pos"]))])
         w_decay = self.cfg.get("w_decay", 0) or 0
         if w_decay > 0:
             # a scalar added to every entry of the loss vector (simulator.py:407-410: w_decay * reduce_sum of the per-weight sums)
@@ -727,11 +775,12 @@ class Simulator:
                 rows.append(torch.stack([torch.as_tensor(v, device=self.device).reshape(()) for v in ls.values()]) * tw[t])
         return rows
 
-    def _window_rows_batched(self, data, tw, in_pos, in_vel, pres):
+    def _window_rows_batched(self, data, tw, in_pos, in_vel, pres, set_rows=None):
         """The weighted per-step losses of window_loss with pipeline key ``train_batched``: each of the len(time_w) steps is ONE
         model.step_batched over all samples, and every sample's loss is formed by model.loss on that sample's rows of pos2,
         pos_correction and num_fluid_neighbors.  The same terms as the per-sample loop, sample-major order of the rows aside
-        (they are summed)."""
+        (they are summed).  With ``train_set_losses`` the sample's weighted Chamfer / EMD columns of the step are appended to
+        ``set_rows``, row for row (:meth:`_set_loss_columns`: one ragged call per name and step)."""
         from ..utils.evaluation_helper import merge_dicts
         model = self.model
         samples = [self._sample_tensors(data, bi) for bi in range(len(data["pos"]))]
@@ -741,6 +790,10 @@ class Simulator:
             items = [[pos[bi], vel[bi], s["grav0"], None, s["box0"], s["boxn0"]] for bi, s in enumerate(samples)]
             pos2, vel2, rs = model.step_batched(items, training=True)
             correction, neighbors = model.pos_correction, model.num_fluid_neighbors
+            extra = None
+            if self.set_losses and set_rows is not None:
+                extra = self._set_loss_columns(pos2, rs, [self._to_device(s["pos"][t + int(pres[bi]) + 1])
+                                                          for bi, s in enumerate(samples)])
             try:
                 for bi, s in enumerate(samples):
                     a, b, pre = rs[bi], rs[bi + 1], int(pres[bi])
@@ -751,6 +804,8 @@ class Simulator:
                                                           self._to_device(target[t + pre]), pre])]
                     ls = merge_dicts(ls, lambda x, y: x + y / len(ls))
                     rows.append(torch.stack([torch.as_tensor(v, device=self.device).reshape(()) for v in ls.values()]) * tw[t])
+                    if extra is not None:
+                        set_rows.append(extra[bi] * tw[t])
             finally:
                 model.pos_correction, model.num_fluid_neighbors = correction, neighbors
         return rows
@@ -832,7 +887,7 @@ class Simulator:
                     self.train_timing["data"] = t_data
                     loss = {}
                     desc = "training -"
-                    for k, v in zip(model.loss_keys(), loss_l):
+                    for k, v in zip(self.loss_keys(), loss_l):
                         desc += " %s: %.05f" % (k, v)
                         loss[k] = float(v)
                     loss["loss"] = float(np.sum(loss_l))

@@ -11,6 +11,8 @@
   emd_loss          losses.py:401-409  approximate-match EMD per batch item (ops.emd; differentiable in both sets with the
                                        match held constant, dmcf_emd_backward; with row splits a ragged batch in one
                                        call, dmcf_emd_ragged, no gradient)
+  emd_loss_ragged   (no counterpart)   emd_loss of a ragged batch that can record: one dmcf_emd_ragged_with_levels call, one
+                                       dmcf_emd_ragged_backward call
 
   get_loss          losses.py:47-110   the training losses mse / weighted_mse / vel / weighted_vel / momentum
   get_optimizer     models/pbf_model.py:508-517  Adam (eps 1e-6), piecewise-constant learning rate (torch.optim.Adam)
@@ -397,7 +399,8 @@ def emd_loss(y_true, y_pred, n=None, m=None, true_row_splits=None, pred_row_spli
 
     ``true_row_splits`` / ``pred_row_splits`` (both or neither, and then no ``n`` / ``m``): a RAGGED batch in one call
     (ops.emd with row splits), ``y_true`` [n_total, 3] and ``y_pred`` [m_total, 3]; -> ``cost / max(n_b, m_b)`` per item,
-    [batch], with the bits of the call on every item alone; an item with both sets empty gives 0.  No gradient."""
+    [batch], with the bits of the call on every item alone; an item with both sets empty gives 0.  No gradient here:
+    :func:`emd_loss_ragged` with ``record=True`` is the form that trains."""
     from ... import ops
     if true_row_splits is not None or pred_row_splits is not None:
         cost = ops.emd(y_true, y_pred, n, m, row_splits1=true_row_splits, row_splits2=pred_row_splits)
@@ -413,6 +416,21 @@ def emd_loss(y_true, y_pred, n=None, m=None, true_row_splits=None, pred_row_spli
     mv = np.full(b, y_pred.shape[1]) if mm is None else mm
     denom = torch.from_numpy(np.maximum(nv, mv).astype(np.float32)).to(cost.device)
     return cost / denom
+
+
+def emd_loss_ragged(y_true, y_pred, true_row_splits, pred_row_splits, record=False):
+    """:func:`emd_loss` of a RAGGED batch, ``y_true`` [n_total, 3|2] and ``y_pred`` [m_total, 3|2] with their row splits ->
+    ``cost / max(n_b, m_b, 1)`` per item, [batch], with the bits of the call on every item alone.  ``record=True``:
+    differentiable in both sets with the match held constant (ops.emd_ragged_recording: one recording forward, one
+    dmcf_emd_ragged_backward call for the whole batch; the divisor is a constant), every item's gradient rows with the bits of
+    emd_loss on the item alone.  ``record=False`` is emd_loss with row splits: inputs that require grad raise
+    NotImplementedError."""
+    from ... import ops
+    cost = (ops.emd_ragged_recording if record else ops.emd_ragged)(y_true, y_pred, true_row_splits, pred_row_splits)
+    s1 = np.asarray(ops._host_row_splits(true_row_splits, "true_row_splits")[0])
+    s2 = np.asarray(ops._host_row_splits(pred_row_splits, "pred_row_splits")[0])
+    denom = np.maximum(np.maximum(np.diff(s1), np.diff(s2)), 1)  # (both sets empty: cost 0 over 1)
+    return cost / torch.from_numpy(denom.astype(np.float32)).to(cost.device)
 
 
 def _pre_factor(kwargs, kw, like):

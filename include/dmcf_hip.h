@@ -23,6 +23,9 @@
  *     (pipelines/simulator.py:222-248, utils/evaluation_helper.py)  scenes of different particle counts)
  *   emd_loss per scene of a validation split                     dmcf_emd_ragged (ABI 2.24: the same, with
  *     (pipelines/simulator.py:247-249, utils/tools/losses.py:401-409)  dmcf_emd's bits for every scene)
+ *   EmdLoss / ChamferLoss terms per sample of a training batch   dmcf_emd_ragged_with_levels / dmcf_emd_ragged_backward
+ *     (utils/tools/losses.py:401-414)                             (ABI 2.25: the ragged EMD's gradient, 4 launches
+ *                                                                 whatever the batch)
  *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
  *                                                                 dmcf_cconv_backward_extents)
  *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
@@ -911,6 +914,35 @@ size_t dmcf_emd_backward_workspace_bytes(int64_t b, int64_t n, int64_t m);
 int dmcf_emd_backward(const float* xyz1, const float* xyz2, int64_t b, int64_t n, int64_t m, const int32_t* count1,
                       const int32_t* count2, const float* levels, const float* grad_cost, float* grad_xyz1, float* grad_xyz2,
                       void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* The gradient of dmcf_emd_ragged (ABI 2.25): the recording forward and the match-free backward over a RAGGED batch, laid out
+ * as for dmcf_emd_ragged (xyz1 [n_total, 3], xyz2 [m_total, 3], both row-splits arrays HOST int64 [batch + 1], validated
+ * here before anything is enqueued).
+ * dmcf_emd_ragged_with_levels enqueues the launches of dmcf_emd_ragged, so cost has its bits, and records levels
+ * [10, n_total + m_total]: levels[L * (n_total + m_total) + row] is ratioL of row `row` of xyz1 after finish step A of level L,
+ * levels[L * (n_total + m_total) + n_total + row] ratioR of row `row` of xyz2 after finish step B (the finish steps write them;
+ * levels is zeroed first, so the rows of an item with either set empty hold exact zeros).  Workspace:
+ * dmcf_emd_ragged_workspace_bytes.  The refusals of dmcf_emd_ragged, and NULL levels: DMCF_EINVAL; every item empty on both
+ * sides: DMCF_OK with nothing written.
+ * dmcf_emd_ragged_backward: grad_xyz1 [n_total, 3] / grad_xyz2 [m_total, 3] from those levels and grad_cost [batch] (device).
+ * Result contract: item b's rows have exactly the bits dmcf_emd_backward gives for item b alone (b = 1, no counts, its own
+ * levels).  Every item keeps the column chunks of its own split plan, both kernels share dmcf_emd_backward's tile walk, and the
+ * combine sums in split order before multiplying by grad_cost[b]; what changes is the launch count: one asynchronous table
+ * copy and at most 4 launches whatever the batch -- the gradient and the combine of each wanted side (dmcf_emd_backward: 4 per
+ * item).  The entry point writes the tables -- a record per (item, 256 rows, column chunk) and per (item, 256 rows) -- from the
+ * validated splits; no kernel reads row splits, and no float atomics are used.  Rows of an item whose other set is empty get
+ * exact zeros.  batch == 0 with n_total == m_total == 0: DMCF_OK.  No item with a pair: DMCF_OK after the wanted gradients of
+ * non-zero length are zeroed, with no other pointer looked at.  batch < 0 or > 2^26, NULL or malformed row splits, n_total or
+ * m_total >= 2^31 - 257, more than INT32_MAX tiles on a side, and, when there is work, NULL points, levels, grad_cost or
+ * workspace: DMCF_EINVAL.  The workspace holds the tables and every item's partials [nsplit, 3, rows], which is why its query
+ * takes the splits; the query returns 0 for arguments the call refuses. */
+int dmcf_emd_ragged_with_levels(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                                const int64_t* row_splits2, int64_t batch, float* cost, float* levels, void* workspace,
+                                size_t workspace_bytes, dmcf_stream_t stream);
+size_t dmcf_emd_ragged_backward_workspace_bytes(int64_t n_total, const int64_t* row_splits1, int64_t m_total,
+                                                const int64_t* row_splits2, int64_t batch);
+int dmcf_emd_ragged_backward(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
+                             const int64_t* row_splits2, int64_t batch, const float* levels, const float* grad_cost,
+                             float* grad_xyz1, float* grad_xyz2, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
 /* gather_point: grad_inp [n_inp, channels] = sum over s with index[s] == t of grad_out[s, :] (repeated indices sum; indices
  * outside [0, n_inp) contribute nothing). */
 size_t dmcf_gather_point_backward_workspace_bytes(int64_t n_index, int64_t n_inp);
