@@ -1156,7 +1156,8 @@ def invert_neighbors_list(num_points, inp_neighbors_index, inp_neighbors_row_spl
     each pair and (``pair_index``) the pair's position in the forward list, in ascending pair order.  The arrays keep the
     length of the forward list; entries past ``row_splits[-1]`` (pairs of rows reaching past the list, or of padded slots) are
     -1.  ``inp_neighbors_attributes``: None / empty or a float32 [P] tensor, returned permuted the same way.
-    ``neighbors_row_count``: int32 [n_out] for padded lists."""
+    ``neighbors_row_count``: int32 [n_out] for padded lists, whose ``inp_neighbors_row_splits`` holds a begin per row (at
+    least n_out entries)."""
     L = _lib.lib()
     index = inp_neighbors_index
     rs = inp_neighbors_row_splits
@@ -1171,8 +1172,13 @@ def invert_neighbors_list(num_points, inp_neighbors_index, inp_neighbors_row_spl
     if attrs is not None and attrs.shape != (P,):
         raise ValueError("inp_neighbors_attributes must be a float32 [P] tensor")
     if neighbors_row_count is not None:
-        if neighbors_row_count.dtype != torch.int32 or neighbors_row_count.shape[0] != n_out:
+        # a padded list: one row per count and a row begin for each, as neighbor_dense takes it (entries of the begins past
+        # the rows, such as the end entry row splits have, are not read)
+        if neighbors_row_count.dtype != torch.int32 or neighbors_row_count.dim() != 1:
             raise TypeError("neighbors_row_count must be int32 [n_out]")
+        n_out = neighbors_row_count.shape[0]
+        if rs.shape[0] < n_out:
+            raise ValueError("padded lists need a row begin per row")
         neighbors_row_count = neighbors_row_count.contiguous()
     inv_index = torch.empty(P, dtype=torch.int32, device=dev)
     inv_pair = torch.empty(P, dtype=torch.int32, device=dev)
