@@ -205,6 +205,16 @@ class SparseConvArgs(ctypes.Structure):
     ]
 
 
+class HistPlan(ctypes.Structure):
+    """struct dmcf_hist_plan (include/dmcf_hip.h)."""
+    _fields_ = [
+        ("per", ctypes.c_int32),
+        ("rank", ctypes.c_int32 * 4),
+        ("gamma", ctypes.c_float * 2),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 class AdamTensor(ctypes.Structure):
     """struct dmcf_adam_tensor (include/dmcf_hip.h)."""
     _fields_ = [
@@ -290,6 +300,7 @@ SYMBOLS = [
     "dmcf_nn_distance_ragged_workspace_bytes", "dmcf_nn_distance_ragged",
     "dmcf_emd_ragged_workspace_bytes", "dmcf_emd_ragged",
     "dmcf_emd_ragged_with_levels", "dmcf_emd_ragged_backward_workspace_bytes", "dmcf_emd_ragged_backward",
+    "dmcf_hist_pair_ragged_workspace_bytes", "dmcf_hist_pair_ragged",
 ]
 
 
@@ -570,6 +581,12 @@ def lib():
     L.dmcf_emd_ragged_backward.restype = c.c_int
     L.dmcf_emd_ragged_backward.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p,
                                            c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    # the percentiles and histograms of compare_dist over a ragged batch (ABI 2.26): HOST row splits and plan
+    L.dmcf_hist_pair_ragged_workspace_bytes.restype = c.c_size_t
+    L.dmcf_hist_pair_ragged_workspace_bytes.argtypes = [c.c_int64, c.c_int64, c.c_int64]
+    L.dmcf_hist_pair_ragged.restype = c.c_int
+    L.dmcf_hist_pair_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.POINTER(HistPlan), c.c_int64,
+                                        c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
     _lib = L
     return L
 

@@ -47,6 +47,9 @@ inline float am_level(int L) {
 // host counts of the batch items (NULL = all): every one in [0, limit] (metrics.hip)
 bool valid_counts(const int32_t* counts, int64_t b, int64_t limit);
 
+// host row splits of `batch` items over `total` rows: start at 0, do not decrease, end at total (metrics.hip)
+bool valid_row_splits(const int64_t* rs, int64_t batch, int64_t total);
+
 // the argument checks of the ragged EMD entry points and their workspace queries: 1 <= batch <= 2^26, totals that leave room
 // for int32 indices, HOST row splits that start at 0, do not decrease and end at the totals (metrics.hip)
 bool er_valid(int64_t n_total, const int64_t* rs1, int64_t m_total, const int64_t* rs2, int64_t batch);

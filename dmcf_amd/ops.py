@@ -3221,6 +3221,88 @@ def emd(xyz1, xyz2, n=None, m=None, row_splits1=None, row_splits2=None):
     return cost if batched else cost[0]
 
 
+HIST_TILE_ROWS = 1024  # DMCF_HIST_TILE_ROWS: rows of each set per workgroup of dmcf_hist_pair_ragged's digit and count launches
+
+
+def percentile_plan(count, q):
+    """Where ``np.percentile(both, q, axis=0)`` looks in the sorted ``both`` of 2 ``count`` float32 values -> ``(k, k_next,
+    gamma)``: the result is numpy's ``_lerp(sorted[k], sorted[k_next], gamma)`` in float32.  The plan depends on the count
+    alone, which is why it is host arithmetic (it travels to dmcf_hist_pair_ragged in its table).
+
+    numpy's arithmetic for float32 data (lib/_function_base_impl.py of numpy 2.x), restated: ``quant = np.true_divide(q,
+    np.float32(100))``; the virtual index of the default method "linear" is ``(n - 1) * quant`` in float32 (numpy prefers
+    this form to ``n * quant + (alpha + quant * (1 - alpha - beta)) - 1`` with alpha = beta = 1, the form of numpy 1.22 -
+    1.26, which rounds differently); ``k = floor(virtual)``, ``k_next = k + 1``, both ``n - 1`` when ``virtual >= n - 1`` and
+    both 0 when ``virtual < 0``; ``gamma = virtual - k`` as float32 (exact).  tests/test_hist_pair_abi.py holds this to the
+    installed numpy bit for bit."""
+    n = 2 * int(count)
+    if n < 2:
+        raise ValueError(f"percentile_plan needs count >= 1, got {count}")
+    quant = np.true_divide(q, np.float32(100))
+    virtual = np.float32(n - 1) * np.float32(quant)
+    k = int(np.floor(virtual))
+    k_next, gamma = k + 1, np.float32(virtual - np.floor(virtual))
+    if virtual >= n - 1:
+        k, k_next, gamma = n - 1, n - 1, np.float32(0)  # (equal neighbours: the weight does not matter)
+    if virtual < 0:
+        k, k_next, gamma = 0, 0, np.float32(0)
+    return k, k_next, gamma
+
+
+def hist_pair_ragged(x, y, row_splits=None, bin_size=25):
+    """The percentiles and the two histograms of ``evaluation_helper.compare_dist(x, y, bin_size)`` for a RAGGED batch in one
+    call (dmcf_hist_pair_ragged: 9 launches, one memset and one table copy whatever the batch; no host read in between).
+
+    ``x``, ``y``: float32 device tensors [n_total, 3] sharing ``row_splits`` (the forms of :func:`nn_distance_ragged`; None:
+    one item).  -> ``(percentiles, counts, offsets)``: percentiles [batch, 2, 3] float32 holds np.percentile(both, 5 | 95,
+    axis=0) of every item's ``both = concatenate((x_b, y_b))``; counts is one int32 device tensor, item b's block being
+    ``counts[offsets[b]:offsets[b + 1]]`` -- first the (per_b + 1)^3 bin counts of x_b in np.ravel_multi_index order, then
+    those of y_b -- with ``per_b = int((cnt_b // bin_size) ** (1 / 3))``; offsets is a host list [batch + 1].  Everything is
+    selected and summed in integers: the values are the host function's, bit for bit, and two calls give equal bits.
+
+    Inputs must be finite: NaN is not checked for and is out of scope (the host function returns NaN percentiles for it).
+    ValueError: x or y not a float32 [n, 3] device tensor, different shapes, malformed splits, an item without rows."""
+    for t, name in ((x, "x"), (y, "y")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_cuda:
+            what = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name} must be a float32 device tensor of shape [n, 3], got {what}")
+    if x.shape != y.shape:
+        raise ValueError(f"x and y must have equal shapes, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.device != y.device:
+        raise ValueError("x and y must be on the same device")
+    if bin_size < 1:
+        raise ValueError(f"bin_size must be positive, got {bin_size}")
+    n = int(x.shape[0])
+    rs = (0, n) if row_splits is None else _host_row_splits(row_splits, "row_splits")[0]
+    _check_row_splits(rs, n, "row_splits")
+    batch = len(rs) - 1
+    plan = (_lib.HistPlan * batch)()
+    offsets = [0]
+    for b in range(batch):
+        cnt = rs[b + 1] - rs[b]
+        if cnt < 1:
+            raise ValueError(f"hist_pair_ragged needs non-empty items: item {b} has no rows")
+        per = int((cnt // bin_size) ** (1 / 3))  # compare_dist's bin_cnt_per_dim; the clip's upper end adds one bin per axis
+        k5, k5n, g5 = percentile_plan(cnt, 5)
+        k95, k95n, g95 = percentile_plan(cnt, 95)
+        plan[b].per = per
+        plan[b].rank[:] = [k5, k5n, k95, k95n]
+        plan[b].gamma[:] = [g5, g95]
+        offsets.append(offsets[-1] + 2 * (per + 1) ** 3)
+    L = _lib.lib()
+    x, y = x.contiguous(), y.contiguous()
+    dev = x.device
+    bins_total = offsets[-1] // 2
+    percentiles = torch.empty((batch, 2, 3), dtype=torch.float32, device=dev)
+    counts = torch.empty(offsets[-1], dtype=torch.int32, device=dev)
+    nbytes = int(L.dmcf_hist_pair_ragged_workspace_bytes(n, batch, bins_total))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    h = (ctypes.c_int64 * (batch + 1))(*rs)
+    _lib.check(L.dmcf_hist_pair_ragged(_ptr(x), _ptr(y), n, h, batch, plan, bins_total, _ptr(percentiles), _ptr(counts), _ptr(ws),
+                                       nbytes, _stream()), "dmcf_hist_pair_ragged")
+    return percentiles, counts, offsets
+
+
 def _adam_args(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, beta_2_power, clip_norm):
     """-> (dmcf_adam_args, host table, [params, grads, ms, vs]) for :func:`adam_step` (device_tensors not yet set)."""
     if not (len(params) == len(grads) == len(ms) == len(vs)):

@@ -15,7 +15,8 @@ state (utils/tf_checkpoint.CheckpointManager) and validates and tests after ever
 change between steps (run_sample.py:173-177 adds inflow), so nothing here assumes a fixed N.  Opt-in batched forms (pipeline
 keys, all default false): ``train_batched`` and ``warm_up_batched`` for the training window and its warm-up, ``valid_batched``
 for run_valid -- ``run_rollout_batched`` advances all scenes with one ``model.step_batched`` per time step and
-``valid_losses_batched`` evaluates a frame of all scenes at once (one dmcf_nn_distance_ragged call for the Chamfer metric).
+``valid_losses_batched`` evaluates a frame of all scenes at once (one dmcf_nn_distance_ragged call for the Chamfer metric, one
+dmcf_emd_ragged call for the EMD, one dmcf_hist_pair_ragged call for the two velocity-histogram KLs).
 ``train_set_losses`` (default none; needs ``train_batched``) adds correspondence-free Chamfer / EMD terms to the training
 window, each ONE recording ragged call per window step over all samples.
 """
@@ -508,8 +509,11 @@ class Simulator:
         the per-scene means are np.mean over the same float32 arrays as in the loop: they equal the loop's bit for bit
         wherever the device arrays do.  ``emd`` is ONE emd_loss call with row splits (dmcf_emd_ragged: every scene's cost has
         the bits of the loop's per-scene call), its [scenes] result travelling in the same host copy.  The two
-        ``vel_diff_val*`` stay per scene on the loop's code."""
-        from ..utils.evaluation_helper import compare_dist, distance
+        ``vel_diff_val*`` are ONE ops.hist_pair_ragged call (dmcf_hist_pair_ragged) on the concatenated target and predicted
+        velocities: its integer bin counts travel in the same host copy, and evaluation_helper._kl_from_counts -- the last
+        lines of compare_dist -- turns them into KL(target || pred) and KL(pred || target), the loop's bits.  A frame whose
+        velocities are not float32 [count, 3] on both sides keeps the loop's per-scene host code."""
+        from ..utils.evaluation_helper import _kl_pairs, compare_dist, distance
         from ..utils.tools.losses import density_loss, emd_loss, get_window_func
         cfg, model, dev = self.cfg, self.model, self._to_device
         full = cfg.get("split") != "train"
@@ -546,6 +550,16 @@ class Simulator:
                 max_dens = density_loss(pos, tgt, pos_in, tgt_in, radius=model.particle_radii[0],
                                         win=get_window_func(model.window_dens), use_max=True, row_splits=rs, in_row_splits=in_rs)
                 parts += [torch.sqrt(d_tgt), dens, max_dens, emd_loss(tgt, pos, true_row_splits=trs, pred_row_splits=rs)]
+                # both vel_diff_val: the histograms of target and predicted velocities of all scenes in one call; the int32
+                # counts travel as bits in the float32 concatenation.  Anything but float32 [count, 3] on both sides: the
+                # loop's host code for this frame
+                tvel, pvel = [valid_data[i]["vel"][t] for i in scenes], [results[i][t][1] for i in scenes]
+                hist_offsets = None
+                if all(isinstance(a, np.ndarray) and a.dtype == np.float32 and isinstance(b, torch.Tensor) and b.is_cuda
+                       and b.dtype == torch.float32 and a.shape == tuple(b.shape) == (c, 3) and c > 0
+                       for a, b, c in zip(tvel, pvel, counts)):
+                    _, hist_counts, hist_offsets = ops.hist_pair_ragged(dev(np.concatenate(tvel)), torch.cat(pvel), rs)
+                    parts.append(hist_counts.view(torch.float32))
             # mse for a single step only: one batched model step from the targets' previous frames
             items = [[dev(valid_data[i]["pos"][t - 1]), dev(valid_data[i]["vel"][t - 1])] + list(results[i][t][2:]) for i in scenes]
             pos_sub, _, srs = model.step_batched(items, training=False)
@@ -555,6 +569,8 @@ class Simulator:
             pos_h, cham, sub_h = chunks[0].reshape(n, 3), chunks[1], chunks[-1].reshape(srs[-1], 3)
             if full:
                 cham2, dens_h, max_dens_h, emd_h = chunks[2:6]
+                if hist_offsets is not None:
+                    kl_tp, kl_pt = _kl_pairs(chunks[6].view(np.int32), hist_offsets)
             for k, i in enumerate(scenes):
                 data = valid_data[i]
                 a, b = rs[k], rs[k + 1]
@@ -566,9 +582,12 @@ class Simulator:
                     loss["max_dens_val"] = float(max_dens_h[k])
                     loss["chamfer_val_2"] = float(np.mean(cham2[trs[k]:trs[k + 1]].astype(np.float32)))
                     loss["emd"] = float(emd_h[k])
-                    vel = results[i][t][1]
-                    loss["vel_diff_val"] = compare_dist(data["vel"][t], vel)
-                    loss["vel_diff_val_2"] = compare_dist(vel, data["vel"][t])
+                    if hist_offsets is not None:
+                        loss["vel_diff_val"], loss["vel_diff_val_2"] = float(kl_tp[k]), float(kl_pt[k])
+                    else:
+                        vel = results[i][t][1]
+                        loss["vel_diff_val"] = compare_dist(data["vel"][t], vel)
+                        loss["vel_diff_val_2"] = compare_dist(vel, data["vel"][t])
                 loss["mse_single_val"] = float(np.mean(distance(data["pos"][t], sub_h[srs[k]:srs[k + 1]])))
                 losses[i][t] = loss
         return losses

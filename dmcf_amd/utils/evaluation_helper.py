@@ -6,7 +6,8 @@ arguments):
                             ops.nn_distance (dmcf_nn_distance) instead of a host cKDTree; with row splits, a
                             batch of scenes of different sizes in one call (dmcf_nn_distance_ragged)
   compare_dist      :43-75  KL divergence of two histograms (one bin per ``bin_size`` points, 1e-5 prior); host numpy,
-                            vectorised, the same value as the reference's per-point loop
+                            vectorised, the same value as the reference's per-point loop.  compare_dist_pair: both
+                            directions for a batch of scenes from one GPU call (dmcf_hist_pair_ragged), the same bits
   merge_dicts       :78-85
 
 ``optimal_assignment_distance`` and ``compute_stats`` are not used by run_valid and are not rebuilt.
@@ -69,11 +70,45 @@ def compare_dist(x, y, bin_size=25):
     def hist(v):
         idx = np.clip(((v - min_v) / bin_w).astype("int32"), 0, bin_cnt_per_dim)
         flat = np.ravel_multi_index(tuple(idx.T), shape) if len(idx) else np.zeros(0, dtype=np.int64)
-        return np.bincount(flat, minlength=int(np.prod(shape))).astype(np.float64) + 1e-5
+        return np.bincount(flat, minlength=int(np.prod(shape)))
 
-    px, py = hist(x), hist(y)
+    return _kl_from_counts(hist(x), hist(y))
+
+
+def _kl_from_counts(cx, cy):
+    """The end of :func:`compare_dist`: the bin counts of both sets (any integer or float arrays of one shape) -> KL(x || y) of
+    the two histograms, every bin starting at 1e-5, both normalised (float64)."""
+    px, py = np.asarray(cx).astype(np.float64) + 1e-5, np.asarray(cy).astype(np.float64) + 1e-5
     px, py = px / px.sum(), py / py.sum()
     return float(np.sum(px * np.log(px / py)))
+
+
+def compare_dist_pair(x, y, bin_size=25, row_splits=None):
+    """Both directions of :func:`compare_dist` for a batch of scenes: ``(kl_xy [batch], kl_yx [batch])``, float64 numpy arrays
+    with ``kl_xy[b] == compare_dist(x_b, y_b, bin_size)`` and ``kl_yx[b] == compare_dist(y_b, x_b, bin_size)`` bit for bit.
+
+    ``x`` and ``y`` [n_total, 3] (float32; numpy arrays or device tensors) share ``row_splits`` (None: one item).  The
+    percentiles and the histograms come from ONE ops.hist_pair_ragged call on the GPU -- both directions use the same
+    percentiles and the same two histograms -- and reach the host in one copy of the integer counts; the KL sums are
+    :func:`_kl_from_counts`, the host function's own last lines, so equal counts give equal bits.  Finite inputs only."""
+    from .. import ops
+    dev = next((t.device for t in (x, y) if isinstance(t, torch.Tensor) and t.is_cuda), torch.device("cuda"))
+
+    def to_dev(v):
+        return v.detach().to(dev) if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+
+    _, counts, offsets = ops.hist_pair_ragged(to_dev(x), to_dev(y), row_splits, bin_size)
+    return _kl_pairs(counts.cpu().numpy(), offsets)
+
+
+def _kl_pairs(counts, offsets):
+    """Host counts in the layout of ops.hist_pair_ragged -> (KL(x || y) [batch], KL(y || x) [batch])."""
+    kl_xy, kl_yx = np.empty(len(offsets) - 1), np.empty(len(offsets) - 1)
+    for b in range(len(offsets) - 1):
+        mid = (offsets[b] + offsets[b + 1]) // 2
+        cx, cy = counts[offsets[b]:mid], counts[mid:offsets[b + 1]]
+        kl_xy[b], kl_yx[b] = _kl_from_counts(cx, cy), _kl_from_counts(cy, cx)
+    return kl_xy, kl_yx
 
 
 def merge_dicts(dicts, op, start_val=0):

@@ -26,6 +26,8 @@
  *   EmdLoss / ChamferLoss terms per sample of a training batch   dmcf_emd_ragged_with_levels / dmcf_emd_ragged_backward
  *     (utils/tools/losses.py:401-414)                             (ABI 2.25: the ragged EMD's gradient, 4 launches
  *                                                                 whatever the batch)
+ *   compare_dist per scene of a validation split                 dmcf_hist_pair_ragged (ABI 2.26: percentiles and
+ *     (pipelines/simulator.py:250-251, utils/evaluation_helper.py:43-75)  histograms of all scenes, the host's bits)
  *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
  *                                                                 dmcf_cconv_backward_extents)
  *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
@@ -943,6 +945,39 @@ size_t dmcf_emd_ragged_backward_workspace_bytes(int64_t n_total, const int64_t* 
 int dmcf_emd_ragged_backward(const float* xyz1, int64_t n_total, const int64_t* row_splits1, const float* xyz2, int64_t m_total,
                              const int64_t* row_splits2, int64_t batch, const float* levels, const float* grad_cost,
                              float* grad_xyz1, float* grad_xyz2, void* workspace, size_t workspace_bytes, dmcf_stream_t stream);
+/* The velocity histograms of compare_dist (utils/evaluation_helper.py:43-75) for a RAGGED batch (ABI 2.26): x and y
+ * [n_total, 3] share the HOST int64 row splits [batch + 1] (validated here before anything is enqueued; every item has at
+ * least one row).  Per item b with cnt rows the call writes
+ *   percentiles[b][0][a], percentiles[b][1][a]   the 5th and 95th percentile of the 2 cnt values x[:, a] u y[:, a] as
+ *                                                np.percentile gives them for float32 data: numpy's _lerp in float32 between
+ *                                                the order statistics plan[b].rank[0], [1] (weight gamma[0]) and rank[2], [3]
+ *                                                (weight gamma[1]);
+ *   counts[off_b + f], counts[off_b + bins_b + f] the number of rows of x, and of y, in flat bin f of the (per + 1)^3 grid:
+ *                                                idx_a = clamp(trunc((v_a - min_a) / bin_w_a), 0, per), bin_w_a =
+ *                                                ((max_a - min_a) + 1e-6f) / per with correctly rounded float32 divisions,
+ *                                                f = (idx_0 (per + 1) + idx_1)(per + 1) + idx_2; per == 0: every row in bin 0;
+ * bins_b = (plan[b].per + 1)^3, off_b = 2 (bins_0 + ... + bins_{b-1}); bins_total is their sum and counts has 2 bins_total
+ * entries.  The plan depends on the items' sizes alone, so the host writes it (ops.percentile_plan); it is validated here:
+ * 0 <= per <= 1023, 0 <= rank < 2 cnt, 0 <= gamma <= 1, the bins summing to bins_total.  The order statistics come from a
+ * radix select (8-bit digits, four passes, integer atomics), the counts from integer atomics: all sums are integer sums, two
+ * calls give identical bits, and the results are those of the host function bit for bit.  -0.0 selects as +0.0.  Inputs must
+ * be finite: NaN is NOT looked for and is out of scope (the host function returns NaN percentiles for it); a quotient beyond
+ * int32 saturates into the clamp where the host's cast is platform-defined.
+ * One memset (the selection state in the workspace), one table copy from pageable host memory and 9 launches whatever the
+ * batch; counts is zeroed by the call.  batch < 1 or > 2^26, n_total >= 2^31 - 257, an item without rows, NULL or malformed
+ * splits, a bad plan, any NULL pointer: DMCF_EINVAL; a short workspace: DMCF_EWORKSPACE; all before anything is enqueued.
+ * The workspace query returns 0 for sizes the call refuses. */
+#define DMCF_HIST_TILE_ROWS 1024 /* rows of x and of y a workgroup takes in the digit and count launches */
+typedef struct dmcf_hist_plan {
+    int32_t per;     /* bins per axis minus one: int((cnt // bin_size) ** (1 / 3)) */
+    int32_t rank[4]; /* k5, its upper neighbour, k95, its upper neighbour: 0-based ranks among the 2 cnt values */
+    float gamma[2];  /* the interpolation weights of the two percentiles */
+    int32_t reserved;
+} dmcf_hist_plan;
+size_t dmcf_hist_pair_ragged_workspace_bytes(int64_t n_total, int64_t batch, int64_t bins_total);
+int dmcf_hist_pair_ragged(const float* x, const float* y, int64_t n_total, const int64_t* row_splits, int64_t batch,
+                          const dmcf_hist_plan* plan, int64_t bins_total, float* percentiles, int32_t* counts, void* workspace,
+                          size_t workspace_bytes, dmcf_stream_t stream);
 /* gather_point: grad_inp [n_inp, channels] = sum over s with index[s] == t of grad_out[s, :] (repeated indices sum; indices
  * outside [0, n_inp) contribute nothing). */
 size_t dmcf_gather_point_backward_workspace_bytes(int64_t n_index, int64_t n_inp);

@@ -5,7 +5,8 @@ the batched validation (the pipeline key valid_batched: run_rollout_batched + va
   boundary points -- the scenes of tools/bench_batched_step.py -- with 4 frames each, so 3 evaluated frames per scene;
   once with split "train" (what run_train's validation after every epoch computes: mse_val, chamfer_val, mse_single_val) and
   once with split "valid" (all nine metrics; the batched variant computes emd for all scenes in one dmcf_emd_ragged call per
-  frame, the two vel_diff_val stay per scene in both variants);
+  frame and the two vel_diff_val in one dmcf_hist_pair_ragged call per frame, where the loop calls the host compare_dist
+  twice per scene);
   and, at the operator level, ops.emd called scene after scene on the split's first and last target frames against one
   ops.emd_ragged call for all scenes (no host copy in either; the costs are checked to be bit-identical)
 
@@ -100,6 +101,7 @@ def main():
                  emd_calls_per_frame_looped=calls_l.get("dmcf_emd", 0) / evaluated,
                  emd_calls_per_frame_batched=calls_b.get("dmcf_emd", 0) / evaluated,
                  emd_ragged_calls_per_frame_batched=calls_b.get("dmcf_emd_ragged", 0) / evaluated,
+                 hist_pair_ragged_calls_per_frame_batched=calls_b.get("dmcf_hist_pair_ragged", 0) / evaluated,
                  worst_metric_rel_diff=worst, metrics=list(want))
         res["splits"][split] = r
         rows.append(f"| {split} | {fmt(r['looped_ms_per_frame'])} | {fmt(r['batched_ms_per_frame'])} | "
@@ -128,8 +130,9 @@ def main():
                 f"frame (all scenes: the rollout step and the metrics), device-synchronised; median (min - max) of {args.reps} "
                 "runs, the two variants alternating in one process after a warm-up.  Split \"train\" is the validation "
                 "`run_train` runs after every epoch (mse_val, chamfer_val, mse_single_val); split \"valid\" computes all nine "
-                "metrics; the batched variant computes emd in one `dmcf_emd_ragged` call per frame, and the two vel_diff_val "
-                "stay per scene in both variants.\n\n"
+                "metrics; the batched variant computes emd in one `dmcf_emd_ragged` call per frame and the two vel_diff_val in "
+                f"one `dmcf_hist_pair_ragged` call per frame ({res['splits']['valid']['hist_pair_ragged_calls_per_frame_batched']:g} "
+                "counted), where the loop calls the host `compare_dist` twice per scene.\n\n"
                 "| split | looped, ms per frame | batched, ms per frame | library calls per frame, looped | batched | "
                 "`dmcf_nn_distance` per frame, looped | `dmcf_nn_distance_ragged` per frame, batched | `dmcf_emd` per frame, "
                 "looped | batched | `dmcf_emd_ragged` per frame, batched | worst relative difference of a metric |\n"
@@ -144,8 +147,8 @@ def main():
         if args.baseline:
             with open(args.baseline) as g:
                 base = json.loads(g.read().strip().splitlines()[-1])
-            f.write("\nThe same command on the parent commit in the same session (its batched validation calls `dmcf_emd` once "
-                    "per scene and frame, each call followed by a host copy), against this commit:\n\n"
+            f.write("\nThe same command on the parent commit in the same session (its batched validation calls the host "
+                    "`compare_dist` twice per scene and frame, each call with its device-to-host copy), against this commit:\n\n"
                     "| split | parent, batched ms per frame | this commit, batched ms per frame |\n|---|---|---|\n")
             for split in ("train", "valid"):
                 f.write(f"| {split} | {fmt(base['splits'][split]['batched_ms_per_frame'])} | "
