@@ -261,6 +261,37 @@ class Sph1dParams(ctypes.Structure):
     ]
 
 
+class Camera(ctypes.Structure):
+    """struct dmcf_camera (include/dmcf_hip.h): 80 bytes."""
+    _fields_ = [
+        ("view", ctypes.c_float * 12),
+        ("focal", ctypes.c_float),
+        ("cx", ctypes.c_float),
+        ("cy", ctypes.c_float),
+        ("near", ctypes.c_float),
+        ("orthographic", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
+class SplatLayer(ctypes.Structure):
+    """struct dmcf_splat_layer (include/dmcf_hip.h): 48 bytes."""
+    _fields_ = [
+        ("keys", ctypes.c_void_p),
+        ("xyz", ctypes.c_void_p),
+        ("n_points", ctypes.c_int64),
+        ("frame_stride", ctypes.c_int64),
+        ("radius", ctypes.c_float),
+        ("color_argb", ctypes.c_uint32),
+        ("flags", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+SPLAT_FARTHEST = 1    # DMCF_SPLAT_FARTHEST
+SPLAT_MAX_LAYERS = 4  # DMCF_SPLAT_MAX_LAYERS
+
+
 # names every entry point include/dmcf_hip.h declares (tests/test_abi.py cross-checks against the header)
 SYMBOLS = [
     "dmcf_version", "dmcf_error_string", "dmcf_last_hip_error",
@@ -301,6 +332,7 @@ SYMBOLS = [
     "dmcf_emd_ragged_workspace_bytes", "dmcf_emd_ragged",
     "dmcf_emd_ragged_with_levels", "dmcf_emd_ragged_backward_workspace_bytes", "dmcf_emd_ragged_backward",
     "dmcf_hist_pair_ragged_workspace_bytes", "dmcf_hist_pair_ragged",
+    "dmcf_splat_depth", "dmcf_splat_shade",
 ]
 
 
@@ -587,6 +619,13 @@ def lib():
     L.dmcf_hist_pair_ragged.restype = c.c_int
     L.dmcf_hist_pair_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.POINTER(HistPlan), c.c_int64,
                                         c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    # the depth-tested sphere splat of the 3-D renderer (ABI 2.27)
+    L.dmcf_splat_depth.restype = c.c_int
+    L.dmcf_splat_depth.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_float, c.POINTER(Camera), c.c_int32,
+                                   c.c_int32, c.c_int32, c.c_void_p, c.c_void_p]
+    L.dmcf_splat_shade.restype = c.c_int
+    L.dmcf_splat_shade.argtypes = [c.POINTER(SplatLayer), c.c_int32, c.POINTER(Camera), c.c_float, c.c_float, c.c_int32, c.c_int32,
+                                   c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p]
     _lib = L
     return L
 

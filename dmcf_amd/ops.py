@@ -3416,6 +3416,206 @@ def rgba8(image):
     return torch.cat([q, torch.full_like(q[..., :1], 255)], dim=-1)
 
 
+Camera = collections.namedtuple("Camera", ["view", "focal", "cx", "cy", "near", "orthographic"])
+Camera.__doc__ = """struct dmcf_camera (include/dmcf_hip.h): ``view`` 12 floats, the row-major 3 x 4 world -> camera matrix (the
+camera looks along +z, x is right, y is down); ``focal`` pixels per world unit at z = 1 (per world unit when ``orthographic``);
+``(cx, cy)`` the principal point; ``near`` >= 0.  :func:`look_at` builds one."""
+
+SplatLayer = collections.namedtuple("SplatLayer", ["keys", "xyz", "radius", "color_argb", "farthest"], defaults=(False,))
+SplatLayer.__doc__ = """One point group of :func:`splat_shade`: the ``keys`` :func:`splat_depth` left for ``xyz`` at ``radius``
+(with the same ``farthest``), and the group's colour 0xAARRGGBB."""
+
+
+def look_at(eye, target, up, width, height, fov_deg=35.0, ortho_height=None, near=1e-3):
+    """A :class:`Camera` at ``eye`` looking at ``target`` with ``up`` pointing up in the image, for a ``width`` x ``height``
+    image: the principal point is the image centre; ``focal = 0.5 height / tan(fov / 2)`` (``fov_deg`` the vertical field of
+    view), or ``height / ortho_height`` for an orthographic camera showing ``ortho_height`` world units from top to bottom.
+    The view matrix is formed in float64 and rounded to float32 once.  Degenerate input (``eye == target``, ``up`` parallel to
+    the view direction, values that are not finite) is a ValueError."""
+    eye, target, up = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (eye, target, up))
+    if eye.shape != (3,) or target.shape != (3,) or up.shape != (3,):
+        raise ValueError("eye, target and up must have 3 components each")
+    if not (np.isfinite(eye).all() and np.isfinite(target).all() and np.isfinite(up).all()):
+        raise ValueError("eye, target and up must be finite")
+    width, height, near = int(width), int(height), float(near)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"width and height must be positive, got {width} x {height}")
+    if not (np.isfinite(near) and near >= 0.0):
+        raise ValueError(f"near must be finite and >= 0, got {near}")
+    forward = target - eye
+    dist = np.linalg.norm(forward)
+    if not dist > 0.0:
+        raise ValueError("eye and target coincide: there is no view direction")
+    forward = forward / dist
+    right = np.cross(forward, up)
+    rn, un = np.linalg.norm(right), np.linalg.norm(up)
+    if not (un > 0.0 and rn > 1e-12 * un):
+        raise ValueError("up is zero or parallel to the view direction")
+    right = right / rn
+    down = np.cross(forward, right)  # x right, y down, z forward: a right-handed frame
+    rows = np.stack([right, down, forward])
+    view = np.concatenate([rows, -(rows @ eye)[:, None]], axis=1)
+    if ortho_height is None:
+        fov = float(fov_deg)
+        if not 0.0 < fov < 180.0:
+            raise ValueError(f"fov_deg must lie in (0, 180), got {fov_deg}")
+        focal = 0.5 * height / np.tan(np.deg2rad(fov) / 2.0)
+    else:
+        if not (np.isfinite(ortho_height) and ortho_height > 0.0):
+            raise ValueError(f"ortho_height must be positive, got {ortho_height}")
+        focal = height / float(ortho_height)
+    f32 = lambda v: float(np.float32(v))  # noqa: E731
+    return Camera(tuple(f32(v) for v in view.reshape(-1)), f32(focal), f32(0.5 * width), f32(0.5 * height), f32(near),
+                  ortho_height is not None)
+
+
+def _camera_struct(camera):
+    if not isinstance(camera, Camera):
+        raise TypeError("camera must be an ops.Camera (see ops.look_at)")
+    if len(camera.view) != 12:
+        raise ValueError(f"camera.view must hold 12 values (3 x 4, row-major), got {len(camera.view)}")
+    c = _lib.Camera()
+    c.view = (ctypes.c_float * 12)(*[float(v) for v in camera.view])
+    c.focal, c.cx, c.cy, c.near = float(camera.focal), float(camera.cx), float(camera.cy), float(camera.near)
+    c.orthographic = 1 if camera.orthographic else 0
+    vals = list(c.view) + [c.focal, c.cx, c.cy, c.near]
+    if not (np.isfinite(vals).all() and c.focal > 0.0 and c.near >= 0.0):
+        raise ValueError("camera: every value must be finite, focal > 0 and near >= 0")
+    return c
+
+
+def _splat_sizes(width, height, min_px):
+    width, height, min_px = int(width), int(height), float(min_px)
+    if width <= 0 or height <= 0 or width > 32768 or height > 32768:
+        raise ValueError(f"width and height must lie in [1, 32768], got {width} x {height}")
+    if not (np.isfinite(min_px) and min_px >= 0.0):
+        raise ValueError(f"min_px must be finite and >= 0, got {min_px}")
+    return width, height, min_px
+
+
+def _splat_points(xyz, name):
+    if not isinstance(xyz, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor")
+    if xyz.dim() not in (2, 3) or xyz.shape[-1] != 3:
+        raise ValueError(f"{name} must have shape [F, N, 3] or [N, 3], got {tuple(xyz.shape)}")
+    return _dev_f32(xyz, name)
+
+
+def _splat_keys(keys, name, device, shape):
+    if not isinstance(keys, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor")
+    if keys.dtype != torch.int64:
+        raise TypeError(f"{name} must be int64 (the uint64 keys' bits), got {keys.dtype}")
+    if not keys.is_cuda:
+        raise _lib.DmcfError(f"{name} is on {keys.device}: the splat runs on the GPU only (no CPU fallback)")
+    if keys.device != device:
+        raise ValueError(f"{name} is on {keys.device}, the points on {device}")
+    if not keys.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if keys.dim() != 3 or (shape is not None and tuple(keys.shape[1:]) != shape):
+        want = f"[F, {shape[0]}, {shape[1]}]" if shape is not None else "[F, H, W]"
+        raise ValueError(f"{name} must have shape {want}, got {tuple(keys.shape)}")
+    return keys
+
+
+def splat_depth(xyz, radius, camera, width, height, farthest=False, min_px=0.75, out=None):
+    """The depth pass of the sphere splat (dmcf_splat_depth; pixel model in include/dmcf_hip.h): per pixel the key
+    ``(bits(z) << 32) | index`` of the nearest sphere of ``xyz`` -- of the farthest one, with the depth word complemented, when
+    ``farthest`` -- minimised into ``out``.  ``xyz``: float32 CUDA ``[F, N, 3]`` (frame f's points into frame f) or ``[N, 3]``
+    (the same points into every frame); ``radius`` in world units; ``min_px`` the smallest radius in pixels a sphere is drawn
+    with.  ``out``: int64 ``[F, H, W]`` holding the uint64 keys' bits, -1 = empty; it fixes the frame count, is NOT cleared (so
+    several groups can share it), and is created filled with -1 when None.  Returns ``out``.  One launch, no host read."""
+    L = _lib.lib()
+    width, height, min_px = _splat_sizes(width, height, min_px)
+    cam = _camera_struct(camera)
+    xyz = _splat_points(xyz, "xyz")
+    if out is None:
+        frames = xyz.shape[0] if xyz.dim() == 3 else 1
+        out = torch.full((frames, height, width), -1, dtype=torch.int64, device=xyz.device)
+    else:
+        _splat_keys(out, "out", xyz.device, (height, width))
+    frames = out.shape[0]
+    if xyz.dim() == 3 and xyz.shape[0] != frames:
+        raise ValueError(f"xyz holds {xyz.shape[0]} frames, out {frames}")
+    if frames > 65535:
+        raise ValueError(f"at most 65535 frames per call, got {frames}")
+    n = xyz.shape[-2]
+    stride = n if xyz.dim() == 3 else 0
+    radius = float(radius)
+    if n == 0 or frames == 0 or not (np.isfinite(radius) and radius > 0.0):
+        return out  # nothing is splatted (the library would not launch either)
+    _lib.check(L.dmcf_splat_depth(_ptr(xyz), n, frames, stride, radius, min_px, ctypes.byref(cam), width, height,
+                                  _lib.SPLAT_FARTHEST if farthest else 0, _ptr(out), _stream()), "dmcf_splat_depth")
+    return out
+
+
+def splat_shade(layers, camera, width, height, out=None, ambient=0.3, min_px=0.75, return_depth=False):
+    """The shade pass of the sphere splat (dmcf_splat_shade): per pixel the layer with the smallest depth wins (ties: the
+    earlier layer), and its sphere is shaded ``ambient + (1 - ambient) nz`` and composited with the layer colour's alpha into
+    ``out``, float32 RGB ``[F, H, W, 3]`` in [0, 1], in place; ``out=None``: a new white image.  ``layers``: up to 4
+    :class:`SplatLayer`, each with the ``xyz``, ``radius`` and ``farthest`` its ``keys`` were made with; ``camera`` and
+    ``min_px`` as in those calls.  Pixels without a sample keep what ``out`` holds.  Returns ``out``, or ``(out, depth)`` with
+    ``depth`` float32 ``[F, H, W]`` (+inf where there is no sample) when ``return_depth``.  One launch.  ``ops.rgba8`` turns
+    the result into 8-bit RGBA."""
+    L = _lib.lib()
+    layers = list(layers)
+    if len(layers) > _lib.SPLAT_MAX_LAYERS:
+        raise ValueError(f"at most {_lib.SPLAT_MAX_LAYERS} layers per call, got {len(layers)}")
+    if not layers and out is None:
+        raise ValueError("splat_shade needs a layer or an image to tell the device and the frame count")
+    width, height, min_px = _splat_sizes(width, height, min_px)
+    ambient = float(ambient)
+    if not 0.0 <= ambient <= 1.0:
+        raise ValueError(f"ambient must lie in [0, 1], got {ambient}")
+    cam = _camera_struct(camera)
+    recs = (_lib.SplatLayer * max(len(layers), 1))()
+    keep = []  # (tensors whose pointers sit in recs)
+    device = out.device if isinstance(out, torch.Tensor) else None
+    frames = None
+    for j, layer in enumerate(layers):
+        if not isinstance(layer, SplatLayer):
+            raise TypeError(f"layers[{j}] must be an ops.SplatLayer")
+        xyz = _splat_points(layer.xyz, f"layers[{j}].xyz")
+        device = xyz.device if device is None else device
+        keys = _splat_keys(layer.keys, f"layers[{j}].keys", device, (height, width))
+        if xyz.device != device:
+            raise ValueError(f"layers[{j}].xyz is on {xyz.device}, expected {device}")
+        frames = keys.shape[0] if frames is None else frames
+        if keys.shape[0] != frames or (xyz.dim() == 3 and xyz.shape[0] != frames):
+            raise ValueError(f"layers[{j}]: {keys.shape[0]} frames of keys, {tuple(xyz.shape)} points, expected {frames} frames")
+        color = int(layer.color_argb)
+        if not 0 <= color <= 0xFFFFFFFF:
+            raise ValueError(f"layers[{j}].color_argb must be a 32-bit ARGB value, got {color:#x}")
+        r = recs[j]
+        r.keys, r.xyz = keys.data_ptr(), xyz.data_ptr()
+        r.n_points = xyz.shape[-2]
+        r.frame_stride = r.n_points if xyz.dim() == 3 else 0
+        r.radius, r.color_argb = float(layer.radius), color
+        r.flags = _lib.SPLAT_FARTHEST if layer.farthest else 0
+        keep.append((keys, xyz))
+    if out is None:
+        out = torch.ones((frames, height, width, 3), dtype=torch.float32, device=device)
+    else:
+        _dev_f32(out, "out")
+        if out.device != device:
+            raise ValueError(f"out is on {out.device}, the layers on {device}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous (it is written in place)")
+        if out.dim() != 4 or tuple(out.shape[1:]) != (height, width, 3):
+            raise ValueError(f"out must have shape [F, {height}, {width}, 3], got {tuple(out.shape)}")
+        if frames is not None and out.shape[0] != frames:
+            raise ValueError(f"out holds {out.shape[0]} frames, the layers {frames}")
+    frames = out.shape[0]
+    if frames > 65535:
+        raise ValueError(f"at most 65535 frames per call, got {frames}")
+    depth = torch.empty((frames, height, width), dtype=torch.float32, device=out.device) if return_depth else None
+    if frames:
+        _lib.check(L.dmcf_splat_shade(recs, len(layers), ctypes.byref(cam), min_px, ambient, width, height, frames, _ptr(out),
+                                      _ptr(depth), _stream()), "dmcf_splat_shade")
+    del keep
+    return (out, depth) if return_depth else out
+
+
 SPH1D_MAX_POINTS = 64  # dmcf_sph1d_rollout: one 64-lane wavefront per scene, lane = point
 SPH1D_LAUNCH_ITERS = 100_000  # worst-case solver iterations (frames * max_iter) one launch may cover: about 1 s at 64 points
 

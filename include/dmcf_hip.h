@@ -28,6 +28,8 @@
  *                                                                 whatever the batch)
  *   compare_dist per scene of a validation split                 dmcf_hist_pair_ragged (ABI 2.26: percentiles and
  *     (pipelines/simulator.py:250-251, utils/evaluation_helper.py:43-75)  histograms of all scenes, the host's bits)
+ *   (no reference counterpart: the reference renders 2-D         dmcf_splat_depth / dmcf_splat_shade (ABI 2.27: a
+ *     results only, utils/draw_sim2d.py)                           depth-tested sphere splat for 3-D result files)
  *   continuous_conv with extents [n_out,1] (:397-399)            dmcf_cconv_forward_extents (gradients:
  *                                                                 dmcf_cconv_backward_extents)
  *   continuous_conv between grid_pos lattices                    dmcf_lattice_conv_forward (gradients, ABI 2.16:
@@ -1126,6 +1128,78 @@ int dmcf_raster_count(const float* xy, int64_t n_points, int64_t n_frames, int64
 int dmcf_raster_discs(const float* xy, int64_t n_points, int64_t n_frames, int64_t frame_stride, float radius, uint32_t color_argb,
                       int32_t width, int32_t height, float* image, void* workspace, size_t workspace_bytes, float* bins,
                       int64_t bin_capacity, dmcf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth-tested sphere splat of the 3-D renderer (ABI 2.27; dmcf_amd/csrc/splat.hip, dmcf_amd/utils/draw_sim3d.py; no reference
+ * counterpart).  Every point is a sphere of world radius r seen through a camera; a DEPTH pass per point group records, per
+ * pixel, which sphere is visible, in a uint64 key; one SHADE pass over up to DMCF_SPLAT_MAX_LAYERS groups writes the image.
+ *
+ * Camera (struct dmcf_camera, sizeof = 80): view is a row-major 3 x 4 matrix, world -> camera; the camera looks along +z, x is
+ * right, y is DOWN (as image rows are).  focal: pixels per world unit at z = 1 (perspective), or pixels per world unit
+ * (orthographic != 0).  (cx, cy): the principal point in pixels.  near >= 0.  All values finite, focal > 0 (else DMCF_EINVAL).
+ *
+ * Pixel model.  Every operation below is ONE float32 round-to-nearest operation, un-fused, in the order written (a * b + c is a
+ * product, rounded, then a sum, rounded; quotients and square roots are the correctly rounded IEEE ones), so that a float32
+ * restatement reproduces every bit (tests/splat_ref.py):
+ *   centre c = (x, y, z), row i of view = (v_i0, v_i1, v_i2, v_i3):
+ *     xc = ((v00 x + v01 y) + v02 z) + v03        yc, zc alike from rows 1 and 2
+ *     m  = focal / zc  (perspective)   or   m = focal  (orthographic)
+ *     sx = cx + m xc        sy = cy + m yc
+ *     R  = max(m r, min_px)        R2 = R R
+ *   pixel (px, py) (column, row), its centre at (px + 0.5, py + 0.5) (exact in float32):
+ *     dx = (px + 0.5) - sx      dy = (py + 0.5) - sy      d2 = dx dx + dy dy
+ *     the sphere covers the pixel iff d2 < R2
+ *     z  = zc - sqrt(R2 - d2) / m          (the impostor: the sphere is orthographic within itself)
+ *   the sample is dropped when z is not finite or z <= near; the sphere is skipped when x, y or z is not finite or
+ *   zc <= near; footprints are clipped to the image.  min_px (finite, >= 0) keeps sub-pixel spheres visible: with
+ *   R >= 0.75 > sqrt(1/2) every on-screen sphere covers at least one pixel centre.
+ *
+ * dmcf_splat_depth: for every sample  atomicMin(keys[f, py, px], key)  with
+ *     key = (uint64(bits(z)) << 32) | index            the NEAREST sphere, or with DMCF_SPLAT_FARTHEST
+ *     key = (uint64(~bits(z)) << 32) | index           the FARTHEST one;
+ *   z > near >= 0, so bits(z) orders as z does; index is the point's index within its frame.  An all-ones key means "empty":
+ *   the CALLER initialises keys (the call never clears them, so several groups can be splatted into one buffer).  A minimum
+ *   over integers is associative and commutative: the key map is the same bits whatever the launch geometry or the arrival
+ *   order, and equal depths go to the lowest index.  No float atomics, no sort, no workspace, one launch.
+ *   xyz: float32 [F, n, 3], frame f's points at xyz + 3 f frame_stride; frame_stride = 0: the same n points into every frame;
+ *   otherwise frame_stride >= n.  keys: uint64 [F, H, W], 8-byte aligned.  Limits (DMCF_EINVAL beyond): 1 <= W, H <= 32768,
+ *   F <= 65535, n < 2^31.  n = 0, F = 0, or a radius that is not finite or <= 0: nothing is launched, keys stay as they are.
+ *
+ * dmcf_splat_shade: per pixel, every layer's non-empty key is decoded to its depth (the high word, complemented first for a
+ *   FARTHEST layer) and the layer with the smallest depth wins; equal depths go to the lowest layer number.  For the winning
+ *   sphere (xyz, radius of ITS layer) sx, sy, R, R2, dx, dy, d2 are recomputed as above, then
+ *     nz = sqrt(max(R2 - d2, 0)) / R        shade = ambient + (1 - ambient) nz          (a headlight Lambert term)
+ *     C  = C (1 - a) + (colour shade) a     per channel, a = alpha / 255, colour = (R, G, B) / 255 of color_argb (0xAARRGGBB)
+ *   image: float32 [F, H, W, 3], composited in place; a pixel without a sample keeps its bits.  depth: float32 [F, H, W] or
+ *   NULL; it receives the winning depth, +inf where there is no sample.  0 <= ambient <= 1.  One lane per pixel, one launch.
+ *   A layer whose n_points is 0 or whose radius is not finite or <= 0 is ignored; more than DMCF_SPLAT_MAX_LAYERS layers is
+ *   DMCF_EINVAL.  The camera, min_px and each layer's xyz / n_points / frame_stride / radius must be those of the depth calls.
+ * ---------------------------------------------------------------------------------------------- */
+#define DMCF_SPLAT_FARTHEST 1
+#define DMCF_SPLAT_MAX_LAYERS 4
+typedef struct dmcf_camera {
+    float view[12];       /* row-major 3 x 4, world -> camera (+z forward, x right, y down) */
+    float focal;          /* pixels per world unit at z = 1, or per world unit when orthographic */
+    float cx, cy;         /* principal point, pixels */
+    float near;           /* >= 0 */
+    int32_t orthographic; /* 0: perspective */
+    int32_t reserved[3];  /* 0; sizeof(dmcf_camera) = 80 */
+} dmcf_camera;
+typedef struct dmcf_splat_layer {
+    const uint64_t* keys; /* [F, H, W], as dmcf_splat_depth left them */
+    const float* xyz;     /* the points of that depth call */
+    int64_t n_points;
+    int64_t frame_stride;
+    float radius;
+    uint32_t color_argb;
+    int32_t flags;        /* DMCF_SPLAT_FARTHEST as in the depth call */
+    int32_t reserved;     /* 0; sizeof(dmcf_splat_layer) = 48 */
+} dmcf_splat_layer;
+
+int dmcf_splat_depth(const float* xyz, int64_t n_points, int64_t n_frames, int64_t frame_stride, float radius, float min_px,
+                     const dmcf_camera* camera, int32_t width, int32_t height, int32_t flags, uint64_t* keys, dmcf_stream_t stream);
+int dmcf_splat_shade(const dmcf_splat_layer* layers, int32_t n_layers, const dmcf_camera* camera, float min_px, float ambient,
+                     int32_t width, int32_t height, int64_t n_frames, float* image, float* depth, dmcf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The 1-D SPH solver that generates the column datasets (ABI 2.17; dmcf_amd/csrc/sph1d.hip): SPH1D.step of
