@@ -122,33 +122,19 @@ def test_block_diagonal_tile_mask():
     assert ops.block_diagonal_tile_mask([(0, 40, 0, 16)]) == 0 and ops.block_diagonal_tile_mask([(0, 4, 0, 80)]) == 0
 
 
-def test_generated_splat_sources_are_current(tmp_path, monkeypatch):
-    """dmcf_amd/csrc/cconv_*_splat*.inc and cconv_pair_*.inc are generated (tools/gen_cls_splat.py, tools/gen_z3_splat.py, tools/gen_pair_splat.py) and committed: the
-    committed text must be what the generators write."""
+def test_generated_splat_sources_are_current(tmp_path):
+    """The .inc files of dmcf_amd/csrc that the splat kernels include are generated (tools/gen_*_splat.py, each with a
+    PRODUCT_FILES list and write_product(outdir)) and committed: the committed text must be what the generators write."""
     import importlib.util
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    csrc = os.path.join(root, "dmcf_amd", "csrc")
-    names = ["cconv_cls_splat.inc", "cconv_cls_splat8.inc", "cconv_z3_splat.inc"]
-    committed = {n: open(os.path.join(csrc, n)).read() for n in names}
-    real_join = os.path.join
-    # the generators write next to the kernels: send their output to a scratch directory instead
-    monkeypatch.setattr(os.path, "join", lambda *a: real_join(str(tmp_path), a[-1]) if a[-1] in names else real_join(*a))
-    for gen in ("gen_cls_splat", "gen_z3_splat"):
-        spec = importlib.util.spec_from_file_location(gen, real_join(root, "tools", gen + ".py"))
-        spec.loader.exec_module(importlib.util.module_from_spec(spec))
-    for n in names:
-        assert open(real_join(str(tmp_path), n)).read() == committed[n], n
-    # tools/gen_pair_splat.py (cconv_pair.hip) takes its output directory as an argument
-    spec = importlib.util.spec_from_file_location("gen_pair_splat", real_join(root, "tools", "gen_pair_splat.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    gen.write_product(str(tmp_path))
-    for n in gen.PRODUCT_FILES:
-        assert open(real_join(str(tmp_path), n)).read() == open(real_join(csrc, n)).read(), n
-    spec = importlib.util.spec_from_file_location("gen_p16_splat", real_join(root, "tools", "gen_p16_splat.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    gen.write_product(str(tmp_path))
-    for n in gen.PRODUCT_FILES:
-        assert open(real_join(str(tmp_path), n)).read() == open(real_join(csrc, n)).read(), n
+    csrc, tools = os.path.join(root, "dmcf_amd", "csrc"), os.path.join(root, "tools")
+    names = sorted(f[:-3] for f in os.listdir(tools) if f.startswith("gen_") and f.endswith("_splat.py"))
+    assert {"gen_cls_splat", "gen_z3_splat", "gen_pair_splat"} <= set(names)
+    for name in names:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(tools, name + ".py"))
+        gen = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(gen)
+        gen.write_product(str(tmp_path))
+        for n in gen.PRODUCT_FILES:
+            assert open(os.path.join(str(tmp_path), n)).read() == open(os.path.join(csrc, n)).read(), n
