@@ -292,48 +292,157 @@ SPLAT_FARTHEST = 1    # DMCF_SPLAT_FARTHEST
 SPLAT_MAX_LAYERS = 4  # DMCF_SPLAT_MAX_LAYERS
 
 
-# names every entry point include/dmcf_hip.h declares (tests/test_abi.py cross-checks against the header)
-SYMBOLS = [
-    "dmcf_version", "dmcf_error_string", "dmcf_last_hip_error",
-    "dmcf_frs_workspace_bytes", "dmcf_frs_build", "dmcf_frs_count", "dmcf_frs_write", "dmcf_frs_search_padded", "dmcf_frs_window_sum",
-    "dmcf_radius_search_count", "dmcf_radius_search_write",
-    "dmcf_cconv_workspace_bytes", "dmcf_cconv_forward", "dmcf_cconv_kernel_name",
-    "dmcf_cconv_forward_extents", "dmcf_cconv_extents_kernel_name",
-    "dmcf_invert_neighbors_list_workspace_bytes", "dmcf_invert_neighbors_list",
-    "dmcf_cconv_backward_workspace_bytes", "dmcf_cconv_backward", "dmcf_cconv_backward_kernel_names",
-    "dmcf_cconv_backward_extents", "dmcf_cconv_backward_extents_kernel_names",
-    "dmcf_cconv_scatter_plan_bytes", "dmcf_cconv_scatter_plan", "dmcf_cconv_scatter_workspace_bytes", "dmcf_cconv_scatter_forward",
-    "dmcf_cconv_scatter_backward_workspace_bytes", "dmcf_cconv_scatter_backward",
-    "dmcf_lattice_conv_workspace_bytes", "dmcf_lattice_conv_forward",
-    "dmcf_lattice_conv_batch_workspace_bytes", "dmcf_lattice_conv_forward_batch",
-    "dmcf_lattice_conv_backward_workspace_bytes", "dmcf_lattice_conv_backward",
-    "dmcf_reduce_subarrays_sum", "dmcf_points_aabb_workspace_bytes", "dmcf_points_aabb", "dmcf_dense_forward",
-    "dmcf_fps_workspace_bytes", "dmcf_farthest_point_sample", "dmcf_gather_point",
-    "dmcf_grid_pos_workspace_bytes", "dmcf_grid_pos_bounds", "dmcf_grid_pos_count", "dmcf_grid_pos_write",
-    "dmcf_ghost_workspace_bytes", "dmcf_ghost_count", "dmcf_ghost_write",
-    "dmcf_nn_distance_workspace_bytes", "dmcf_nn_distance", "dmcf_approx_match_workspace_bytes", "dmcf_approx_match",
-    "dmcf_match_cost_workspace_bytes", "dmcf_match_cost", "dmcf_emd_workspace_bytes", "dmcf_emd",
-    "dmcf_neighbor_dense_forward", "dmcf_neighbor_dense_backward_workspace_bytes", "dmcf_neighbor_dense_backward",
-    "dmcf_neighbor_dense_kernel_names", "dmcf_adam_step_workspace_bytes", "dmcf_adam_step", "dmcf_adam_step_kernel_names",
-    "dmcf_raster_workspace_bytes", "dmcf_raster_count", "dmcf_raster_discs",
-    "dmcf_nn_distance_backward_workspace_bytes", "dmcf_nn_distance_backward", "dmcf_match_cost_backward_workspace_bytes",
-    "dmcf_match_cost_backward", "dmcf_emd_with_levels", "dmcf_emd_backward_workspace_bytes", "dmcf_emd_backward",
-    "dmcf_gather_point_backward_workspace_bytes", "dmcf_gather_point_backward",
-    "dmcf_frs_window_sum_backward",
-    "dmcf_sph1d_rollout",
-    "dmcf_sparse_conv_forward", "dmcf_sparse_conv_backward_workspace_bytes", "dmcf_sparse_conv_backward",
-    "dmcf_sparse_conv_kernel_names",
-    "dmcf_frs_workspace_bytes_batched", "dmcf_frs_build_batched", "dmcf_frs_count_batched", "dmcf_frs_write_batched",
-    "dmcf_radius_search_count_batched", "dmcf_radius_search_write_batched",
-    "dmcf_grid_pos_workspace_bytes_batched", "dmcf_grid_pos_bounds_batched", "dmcf_grid_pos_count_batched",
-    "dmcf_grid_pos_write_batched", "dmcf_points_aabb_batched",
-    "dmcf_frs_window_sum_batched", "dmcf_frs_window_sum_backward_batched",
-    "dmcf_nn_distance_ragged_workspace_bytes", "dmcf_nn_distance_ragged",
-    "dmcf_emd_ragged_workspace_bytes", "dmcf_emd_ragged",
-    "dmcf_emd_ragged_with_levels", "dmcf_emd_ragged_backward_workspace_bytes", "dmcf_emd_ragged_backward",
-    "dmcf_hist_pair_ragged_workspace_bytes", "dmcf_hist_pair_ragged",
-    "dmcf_splat_depth", "dmcf_splat_shade",
-]
+_int, _i32, _u32, _i64, _f32, _size = (ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_float,
+                                        ctypes.c_size_t)
+_ptr, _str, _P = ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER  # (_ptr: device and host pointers, and dmcf_stream_t)
+
+# signatures several entry points share: (restype, argtypes) where they are the same call, the leading arguments otherwise
+_BYTES_N = (_size, (_i64,))                 # (n) -> size_t
+_BYTES_NM = (_size, (_i64, _i64))           # (n, m) -> size_t
+_BYTES_BNM = (_size, (_i64, _i64, _i64))    # (b, n, m) -> size_t, and the other queries over three counts
+_BYTES_RAGGED = (_size, (_i64, _P(_i64), _i64, _P(_i64), _i64))  # (n_total, HOST row_splits1, m_total, HOST row_splits2, batch)
+_ITEMS = (_ptr, _i64)                       # row_splits, batch: what a *_batched entry point takes after (points, n)
+_FRS = (_ptr, _i64, _i64, _f32, _int, _ptr, _size)  # queries, n_queries, n_points, radius, flags, workspace, workspace_bytes
+_FRS_BATCHED = (_ptr, _i64, *_ITEMS, _i64, _f32, _int, _ptr, _size)
+_RADIUS = (_ptr, _i64, _i64, _ptr, _f32, _int, _ptr, _size)  # queries, n_queries, n_points, radii, max_radius, flags, workspace, ..
+_RADIUS_BATCHED = (_ptr, _i64, *_ITEMS, _i64, _ptr, _f32, _int, _ptr, _size)
+_WINDOW_SUM = (_ptr, _i64, _i64, _f32, _int, _int)  # queries, n_queries, n_points, radius, flags, window
+_WINDOW_SUM_BATCHED = (_ptr, _i64, *_ITEMS, _i64, _f32, _int, _int)
+_GRID = (_P(_f32), _int, _int, _f32, _ptr, _size, _ptr, _i64)  # HOST voxel_size, centralize, pad, hyst, workspace, .., cell_table, ..
+_GHOST = (_ptr, _i64, _ptr, _i32, _ptr, _i32, _ptr)  # points, n, boxes, n_boxes, widths2, n_widths, totals / rows
+_PADDED = (_ptr, _ptr, _i64, _i64, _i64)    # xyz1, xyz2, b, n, m: the metrics on padded batches
+_RAGGED = (_ptr, _i64, _P(_i64), _ptr, _i64, _P(_i64), _i64)  # xyz1, n_total, HOST row_splits1, xyz2, m_total, HOST row_splits2, batch
+_COUNTS = (_P(_i32), _P(_i32))              # HOST count1, count2 (or NULL)
+_MATCH = (_int, (*_PADDED, *_COUNTS, _ptr, _ptr, _size, _ptr))  # .., match / cost, workspace, workspace_bytes, stream
+_NAME = (_str, _size)                       # name(s), name_bytes: the diagnostics' output
+_RASTER = (_ptr, _i64, _i64, _i64, _f32)    # xy, n_points, n_frames, frame_stride, radius
+
+# Every entry point include/dmcf_hip.h declares, in the header's order: name -> (restype, argtypes).  tests/test_abi.py holds
+# the header, this table and the struct mirrors above together.
+PROTOTYPES = {
+    "dmcf_version": (_int, ()),
+    "dmcf_error_string": (_str, (_int,)),
+    "dmcf_last_hip_error": (_int, ()),
+    "dmcf_frs_workspace_bytes": _BYTES_NM,
+    "dmcf_frs_build": (_int, (_ptr, _i64, _f32, _ptr, _size, _ptr)),
+    "dmcf_frs_count": (_int, (*_FRS, _ptr, _ptr)),
+    "dmcf_frs_write": (_int, (*_FRS, _ptr, _ptr, _ptr, _i64, _ptr)),
+    "dmcf_frs_search_padded": (_int, (*_FRS, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr)),
+    "dmcf_frs_window_sum": (_int, (*_WINDOW_SUM, _ptr, _size, _ptr, _ptr)),
+    # gradient of the window sum (ABI 2.14)
+    "dmcf_frs_window_sum_backward": (_int, (*_WINDOW_SUM, _ptr, _ptr, _ptr, _size, _ptr, _ptr)),
+    "dmcf_radius_search_count": (_int, (*_RADIUS, _ptr, _ptr)),
+    "dmcf_radius_search_write": (_int, (*_RADIUS, _ptr, _ptr, _ptr, _i64, _ptr)),
+    # both searches with points_row_splits / queries_row_splits (ABI 2.20)
+    "dmcf_frs_workspace_bytes_batched": _BYTES_BNM,
+    "dmcf_frs_build_batched": (_int, (_ptr, _i64, *_ITEMS, _f32, _ptr, _size, _ptr)),
+    "dmcf_frs_count_batched": (_int, (*_FRS_BATCHED, _ptr, _ptr)),
+    "dmcf_frs_write_batched": (_int, (*_FRS_BATCHED, _ptr, _ptr, _ptr, _i64, _ptr)),
+    "dmcf_radius_search_count_batched": (_int, (*_RADIUS_BATCHED, _ptr, _ptr)),
+    "dmcf_radius_search_write_batched": (_int, (*_RADIUS_BATCHED, _ptr, _ptr, _ptr, _i64, _ptr)),
+    # the window sum and its gradient with row splits (ABI 2.22)
+    "dmcf_frs_window_sum_batched": (_int, (*_WINDOW_SUM_BATCHED, _ptr, _size, _ptr, _ptr, _ptr)),
+    "dmcf_frs_window_sum_backward_batched": (_int, (*_WINDOW_SUM_BATCHED, _ptr, _ptr, _ptr, _size, _ptr, _ptr)),
+    "dmcf_cconv_workspace_bytes": (_size, (_P(CconvArgs),)),
+    "dmcf_cconv_forward": (_int, (_P(CconvArgs), _ptr, _size, _ptr)),
+    "dmcf_cconv_kernel_name": (_int, (_P(CconvArgs), *_NAME)),
+    "dmcf_cconv_forward_extents": (_int, (_P(CconvArgs), _ptr, _ptr, _size, _ptr)),
+    "dmcf_cconv_extents_kernel_name": (_int, (_P(CconvArgs), *_NAME)),
+    "dmcf_invert_neighbors_list_workspace_bytes": _BYTES_N,
+    "dmcf_invert_neighbors_list": (_int, (_i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_cconv_backward_workspace_bytes": (_size, (_P(CconvArgs), _P(CconvBackwardArgs))),
+    "dmcf_cconv_backward": (_int, (_P(CconvArgs), _P(CconvBackwardArgs), _ptr, _size, _ptr)),
+    "dmcf_cconv_backward_kernel_names": (_int, (_P(CconvArgs), _P(CconvBackwardArgs), *_NAME)),
+    # gradients through per-point extents (ABI 2.15)
+    "dmcf_cconv_backward_extents": (_int, (_P(CconvArgs), _P(CconvBackwardArgs), _ptr, _ptr, _size, _ptr)),
+    "dmcf_cconv_backward_extents_kernel_names": (_int, (_P(CconvArgs), _P(CconvBackwardArgs), *_NAME)),
+    "dmcf_cconv_scatter_plan_bytes": _BYTES_N,
+    "dmcf_cconv_scatter_plan": (_int, (_ptr, _i64, _ptr, _i64, _f32, _f32, _i32, _ptr, _size, _ptr)),
+    "dmcf_cconv_scatter_workspace_bytes": (_size, (_P(CconvScatterArgs),)),
+    "dmcf_cconv_scatter_forward": (_int, (_P(CconvScatterArgs), _ptr, _size, _ptr)),
+    # the backward of the scatter form (ABI 2.19)
+    "dmcf_cconv_scatter_backward_workspace_bytes": (_size, (_P(CconvScatterArgs), _P(CconvScatterBackwardArgs))),
+    "dmcf_cconv_scatter_backward": (_int, (_P(CconvScatterArgs), _P(CconvScatterBackwardArgs), _ptr, _size, _ptr)),
+    "dmcf_lattice_conv_workspace_bytes": (_size, (_P(LatticeConvArgs),)),
+    "dmcf_lattice_conv_forward": (_int, (_P(LatticeConvArgs), _ptr, _size, _ptr)),
+    "dmcf_lattice_conv_batch_workspace_bytes": (_size, (_P(LatticeConvArgs), _i32)),
+    "dmcf_lattice_conv_forward_batch": (_int, (_P(LatticeConvArgs), _i32, _ptr, _size, _ptr)),
+    # gradients of the lattice form (ABI 2.16)
+    "dmcf_lattice_conv_backward_workspace_bytes": (_size, (_P(LatticeConvArgs), _i32)),
+    "dmcf_lattice_conv_backward": (_int, (_P(LatticeConvArgs), _i32, _ptr, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_reduce_subarrays_sum": (_int, (_ptr, _ptr, _i64, _ptr, _ptr)),
+    "dmcf_dense_forward": (_int, (_ptr, _i64, _i32, _ptr, _i32, _ptr, _ptr, _ptr, _ptr)),
+    "dmcf_points_aabb_workspace_bytes": (_size, ()),
+    "dmcf_points_aabb": (_int, (_ptr, _i64, _ptr, _ptr, _size, _ptr)),
+    "dmcf_points_aabb_batched": (_int, (_ptr, _i64, *_ITEMS, _ptr, _ptr)),  # (ABI 2.21, with grid_pos below)
+    "dmcf_ghost_workspace_bytes": (_size, (_i64, _i32, _i32)),
+    "dmcf_ghost_count": (_int, (*_GHOST, _ptr, _size, _ptr)),
+    "dmcf_ghost_write": (_int, (*_GHOST, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_grid_pos_workspace_bytes": _BYTES_N,
+    "dmcf_grid_pos_bounds": (_int, (_ptr, _i64, _P(_f32), _int, _ptr, _int, _f32, _ptr, _size, _ptr)),
+    "dmcf_grid_pos_count": (_int, (_ptr, _i64, *_GRID, _ptr)),
+    "dmcf_grid_pos_write": (_int, (_ptr, _i64, *_GRID, _ptr, _i64, _ptr)),
+    # grid_pos and the fluid box with row splits (ABI 2.21)
+    "dmcf_grid_pos_workspace_bytes_batched": _BYTES_NM,
+    "dmcf_grid_pos_bounds_batched": (_int, (_ptr, _i64, *_ITEMS, _P(_f32), _int, _ptr, _int, _f32, _ptr, _size, _ptr)),
+    "dmcf_grid_pos_count_batched": (_int, (_ptr, _i64, *_ITEMS, *_GRID, _ptr, _ptr)),
+    "dmcf_grid_pos_write_batched": (_int, (_ptr, _i64, *_ITEMS, *_GRID, _ptr, _i64, _ptr)),
+    "dmcf_fps_workspace_bytes": _BYTES_N,
+    "dmcf_farthest_point_sample": (_int, (_ptr, _i64, _i64, _ptr, _size, _ptr, _ptr)),
+    "dmcf_gather_point": (_int, (_ptr, _ptr, _i64, _int, _ptr, _ptr)),
+    "dmcf_nn_distance_workspace_bytes": _BYTES_BNM,
+    "dmcf_nn_distance": (_int, (*_PADDED, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr)),
+    # nn_distance over a ragged batch (ABI 2.23): HOST row splits
+    "dmcf_nn_distance_ragged_workspace_bytes": _BYTES_BNM,
+    "dmcf_nn_distance_ragged": (_int, (*_RAGGED, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_approx_match_workspace_bytes": _BYTES_BNM,
+    "dmcf_approx_match": _MATCH,
+    "dmcf_match_cost_workspace_bytes": _BYTES_BNM,
+    "dmcf_match_cost": (_int, (*_PADDED, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_emd_workspace_bytes": _BYTES_BNM,
+    "dmcf_emd": _MATCH,
+    # the fused EMD over a ragged batch (ABI 2.24): HOST row splits, read by the workspace query too
+    "dmcf_emd_ragged_workspace_bytes": _BYTES_RAGGED,
+    "dmcf_emd_ragged": (_int, (*_RAGGED, _ptr, _ptr, _size, _ptr)),
+    # metric gradients (ABI 2.13)
+    "dmcf_nn_distance_backward_workspace_bytes": _BYTES_BNM,
+    "dmcf_nn_distance_backward": (_int, (*_PADDED, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_match_cost_backward_workspace_bytes": _BYTES_BNM,
+    "dmcf_match_cost_backward": (_int, (*_PADDED, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_emd_with_levels": (_int, (*_PADDED, *_COUNTS, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_emd_backward_workspace_bytes": _BYTES_BNM,
+    "dmcf_emd_backward": (_int, (*_PADDED, *_COUNTS, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr)),
+    # the gradient of the ragged EMD (ABI 2.25): the recording forward, and the backward with its own workspace query
+    "dmcf_emd_ragged_with_levels": (_int, (*_RAGGED, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_emd_ragged_backward_workspace_bytes": _BYTES_RAGGED,
+    "dmcf_emd_ragged_backward": (_int, (*_RAGGED, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr)),
+    # the percentiles and histograms of compare_dist over a ragged batch (ABI 2.26): HOST row splits and plan
+    "dmcf_hist_pair_ragged_workspace_bytes": _BYTES_BNM,
+    "dmcf_hist_pair_ragged": (_int, (_ptr, _ptr, _i64, _P(_i64), _i64, _P(HistPlan), _i64, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_gather_point_backward_workspace_bytes": _BYTES_NM,  # (ABI 2.13)
+    "dmcf_gather_point_backward": (_int, (_ptr, _ptr, _i64, _int, _i64, _ptr, _ptr, _size, _ptr)),
+    "dmcf_neighbor_dense_forward": (_int, (_P(NeighborDenseArgs), _ptr)),
+    "dmcf_neighbor_dense_backward_workspace_bytes": (_size, (_P(NeighborDenseBackwardArgs),)),
+    "dmcf_neighbor_dense_backward": (_int, (_P(NeighborDenseBackwardArgs), _ptr, _size, _ptr)),
+    "dmcf_neighbor_dense_kernel_names": (_int, (_P(NeighborDenseArgs), _P(NeighborDenseBackwardArgs), *_NAME)),
+    "dmcf_adam_step_workspace_bytes": (_size, (_P(AdamArgs),)),
+    "dmcf_adam_step": (_int, (_P(AdamArgs), _ptr, _size, _ptr)),
+    "dmcf_adam_step_kernel_names": (_int, (_P(AdamArgs), *_NAME)),
+    "dmcf_raster_workspace_bytes": (_size, (_i64, _i64, _i64, _i32, _i32)),
+    "dmcf_raster_count": (_int, (*_RASTER, _i32, _i32, _ptr, _size, _ptr, _ptr)),
+    "dmcf_raster_discs": (_int, (*_RASTER, _u32, _i32, _i32, _ptr, _ptr, _size, _ptr, _i64, _ptr)),
+    # the depth-tested sphere splat of the 3-D renderer (ABI 2.27)
+    "dmcf_splat_depth": (_int, (*_RASTER, _f32, _P(Camera), _i32, _i32, _i32, _ptr, _ptr)),
+    "dmcf_splat_shade": (_int, (_P(SplatLayer), _i32, _P(Camera), _f32, _f32, _i32, _i32, _i64, _ptr, _ptr, _ptr)),
+    # the column datasets' 1-D SPH solver (ABI 2.17)
+    "dmcf_sph1d_rollout": (_int, (_ptr, _ptr, _i64, _i32, _P(Sph1dParams), _i32, _ptr, _ptr, _ptr, _ptr)),
+    # the voxel convolution of SparseConv / SparseConvTranspose (ABI 2.18)
+    "dmcf_sparse_conv_forward": (_int, (_P(SparseConvArgs), _ptr)),
+    "dmcf_sparse_conv_backward_workspace_bytes": (_size, (_P(SparseConvArgs), _int)),
+    "dmcf_sparse_conv_backward": (_int, (_P(SparseConvArgs), _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _size, _ptr)),
+    "dmcf_sparse_conv_kernel_names": (_int, (_P(SparseConvArgs), _int, *_NAME)),
+}
+SYMBOLS = list(PROTOTYPES)  # (tests and tools import the names under this one)
 
 
 def build(force=False):
@@ -355,279 +464,18 @@ def lib():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    c = ctypes
-    L.dmcf_version.restype = c.c_int
-    L.dmcf_error_string.restype = c.c_char_p
-    L.dmcf_error_string.argtypes = [c.c_int]
-    L.dmcf_last_hip_error.restype = c.c_int
-    L.dmcf_frs_workspace_bytes.restype = c.c_size_t
-    L.dmcf_frs_workspace_bytes.argtypes = [c.c_int64, c.c_int64]
-    L.dmcf_frs_build.restype = c.c_int
-    L.dmcf_frs_build.argtypes = [c.c_void_p, c.c_int64, c.c_float, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_frs_count.restype = c.c_int
-    L.dmcf_frs_count.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_void_p, c.c_size_t,
-                                 c.c_void_p, c.c_void_p]
-    L.dmcf_frs_write.restype = c.c_int
-    L.dmcf_frs_write.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_void_p, c.c_size_t,
-                                 c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
-    L.dmcf_frs_search_padded.restype = c.c_int
-    L.dmcf_frs_search_padded.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_void_p, c.c_size_t, c.c_int64,
-                                         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
-    L.dmcf_frs_window_sum.restype = c.c_int
-    L.dmcf_frs_window_sum.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_int, c.c_void_p, c.c_size_t,
-                                      c.c_void_p, c.c_void_p]
-    L.dmcf_radius_search_count.restype = c.c_int
-    L.dmcf_radius_search_count.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float, c.c_int, c.c_void_p, c.c_size_t,
-                                           c.c_void_p, c.c_void_p]
-    L.dmcf_radius_search_write.restype = c.c_int
-    L.dmcf_radius_search_write.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float, c.c_int, c.c_void_p, c.c_size_t,
-                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
-    L.dmcf_cconv_workspace_bytes.restype = c.c_size_t
-    L.dmcf_cconv_workspace_bytes.argtypes = [c.POINTER(CconvArgs)]
-    L.dmcf_cconv_forward.restype = c.c_int
-    L.dmcf_cconv_forward.argtypes = [c.POINTER(CconvArgs), c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_cconv_kernel_name.restype = c.c_int
-    L.dmcf_cconv_kernel_name.argtypes = [c.POINTER(CconvArgs), c.c_char_p, c.c_size_t]
-    L.dmcf_cconv_forward_extents.restype = c.c_int
-    L.dmcf_cconv_forward_extents.argtypes = [c.POINTER(CconvArgs), c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_cconv_extents_kernel_name.restype = c.c_int
-    L.dmcf_cconv_extents_kernel_name.argtypes = [c.POINTER(CconvArgs), c.c_char_p, c.c_size_t]
-    L.dmcf_invert_neighbors_list_workspace_bytes.restype = c.c_size_t
-    L.dmcf_invert_neighbors_list_workspace_bytes.argtypes = [c.c_int64]
-    L.dmcf_invert_neighbors_list.restype = c.c_int
-    L.dmcf_invert_neighbors_list.argtypes = [c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p,
-                                             c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_cconv_backward_workspace_bytes.restype = c.c_size_t
-    L.dmcf_cconv_backward_workspace_bytes.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs)]
-    L.dmcf_cconv_backward.restype = c.c_int
-    L.dmcf_cconv_backward.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_cconv_backward_kernel_names.restype = c.c_int
-    L.dmcf_cconv_backward_kernel_names.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_char_p, c.c_size_t]
-    # gradients through per-point extents (ABI 2.15)
-    L.dmcf_cconv_backward_extents.restype = c.c_int
-    L.dmcf_cconv_backward_extents.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_void_p, c.c_void_p, c.c_size_t,
-                                              c.c_void_p]
-    L.dmcf_cconv_backward_extents_kernel_names.restype = c.c_int
-    L.dmcf_cconv_backward_extents_kernel_names.argtypes = [c.POINTER(CconvArgs), c.POINTER(CconvBackwardArgs), c.c_char_p, c.c_size_t]
-    L.dmcf_cconv_scatter_plan_bytes.restype = c.c_size_t
-    L.dmcf_cconv_scatter_plan_bytes.argtypes = [c.c_int64]
-    L.dmcf_cconv_scatter_plan.restype = c.c_int
-    L.dmcf_cconv_scatter_plan.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_float, c.c_float, c.c_int32, c.c_void_p,
-                                          c.c_size_t, c.c_void_p]
-    L.dmcf_cconv_scatter_workspace_bytes.restype = c.c_size_t
-    L.dmcf_cconv_scatter_workspace_bytes.argtypes = [c.POINTER(CconvScatterArgs)]
-    L.dmcf_cconv_scatter_forward.restype = c.c_int
-    L.dmcf_cconv_scatter_forward.argtypes = [c.POINTER(CconvScatterArgs), c.c_void_p, c.c_size_t, c.c_void_p]
-    # the backward of the scatter form (ABI 2.19)
-    L.dmcf_cconv_scatter_backward_workspace_bytes.restype = c.c_size_t
-    L.dmcf_cconv_scatter_backward_workspace_bytes.argtypes = [c.POINTER(CconvScatterArgs), c.POINTER(CconvScatterBackwardArgs)]
-    L.dmcf_cconv_scatter_backward.restype = c.c_int
-    L.dmcf_cconv_scatter_backward.argtypes = [c.POINTER(CconvScatterArgs), c.POINTER(CconvScatterBackwardArgs), c.c_void_p, c.c_size_t,
-                                              c.c_void_p]
-    L.dmcf_lattice_conv_workspace_bytes.restype = c.c_size_t
-    L.dmcf_lattice_conv_workspace_bytes.argtypes = [c.POINTER(LatticeConvArgs)]
-    L.dmcf_lattice_conv_forward.restype = c.c_int
-    L.dmcf_lattice_conv_forward.argtypes = [c.POINTER(LatticeConvArgs), c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_lattice_conv_batch_workspace_bytes.restype = c.c_size_t
-    L.dmcf_lattice_conv_batch_workspace_bytes.argtypes = [c.POINTER(LatticeConvArgs), c.c_int32]
-    L.dmcf_lattice_conv_forward_batch.restype = c.c_int
-    L.dmcf_lattice_conv_forward_batch.argtypes = [c.POINTER(LatticeConvArgs), c.c_int32, c.c_void_p, c.c_size_t, c.c_void_p]
-    # gradients of the lattice form (ABI 2.16)
-    L.dmcf_lattice_conv_backward_workspace_bytes.restype = c.c_size_t
-    L.dmcf_lattice_conv_backward_workspace_bytes.argtypes = [c.POINTER(LatticeConvArgs), c.c_int32]
-    L.dmcf_lattice_conv_backward.restype = c.c_int
-    L.dmcf_lattice_conv_backward.argtypes = [c.POINTER(LatticeConvArgs), c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
-                                             c.c_size_t, c.c_void_p]
-    L.dmcf_dense_forward.restype = c.c_int
-    L.dmcf_dense_forward.argtypes = [c.c_void_p, c.c_int64, c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p,
-                                     c.c_void_p]
-    L.dmcf_ghost_workspace_bytes.restype = c.c_size_t
-    L.dmcf_ghost_workspace_bytes.argtypes = [c.c_int64, c.c_int32, c.c_int32]
-    L.dmcf_ghost_count.restype = c.c_int
-    L.dmcf_ghost_count.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p,
-                                   c.c_size_t, c.c_void_p]
-    L.dmcf_ghost_write.restype = c.c_int
-    L.dmcf_ghost_write.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p,
-                                   c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_points_aabb_workspace_bytes.restype = c.c_size_t
-    L.dmcf_points_aabb_workspace_bytes.argtypes = []
-    L.dmcf_points_aabb.restype = c.c_int
-    L.dmcf_points_aabb.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_reduce_subarrays_sum.restype = c.c_int
-    L.dmcf_reduce_subarrays_sum.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
-    L.dmcf_fps_workspace_bytes.restype = c.c_size_t
-    L.dmcf_fps_workspace_bytes.argtypes = [c.c_int64]
-    L.dmcf_farthest_point_sample.restype = c.c_int
-    L.dmcf_farthest_point_sample.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
-    L.dmcf_gather_point.restype = c.c_int
-    L.dmcf_gather_point.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_void_p, c.c_void_p]
-    L.dmcf_grid_pos_workspace_bytes.restype = c.c_size_t
-    L.dmcf_grid_pos_workspace_bytes.argtypes = [c.c_int64]
-    f3 = c.POINTER(c.c_float)
-    L.dmcf_grid_pos_bounds.restype = c.c_int
-    L.dmcf_grid_pos_bounds.argtypes = [c.c_void_p, c.c_int64, f3, c.c_int, c.c_void_p, c.c_int, c.c_float, c.c_void_p,
-                                       c.c_size_t, c.c_void_p]
-    L.dmcf_grid_pos_count.restype = c.c_int
-    L.dmcf_grid_pos_count.argtypes = [c.c_void_p, c.c_int64, f3, c.c_int, c.c_int, c.c_float, c.c_void_p, c.c_size_t,
-                                      c.c_void_p, c.c_int64, c.c_void_p]
-    L.dmcf_grid_pos_write.restype = c.c_int
-    L.dmcf_grid_pos_write.argtypes = [c.c_void_p, c.c_int64, f3, c.c_int, c.c_int, c.c_float, c.c_void_p, c.c_size_t,
-                                      c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p]
-    for q in ("dmcf_nn_distance_workspace_bytes", "dmcf_approx_match_workspace_bytes", "dmcf_match_cost_workspace_bytes",
-              "dmcf_emd_workspace_bytes"):
-        getattr(L, q).restype = c.c_size_t
-        getattr(L, q).argtypes = [c.c_int64, c.c_int64, c.c_int64]
-    L.dmcf_nn_distance.restype = c.c_int
-    L.dmcf_nn_distance.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
-                                   c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    i32p = c.POINTER(c.c_int32)
-    for f in ("dmcf_approx_match", "dmcf_emd"):
-        getattr(L, f).restype = c.c_int
-        getattr(L, f).argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, i32p, i32p, c.c_void_p, c.c_void_p,
-                                  c.c_size_t, c.c_void_p]
-    L.dmcf_match_cost.restype = c.c_int
-    L.dmcf_match_cost.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
-                                  c.c_size_t, c.c_void_p]
-    L.dmcf_neighbor_dense_forward.restype = c.c_int
-    L.dmcf_neighbor_dense_forward.argtypes = [c.POINTER(NeighborDenseArgs), c.c_void_p]
-    L.dmcf_neighbor_dense_backward_workspace_bytes.restype = c.c_size_t
-    L.dmcf_neighbor_dense_backward_workspace_bytes.argtypes = [c.POINTER(NeighborDenseBackwardArgs)]
-    L.dmcf_neighbor_dense_backward.restype = c.c_int
-    L.dmcf_neighbor_dense_backward.argtypes = [c.POINTER(NeighborDenseBackwardArgs), c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_neighbor_dense_kernel_names.restype = c.c_int
-    L.dmcf_neighbor_dense_kernel_names.argtypes = [c.POINTER(NeighborDenseArgs), c.POINTER(NeighborDenseBackwardArgs), c.c_char_p,
-                                                   c.c_size_t]
-    L.dmcf_adam_step_workspace_bytes.restype = c.c_size_t
-    L.dmcf_adam_step_workspace_bytes.argtypes = [c.POINTER(AdamArgs)]
-    L.dmcf_adam_step.restype = c.c_int
-    L.dmcf_adam_step.argtypes = [c.POINTER(AdamArgs), c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_adam_step_kernel_names.restype = c.c_int
-    L.dmcf_adam_step_kernel_names.argtypes = [c.POINTER(AdamArgs), c.c_char_p, c.c_size_t]
-    L.dmcf_raster_workspace_bytes.restype = c.c_size_t
-    L.dmcf_raster_workspace_bytes.argtypes = [c.c_int64, c.c_int64, c.c_int64, c.c_int32, c.c_int32]
-    L.dmcf_raster_count.restype = c.c_int
-    L.dmcf_raster_count.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_int32, c.c_int32, c.c_void_p, c.c_size_t,
-                                    c.c_void_p, c.c_void_p]
-    L.dmcf_raster_discs.restype = c.c_int
-    L.dmcf_raster_discs.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_uint32, c.c_int32, c.c_int32, c.c_void_p,
-                                    c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p]
-    # metric gradients (ABI 2.13)
-    for q in ("dmcf_nn_distance_backward_workspace_bytes", "dmcf_match_cost_backward_workspace_bytes",
-              "dmcf_emd_backward_workspace_bytes"):
-        getattr(L, q).restype = c.c_size_t
-        getattr(L, q).argtypes = [c.c_int64, c.c_int64, c.c_int64]
-    L.dmcf_nn_distance_backward.restype = c.c_int
-    L.dmcf_nn_distance_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
-                                            c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_match_cost_backward.restype = c.c_int
-    L.dmcf_match_cost_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
-                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_emd_with_levels.restype = c.c_int
-    L.dmcf_emd_with_levels.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, i32p, i32p, c.c_void_p, c.c_void_p,
-                                       c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_emd_backward.restype = c.c_int
-    L.dmcf_emd_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, i32p, i32p, c.c_void_p, c.c_void_p,
-                                    c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_gather_point_backward_workspace_bytes.restype = c.c_size_t
-    L.dmcf_gather_point_backward_workspace_bytes.argtypes = [c.c_int64, c.c_int64]
-    L.dmcf_gather_point_backward.restype = c.c_int
-    L.dmcf_gather_point_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int64, c.c_void_p, c.c_void_p,
-                                             c.c_size_t, c.c_void_p]
-    # gradient of the window sum (ABI 2.14)
-    L.dmcf_frs_window_sum_backward.restype = c.c_int
-    L.dmcf_frs_window_sum_backward.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
-                                               c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
-    # the column datasets' 1-D SPH solver (ABI 2.17)
-    L.dmcf_sph1d_rollout.restype = c.c_int
-    L.dmcf_sph1d_rollout.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_int32, c.POINTER(Sph1dParams), c.c_int32, c.c_void_p,
-                                     c.c_void_p, c.c_void_p, c.c_void_p]
-    # the voxel convolution of SparseConv / SparseConvTranspose (ABI 2.18)
-    L.dmcf_sparse_conv_forward.restype = c.c_int
-    L.dmcf_sparse_conv_forward.argtypes = [c.POINTER(SparseConvArgs), c.c_void_p]
-    L.dmcf_sparse_conv_backward_workspace_bytes.restype = c.c_size_t
-    L.dmcf_sparse_conv_backward_workspace_bytes.argtypes = [c.POINTER(SparseConvArgs), c.c_int]
-    L.dmcf_sparse_conv_backward.restype = c.c_int
-    L.dmcf_sparse_conv_backward.argtypes = [c.POINTER(SparseConvArgs), c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
-                                            c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_sparse_conv_kernel_names.restype = c.c_int
-    L.dmcf_sparse_conv_kernel_names.argtypes = [c.POINTER(SparseConvArgs), c.c_int, c.c_char_p, c.c_size_t]
-    # both searches with points_row_splits / queries_row_splits (ABI 2.20)
-    L.dmcf_frs_workspace_bytes_batched.restype = c.c_size_t
-    L.dmcf_frs_workspace_bytes_batched.argtypes = [c.c_int64, c.c_int64, c.c_int64]
-    L.dmcf_frs_build_batched.restype = c.c_int
-    L.dmcf_frs_build_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_float, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_frs_count_batched.restype = c.c_int
-    L.dmcf_frs_count_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_void_p,
-                                         c.c_size_t, c.c_void_p, c.c_void_p]
-    L.dmcf_frs_write_batched.restype = c.c_int
-    L.dmcf_frs_write_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_void_p,
-                                         c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
-    L.dmcf_radius_search_count_batched.restype = c.c_int
-    L.dmcf_radius_search_count_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float,
-                                                   c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
-    L.dmcf_radius_search_write_batched.restype = c.c_int
-    L.dmcf_radius_search_write_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_float,
-                                                   c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
-                                                   c.c_void_p]
-    # grid_pos and the fluid box with row splits (ABI 2.21)
-    L.dmcf_grid_pos_workspace_bytes_batched.restype = c.c_size_t
-    L.dmcf_grid_pos_workspace_bytes_batched.argtypes = [c.c_int64, c.c_int64]
-    L.dmcf_grid_pos_bounds_batched.restype = c.c_int
-    L.dmcf_grid_pos_bounds_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, f3, c.c_int, c.c_void_p, c.c_int,
-                                               c.c_float, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_grid_pos_count_batched.restype = c.c_int
-    L.dmcf_grid_pos_count_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, f3, c.c_int, c.c_int, c.c_float,
-                                              c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
-    L.dmcf_grid_pos_write_batched.restype = c.c_int
-    L.dmcf_grid_pos_write_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, f3, c.c_int, c.c_int, c.c_float,
-                                              c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p]
-    L.dmcf_points_aabb_batched.restype = c.c_int
-    L.dmcf_points_aabb_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
-    # the window sum and its gradient with row splits (ABI 2.22)
-    L.dmcf_frs_window_sum_batched.restype = c.c_int
-    L.dmcf_frs_window_sum_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int, c.c_int,
-                                              c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
-    L.dmcf_frs_window_sum_backward_batched.restype = c.c_int
-    L.dmcf_frs_window_sum_backward_batched.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_float, c.c_int,
-                                                       c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p,
-                                                       c.c_void_p]
-    # nn_distance over a ragged batch (ABI 2.23): HOST row splits
-    L.dmcf_nn_distance_ragged_workspace_bytes.restype = c.c_size_t
-    L.dmcf_nn_distance_ragged_workspace_bytes.argtypes = [c.c_int64, c.c_int64, c.c_int64]
-    i64p = c.POINTER(c.c_int64)
-    L.dmcf_nn_distance_ragged.restype = c.c_int
-    L.dmcf_nn_distance_ragged.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p,
-                                          c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    # the fused EMD over a ragged batch (ABI 2.24): HOST row splits, read by the workspace query too
-    L.dmcf_emd_ragged_workspace_bytes.restype = c.c_size_t
-    L.dmcf_emd_ragged_workspace_bytes.argtypes = [c.c_int64, i64p, c.c_int64, i64p, c.c_int64]
-    L.dmcf_emd_ragged.restype = c.c_int
-    L.dmcf_emd_ragged.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p, c.c_void_p,
-                                  c.c_size_t, c.c_void_p]
-    # the gradient of the ragged EMD (ABI 2.25): the recording forward, and the backward with its own workspace query
-    L.dmcf_emd_ragged_with_levels.restype = c.c_int
-    L.dmcf_emd_ragged_with_levels.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p,
-                                              c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    L.dmcf_emd_ragged_backward_workspace_bytes.restype = c.c_size_t
-    L.dmcf_emd_ragged_backward_workspace_bytes.argtypes = [c.c_int64, i64p, c.c_int64, i64p, c.c_int64]
-    L.dmcf_emd_ragged_backward.restype = c.c_int
-    L.dmcf_emd_ragged_backward.argtypes = [c.c_void_p, c.c_int64, i64p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.c_void_p,
-                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    # the percentiles and histograms of compare_dist over a ragged batch (ABI 2.26): HOST row splits and plan
-    L.dmcf_hist_pair_ragged_workspace_bytes.restype = c.c_size_t
-    L.dmcf_hist_pair_ragged_workspace_bytes.argtypes = [c.c_int64, c.c_int64, c.c_int64]
-    L.dmcf_hist_pair_ragged.restype = c.c_int
-    L.dmcf_hist_pair_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, i64p, c.c_int64, c.POINTER(HistPlan), c.c_int64,
-                                        c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
-    # the depth-tested sphere splat of the 3-D renderer (ABI 2.27)
-    L.dmcf_splat_depth.restype = c.c_int
-    L.dmcf_splat_depth.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_float, c.POINTER(Camera), c.c_int32,
-                                   c.c_int32, c.c_int32, c.c_void_p, c.c_void_p]
-    L.dmcf_splat_shade.restype = c.c_int
-    L.dmcf_splat_shade.argtypes = [c.POINTER(SplatLayer), c.c_int32, c.POINTER(Camera), c.c_float, c.c_float, c.c_int32, c.c_int32,
-                                   c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        entry = getattr(L, name)
+        entry.restype, entry.argtypes = restype, list(argtypes)
     _lib = L
     return L
+
+
+def call(name, *args):
+    """Call the entry point `name`, which returns a DMCF_* status; anything but DMCF_OK raises DmcfError."""
+    rc = getattr(lib(), name)(*args)
+    if rc != 0:
+        check(rc, name)
 
 
 def check(rc, what):

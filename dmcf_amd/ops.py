@@ -161,7 +161,7 @@ MAPPINGS = {"ball_to_cube_radial": 0, "ball_to_cube_volume_preserving": 1, "iden
 INTERPOLATIONS = {"linear": 0, "linear_border": 1, "nearest_neighbor": 2}
 WINDOWS = {None: 0, "explicit": 1, "poly6": 2, "cubic": 3, "linear": 4, "peak": 5, "cubic_grad": 6}
 
-FLAG_ALIGN_CORNERS, FLAG_NORMALIZE, FLAG_SYMMETRIC, FLAG_ACCUMULATE, FLAG_SKIP_SELF, FLAG_FILTER_PACKED = 1, 2, 4, 8, 16, 32
+FLAG_ALIGN_CORNERS, FLAG_NORMALIZE, FLAG_SYMMETRIC, FLAG_ACCUMULATE, FLAG_SKIP_SELF, FLAG_FILTER_PACKED = 1, 2, 4, 8, 16, 32  # DMCF_FLAG_*
 
 
 class LaunchTimer:
@@ -222,6 +222,14 @@ def _dev_f32(t, name, cols=None):
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _workspace(device, query, *args, least=1):
+    """The scratch buffer of one call -> (uint8 tensor, bytes to pass with it).  ``query``: the name of the entry point's
+    ``*_workspace_bytes`` function, ``args`` its arguments.  The tensor has at least ``least`` bytes: a query that answers 0
+    still gives the call a pointer that is not NULL."""
+    nbytes = int(getattr(_lib.lib(), query)(*args))
+    return torch.empty(max(nbytes, least), dtype=torch.uint8, device=device), nbytes
 
 
 class SpatialHashTable:
@@ -305,7 +313,6 @@ def build_spatial_hash_table(points, radius, n_queries=None, points_row_splits=N
         host, dev = _host_row_splits(points_row_splits, "points_row_splits")
         _check_row_splits(host, points.shape[0], "points_row_splits")
         batch = len(host) - 1
-    L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     n = points.shape[0]
     m = n if n_queries is None else int(n_queries)
@@ -315,11 +322,10 @@ def build_spatial_hash_table(points, radius, n_queries=None, points_row_splits=N
         rs_dev = _row_splits_on(host, dev, points.device)
     t0 = timer.begin() if timer is not None else None
     if batch is None:
-        _lib.check(L.dmcf_frs_build(_ptr(points), n, float(radius), _ptr(ws), nbytes, _stream()), "dmcf_frs_build")
+        _lib.call("dmcf_frs_build", _ptr(points), n, float(radius), _ptr(ws), nbytes, _stream())
         kind, meta = "frs_build", dict(n_points=n)
     else:
-        _lib.check(L.dmcf_frs_build_batched(_ptr(points), n, _ptr(rs_dev), batch, float(radius), _ptr(ws), nbytes, _stream()),
-                   "dmcf_frs_build_batched")
+        _lib.call("dmcf_frs_build_batched", _ptr(points), n, _ptr(rs_dev), batch, float(radius), _ptr(ws), nbytes, _stream())
         kind, meta = "frs_build_batched", dict(n_points=n, batch=batch)
     if timer is not None:
         timer.end(kind, meta, t0)
@@ -384,7 +390,7 @@ def _size_class(x):
     return (x + g - 1) // g * g
 
 
-FRS_IGNORE_QUERY_POINT, FRS_OPEN3D_CORNER_VOXELS, FRS_OPEN3D_VOXEL_WALK, FRS_METRIC_LINF = 1, 2, 4, 8
+FRS_IGNORE_QUERY_POINT, FRS_OPEN3D_CORNER_VOXELS, FRS_OPEN3D_VOXEL_WALK, FRS_METRIC_LINF = 1, 2, 4, 8  # DMCF_FRS_*
 
 # Which neighbour SET the searches return (include/dmcf_hip.h, DMCF_FRS_*):
 #   "distance"        every point with d^2 <= R^2 -- what open3d's walk over the query's own voxel and the 8 corner voxels of
@@ -466,7 +472,6 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
             raise NotImplementedError(f"DMCF_FRS_SET={search_set()} has no batched form: the open3d walk emulations know nothing of items")
         p_splits, (q_host, q_dev) = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
         batch = len(q_host) - 1
-    L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     queries = _dev_f32(queries, "queries", 3)
     radius = float(radius)
@@ -509,9 +514,8 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
         if max_count is None:  # (a caller with many searches per step hands out slots of ONE zeroed tensor: a fill less per search)
             max_count = torch.zeros(1, dtype=torch.int32, device=dev)
         t0 = timer.begin() if timer is not None else None  # (after the allocations: a hipMalloc is not kernel time)
-        _lib.check(L.dmcf_frs_search_padded(_ptr(queries), m, n, radius, flags, _ptr(ws), nbytes, stride, _ptr(row_splits),
-                                            _ptr(counts), _ptr(index), _ptr(dist) if return_distances else None,
-                                            _ptr(max_count), _stream()), "dmcf_frs_search_padded")
+        _lib.call("dmcf_frs_search_padded", _ptr(queries), m, n, radius, flags, _ptr(ws), nbytes, stride, _ptr(row_splits),
+                  _ptr(counts), _ptr(index), _ptr(dist) if return_distances else None, _ptr(max_count), _stream())
         keep = (points, queries, ws)  # noqa: F841
         res = PaddedNeighborList(index, row_splits, dist, counts, max_count, stride,
                                  lambda: fixed_radius_search(points, queries, radius, ignore_query_point, return_distances,
@@ -524,13 +528,12 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
     if batched:
         q_rs = _row_splits_on(q_host, q_dev, dev)
         item = (_ptr(q_rs), batch)
-        count, write_rows = L.dmcf_frs_count_batched, L.dmcf_frs_write_batched
-        names = ("dmcf_frs_count_batched", "dmcf_frs_write_batched")
+        count, write_rows = "dmcf_frs_count_batched", "dmcf_frs_write_batched"
     else:
         q_rs, item = None, ()
-        count, write_rows, names = L.dmcf_frs_count, L.dmcf_frs_write, ("dmcf_frs_count", "dmcf_frs_write")
+        count, write_rows = "dmcf_frs_count", "dmcf_frs_write"
     t0 = timer.begin() if timer is not None else None
-    _lib.check(count(_ptr(queries), m, *item, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _stream()), names[0])
+    _lib.call(count, _ptr(queries), m, *item, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _stream())
     if timer is not None and not batched:
         timer.end("frs_count", dict(n_points=n, n_queries=m), t0)
 
@@ -538,8 +541,8 @@ def fixed_radius_search(points, queries, radius, ignore_query_point=False, retur
         index = torch.empty(capacity, dtype=torch.int32, device=dev)
         dist = torch.empty(capacity if return_distances else 0, dtype=torch.float32, device=dev)
         if capacity > 0 and m > 0:
-            _lib.check(write_rows(_ptr(queries), m, *item, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _ptr(index),
-                                  _ptr(dist) if return_distances else None, capacity, _stream()), names[1])
+            _lib.call(write_rows, _ptr(queries), m, *item, n, radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _ptr(index),
+                      _ptr(dist) if return_distances else None, capacity, _stream())
         return index, dist
 
     if capacity_hint is None:
@@ -617,7 +620,6 @@ def radius_search(points, queries, radii, ignore_query_point=False, return_dista
     if batched:
         p_splits, (q_host, q_dev) = _batched_row_splits(points, queries, points_row_splits, queries_row_splits)
         batch = len(q_host) - 1
-    L = _lib.lib()
     points = _dev_f32(points, "points", 3)
     queries = _dev_f32(queries, "queries", 3)
     radii = _dev_f32(radii, "radii")
@@ -639,21 +641,19 @@ def radius_search(points, queries, radii, ignore_query_point=False, return_dista
     if batched:
         q_rs = _row_splits_on(q_host, q_dev, dev)
         item = (_ptr(q_rs), batch)
-        count, write, names = (L.dmcf_radius_search_count_batched, L.dmcf_radius_search_write_batched,
-                               ("dmcf_radius_search_count_batched", "dmcf_radius_search_write_batched"))
+        count, write = "dmcf_radius_search_count_batched", "dmcf_radius_search_write_batched"
     else:
         item = ()
-        count, write, names = (L.dmcf_radius_search_count, L.dmcf_radius_search_write,
-                               ("dmcf_radius_search_count", "dmcf_radius_search_write"))
+        count, write = "dmcf_radius_search_count", "dmcf_radius_search_write"
     t0 = timer.begin() if timer is not None else None
-    _lib.check(count(_ptr(queries), m, *item, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _stream()), names[0])
+    _lib.call(count, _ptr(queries), m, *item, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _stream())
     total = int(row_splits[-1].item())  # the one host round trip of the two-phase search, as in fixed_radius_search
     capacity = pair_capacity(total) if total else 0
     index = torch.empty(capacity, dtype=torch.int32, device=dev)
     dist = torch.empty(capacity if return_distances else 0, dtype=torch.float32, device=dev)
     if capacity > 0:
-        _lib.check(write(_ptr(queries), m, *item, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _ptr(index),
-                         _ptr(dist) if return_distances else None, capacity, _stream()), names[1])
+        _lib.call(write, _ptr(queries), m, *item, n, _ptr(radii), max_radius, flags, _ptr(ws), nbytes, _ptr(row_splits), _ptr(index),
+                  _ptr(dist) if return_distances else None, capacity, _stream())
     if timer is not None:
         timer.end("radius_search", dict(n_points=n, n_queries=m, pairs=total, distances=bool(return_distances)), t0)
     if return_distances and normalize_distances and total > 0:
@@ -722,13 +722,14 @@ def _extent_operands(extent, n_out):
     return ext, 1.0  # (args->extent is ignored by the *_extents entry points; the workspace query wants a positive one)
 
 
-def _kernel_name(fn, *args, size=96, what=None):
-    """The string (bytes) the ``*_kernel_name(s)`` entry point ``fn`` writes for ``args`` into a buffer of ``size`` bytes.
-    ``what``: the name to check its status under (None: unchecked)."""
+def _kernel_name(entry, *args, size=96, checked=True):
+    """The string (bytes) the ``*_kernel_name(s)`` entry point named ``entry`` writes for ``args`` into a buffer of ``size``
+    bytes.  ``checked=False``: the status is not looked at (a call that fails leaves the buffer empty)."""
     name = ctypes.create_string_buffer(size)
-    rc = fn(*args, name, size)
-    if what is not None:
-        _lib.check(rc, what)
+    if checked:
+        _lib.call(entry, *args, name, size)
+    else:
+        getattr(_lib.lib(), entry)(*args, name, size)
     return name.value
 
 
@@ -916,7 +917,6 @@ def lattice_conv(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel,
                    base_dims=base_dims, window=window, window_fac=window_fac, align_corners=align_corners,
                    coordinate_mapping=coordinate_mapping, interpolation=interpolation, parts=parts)
         return LatticeConvFunction.apply(filters, inp_volume, bias, geo, dict(fill=fill, n_out_launch=n_out_launch))
-    L = _lib.lib()
     dev = filters.device
     cin, cout = filters.shape[3], filters.shape[4]
     if out is None:
@@ -930,15 +930,14 @@ def lattice_conv(filters, inp_volume, inp_min, out_table, out_min, n_out, voxel,
                                      coordinate_mapping=coordinate_mapping, interpolation=interpolation, bias=bias, out=out,
                                      accumulate=accumulate, parts=parts)
     if len(arr) == 1:
-        nbytes = L.dmcf_lattice_conv_workspace_bytes(arr)
+        ws, nbytes = _workspace(dev, "dmcf_lattice_conv_workspace_bytes", arr, least=0)
     else:
-        nbytes = L.dmcf_lattice_conv_batch_workspace_bytes(arr, len(arr))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = _workspace(dev, "dmcf_lattice_conv_batch_workspace_bytes", arr, len(arr), least=0)
     t0 = timer.begin() if timer is not None else None
     if len(arr) == 1:
-        _lib.check(L.dmcf_lattice_conv_forward(arr, _ptr(ws), nbytes, _stream()), "dmcf_lattice_conv_forward")
+        _lib.call("dmcf_lattice_conv_forward", arr, _ptr(ws), nbytes, _stream())
     else:
-        _lib.check(L.dmcf_lattice_conv_forward_batch(arr, len(arr), _ptr(ws), nbytes, _stream()), "dmcf_lattice_conv_forward_batch")
+        _lib.call("dmcf_lattice_conv_forward_batch", arr, len(arr), _ptr(ws), nbytes, _stream())
     if timer is not None:
         # bench accounting: this form reads no neighbour list, so it is charged what it does read and write -- the input
         # volume once, the per-offset matrices, the cell -> point table and the output rows (``pairs_equiv`` = the pairs the
@@ -963,7 +962,6 @@ def lattice_conv_backward(filters, inp_volume, inp_min, out_table, out_min, n_ou
     ``inp_volume`` (zero in cells no output reaches), ``grad_filters`` that of ``filters`` (summed over all ``parts``).  Rows
     of ``grad_out`` whose point is not in ``out_table`` contribute nothing.  One call of the entry point; no neighbour
     list, no inversion, no float atomics (two calls return the same bits)."""
-    L = _lib.lib()
     filters = _dev_f32(filters, "filters")
     dev = filters.device
     grad_out = _dev_f32(grad_out, "grad_out", filters.shape[4])
@@ -977,11 +975,9 @@ def lattice_conv_backward(filters, inp_volume, inp_min, out_table, out_min, n_ou
                                  coordinate_mapping=coordinate_mapping, interpolation=interpolation, out=grad_out, parts=parts)
     gv = torch.empty_like(inp_volume) if need_volume else None
     gw = torch.empty_like(filters) if need_filters else None
-    nbytes = int(L.dmcf_lattice_conv_backward_workspace_bytes(arr, len(arr)))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_lattice_conv_backward_workspace_bytes", arr, len(arr), least=0)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_lattice_conv_backward(arr, len(arr), _ptr(grad_out), _ptr(gv), _ptr(gw), _ptr(ws), nbytes, _stream()),
-               "dmcf_lattice_conv_backward")
+    _lib.call("dmcf_lattice_conv_backward", arr, len(arr), _ptr(grad_out), _ptr(gv), _ptr(gw), _ptr(ws), nbytes, _stream())
     if timer is not None:
         timer.end("cconv_backward", dict(n_out=int(n_out), cin=int(filters.shape[3]), cout=int(filters.shape[4]),
                                          filters=bool(need_filters), features=bool(need_volume), lattice=True, parts=len(arr),
@@ -1103,9 +1099,9 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
                           normalize=normalize, symmetric=symmetric, sym_axis=sym_axis, bias=bias, out=out, accumulate=accumulate,
                           neighbors_row_count=neighbors_row_count, filter_tile_mask=filter_tile_mask, skip_self=skip_self,
                           row_length_hint=row_length_hint)
-    kernel_name = L.dmcf_cconv_kernel_name if ext is None else L.dmcf_cconv_extents_kernel_name
+    kernel_name = "dmcf_cconv_kernel_name" if ext is None else "dmcf_cconv_extents_kernel_name"
     if name_only:
-        return _kernel_name(kernel_name, ctypes.byref(a), what="dmcf_cconv_kernel_name").decode()
+        return _kernel_name(kernel_name, ctypes.byref(a)).decode()
     nbytes = L.dmcf_cconv_workspace_bytes(ctypes.byref(a))
     ws = None
     if packed_cache is not None and ext is None:
@@ -1117,7 +1113,7 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
         # calls (copy_, load_state_dict, optimiser steps) bump the counter; a write through ``.data`` does not -- after one,
         # call ``layer.invalidate_packed()``.  Derived tensors (a fresh object per call) never hit.
         key = (filters._version, tuple(filters.shape), bool(symmetric), int(sym_axis),
-               _kernel_name(L.dmcf_cconv_kernel_name, ctypes.byref(a)), str(filters.device))
+               _kernel_name("dmcf_cconv_kernel_name", ctypes.byref(a), checked=False), str(filters.device))
         ws = packed_cache.get("ws")
         if packed_cache.get("src") is filters and packed_cache.get("key") == key and ws is not None and ws.numel() >= nbytes:
             a.flags |= FLAG_FILTER_PACKED
@@ -1131,15 +1127,15 @@ def cconv_forward(filters, out_positions, extent, inp_positions, inp_features, n
         ws = torch.empty(nbytes, dtype=torch.uint8, device=filters.device)
     t0 = timer.begin() if timer is not None else None
     if ext is None:
-        _lib.check(L.dmcf_cconv_forward(ctypes.byref(a), _ptr(ws), nbytes, _stream()), "dmcf_cconv_forward")
+        _lib.call("dmcf_cconv_forward", ctypes.byref(a), _ptr(ws), nbytes, _stream())
     else:
-        _lib.check(L.dmcf_cconv_forward_extents(ctypes.byref(a), _ptr(ext), _ptr(ws), nbytes, _stream()), "dmcf_cconv_forward_extents")
+        _lib.call("dmcf_cconv_forward_extents", ctypes.byref(a), _ptr(ext), _ptr(ws), nbytes, _stream())
     if timer is not None:
         kdims = [int(d) for d in filters.shape[:3]]
         if symmetric:
             kdims[int(sym_axis)] *= 2
         timer.end("cconv", dict(pairs=n_pairs_ref if n_pairs_ref is not None else int(a.n_pairs), n_out=n_out, cin=int(filters.shape[3]), cout=cout,
-                                K=kdims[0] * kdims[1] * kdims[2], symmetric=bool(symmetric), kernel=_kernel_name(kernel_name, ctypes.byref(a)).decode(),
+                                K=kdims[0] * kdims[1] * kdims[2], symmetric=bool(symmetric), kernel=_kernel_name(kernel_name, ctypes.byref(a), checked=False).decode(),
                                 pair_values=bool(a.neighbors_value), accumulate=bool(accumulate)), t0)
     return out
 
@@ -1158,7 +1154,6 @@ def invert_neighbors_list(num_points, inp_neighbors_index, inp_neighbors_row_spl
     -1.  ``inp_neighbors_attributes``: None / empty or a float32 [P] tensor, returned permuted the same way.
     ``neighbors_row_count``: int32 [n_out] for padded lists, whose ``inp_neighbors_row_splits`` holds a begin per row (at
     least n_out entries)."""
-    L = _lib.lib()
     index = inp_neighbors_index
     rs = inp_neighbors_row_splits
     if index.dtype != torch.int32 or rs.dtype != torch.int64:
@@ -1184,12 +1179,11 @@ def invert_neighbors_list(num_points, inp_neighbors_index, inp_neighbors_row_spl
     inv_pair = torch.empty(P, dtype=torch.int32, device=dev)
     inv_rs = torch.empty(n_inp + 1, dtype=torch.int64, device=dev)
     inv_attr = torch.empty(P, dtype=torch.float32, device=dev) if attrs is not None else torch.empty(0, dtype=torch.float32, device=dev)
-    nbytes = int(L.dmcf_invert_neighbors_list_workspace_bytes(P))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_invert_neighbors_list_workspace_bytes", P, least=0)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_invert_neighbors_list(n_inp, _ptr(index), _ptr(rs), _ptr(neighbors_row_count), n_out, P, _ptr(attrs),
-                                            _ptr(inv_index), _ptr(inv_rs), _ptr(inv_pair), _ptr(inv_attr) if attrs is not None else None,
-                                            _ptr(ws), nbytes, _stream()), "dmcf_invert_neighbors_list")
+    _lib.call("dmcf_invert_neighbors_list", n_inp, _ptr(index), _ptr(rs), _ptr(neighbors_row_count), n_out, P, _ptr(attrs),
+              _ptr(inv_index), _ptr(inv_rs), _ptr(inv_pair), _ptr(inv_attr) if attrs is not None else None, _ptr(ws), nbytes,
+              _stream())
     if timer is not None:
         timer.end("invert", dict(pairs=P, n_inp=n_inp), t0)
     return InvertedNeighbors(inv_index, inv_rs, inv_attr, inv_pair)
@@ -1208,7 +1202,6 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
     kernel.  ``extent``: what ``cconv_forward`` accepts -- a scalar, or one extent per output row (a tensor [n_out] or
     [n_out, 1], finite and positive: ValueError otherwise), which takes dmcf_cconv_backward_extents: every pair at the extent of
     its output row.  Extents get no gradient."""
-    L = _lib.lib()
     n_out, n_inp = out_positions.shape[0], inp_positions.shape[0]
     cin = filters.shape[3]
     dev = filters.device
@@ -1233,7 +1226,7 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
                           skip_self=skip_self)
     b = _lib.CconvBackwardArgs()
     b.struct_size = ctypes.sizeof(_lib.CconvBackwardArgs)
-    b.flags = 1 if accumulate else 0
+    b.flags = 1 if accumulate else 0  # DMCF_BWD_ACCUMULATE
     b.grad_out = grad_out.data_ptr()
     if need_features:
         if inverted is None:
@@ -1246,14 +1239,12 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
         b.grad_inp_features = grad_inp_features.data_ptr()
     if need_filters:
         b.grad_filters = grad_filters.data_ptr()
-    nbytes = int(L.dmcf_cconv_backward_workspace_bytes(ctypes.byref(a), ctypes.byref(b)))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_cconv_backward_workspace_bytes", ctypes.byref(a), ctypes.byref(b), least=0)
     t0 = timer.begin() if timer is not None else None
     if ext is None:
-        _lib.check(L.dmcf_cconv_backward(ctypes.byref(a), ctypes.byref(b), _ptr(ws), nbytes, _stream()), "dmcf_cconv_backward")
+        _lib.call("dmcf_cconv_backward", ctypes.byref(a), ctypes.byref(b), _ptr(ws), nbytes, _stream())
     else:
-        _lib.check(L.dmcf_cconv_backward_extents(ctypes.byref(a), ctypes.byref(b), _ptr(ext), _ptr(ws), nbytes, _stream()),
-                   "dmcf_cconv_backward_extents")
+        _lib.call("dmcf_cconv_backward_extents", ctypes.byref(a), ctypes.byref(b), _ptr(ext), _ptr(ws), nbytes, _stream())
     if timer is not None:
         timer.end("cconv_backward", dict(n_out=n_out, cin=int(cin), cout=int(filters.shape[4]), filters=bool(need_filters),
                                          features=bool(need_features),
@@ -1265,9 +1256,8 @@ def cconv_backward(filters, out_positions, extent, inp_positions, inp_features, 
 def cconv_backward_kernel_names(a, b, extents=False):
     """';'-separated names of the kernels dmcf_cconv_backward -- ``extents``: dmcf_cconv_backward_extents, whose geometry kernels
     carry the suffix _ext -- launches for these (ctypes) arguments."""
-    L = _lib.lib()
-    fn = L.dmcf_cconv_backward_extents_kernel_names if extents else L.dmcf_cconv_backward_kernel_names
-    return _kernel_name(fn, ctypes.byref(a), ctypes.byref(b), size=256, what="dmcf_cconv_backward_kernel_names").decode()
+    entry = "dmcf_cconv_backward_extents_kernel_names" if extents else "dmcf_cconv_backward_kernel_names"
+    return _kernel_name(entry, ctypes.byref(a), ctypes.byref(b), size=256).decode()
 
 
 class CconvFunction(torch.autograd.Function):
@@ -1295,7 +1285,7 @@ class CconvFunction(torch.autograd.Function):
         return gw, gf, None, None
 
 
-ND_RELU, ND_W_TRANSPOSED = 1, 2
+ND_RELU, ND_W_TRANSPOSED = 1, 2  # DMCF_ND_*
 
 
 class SharedInverse:
@@ -1355,7 +1345,6 @@ def _nd_operands(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, r
 
 def _nd_forward(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, relu, residual, neighbors_row_count, record=False):
     """dmcf_neighbor_dense_forward; returns out (and with ``record`` the aggregate S [n_out, Cin] and counts c [n_out])."""
-    L = _lib.lib()
     (x, kernel, bias, index, rs, n_in, residual, count, n_out, cin, cout) = _nd_operands(
         x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, residual, neighbors_row_count)
     dev = x.device
@@ -1377,7 +1366,7 @@ def _nd_forward(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, re
         c = torch.empty(n_out, dtype=torch.float32, device=dev)
         a.record_s, a.record_count = s.data_ptr(), c.data_ptr()
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_neighbor_dense_forward(ctypes.byref(a), _stream()), "dmcf_neighbor_dense_forward")
+    _lib.call("dmcf_neighbor_dense_forward", ctypes.byref(a), _stream())
     if timer is not None:
         timer.end("neighbor_dense", dict(n_out=n_out, cin=int(cin), cout=int(cout), pairs=int(index.shape[0]),
                                          kernel=neighbor_dense_kernel_names(a, None)), t0)
@@ -1387,8 +1376,8 @@ def _nd_forward(x, kernel, bias, neighbors_index, neighbors_row_splits, n_in, re
 def neighbor_dense_kernel_names(fwd, bwd):
     """';'-separated names of the kernels dmcf_neighbor_dense_forward (``fwd``) and / or _backward (``bwd``) launch for these
     (ctypes) arguments."""
-    return _kernel_name(_lib.lib().dmcf_neighbor_dense_kernel_names, None if fwd is None else ctypes.byref(fwd),
-                        None if bwd is None else ctypes.byref(bwd), size=256, what="dmcf_neighbor_dense_kernel_names").decode()
+    return _kernel_name("dmcf_neighbor_dense_kernel_names", None if fwd is None else ctypes.byref(fwd),
+                        None if bwd is None else ctypes.byref(bwd), size=256).decode()
 
 
 def neighbor_dense_backward(x, kernel, grad_out, s, count, n_in=None, relu=True, inverted=None, neighbors_index=None,
@@ -1397,7 +1386,6 @@ def neighbor_dense_backward(x, kernel, grad_out, s, count, n_in=None, relu=True,
     from the forward's recorded aggregate ``s`` and counts ``count``.  ``inverted``: an ``invert_neighbors_list`` result of the
     forward list over at least ``n_in`` input rows, or a :class:`SharedInverse`; formed from ``neighbors_index`` /
     ``neighbors_row_splits`` when None and the input gradient is wanted.  grad_x has x's rows; rows past ``n_in`` get 0."""
-    L = _lib.lib()
     kernel = _dev_f32(kernel, "kernel")
     cin, cout = kernel.shape
     x = _dev_f32(x, "x", cin)
@@ -1443,10 +1431,9 @@ def neighbor_dense_backward(x, kernel, grad_out, s, count, n_in=None, relu=True,
             b.grad_bias = gb.data_ptr()
     if gx is None and gw is None and gb is None:
         return None, None, None
-    nbytes = int(L.dmcf_neighbor_dense_backward_workspace_bytes(ctypes.byref(b)))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_neighbor_dense_backward_workspace_bytes", ctypes.byref(b))
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_neighbor_dense_backward(ctypes.byref(b), _ptr(ws), nbytes, _stream()), "dmcf_neighbor_dense_backward")
+    _lib.call("dmcf_neighbor_dense_backward", ctypes.byref(b), _ptr(ws), nbytes, _stream())
     if timer is not None:
         timer.end("neighbor_dense_backward", dict(n_out=n_out, cin=int(cin), cout=int(cout),
                                                   kernel=neighbor_dense_kernel_names(None, b)), t0)
@@ -1530,8 +1517,8 @@ def scatter_plan(inp_positions, out_positions, voxel, radius, block_cells=None):
     nbytes = L.dmcf_cconv_scatter_plan_bytes(n)
     buf = torch.empty(nbytes, dtype=torch.uint8, device=inp.device)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_cconv_scatter_plan(_ptr(inp), n, _ptr(out), out.shape[0], float(voxel), 2.0 * float(radius), m, _ptr(buf), nbytes,
-                                         _stream()), "dmcf_cconv_scatter_plan")
+    _lib.call("dmcf_cconv_scatter_plan", _ptr(inp), n, _ptr(out), out.shape[0], float(voxel), 2.0 * float(radius), m, _ptr(buf),
+              nbytes, _stream())
     if timer is not None:
         timer.end("scatter_plan", dict(n_points=n), t0)
     return ScatterPlan(buf, voxel, m, scatter_reach(radius, voxel), n, (inp, out))
@@ -1610,7 +1597,6 @@ def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_fea
     output's).  Every operand is checked as in a plain call, before the node is made.  ``out=`` / ``accumulate=True`` raise
     ValueError there.  Otherwise the call is exactly the inference path."""
     recording = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (filters, inp_features, bias))
-    L = _lib.lib()
     checked = _scatter_operands("cconv_scatter_forward", filters, out_positions, inp_positions, inp_features, t_index, t_row_begin,
                                 t_row_count, window)
     cin, cout = int(checked[0].shape[3]), int(checked[0].shape[4])
@@ -1669,10 +1655,9 @@ def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_fea
     a.bias = _ptr(bias) if bias is not None else None
     a.out = _ptr(out)
     a.error_flag = _ptr(error_flag) if error_flag is not None else None
-    nbytes = L.dmcf_cconv_scatter_workspace_bytes(ctypes.byref(a))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=filters.device)
+    ws, nbytes = _workspace(filters.device, "dmcf_cconv_scatter_workspace_bytes", ctypes.byref(a), least=0)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_cconv_scatter_forward(ctypes.byref(a), _ptr(ws), nbytes, _stream()), "dmcf_cconv_scatter_forward")
+    _lib.call("dmcf_cconv_scatter_forward", ctypes.byref(a), _ptr(ws), nbytes, _stream())
     if timer is not None:
         pairs = n_pairs_ref if n_pairs_ref is not None else (t_row_count.sum() if t_row_count is not None else t_row_begin[-1])
         timer.end("cconv", dict(pairs=pairs, n_out=n_out, cin=cin, cout=cout, K=64, symmetric=False,
@@ -1704,7 +1689,6 @@ def cconv_scatter_backward(filters, out_positions, extent, inp_positions, inp_fe
     row splits) gives both: no plan, no list inversion, no float atomics (two calls return the same bits).  Operands as
     cconv_scatter_forward takes them, checked as strictly.  Rows of ``grad_inp_features`` of input points without pairs are
     zero.  Empty point sets or an empty ``t_index`` give zero gradients without a launch."""
-    L = _lib.lib()
     filters, out_positions, inp_positions, inp_features = _scatter_operands(
         "cconv_scatter_backward", filters, out_positions, inp_positions, inp_features, t_index, t_row_begin, t_row_count, window)
     cin, cout = int(filters.shape[3]), int(filters.shape[4])
@@ -1728,10 +1712,9 @@ def cconv_scatter_backward(filters, out_positions, extent, inp_positions, inp_fe
     b.grad_out = _ptr(grad_out)
     b.grad_filters = _ptr(gw) if need_filters else None
     b.grad_inp_features = _ptr(gf) if need_features else None
-    nbytes = int(L.dmcf_cconv_scatter_backward_workspace_bytes(ctypes.byref(a), ctypes.byref(b)))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_cconv_scatter_backward_workspace_bytes", ctypes.byref(a), ctypes.byref(b), least=0)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_cconv_scatter_backward(ctypes.byref(a), ctypes.byref(b), _ptr(ws), nbytes, _stream()), "dmcf_cconv_scatter_backward")
+    _lib.call("dmcf_cconv_scatter_backward", ctypes.byref(a), ctypes.byref(b), _ptr(ws), nbytes, _stream())
     if timer is not None:
         timer.end("cconv_backward", dict(n_out=n_out, n_inp=n_inp, cin=cin, cout=cout, filters=bool(need_filters),
                                          features=bool(need_features), kernel="cconv_sct_bwd"), t0)
@@ -1789,7 +1772,7 @@ def continuous_conv(filters, out_positions, extents, offset, inp_positions, inp_
                          coordinate_mapping=coordinate_mapping, interpolation=interpolation, normalize=normalize)
 
 
-SPARSE_NEGATE, SPARSE_W_TRANSPOSED, SPARSE_ACCUMULATE = 1, 2, 4
+SPARSE_NEGATE, SPARSE_W_TRANSPOSED, SPARSE_ACCUMULATE = 1, 2, 4  # DMCF_SPARSE_*
 
 
 def _sparse_offset(offset):
@@ -1866,8 +1849,7 @@ def _sparse_args(filters, row_positions, col_positions, col_features, index, row
 
 def sparse_conv_kernel_names(a, backward=0):
     """';'-separated kernels dmcf_sparse_conv_forward (``backward`` 0) / _backward (1: filters, 2: features, 3: both) launches."""
-    return _kernel_name(_lib.lib().dmcf_sparse_conv_kernel_names, ctypes.byref(a), int(backward), size=128,
-                        what="dmcf_sparse_conv_kernel_names").decode()
+    return _kernel_name("dmcf_sparse_conv_kernel_names", ctypes.byref(a), int(backward), size=128).decode()
 
 
 def sparse_gather(filters, row_positions, col_positions, col_features, index, row_splits, extent, offset, flags=0, row_scale=None,
@@ -1893,7 +1875,7 @@ def sparse_gather(filters, row_positions, col_positions, col_features, index, ro
         return out
     a.out = out.data_ptr()
     t0 = timer.begin() if timer is not None else None
-    _lib.check(_lib.lib().dmcf_sparse_conv_forward(ctypes.byref(a), _stream()), "dmcf_sparse_conv_forward")
+    _lib.call("dmcf_sparse_conv_forward", ctypes.byref(a), _stream())
     if timer is not None:
         timer.end("sparse_conv", dict(n_rows=int(a.n_rows), cin=int(filters.shape[3]), cout=int(filters.shape[4])), t0)
     del keep
@@ -1905,7 +1887,6 @@ def sparse_gather_backward(filters, row_positions, col_positions, col_features, 
     """dmcf_sparse_conv_backward: ``(grad_filters, grad_col_features)`` of :func:`sparse_gather` with these arguments.
     ``inverted``: an ``invert_neighbors_list(n_cols, index, row_splits)`` result (formed here when the feature gradient is
     wanted and none is given)."""
-    L = _lib.lib()
     offset = _sparse_offset(offset)
     a, keep, dev = _sparse_args(filters, row_positions, col_positions, col_features, index, row_splits, extent, offset,
                                 flags & ~SPARSE_ACCUMULATE, row_scale, col_scale)
@@ -1929,11 +1910,10 @@ def sparse_gather_backward(filters, row_positions, col_positions, col_features, 
             inverted = invert_neighbors_list(a.n_cols, keep[4], keep[5])
         inv_index, inv_rs = inverted.neighbors_index, inverted.neighbors_row_splits
         inv_pairs = inv_index.shape[0]
-    nbytes = int(L.dmcf_sparse_conv_backward_workspace_bytes(ctypes.byref(a), 1 if need_filters else 0))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_sparse_conv_backward_workspace_bytes", ctypes.byref(a), 1 if need_filters else 0, least=16)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_sparse_conv_backward(ctypes.byref(a), _ptr(grad_out), _ptr(inv_index), _ptr(inv_rs), inv_pairs, _ptr(gw), _ptr(gf),
-                                           _ptr(ws), nbytes, _stream()), "dmcf_sparse_conv_backward")
+    _lib.call("dmcf_sparse_conv_backward", ctypes.byref(a), _ptr(grad_out), _ptr(inv_index), _ptr(inv_rs), inv_pairs, _ptr(gw),
+              _ptr(gf), _ptr(ws), nbytes, _stream())
     if timer is not None:
         timer.end("sparse_conv_backward", dict(n_rows=int(a.n_rows), filters=bool(need_filters), features=bool(need_features)), t0)
     del keep
@@ -2032,7 +2012,6 @@ def dense_supported(x, kernel):
 
 def dense_forward(x, kernel, bias=None, residual=None):
     """``x @ kernel (+ bias) (+ residual)``: the networks' Dense layers on a million rows (dmcf_dense_forward)."""
-    L = _lib.lib()
     n, k = x.shape
     m = kernel.shape[1]
     kernel = _dev_f32(kernel, "kernel")
@@ -2041,8 +2020,8 @@ def dense_forward(x, kernel, bias=None, residual=None):
         residual = _dev_f32(residual, "residual")
         if tuple(residual.shape) != (n, m):
             raise ValueError("residual must be [n, m]")
-    _lib.check(L.dmcf_dense_forward(_ptr(x), n, k, _ptr(kernel), m, _ptr(bias) if bias is not None else None,
-                                    _ptr(residual) if residual is not None else None, _ptr(out), _stream()), "dmcf_dense_forward")
+    _lib.call("dmcf_dense_forward", _ptr(x), n, k, _ptr(kernel), m, _ptr(bias) if bias is not None else None,
+              _ptr(residual) if residual is not None else None, _ptr(out), _stream())
     return out
 
 
@@ -2058,12 +2037,11 @@ def points_aabb(points, row_splits=None):
         if points.dim() != 2 or points.shape[1] != 3:
             raise ValueError("points must be [n, 3]")
         _check_row_splits(host, points.shape[0], "row_splits")
-        L = _lib.lib()
         points = _dev_f32(points, "points")
         batch = len(host) - 1
         out = torch.empty((batch, 6), dtype=torch.float32, device=points.device)
-        _lib.check(L.dmcf_points_aabb_batched(_ptr(points), points.shape[0], _ptr(_row_splits_on(host, dev, points.device)), batch,
-                                              _ptr(out), _stream()), "dmcf_points_aabb_batched")
+        _lib.call("dmcf_points_aabb_batched", _ptr(points), points.shape[0], _ptr(_row_splits_on(host, dev, points.device)), batch,
+                  _ptr(out), _stream())
         return out[:, :3], out[:, 3:]
     L = _lib.lib()
     points = _dev_f32(points, "points")
@@ -2072,20 +2050,18 @@ def points_aabb(points, row_splits=None):
     out = torch.empty(6, dtype=torch.float32, device=points.device)
     wsb = int(L.dmcf_points_aabb_workspace_bytes())
     ws = torch.empty(wsb // 4, dtype=torch.float32, device=points.device)
-    _lib.check(L.dmcf_points_aabb(_ptr(points), points.shape[0], _ptr(out), _ptr(ws), wsb, _stream()), "dmcf_points_aabb")
+    _lib.call("dmcf_points_aabb", _ptr(points), points.shape[0], _ptr(out), _ptr(ws), wsb, _stream())
     return out[:3], out[3:]
 
 
 def reduce_subarrays_sum(values, row_splits):
     """Mirror of ``o3dml.ops.reduce_subarrays_sum`` (models/pbf_model.py:450-453)."""
-    L = _lib.lib()
     values = _dev_f32(values, "values")
     if row_splits.dtype != torch.int64:
         raise TypeError("row_splits must be int64")
     n_rows = row_splits.shape[0] - 1
     out = torch.empty(n_rows, dtype=torch.float32, device=values.device)
-    _lib.check(L.dmcf_reduce_subarrays_sum(_ptr(values), _ptr(row_splits.contiguous()), n_rows, _ptr(out), _stream()),
-               "dmcf_reduce_subarrays_sum")
+    _lib.call("dmcf_reduce_subarrays_sum", _ptr(values), _ptr(row_splits.contiguous()), n_rows, _ptr(out), _stream())
     return out
 
 
@@ -2096,13 +2072,11 @@ def neighbor_counts(row_splits):
         return row_splits.row_count.to(torch.float32)
     if isinstance(row_splits, NeighborSearchResult):
         row_splits = row_splits.neighbors_row_splits
-    L = _lib.lib()
     if row_splits.dtype != torch.int64 or not row_splits.is_cuda:
         raise _lib.DmcfError("row_splits must be an int64 GPU tensor")
     n_rows = row_splits.shape[0] - 1
     out = torch.empty(n_rows, dtype=torch.float32, device=row_splits.device)
-    _lib.check(L.dmcf_reduce_subarrays_sum(None, _ptr(row_splits.contiguous()), n_rows, _ptr(out), _stream()),
-               "dmcf_reduce_subarrays_sum")
+    _lib.call("dmcf_reduce_subarrays_sum", None, _ptr(row_splits.contiguous()), n_rows, _ptr(out), _stream())
     return out
 
 
@@ -2209,7 +2183,7 @@ def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=No
     cflag = 1 if centralize else 0
     # the entry points of the call and what the batched ones take after (positions, n): the un-batched ones take no row splits
     if batched:
-        names = ["dmcf_grid_pos_bounds_batched", "dmcf_grid_pos_count_batched", "dmcf_grid_pos_write_batched"]
+        bounds_fn, count_fn, write_fn = "dmcf_grid_pos_bounds_batched", "dmcf_grid_pos_count_batched", "dmcf_grid_pos_write_batched"
         rs = _row_splits_on(host, dev, pos.device)
         items = (_ptr(rs), batch)
         cen = _dev_f32(center, "center") if center is not None else None
@@ -2217,17 +2191,16 @@ def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=No
         if ws_bytes == 0:
             raise _lib.DmcfError(f"grid_pos: a batch of {batch} items is not supported")
     else:
-        names = ["dmcf_grid_pos_bounds", "dmcf_grid_pos_count", "dmcf_grid_pos_write"]
+        bounds_fn, count_fn, write_fn = "dmcf_grid_pos_bounds", "dmcf_grid_pos_count", "dmcf_grid_pos_write"
         items, batch = (), 1
         cen = _dev_f32(center.reshape(3), "center") if center is not None else None
         ws_bytes = L.dmcf_grid_pos_workspace_bytes(n)
-    bounds_fn, count_fn, write_fn = (getattr(L, name) for name in names)
     levels = []
     for v in voxel_sizes:
         vs = (ctypes.c_float * 3)(*[float(x) for x in np.asarray(v, dtype=np.float32).reshape(3)])
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
-        _lib.check(bounds_fn(_ptr(pos), n, *items, vs, cflag, _ptr(cen) if cen is not None else None, int(pad), float(hyst),
-                             _ptr(ws), ws_bytes, _stream()), names[0])
+        _lib.call(bounds_fn, _ptr(pos), n, *items, vs, cflag, _ptr(cen) if cen is not None else None, int(pad), float(hyst),
+                  _ptr(ws), ws_bytes, _stream())
         # (ors: the output row splits, the batched count pass's extra argument)
         levels.append(dict(vs=vs, ws=ws, ors=torch.empty(batch + 1, dtype=torch.int64, device=pos.device) if batched else None))
 
@@ -2248,8 +2221,8 @@ def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=No
 
     def count(lv, capacity):
         lv["table"], lv["capacity"] = _grid_cell_table(capacity, pos.device), capacity
-        _lib.check(count_fn(_ptr(pos), n, *items, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
-                            _ptr(lv["table"]), capacity, *([_ptr(lv["ors"])] if batched else []), _stream()), names[1])
+        _lib.call(count_fn, _ptr(pos), n, *items, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
+                  _ptr(lv["table"]), capacity, *([_ptr(lv["ors"])] if batched else []), _stream())
 
     # (the estimates are keyed with the batch size: a training loop asks for the same batch step after step)
     key = (tuple(tuple(float(x) for x in lv["vs"]) for lv in levels), bool(centralize), int(pad), float(hyst))
@@ -2261,8 +2234,8 @@ def grid_pos_many(pos, voxel_sizes, centralize=False, pad=0, hyst=0.1, center=No
         total = sum(lv["totals"])
         out = torch.empty((total, 3), dtype=torch.float32, device=pos.device)
         if total:
-            _lib.check(write_fn(_ptr(pos), n, *items, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
-                                _ptr(lv["table"]), lv["capacity"], _ptr(out), total, _stream()), names[2])
+            _lib.call(write_fn, _ptr(pos), n, *items, lv["vs"], cflag, int(pad), float(hyst), _ptr(lv["ws"]), ws_bytes,
+                      _ptr(lv["table"]), lv["capacity"], _ptr(out), total, _stream())
         if batched:
             out_host = [0]
             for t in lv["totals"]:
@@ -2304,7 +2277,6 @@ class GhostSelection:
     def write(self, sizes):
         """``sizes``: entries of list(w) per width (host ints: the row sums of ``totals``, read by the caller -- or known from the
         ranks that counted the same points).  -> [int64 tensor of list(w) for every w]: box-major, ascending point index."""
-        L = _lib.lib()
         W, B = self.totals.shape
         sizes = [int(v) for v in sizes]
         starts = [0]
@@ -2313,8 +2285,8 @@ class GhostSelection:
         rows = torch.empty(max(sum(sizes), 1), dtype=torch.int64, device=self.pos.device)
         c64 = ctypes.c_int64 * W
         w2 = (ctypes.c_float * W)(*self.widths2)
-        _lib.check(L.dmcf_ghost_write(_ptr(self.pos), self.pos.shape[0], _ptr(self.boxes), B, w2, W, _ptr(rows), c64(*starts), c64(*sizes),
-                                      _ptr(self.ws), self.ws.numel(), _stream()), "dmcf_ghost_write")
+        _lib.call("dmcf_ghost_write", _ptr(self.pos), self.pos.shape[0], _ptr(self.boxes), B, w2, W, _ptr(rows), c64(*starts),
+                  c64(*sizes), _ptr(self.ws), self.ws.numel(), _stream())
         return [rows[starts[w]: starts[w] + sizes[w]] for w in range(W)]
 
 
@@ -2323,17 +2295,14 @@ def ghost_select(pos, boxes, widths2):
     number of ``widths2`` (host floats, DESCENDING) its squared distance to the box does not exceed.  ``widths2`` = [-1.0] selects
     OWNERSHIP instead (lo <= x < hi per axis): one list, the stable order of the points by owning box.  Returns a
     :class:`GhostSelection`."""
-    L = _lib.lib()
     pos = _dev_f32(pos, "pos", 3)
     boxes = _dev_f32(boxes.reshape(-1, 6), "boxes", 6)
     B, W = boxes.shape[0], len(widths2)
     widths2 = [float(np.float32(v)) for v in widths2]
-    nbytes = L.dmcf_ghost_workspace_bytes(pos.shape[0], B, W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=pos.device)
+    ws, nbytes = _workspace(pos.device, "dmcf_ghost_workspace_bytes", pos.shape[0], B, W, least=0)
     totals = torch.empty((W, B), dtype=torch.int64, device=pos.device)
     w2 = (ctypes.c_float * W)(*widths2)
-    _lib.check(L.dmcf_ghost_count(_ptr(pos), pos.shape[0], _ptr(boxes), B, w2, W, _ptr(totals), _ptr(ws), nbytes, _stream()),
-               "dmcf_ghost_count")
+    _lib.call("dmcf_ghost_count", _ptr(pos), pos.shape[0], _ptr(boxes), B, w2, W, _ptr(totals), _ptr(ws), nbytes, _stream())
     return GhostSelection(pos, boxes, widths2, ws, totals)
 
 
@@ -2341,7 +2310,6 @@ def _window_sum_impl(points, queries, radius, window, flags, hash_table, batched
     """dmcf_frs_window_sum, or with ``batched`` (WindowSumFunction's triple) dmcf_frs_window_sum_batched, under the span
     frs_window_sum_batched -> (out, item_max or None, the search structure over ``points`` that served the call, the queries'
     device splits or None)."""
-    L = _lib.lib()
     n, m = points.shape[0], queries.shape[0]
     dev = points.device
     p_splits, (q_host, q_dev), want_max = batched if batched is not None else (None, (None, None), False)
@@ -2351,14 +2319,14 @@ def _window_sum_impl(points, queries, radius, window, flags, hash_table, batched
     out = torch.empty(m, dtype=torch.float32, device=dev)
     q_rs = item_max = None
     if batched is None:
-        entry, name, item, tail = L.dmcf_frs_window_sum, "dmcf_frs_window_sum", (), ()
+        entry, item, tail = "dmcf_frs_window_sum", (), ()
     else:
         q_rs = _row_splits_on(q_host, q_dev, dev)
         item_max = torch.empty(batch, dtype=torch.float32, device=dev) if want_max else None
-        entry, name, item, tail = L.dmcf_frs_window_sum_batched, "dmcf_frs_window_sum_batched", (_ptr(q_rs), batch), (_ptr(item_max),)
+        entry, item, tail = "dmcf_frs_window_sum_batched", (_ptr(q_rs), batch), (_ptr(item_max),)
     t0 = timer.begin() if timer is not None and batched is not None else None
-    _lib.check(entry(_ptr(queries), m, *item, n, radius, flags, WINDOWS[window], _ptr(hash_table.workspace), nbytes, _ptr(out), *tail,
-                     _stream()), name)
+    _lib.call(entry, _ptr(queries), m, *item, n, radius, flags, WINDOWS[window], _ptr(hash_table.workspace), nbytes, _ptr(out), *tail,
+              _stream())
     if t0 is not None:
         timer.end("frs_window_sum_batched", dict(n_points=n, n_queries=m, batch=batch), t0)
     return out, item_max, hash_table, q_rs
@@ -2373,7 +2341,6 @@ def window_sum_backward(queries, hash_table, radius, window, coef_queries=None, 
     ``queries_row_splits`` (as for the batched search, with as many items as the structure): on the batched structure of some
     concatenated point sets (dmcf_frs_window_sum_backward_batched), the sums of a query running over the points of its own
     item.  A batched structure needs them, the structure of a single point set takes none (ValueError either way)."""
-    L = _lib.lib()
     batched = queries_row_splits is not None
     if batched and hash_table.row_splits is None:
         raise ValueError("hash_table is not a batched structure (build_spatial_hash_table(..., points_row_splits=...))")
@@ -2397,14 +2364,14 @@ def window_sum_backward(queries, hash_table, radius, window, coef_queries=None, 
     if batched:
         q_rs = _row_splits_on(q_host, q_dev, dev)
         batch = len(q_host) - 1
-        entry, name, item = L.dmcf_frs_window_sum_backward_batched, "dmcf_frs_window_sum_backward_batched", (_ptr(q_rs), batch)
+        entry, item = "dmcf_frs_window_sum_backward_batched", (_ptr(q_rs), batch)
     else:
         batch = None
-        entry, name, item = L.dmcf_frs_window_sum_backward, "dmcf_frs_window_sum_backward", ()
+        entry, item = "dmcf_frs_window_sum_backward", ()
     nbytes = _frs_workspace_bytes(n, hash_table.n_queries_capacity, batch)
     grad = torch.empty((m, 3), dtype=torch.float32, device=dev)
-    _lib.check(entry(_ptr(queries), m, *item, n, radius, frs_flags(ignore_query_point, batched), WINDOWS[window], _ptr(cq), _ptr(cp),
-                     _ptr(hash_table.workspace), nbytes, _ptr(grad), _stream()), name)
+    _lib.call(entry, _ptr(queries), m, *item, n, radius, frs_flags(ignore_query_point, batched), WINDOWS[window], _ptr(cq), _ptr(cp),
+              _ptr(hash_table.workspace), nbytes, _ptr(grad), _stream())
     return grad
 
 
@@ -2545,18 +2512,15 @@ def window_sum(points, queries, radius, window=None, ignore_query_point=False, h
 def farthest_point_sample(npoint, inp):
     """Mirror of ``utils/tools/sampling.py: farthest_point_sample(npoint, inp)``: ``inp`` [1, n, 3] -> int32 [1, npoint]
     (dmcf_farthest_point_sample; the batch dimension of this path is always 1, utils/tools/losses.py:278-279)."""
-    L = _lib.lib()
     if inp.dim() != 3 or inp.shape[0] != 1 or inp.shape[2] != 3:
         raise ValueError("farthest_point_sample expects a [1, n, 3] tensor")
     pts = _dev_f32(inp[0], "inp", 3)
     n, m = pts.shape[0], int(npoint)
     if m > 0 and n == 0:
         raise ValueError("cannot sample from an empty point set")
-    nbytes = L.dmcf_fps_workspace_bytes(n)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+    ws, nbytes = _workspace(pts.device, "dmcf_fps_workspace_bytes", n, least=0)
     idx = torch.empty(m, dtype=torch.int32, device=pts.device)
-    _lib.check(L.dmcf_farthest_point_sample(_ptr(pts), n, m, _ptr(ws), nbytes, _ptr(idx), _stream()),
-               "dmcf_farthest_point_sample")
+    _lib.call("dmcf_farthest_point_sample", _ptr(pts), n, m, _ptr(ws), nbytes, _ptr(idx), _stream())
     return idx.unsqueeze(0)
 
 
@@ -2594,16 +2558,14 @@ def _sets3(xyz1, xyz2):
 
 
 def _gather_point_impl(x, ii):
-    L = _lib.lib()
     out = torch.empty((ii.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
-    _lib.check(L.dmcf_gather_point(_ptr(x), _ptr(ii), ii.shape[0], x.shape[1], _ptr(out), _stream()), "dmcf_gather_point")
+    _lib.call("dmcf_gather_point", _ptr(x), _ptr(ii), ii.shape[0], x.shape[1], _ptr(out), _stream())
     return out
 
 
 def gather_point_backward(grad_out, idx, n_inp):
     """dmcf_gather_point_backward: grad_inp [n_inp, c] = sum of the rows of ``grad_out`` [m, c] whose ``idx`` [m] (int32) points
     at the row; repeated indices sum, in ascending order of m (no atomics)."""
-    L = _lib.lib()
     g = _dev_f32(grad_out, "grad_out")
     if g.dim() != 2 or g.shape[1] == 0:
         raise ValueError(f"grad_out must have shape [m, c] with c > 0, got {tuple(g.shape)}")
@@ -2613,10 +2575,8 @@ def gather_point_backward(grad_out, idx, n_inp):
     if n_inp < 0:
         raise ValueError(f"n_inp must be >= 0, got {n_inp}")
     grad_inp = torch.empty((n_inp, c), dtype=torch.float32, device=g.device)
-    nbytes = int(L.dmcf_gather_point_backward_workspace_bytes(m, n_inp))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=g.device)
-    _lib.check(L.dmcf_gather_point_backward(_ptr(g), _ptr(idx), m, c, int(n_inp), _ptr(grad_inp), _ptr(ws), nbytes, _stream()),
-               "dmcf_gather_point_backward")
+    ws, nbytes = _workspace(g.device, "dmcf_gather_point_backward_workspace_bytes", m, n_inp)
+    _lib.call("dmcf_gather_point_backward", _ptr(g), _ptr(idx), m, c, int(n_inp), _ptr(grad_inp), _ptr(ws), nbytes, _stream())
     return grad_inp
 
 
@@ -2703,7 +2663,6 @@ def _counts_ptr(arr):
 
 
 def _nn_distance_impl(a, b):
-    L = _lib.lib()
     nb, n, m = a.shape[0], a.shape[1], b.shape[1]
     dev = a.device
     d1 = torch.empty((nb, n), dtype=torch.float32, device=dev)
@@ -2711,10 +2670,9 @@ def _nn_distance_impl(a, b):
     d2 = torch.empty((nb, m), dtype=torch.float32, device=dev)
     i2 = torch.empty((nb, m), dtype=torch.int32, device=dev)
     if nb > 0:
-        nbytes = int(L.dmcf_nn_distance_workspace_bytes(nb, n, m))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _lib.check(L.dmcf_nn_distance(_ptr(a), _ptr(b), nb, n, m, _ptr(d1), _ptr(i1), _ptr(d2), _ptr(i2), _ptr(ws), nbytes,
-                                      _stream()), "dmcf_nn_distance")
+        ws, nbytes = _workspace(dev, "dmcf_nn_distance_workspace_bytes", nb, n, m)
+        _lib.call("dmcf_nn_distance", _ptr(a), _ptr(b), nb, n, m, _ptr(d1), _ptr(i1), _ptr(d2), _ptr(i2), _ptr(ws), nbytes,
+                  _stream())
     return d1, i1, d2, i2
 
 
@@ -2722,7 +2680,6 @@ def nn_distance_backward(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, need1=T
     """dmcf_nn_distance_backward on [b, n, 3] / [b, m, 3] point sets and the forward's int32 indices: (grad_xyz1, grad_xyz2)
     (None where not wanted).  ``grad_dist1`` / ``grad_dist2`` None: zero.  No atomics: the scattered terms are gathered through a
     sort of the index list."""
-    L = _lib.lib()
     xyz1, xyz2 = _sets3(xyz1, xyz2)
     nb, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
     if nb > 0 and (n == 0 or m == 0):
@@ -2735,10 +2692,9 @@ def nn_distance_backward(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, need1=T
     gx1 = torch.empty((nb, n, 3), dtype=torch.float32, device=dev) if need1 else None
     gx2 = torch.empty((nb, m, 3), dtype=torch.float32, device=dev) if need2 else None
     if nb > 0 and (need1 or need2):
-        nbytes = int(L.dmcf_nn_distance_backward_workspace_bytes(nb, n, m))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _lib.check(L.dmcf_nn_distance_backward(_ptr(xyz1), _ptr(xyz2), nb, n, m, _ptr(idx1), _ptr(idx2), _ptr(g1), _ptr(g2),
-                                               _ptr(gx1), _ptr(gx2), _ptr(ws), nbytes, _stream()), "dmcf_nn_distance_backward")
+        ws, nbytes = _workspace(dev, "dmcf_nn_distance_backward_workspace_bytes", nb, n, m)
+        _lib.call("dmcf_nn_distance_backward", _ptr(xyz1), _ptr(xyz2), nb, n, m, _ptr(idx1), _ptr(idx2), _ptr(g1), _ptr(g2),
+                  _ptr(gx1), _ptr(gx2), _ptr(ws), nbytes, _stream())
     return gx1, gx2
 
 
@@ -2843,18 +2799,16 @@ def nn_distance_ragged(xyz1, xyz2, row_splits1, row_splits2, want1=True, want2=T
 
 def _nn_distance_ragged_impl(a, b, s1, s2, want1, want2):
     batch = len(s1) - 1
-    L = _lib.lib()
     n, m, dev = a.shape[1], b.shape[1], a.device
     d1 = torch.empty(n, dtype=torch.float32, device=dev) if want1 else None
     i1 = torch.empty(n, dtype=torch.int32, device=dev) if want1 else None
     d2 = torch.empty(m, dtype=torch.float32, device=dev) if want2 else None
     i2 = torch.empty(m, dtype=torch.int32, device=dev) if want2 else None
     if n > 0:
-        nbytes = int(L.dmcf_nn_distance_ragged_workspace_bytes(n, m, batch))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        ws, nbytes = _workspace(dev, "dmcf_nn_distance_ragged_workspace_bytes", n, m, batch)
         h1, h2 = (ctypes.c_int64 * (batch + 1))(*s1), (ctypes.c_int64 * (batch + 1))(*s2)
-        _lib.check(L.dmcf_nn_distance_ragged(_ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(d1), _ptr(i1), _ptr(d2), _ptr(i2),
-                                             _ptr(ws), nbytes, _stream()), "dmcf_nn_distance_ragged")
+        _lib.call("dmcf_nn_distance_ragged", _ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(d1), _ptr(i1), _ptr(d2), _ptr(i2),
+                  _ptr(ws), nbytes, _stream())
     return d1, i1, d2, i2
 
 
@@ -2892,7 +2846,6 @@ def approx_match(xyz1, xyz2, n=None, m=None):
     """Mirror of ``utils/tools/tf_approxmatch.py: approx_match(xyz1, xyz2, n, m)`` -> match [b, m, n] (dmcf_approx_match).
     ``n`` / ``m``: per-batch point counts (None: all points); rows and columns past a count are 0.  Refuses, before anything
     runs, a dense matrix that would not fit on the device: use :func:`emd` for the cost alone."""
-    L = _lib.lib()
     a, b, batched = _pair_batch(xyz1, xyz2)
     nb, nn_, mm = a.shape[0], a.shape[1], b.shape[1]
     c1, c2 = _host_counts(n, nb, nn_, "n"), _host_counts(m, nb, mm, "m")
@@ -2900,17 +2853,15 @@ def approx_match(xyz1, xyz2, n=None, m=None):
         raise MemoryError(f"approx_match: the dense match [{nb}, {mm}, {nn_}] needs {4 * nb * nn_ * mm / 2 ** 30:.1f} GiB, more "
                           "than the device has free; ops.emd computes the matching cost without forming it")
     match = torch.empty((nb, mm, nn_), dtype=torch.float32, device=a.device)
-    nbytes = int(L.dmcf_approx_match_workspace_bytes(nb, nn_, mm))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
-    _lib.check(L.dmcf_approx_match(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(match), _ptr(ws), nbytes,
-                                   _stream()), "dmcf_approx_match")
+    ws, nbytes = _workspace(a.device, "dmcf_approx_match_workspace_bytes", nb, nn_, mm)
+    _lib.call("dmcf_approx_match", _ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(match), _ptr(ws), nbytes,
+              _stream())
     return match if batched else match[0]
 
 
 def match_cost_backward(xyz1, xyz2, match, grad_cost, need1=True, need2=True):
     """dmcf_match_cost_backward: (grad_xyz1 [b, n, 3], grad_xyz2 [b, m, 3]) of ``match_cost`` for [b, n, 3] / [b, m, 3] sets, a
     dense match [b, m, n] and grad_cost [b] (None where not wanted)."""
-    L = _lib.lib()
     xyz1, xyz2 = _sets3(xyz1, xyz2)
     nb, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
     dev = xyz1.device
@@ -2919,10 +2870,9 @@ def match_cost_backward(xyz1, xyz2, match, grad_cost, need1=True, need2=True):
     gx1 = torch.empty((nb, n, 3), dtype=torch.float32, device=dev) if need1 else None
     gx2 = torch.empty((nb, m, 3), dtype=torch.float32, device=dev) if need2 else None
     if nb > 0 and (need1 or need2):
-        nbytes = int(L.dmcf_match_cost_backward_workspace_bytes(nb, n, m))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _lib.check(L.dmcf_match_cost_backward(_ptr(xyz1), _ptr(xyz2), nb, n, m, _ptr(match), _ptr(gc), _ptr(gx1), _ptr(gx2), _ptr(ws),
-                                              nbytes, _stream()), "dmcf_match_cost_backward")
+        ws, nbytes = _workspace(dev, "dmcf_match_cost_backward_workspace_bytes", nb, n, m)
+        _lib.call("dmcf_match_cost_backward", _ptr(xyz1), _ptr(xyz2), nb, n, m, _ptr(match), _ptr(gc), _ptr(gx1), _ptr(gx2),
+                  _ptr(ws), nbytes, _stream())
     return gx1, gx2
 
 
@@ -2961,12 +2911,10 @@ def match_cost(xyz1, xyz2, match):
 
 
 def _match_cost_impl(a, b, mt):
-    L = _lib.lib()
     nb, n, m = a.shape[0], a.shape[1], b.shape[1]
     cost = torch.empty(nb, dtype=torch.float32, device=a.device)
-    nbytes = int(L.dmcf_match_cost_workspace_bytes(nb, n, m))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
-    _lib.check(L.dmcf_match_cost(_ptr(a), _ptr(b), nb, n, m, _ptr(mt), _ptr(cost), _ptr(ws), nbytes, _stream()), "dmcf_match_cost")
+    ws, nbytes = _workspace(a.device, "dmcf_match_cost_workspace_bytes", nb, n, m)
+    _lib.call("dmcf_match_cost", _ptr(a), _ptr(b), nb, n, m, _ptr(mt), _ptr(cost), _ptr(ws), nbytes, _stream())
     return cost
 
 
@@ -2974,17 +2922,15 @@ EMD_LEVELS = 10  # levels of the approximate match (dmcf_emd_with_levels records
 
 
 def _emd_impl(a, b, c1, c2, levels=None):
-    L = _lib.lib()
     nb, nn_, mm = a.shape[0], a.shape[1], b.shape[1]
     cost = torch.empty(nb, dtype=torch.float32, device=a.device)
-    nbytes = int(L.dmcf_emd_workspace_bytes(nb, nn_, mm))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
+    ws, nbytes = _workspace(a.device, "dmcf_emd_workspace_bytes", nb, nn_, mm)
     if levels is None:
-        _lib.check(L.dmcf_emd(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(ws), nbytes,
-                              _stream()), "dmcf_emd")
+        _lib.call("dmcf_emd", _ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(ws), nbytes,
+                  _stream())
     else:
-        _lib.check(L.dmcf_emd_with_levels(_ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(levels),
-                                          _ptr(ws), nbytes, _stream()), "dmcf_emd_with_levels")
+        _lib.call("dmcf_emd_with_levels", _ptr(a), _ptr(b), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(cost), _ptr(levels),
+                  _ptr(ws), nbytes, _stream())
     return cost
 
 
@@ -3003,7 +2949,6 @@ def emd_backward(xyz1, xyz2, levels, grad_cost, n=None, m=None, need1=True, need
     """dmcf_emd_backward: (grad_xyz1 [b, n, 3], grad_xyz2 [b, m, 3]) of :func:`emd` with the match held constant, from the
     ``levels`` of :func:`emd_with_levels` (same [b, n, 3] / [b, m, 3] sets and counts) and grad_cost [b], without forming the
     match; rows past a count are 0."""
-    L = _lib.lib()
     xyz1, xyz2 = _sets3(xyz1, xyz2)
     nb, nn_, mm = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
     c1, c2 = _host_counts(n, nb, nn_, "n"), _host_counts(m, nb, mm, "m")
@@ -3013,10 +2958,9 @@ def emd_backward(xyz1, xyz2, levels, grad_cost, n=None, m=None, need1=True, need
     gx1 = torch.empty((nb, nn_, 3), dtype=torch.float32, device=dev) if need1 else None
     gx2 = torch.empty((nb, mm, 3), dtype=torch.float32, device=dev) if need2 else None
     if nb > 0 and (need1 or need2):
-        nbytes = int(L.dmcf_emd_backward_workspace_bytes(nb, nn_, mm))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _lib.check(L.dmcf_emd_backward(_ptr(xyz1), _ptr(xyz2), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(levels), _ptr(gc),
-                                       _ptr(gx1), _ptr(gx2), _ptr(ws), nbytes, _stream()), "dmcf_emd_backward")
+        ws, nbytes = _workspace(dev, "dmcf_emd_backward_workspace_bytes", nb, nn_, mm)
+        _lib.call("dmcf_emd_backward", _ptr(xyz1), _ptr(xyz2), nb, nn_, mm, _counts_ptr(c1), _counts_ptr(c2), _ptr(levels),
+                  _ptr(gc), _ptr(gx1), _ptr(gx2), _ptr(ws), nbytes, _stream())
     return gx1, gx2
 
 
@@ -3090,17 +3034,14 @@ def _emd_ragged_impl(a, b, s1, s2, levels=None):
     n, m, dev = a.shape[1], b.shape[1], a.device
     if n == 0 and m == 0:  # (every item empty: the library enqueues nothing and leaves cost alone)
         return torch.zeros(batch, dtype=torch.float32, device=dev)
-    L = _lib.lib()
     cost = torch.empty(batch, dtype=torch.float32, device=dev)
     h1, h2 = _host_i64(s1), _host_i64(s2)
-    nbytes = int(L.dmcf_emd_ragged_workspace_bytes(n, h1, m, h2, batch))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_emd_ragged_workspace_bytes", n, h1, m, h2, batch)
     if levels is None:
-        _lib.check(L.dmcf_emd_ragged(_ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(cost), _ptr(ws), nbytes, _stream()),
-                   "dmcf_emd_ragged")
+        _lib.call("dmcf_emd_ragged", _ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(cost), _ptr(ws), nbytes, _stream())
     else:
-        _lib.check(L.dmcf_emd_ragged_with_levels(_ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(cost), _ptr(levels), _ptr(ws), nbytes,
-                                                 _stream()), "dmcf_emd_ragged_with_levels")
+        _lib.call("dmcf_emd_ragged_with_levels", _ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(cost), _ptr(levels), _ptr(ws), nbytes,
+                  _stream())
     return cost
 
 
@@ -3159,12 +3100,10 @@ def emd_ragged_backward(xyz1, xyz2, row_splits1, row_splits2, levels, grad_cost,
     gx1 = torch.empty((n, 3), dtype=torch.float32, device=dev) if need1 else None
     gx2 = torch.empty((m, 3), dtype=torch.float32, device=dev) if need2 else None
     if (need1 or need2) and n + m > 0:
-        L = _lib.lib()
         h1, h2 = _host_i64(s1), _host_i64(s2)
-        nbytes = int(L.dmcf_emd_ragged_backward_workspace_bytes(n, h1, m, h2, batch))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _lib.check(L.dmcf_emd_ragged_backward(_ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(levels), _ptr(gc), _ptr(gx1), _ptr(gx2),
-                                              _ptr(ws), nbytes, _stream()), "dmcf_emd_ragged_backward")
+        ws, nbytes = _workspace(dev, "dmcf_emd_ragged_backward_workspace_bytes", n, h1, m, h2, batch)
+        _lib.call("dmcf_emd_ragged_backward", _ptr(a), n, h1, _ptr(b), m, h2, batch, _ptr(levels), _ptr(gc), _ptr(gx1), _ptr(gx2),
+                  _ptr(ws), nbytes, _stream())
     return gx1, gx2
 
 
@@ -3289,17 +3228,15 @@ def hist_pair_ragged(x, y, row_splits=None, bin_size=25):
         plan[b].rank[:] = [k5, k5n, k95, k95n]
         plan[b].gamma[:] = [g5, g95]
         offsets.append(offsets[-1] + 2 * (per + 1) ** 3)
-    L = _lib.lib()
     x, y = x.contiguous(), y.contiguous()
     dev = x.device
     bins_total = offsets[-1] // 2
     percentiles = torch.empty((batch, 2, 3), dtype=torch.float32, device=dev)
     counts = torch.empty(offsets[-1], dtype=torch.int32, device=dev)
-    nbytes = int(L.dmcf_hist_pair_ragged_workspace_bytes(n, batch, bins_total))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_hist_pair_ragged_workspace_bytes", n, batch, bins_total)
     h = (ctypes.c_int64 * (batch + 1))(*rs)
-    _lib.check(L.dmcf_hist_pair_ragged(_ptr(x), _ptr(y), n, h, batch, plan, bins_total, _ptr(percentiles), _ptr(counts), _ptr(ws),
-                                       nbytes, _stream()), "dmcf_hist_pair_ragged")
+    _lib.call("dmcf_hist_pair_ragged", _ptr(x), _ptr(y), n, h, batch, plan, bins_total, _ptr(percentiles), _ptr(counts), _ptr(ws),
+              nbytes, _stream())
     return percentiles, counts, offsets
 
 
@@ -3331,7 +3268,7 @@ def adam_step_kernel_names(params, grads, ms, vs, clip_norm=None):
     """';'-separated names of the kernels dmcf_adam_step launches for these tensors (rocprofv3's kernel names)."""
     a, recs = _adam_args(params, grads, ms, vs, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, clip_norm)
     a.device_tensors = 1 if len(params) else None  # (validated for presence only: nothing is read)
-    return _kernel_name(_lib.lib().dmcf_adam_step_kernel_names, ctypes.byref(a), size=64, what="dmcf_adam_step_kernel_names").decode()
+    return _kernel_name("dmcf_adam_step_kernel_names", ctypes.byref(a), size=64).decode()
 
 
 def adam_step(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, beta_2_power, clip_norm=None):
@@ -3340,7 +3277,6 @@ def adam_step(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, 
     gradient clipped per tensor to ``clip_norm`` first when that is > 0 (tf.clip_by_norm).  Lists of contiguous float32 device
     tensors; the scalars are Keras' coefficients for the iteration (utils/tools/losses.KerasAdam computes them).  One launch
     (two with clipping); the descriptor table goes to the device in one copy."""
-    L = _lib.lib()
     a, recs = _adam_args(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, beta_2_power, clip_norm)
     if not params:
         return
@@ -3348,10 +3284,9 @@ def adam_step(params, grads, ms, vs, lr, beta_1, beta_2, epsilon, beta_1_power, 
     raw = torch.frombuffer(bytearray(ctypes.string_at(recs, ctypes.sizeof(_lib.AdamTensor) * len(params))), dtype=torch.uint8)
     table = raw.to(dev, non_blocking=False)
     a.device_tensors = table.data_ptr()
-    nbytes = int(L.dmcf_adam_step_workspace_bytes(ctypes.byref(a)))
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(dev, "dmcf_adam_step_workspace_bytes", ctypes.byref(a), least=8)
     t0 = timer.begin() if timer is not None else None
-    _lib.check(L.dmcf_adam_step(ctypes.byref(a), _ptr(ws), nbytes, _stream()), "dmcf_adam_step")
+    _lib.call("dmcf_adam_step", ctypes.byref(a), _ptr(ws), nbytes, _stream())
     if timer is not None:
         timer.end("adam_step", dict(tensors=len(params), kernel=adam_step_kernel_names(params, grads, ms, vs, clip_norm)), t0)
     # (the table and the workspace are freed into torch's caching allocator, which keeps them from reuse until the stream has
@@ -3400,12 +3335,11 @@ def raster_discs(xy, radius, color_argb, width, height, out=None):
         raise ValueError(f"dmcf_raster: unsupported size (n={n}, frames={frames}, {width} x {height})")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=xy.device)
     total = torch.empty(1, dtype=torch.int64, device=xy.device)
-    _lib.check(L.dmcf_raster_count(_ptr(xy), n, frames, stride, radius, width, height, _ptr(ws), nbytes, _ptr(total), _stream()),
-               "dmcf_raster_count")
+    _lib.call("dmcf_raster_count", _ptr(xy), n, frames, stride, radius, width, height, _ptr(ws), nbytes, _ptr(total), _stream())
     cap = int(total.item())
     bins = torch.empty((max(cap, 1), 2), dtype=torch.float32, device=xy.device)
-    _lib.check(L.dmcf_raster_discs(_ptr(xy), n, frames, stride, radius, color_argb, width, height, _ptr(out), _ptr(ws), nbytes,
-                                   _ptr(bins), cap, _stream()), "dmcf_raster_discs")
+    _lib.call("dmcf_raster_discs", _ptr(xy), n, frames, stride, radius, color_argb, width, height, _ptr(out), _ptr(ws), nbytes,
+              _ptr(bins), cap, _stream())
     return out
 
 
@@ -3525,7 +3459,6 @@ def splat_depth(xyz, radius, camera, width, height, farthest=False, min_px=0.75,
     (the same points into every frame); ``radius`` in world units; ``min_px`` the smallest radius in pixels a sphere is drawn
     with.  ``out``: int64 ``[F, H, W]`` holding the uint64 keys' bits, -1 = empty; it fixes the frame count, is NOT cleared (so
     several groups can share it), and is created filled with -1 when None.  Returns ``out``.  One launch, no host read."""
-    L = _lib.lib()
     width, height, min_px = _splat_sizes(width, height, min_px)
     cam = _camera_struct(camera)
     xyz = _splat_points(xyz, "xyz")
@@ -3544,8 +3477,8 @@ def splat_depth(xyz, radius, camera, width, height, farthest=False, min_px=0.75,
     radius = float(radius)
     if n == 0 or frames == 0 or not (np.isfinite(radius) and radius > 0.0):
         return out  # nothing is splatted (the library would not launch either)
-    _lib.check(L.dmcf_splat_depth(_ptr(xyz), n, frames, stride, radius, min_px, ctypes.byref(cam), width, height,
-                                  _lib.SPLAT_FARTHEST if farthest else 0, _ptr(out), _stream()), "dmcf_splat_depth")
+    _lib.call("dmcf_splat_depth", _ptr(xyz), n, frames, stride, radius, min_px, ctypes.byref(cam), width, height,
+              _lib.SPLAT_FARTHEST if farthest else 0, _ptr(out), _stream())
     return out
 
 
@@ -3557,7 +3490,6 @@ def splat_shade(layers, camera, width, height, out=None, ambient=0.3, min_px=0.7
     ``min_px`` as in those calls.  Pixels without a sample keep what ``out`` holds.  Returns ``out``, or ``(out, depth)`` with
     ``depth`` float32 ``[F, H, W]`` (+inf where there is no sample) when ``return_depth``.  One launch.  ``ops.rgba8`` turns
     the result into 8-bit RGBA."""
-    L = _lib.lib()
     layers = list(layers)
     if len(layers) > _lib.SPLAT_MAX_LAYERS:
         raise ValueError(f"at most {_lib.SPLAT_MAX_LAYERS} layers per call, got {len(layers)}")
@@ -3610,8 +3542,8 @@ def splat_shade(layers, camera, width, height, out=None, ambient=0.3, min_px=0.7
         raise ValueError(f"at most 65535 frames per call, got {frames}")
     depth = torch.empty((frames, height, width), dtype=torch.float32, device=out.device) if return_depth else None
     if frames:
-        _lib.check(L.dmcf_splat_shade(recs, len(layers), ctypes.byref(cam), min_px, ambient, width, height, frames, _ptr(out),
-                                      _ptr(depth), _stream()), "dmcf_splat_shade")
+        _lib.call("dmcf_splat_shade", recs, len(layers), ctypes.byref(cam), min_px, ambient, width, height, frames, _ptr(out),
+                  _ptr(depth), _stream())
     del keep
     return (out, depth) if return_depth else out
 
@@ -3634,7 +3566,6 @@ def sph1d_rollout(state, n_tot, frames, h, rest_dens, stiffness, visc, gravity, 
     The rollout is cut into launches of ``max(1, launch_iters // max_iter)`` frames, so that no launch covers more than
     ``launch_iters`` solver iterations in the worst case (one frame's ``max_iter`` cannot be cut further); the state is carried
     from launch to launch, and the result has the bits of a single launch."""
-    L = _lib.lib()
     state = _dev_f32(state, "state")
     if state.dim() != 3 or state.shape[2] != 3:
         raise ValueError(f"state must have shape [S, P, 3], got {tuple(state.shape)}")
@@ -3663,6 +3594,6 @@ def sph1d_rollout(state, n_tot, frames, h, rest_dens, stiffness, visc, gravity, 
     per = max(1, int(launch_iters) // max_iter)
     for t0 in range(0, max(frames, 1), per):
         k = min(per, frames - t0)
-        _lib.check(L.dmcf_sph1d_rollout(_ptr(out), _ptr(n_tot), S, P, ctypes.byref(p), k, _ptr(seq[t0:]) if k else None, _ptr(out),
-                                        _ptr(iters[t0:]) if k else None, _stream()), "dmcf_sph1d_rollout")
+        _lib.call("dmcf_sph1d_rollout", _ptr(out), _ptr(n_tot), S, P, ctypes.byref(p), k, _ptr(seq[t0:]) if k else None, _ptr(out),
+                  _ptr(iters[t0:]) if k else None, _stream())
     return seq, out, iters
