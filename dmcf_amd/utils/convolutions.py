@@ -436,6 +436,76 @@ def _rank1_extents(extents, out_positions):
             and (extents.numel() > 1 or extents.numel() == out_positions.shape[0]))
 
 
+# What the layers prepare for ops.cconv_forward, whichever route a call takes.  A neighbour list with its window is always the
+# same six operands: (neighbors_index, neighbors_row_splits, neighbors_row_count, window, window_fac, neighbors_value).
+
+def _scalar_extent(extents, cited):
+    """A scalar extent as a Python float; ``cited``: the lines of the reference's class that the refusal names."""
+    if isinstance(extents, torch.Tensor):
+        if extents.dim() > 0 and extents.numel() != 1:
+            raise NotImplementedError(f"extents must be a scalar or of rank 1, [n_out] (convolutions.py:{cited})")
+        return float(extents)
+    return float(np.float32(extents))
+
+
+def _search_radius(extent):
+    """extent / 2 in float32 arithmetic (:353, :997)."""
+    return float(np.float32(0.5) * np.float32(extent))
+
+
+def _callers_list(user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance):
+    """The six operands of the caller's own neighbour list (:341-349, :984-993); None if the caller gave none."""
+    if user_neighbors_index is None or user_neighbors_row_splits is None:
+        return None
+    if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
+        return user_neighbors_index, user_neighbors_row_splits, None, "explicit", 1.0, user_neighbors_importance
+    return user_neighbors_index, user_neighbors_row_splits, None, None, 1.0, None
+
+
+def _window_operands(window_function, nns, radius):
+    """The six operands of a FixedRadiusSearch result at ``radius`` (:359-379, :1015-1019)."""
+    # raw(): buffers that may be longer than P (no host round trip); the kernels only follow row_splits
+    neighbors_index, neighbors_row_splits, raw_dist = nns.raw()
+    row_count = getattr(nns, "row_count", None)  # padded rows of the single-pass search
+    if window_function is None:
+        return neighbors_index, neighbors_row_splits, row_count, None, 1.0, None
+    if isinstance(window_function, WindowFunction):
+        # d^2; q = d^2/R^2 is formed in the kernel
+        return neighbors_index, neighbors_row_splits, row_count, window_function.name, window_function.fac, raw_dist
+    q = nns.neighbors_distance / (np.float32(radius) * np.float32(radius))
+    neighbors_index = nns.neighbors_index  # compact CSR form (synchronises)
+    if row_count is not None:
+        neighbors_row_splits, row_count = nns.csr_row_splits, None
+    return neighbors_index, neighbors_row_splits, row_count, "explicit", 1.0, window_function(q).to(torch.float32)
+
+
+def _extents_lists(layer, inp_positions, out_positions, extents, user_neighbors_index, user_neighbors_row_splits,
+                   user_neighbors_importance):
+    """The six operands of the rank-1 branch, for ContinuousConv (inference and recording) and PointSampling alike: the
+    caller's list, or a RadiusSearch at radii = extents / 2 (:366-370, :1006-1010; kept in ``layer.nns``).  Call under no_grad."""
+    n_out = out_positions.shape[0]
+    if extents.shape[0] != n_out:
+        raise ValueError(f"extents of rank 1 must hold one value per output point ({n_out}), got {extents.shape[0]}")
+    lists = _callers_list(user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
+    if lists is not None:
+        return lists
+    named = isinstance(layer.window_function, WindowFunction)
+    # (a named window is evaluated in the kernel on d^2 re-formed from the positions: no distances needed)
+    search = layer.radius_search.index_only() if named else layer.radius_search
+    layer.__dict__["nns"] = search(inp_positions, out_positions, 0.5 * extents)  # :367
+    neighbors_index, neighbors_row_splits, dist = layer.nns
+    window, window_fac, neighbors_value = None, 1.0, None
+    if layer.window_function is not None:
+        # The reference's rank-1 branch never binds neighbors_distance_normalized (:366-379: only the rank-0 branch
+        # does), so with a window TensorFlow raises there.  Implemented is the evident intent: the window on the
+        # RadiusSearch distances normalised per query, d^2 / r_i^2 (its normalize_distances=True, :212-216).
+        if named:
+            window, window_fac = layer.window_function.name, layer.window_function.fac  # q = d^2 / r_i^2 in the kernel
+        else:
+            window, neighbors_value = "explicit", layer.window_function(dist).to(torch.float32)
+    return neighbors_index, neighbors_row_splits, None, window, window_fac, neighbors_value
+
+
 class PlainAttributes:
     """Mix-in for the modules of this package: attributes that are neither parameters, buffers nor sub-modules go straight to the
     instance dictionary.  torch.nn.Module.__setattr__ walks its registries and type checks for every assignment -- a layer sets
@@ -623,10 +693,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             nns = self.radius_search(inp_positions, out_positions, 0.5 * extents.detach(), **splits)  # :367, normalised by the search
             q = nns.neighbors_distance
         else:
-            if isinstance(extents, torch.Tensor) and extents.dim() > 0 and extents.numel() != 1:
-                raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:352-372)")
-            extent = float(extents) if isinstance(extents, torch.Tensor) else float(np.float32(extents))
-            radius = float(np.float32(0.5) * np.float32(extent))  # :353
+            radius = _search_radius(_scalar_extent(extents, "352-372"))
             if hash_table is not None:
                 splits["hash_table"] = hash_table
             nns = self.fixed_radius_search(inp_positions, out_positions, radius, **splits)
@@ -664,8 +731,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         d = self.__dict__
         acc, extra_bias = self.accumulate_into, self.extra_bias
         d["accumulate_into"] = d["extra_bias"] = None
-        window, window_fac, neighbors_value = None, 1.0, None
-        row_count = None
+        users = (user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
         rank1 = _rank1_extents(extents, out_positions)
         if rank1 and not self.record_per_point_extents:
             raise NotImplementedError("ContinuousConv with per-point extents (rank 1) records only when built with "
@@ -675,14 +741,9 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             # extents go to ops.cconv_forward as a tensor and get no gradient, as in Open3D
             with torch.no_grad():
                 extent = extents.detach()
-                neighbors_index, neighbors_row_splits, window, window_fac, neighbors_value = self._extents_lists(
-                    inp_positions, out_positions, extent, user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
-        elif isinstance(extents, torch.Tensor):
-            if extents.dim() > 0 and extents.numel() != 1:
-                raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:352-372)")
-            extent = float(extents)
+                lists = _extents_lists(self, inp_positions, out_positions, extent, *users)
         else:
-            extent = float(np.float32(extents))
+            extent = _scalar_extent(extents, "352-372")
         lat = None
         if self.record_lattice_form and not rank1 and (user_neighbors_index is None or user_neighbors_row_splits is None):
             lat = self._lattice_form(inp_features, inp_positions, out_positions, inp_importance, hash_table, extent)
@@ -694,40 +755,21 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             d["_pairs_last"] = 0
             d["_conv_values"] = None
             out_features = lat.conv(ops, self.kernel, inp_features, out_positions.shape[0], extent,
-                                    window=self.window_function.name, window_fac=self.window_function.fac,
-                                    align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
-                                    interpolation=self.interpolation)
+                                    window=self.window_function.name, window_fac=self.window_function.fac, **self._geometry())
             return self._train_epilogue(out_features, inp_features, acc, extra_bias)
         if (self.record_scatter_form and not rank1 and user_neighbors_index is None and user_neighbors_row_splits is None
                 and self._scatter_train_form(inp_features, inp_positions, out_positions, inp_importance, hash_table)):
             out_features = self._scatter_train(inp_features, inp_positions, out_positions, extent)
             return self._train_epilogue(out_features, inp_features, acc, extra_bias)
-        if rank1:
-            pass
-        elif user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
-            neighbors_index, neighbors_row_splits = user_neighbors_index, user_neighbors_row_splits
-            if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
-                window, neighbors_value = "explicit", user_neighbors_importance
-        else:
-            radius = float(np.float32(0.5) * np.float32(extent))  # :353
-            with torch.no_grad():
-                # (an exact search of its own, outside the step's list cache: the backward needs the list after the step)
-                if hash_table is not None:
+        if not rank1:
+            lists = _callers_list(*users)
+            if lists is None:
+                radius = _search_radius(extent)
+                with torch.no_grad():
+                    # (an exact search of its own, outside the step's list cache: the backward needs the list after the step)
                     d["nns"] = self.fixed_radius_search(inp_positions, out_positions, radius, hash_table=hash_table)
-                else:
-                    d["nns"] = self.fixed_radius_search(inp_positions, out_positions, radius)
-                neighbors_index, neighbors_row_splits, raw_dist = self.nns.raw()
-                row_count = getattr(self.nns, "row_count", None)
-                if self.window_function is not None:  # :359-379
-                    if isinstance(self.window_function, WindowFunction):
-                        window, window_fac = self.window_function.name, self.window_function.fac
-                        neighbors_value = raw_dist
-                    else:
-                        q = self.nns.neighbors_distance / (np.float32(radius) * np.float32(radius))
-                        neighbors_index = self.nns.neighbors_index
-                        if row_count is not None:
-                            neighbors_row_splits, row_count = self.nns.csr_row_splits, None
-                        window, neighbors_value = "explicit", self.window_function(q).to(torch.float32)
+                    lists = _window_operands(self.window_function, self.nns, radius)
+        neighbors_index, neighbors_row_splits, row_count, window, window_fac, neighbors_value = lists
         d["_n_out_last"] = out_positions.shape[0]
         d["_pairs_last"] = neighbors_index.shape[0]
         kernel, symmetric = self._conv_kernel()
@@ -735,11 +777,8 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         out_features = ops.cconv_forward(
             kernel, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
             neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
-            align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
-            interpolation=self.interpolation, normalize=self.normalize, symmetric=symmetric, sym_axis=self.sym_axis,
-            neighbors_row_count=row_count, row_length_hint=self.row_length_hint,
-            packed_cache=self._packed if (kernel is self.kernel and os.environ.get("DMCF_CACHE_PACKED_FILTERS", "1") != "0")
-            else None, **({"record_per_point_extents": True} if rank1 else {}))
+            neighbors_row_count=row_count, row_length_hint=self.row_length_hint, packed_cache=self._packed_cache(kernel),
+            **self._geometry(symmetric), **({"record_per_point_extents": True} if rank1 else {}))
         return self._train_epilogue(out_features, inp_features, acc, extra_bias)
 
     def _scatter_train(self, inp_features, inp_positions, out_positions, extent):
@@ -747,7 +786,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         transposed list of an exact search with the roles swapped (the neighbour set is symmetric, so the list holds the forward's
         pairs).  The forward inside the node is what inference computes for these operands."""
         d = self.__dict__
-        radius = float(np.float32(0.5) * np.float32(extent))  # :353
+        radius = _search_radius(extent)
         window, window_fac = self.window_function.name, self.window_function.fac
         with torch.no_grad():
             # (a search of its own, outside the step's list cache: the backward needs the list after the step)
@@ -774,9 +813,8 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                 nns = self.fixed_radius_search(inp_positions, out_positions, radius)
                 idx, rs, raw_dist = nns.raw()
                 return ops.cconv_forward(w, out_positions, extent, inp_positions, f, idx, rs, neighbors_value=raw_dist, window=window,
-                                         window_fac=window_fac, align_corners=True, coordinate_mapping=self.coordinate_mapping,
-                                         interpolation=self.interpolation, neighbors_row_count=getattr(nns, "row_count", None),
-                                         row_length_hint=self.row_length_hint)
+                                         window_fac=window_fac, neighbors_row_count=getattr(nns, "row_count", None),
+                                         row_length_hint=self.row_length_hint, **self._geometry())
         return ops.ScatterConvFunction.apply(self.kernel, inp_features, out_positions, inp_positions, t_idx, t_rb, t_cnt, geo, run)
 
     def _train_epilogue(self, out_features, inp_features, acc, extra_bias):
@@ -811,34 +849,22 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         if _rank1_extents(extents, out_positions):
             return self._forward_extents(inp_features, inp_positions, out_positions, extents, inp_importance, user_neighbors_index,
                                          user_neighbors_row_splits, user_neighbors_importance, acc, extra_bias)
-        if isinstance(extents, torch.Tensor):
-            if extents.dim() > 0 and extents.numel() != 1:
-                raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:352-372)")
-            extent = float(extents)
-        else:
-            extent = float(np.float32(extents))
-        window, window_fac, neighbors_value, n_pairs_ref, row_count = None, 1.0, None, None, None
-        skip_self = False
-        if user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
-            neighbors_index, neighbors_row_splits = user_neighbors_index, user_neighbors_row_splits
-            if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
-                window, neighbors_value = "explicit", user_neighbors_importance
-        else:
+        extent = _scalar_extent(extents, "352-372")
+        n_pairs_ref, skip_self = None, False
+        lists = _callers_list(user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
+        if lists is None:
             lat = self._lattice_form(inp_features, inp_positions, out_positions, inp_importance,
                                      fixed_radius_search_hash_table, extent)
             if lat is not None:
                 # both point sets are grid_pos lattices of this step: no search, no per-pair geometry
                 # (dmcf_lattice_conv_forward; DMCF_LATTICE_CONV=0 keeps the neighbour-list form)
                 d["nns"] = None
-                fuse_bias = self.use_bias and not self.use_dense_layer_for_center
                 d["_n_out_last"] = out_positions.shape[0]
                 d["_pairs_last"] = 0  # no pair list in this form
                 out_features = lat.conv(
                     ops, self.kernel, inp_features, out_positions.shape[0], extent,
-                    window=self.window_function.name, window_fac=self.window_function.fac,
-                    align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
-                    interpolation=self.interpolation, bias=self._epilogue_bias(fuse_bias, extra_bias),
-                    out=acc, accumulate=acc is not None)
+                    window=self.window_function.name, window_fac=self.window_function.fac, **self._geometry(),
+                    bias=self._epilogue_bias(extra_bias), out=acc, accumulate=acc is not None)
                 stray = lat.strays()
                 if stray is not None:
                     # output points outside the lattice's core (stray particles' cells, dmcf_amd/lattice.py): the same layer
@@ -846,21 +872,20 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                     # does not write: zero, or the value to accumulate to).  The row set has an estimated capacity inside a
                     # rollout: ``valid`` zeroes the padding rows
                     idx_s, pos_s, valid = stray
-                    radius = float(np.float32(0.5) * np.float32(extent))
-                    nns = _CACHE.search(self.fixed_radius_search, inp_positions, pos_s, radius, distances=False)
+                    nns = _CACHE.search(self.fixed_radius_search, inp_positions, pos_s, _search_radius(extent), distances=False)
                     ni, nrs, raw_dist = nns.raw()
+                    # (normalize and symmetric are off wherever this form applies; the rows are short whatever the layer's are)
                     res = ops.cconv_forward(
                         self.kernel, pos_s, extent, inp_positions, inp_features, ni, nrs, neighbors_value=raw_dist,
-                        window=self.window_function.name, window_fac=self.window_function.fac, align_corners=self.align_corners,
-                        coordinate_mapping=self.coordinate_mapping, interpolation=self.interpolation,
-                        bias=self._epilogue_bias(fuse_bias, extra_bias), n_pairs_ref=pairs_ref(nns),
+                        window=self.window_function.name, window_fac=self.window_function.fac, **self._geometry(),
+                        bias=self._epilogue_bias(extra_bias), n_pairs_ref=pairs_ref(nns),
                         neighbors_row_count=getattr(nns, "row_count", None), row_length_hint=1)
                     if valid is not None:
                         res = res * valid
                     out_features.index_add_(0, idx_s, res)
                 d["_conv_values"], d["_conv_output"] = None, (None if _CACHE.depth > 0 else out_features)
                 return self._finish(out_features, inp_features, extra_bias if self.use_dense_layer_for_center else None)
-            radius = float(np.float32(0.5) * np.float32(extent))  # :353
+            radius = _search_radius(extent)
             sct = self._scatter_form(inp_features, inp_positions, out_positions, inp_importance, fixed_radius_search_hash_table,
                                      radius)
             if sct is not None:
@@ -873,14 +898,13 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                 d["nns"] = None
                 d["_n_out_last"] = out_positions.shape[0]
                 d["_pairs_last"] = tl
-                fuse_bias = self.use_bias and not self.use_dense_layer_for_center
                 # (the kernel's guard -- a pair outside its block's box, i.e. a plan that does not match the positions -- is read with
                 # the step's one synchronisation and fails loudly; it has never fired)
                 flag = _CACHE._max_count_slot(inp_positions.device) if _CACHE.depth > 0 else torch.zeros(1, dtype=torch.int32, device=inp_positions.device)
                 out_features = ops.cconv_scatter_forward(
                     self.kernel, out_positions, extent, inp_positions, inp_features, t_idx, t_rb, getattr(tl, "row_count", None),
                     _CACHE.scatter_plan(inp_positions, out_positions, voxel, radius, m), window=self.window_function.name,
-                    window_fac=self.window_function.fac, bias=self._epilogue_bias(fuse_bias, extra_bias), out=acc,
+                    window_fac=self.window_function.fac, bias=self._epilogue_bias(extra_bias), out=acc,
                     accumulate=acc is not None, n_pairs_ref=pairs_ref(tl), error_flag=flag)
                 _CACHE.report(flag, _scatter_guard)
                 d["_conv_values"], d["_conv_output"] = None, (None if _CACHE.depth > 0 else out_features)
@@ -896,32 +920,58 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                 d["nns"] = shared if skip_self else _CACHE.search(
                     self.fixed_radius_search, inp_positions, out_positions, radius,
                     distances=not isinstance(self.window_function, WindowFunction))
-            # raw(): buffers that may be longer than P (no host round trip); the kernels only follow row_splits
-            neighbors_index, neighbors_row_splits, raw_dist = self.nns.raw()
-            row_count = getattr(self.nns, "row_count", None)  # padded rows of the single-pass search
             n_pairs_ref = pairs_ref(self.nns)
-            if self.window_function is not None:  # :359-379
-                if isinstance(self.window_function, WindowFunction):
-                    window, window_fac = self.window_function.name, self.window_function.fac
-                    neighbors_value = raw_dist  # d^2; q = d^2/R^2 is formed in the kernel
-                else:
-                    q = self.nns.neighbors_distance / (np.float32(radius) * np.float32(radius))
-                    neighbors_index = self.nns.neighbors_index  # compact CSR form (synchronises)
-                    if row_count is not None:
-                        neighbors_row_splits, row_count = self.nns.csr_row_splits, None
-                    window, neighbors_value = "explicit", self.window_function(q).to(torch.float32)
+            lists = _window_operands(self.window_function, self.nns, radius)
+        neighbors_index, neighbors_row_splits, row_count, window, window_fac, neighbors_value = lists
         # stats (convolutions.py:385-388) are formed lazily (property _avg_neighbors): no host sync here
         d["_n_out_last"] = out_positions.shape[0]
         d["_pairs_last"] = self.nns if (n_pairs_ref is None and getattr(self, "nns", None) is not None and user_neighbors_index is None) \
             else (n_pairs_ref if n_pairs_ref is not None else neighbors_index.shape[0])
 
         kernel, symmetric = self._conv_kernel()
-        # The reference keeps the operands of the last call for inspection (convolutions.py:398-413).  Inside a rollout
-        # step (neighbor_cache scope) that would pin every layer's neighbour list (GBs each) and activations into the
-        # next step: there only the small entries are kept.
+        in_step = self._keep_operands(kernel, out_positions, extent, inp_positions, inp_features, inp_importance, neighbors_index,
+                                      neighbors_row_splits, neighbors_value)
+        # the operands of the launch and of the question which kernel serves it
+        operands = dict(neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
+                        neighbors_row_count=row_count, **self._geometry(symmetric))
+        out_features = ops.cconv_forward(
+            kernel, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits, **operands,
+            bias=self._epilogue_bias(extra_bias), n_pairs_ref=n_pairs_ref, skip_self=skip_self,
+            row_length_hint=self.row_length_hint, out=acc, accumulate=acc is not None, packed_cache=self._packed_cache(kernel))
+        if self._direct_kernel is None and in_step and self.radius_search_ignore_query_points:
+            # (asked once per layer: the dispatch looks at the layer, never at the list)
+            self._direct_kernel = ops.cconv_forward(
+                kernel, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits, **operands,
+                name_only=True).startswith("cconv_direct_kernel")
+            if self._shares_list() and user_neighbors_index is None and fixed_radius_search_hash_table is None:
+                # announce this layer as one more consumer of the list it will take from the next step on (the cache hands a
+                # list's buffers back after the number of consumers it saw in the previous step)
+                _CACHE.with_query_points(self.fixed_radius_search, inp_positions, out_positions, _search_radius(extent))
+        d["_conv_output"] = None if in_step else out_features
+        return self._finish(out_features, inp_features, extra_bias if self.use_dense_layer_for_center else None)
+
+    def _geometry(self, symmetric=None):
+        """The layer's fixed options as keywords of ops.cconv_forward.  ``symmetric`` None: the mapping alone -- what the
+        lattice form takes, and the list calls beside it (stray rows, the list forward of the scatter route), which run only
+        where normalize and symmetric are off."""
+        geometry = dict(align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping, interpolation=self.interpolation)
+        if symmetric is not None:
+            geometry.update(normalize=self.normalize, symmetric=symmetric, sym_axis=self.sym_axis)
+        return geometry
+
+    def _packed_cache(self, kernel):
+        """Where ops.cconv_forward keeps the packed filter of this layer (a derived filter tensor -- circular -- is a new object
+        every call: never cached)."""
+        return self._packed if (kernel is self.kernel and os.environ.get("DMCF_CACHE_PACKED_FILTERS", "1") != "0") else None
+
+    def _keep_operands(self, kernel, out_positions, extents, inp_positions, inp_features, inp_importance, neighbors_index,
+                       neighbors_row_splits, neighbors_value):
+        """The reference keeps the operands of the last call for inspection (``_conv_values``, convolutions.py:398-413).  Inside a
+        rollout step (neighbor_cache scope) that would pin every layer's neighbour list (GBs each) and activations into the
+        next step: there only the small entries are kept.  Returns whether the call is inside a step."""
         in_step = _CACHE.depth > 0
-        d["_conv_values"] = {
-            "filters": kernel, "out_positions": out_positions, "extents": extent, "offset": self.offset,
+        self.__dict__["_conv_values"] = {
+            "filters": kernel, "out_positions": out_positions, "extents": extents, "offset": self.offset,
             "inp_positions": inp_positions, "inp_features": None if in_step else inp_features,
             "inp_importance": inp_importance,
             "neighbors_index": None if in_step else neighbors_index, "neighbors_row_splits": neighbors_row_splits,
@@ -929,32 +979,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             "coordinate_mapping": self.coordinate_mapping, "interpolation": self.interpolation,
             "normalize": self.normalize,
         }
-        fuse_bias = self.use_bias and not self.use_dense_layer_for_center
-        out_features = ops.cconv_forward(
-            kernel, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
-            neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
-            align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
-            interpolation=self.interpolation, normalize=self.normalize, symmetric=symmetric, sym_axis=self.sym_axis,
-            bias=self._epilogue_bias(fuse_bias, extra_bias), n_pairs_ref=n_pairs_ref,
-            neighbors_row_count=row_count, skip_self=skip_self, row_length_hint=self.row_length_hint,
-            out=acc, accumulate=acc is not None,
-            packed_cache=self._packed if (kernel is self.kernel and os.environ.get("DMCF_CACHE_PACKED_FILTERS", "1") != "0")
-            else None)  # (a derived filter tensor -- circular -- is a new object every call: never cached)
-        if self._direct_kernel is None and in_step and self.radius_search_ignore_query_points:
-            # (asked once per layer: the dispatch looks at the layer, never at the list)
-            self._direct_kernel = ops.cconv_forward(
-                kernel, out_positions, extent, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
-                neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
-                align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
-                interpolation=self.interpolation, normalize=self.normalize, symmetric=symmetric, sym_axis=self.sym_axis,
-                neighbors_row_count=row_count, name_only=True).startswith("cconv_direct_kernel")
-            if self._shares_list() and user_neighbors_index is None and fixed_radius_search_hash_table is None:
-                # announce this layer as one more consumer of the list it will take from the next step on (the cache hands a
-                # list's buffers back after the number of consumers it saw in the previous step)
-                _CACHE.with_query_points(self.fixed_radius_search, inp_positions, out_positions,
-                                         float(np.float32(0.5) * np.float32(extent)))
-        d["_conv_output"] = None if in_step else out_features
-        return self._finish(out_features, inp_features, extra_bias if self.use_dense_layer_for_center else None)
+        return in_step
 
     def _conv_kernel(self):
         """(filter tensor, fused ASCC?) of a call: the circular expansion (convolutions.py:395-409) or the stored kernel."""
@@ -971,36 +996,6 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
                                       "models/pbf_model.py:203)")
         return kernel, symmetric
 
-    def _extents_lists(self, inp_positions, out_positions, extents, user_neighbors_index, user_neighbors_row_splits,
-                       user_neighbors_importance):
-        """Search + window of the rank-1 branch, for the inference and the training call alike: (neighbors_index,
-        neighbors_row_splits, window, window_fac, neighbors_value) -- the caller's list (:341-349), or a RadiusSearch at
-        radii = extents / 2 (kept in ``.nns``).  Call under no_grad."""
-        n_out = out_positions.shape[0]
-        if extents.shape[0] != n_out:
-            raise ValueError(f"extents of rank 1 must hold one value per output point ({n_out}), got {extents.shape[0]}")
-        window, window_fac, neighbors_value = None, 1.0, None
-        if user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :341-349
-            neighbors_index, neighbors_row_splits = user_neighbors_index, user_neighbors_row_splits
-            if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
-                window, neighbors_value = "explicit", user_neighbors_importance
-        else:
-            radii = 0.5 * extents  # :367
-            named = isinstance(self.window_function, WindowFunction)
-            # (a named window is evaluated in the kernel on d^2 re-formed from the positions: no distances needed)
-            search = self.radius_search.index_only() if named else self.radius_search
-            self.__dict__["nns"] = search(inp_positions, out_positions, radii)
-            neighbors_index, neighbors_row_splits, dist = self.nns
-            if self.window_function is not None:
-                # The reference's rank-1 branch never binds neighbors_distance_normalized (:366-379: only the rank-0 branch
-                # does), so with a window TensorFlow raises there.  Implemented is the evident intent: the window on the
-                # RadiusSearch distances normalised per query, d^2 / r_i^2 (its normalize_distances=True, :212-216).
-                if named:
-                    window, window_fac = self.window_function.name, self.window_function.fac  # q = d^2 / r_i^2 in the kernel
-                else:
-                    window, neighbors_value = "explicit", self.window_function(dist).to(torch.float32)
-        return neighbors_index, neighbors_row_splits, window, window_fac, neighbors_value
-
     def _forward_extents(self, inp_features, inp_positions, out_positions, extents, inp_importance, user_neighbors_index,
                          user_neighbors_row_splits, user_neighbors_importance, acc, extra_bias):
         """The branch for extents of rank 1 (convolutions.py:366-370, then :397-399): a radius per output point (RadiusSearch),
@@ -1009,36 +1004,25 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         cache: all of them key on one radius."""
         d = self.__dict__
         n_out = out_positions.shape[0]
-        neighbors_index, neighbors_row_splits, window, window_fac, neighbors_value = self._extents_lists(
-            inp_positions, out_positions, extents, user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
+        neighbors_index, neighbors_row_splits, _, window, window_fac, neighbors_value = _extents_lists(
+            self, inp_positions, out_positions, extents, user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
         d["_n_out_last"] = n_out
         d["_pairs_last"] = neighbors_index.shape[0]
         kernel, symmetric = self._conv_kernel()
-        in_step = _CACHE.depth > 0
-        d["_conv_values"] = {
-            "filters": kernel, "out_positions": out_positions, "extents": extents.reshape(n_out, 1), "offset": self.offset,
-            "inp_positions": inp_positions, "inp_features": None if in_step else inp_features,
-            "inp_importance": inp_importance,
-            "neighbors_index": None if in_step else neighbors_index, "neighbors_row_splits": neighbors_row_splits,
-            "neighbors_importance": None if in_step else neighbors_value, "align_corners": self.align_corners,
-            "coordinate_mapping": self.coordinate_mapping, "interpolation": self.interpolation,
-            "normalize": self.normalize,
-        }
-        fuse_bias = self.use_bias and not self.use_dense_layer_for_center
+        in_step = self._keep_operands(kernel, out_positions, extents.reshape(n_out, 1), inp_positions, inp_features, inp_importance,
+                                      neighbors_index, neighbors_row_splits, neighbors_value)
         out_features = ops.cconv_forward(
             kernel, out_positions, extents, inp_positions, inp_features, neighbors_index, neighbors_row_splits,
             neighbors_value=neighbors_value, window=window, window_fac=window_fac, inp_importance=inp_importance,
-            align_corners=self.align_corners, coordinate_mapping=self.coordinate_mapping,
-            interpolation=self.interpolation, normalize=self.normalize, symmetric=symmetric, sym_axis=self.sym_axis,
-            bias=self._epilogue_bias(fuse_bias, extra_bias), out=acc, accumulate=acc is not None)
+            **self._geometry(symmetric), bias=self._epilogue_bias(extra_bias), out=acc, accumulate=acc is not None)
         d["_conv_output"] = None if in_step else out_features
         return self._finish(out_features, inp_features, extra_bias if self.use_dense_layer_for_center else None)
 
-    def _epilogue_bias(self, fuse_bias, extra_bias):
-        """The vector the kernel's epilogue adds: the layer's bias (when the epilogue may form it) + the caller's."""
+    def _epilogue_bias(self, extra_bias):
+        """The vector the kernel's epilogue adds: the layer's bias + the caller's."""
         if self.use_dense_layer_for_center:
             return None  # (bias and the caller's vector follow the dense term, _finish)
-        bias = self.bias if fuse_bias else None
+        bias = self.bias if self.use_bias else None
         if extra_bias is None:
             return bias
         return extra_bias if bias is None else bias + extra_bias
@@ -1063,22 +1047,33 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             out_features = self.activation(out_features)
         return out_features
 
-    def _scatter_form(self, inp_features, inp_positions, out_positions, inp_importance, hash_table, radius):
-        """(voxel, block_cells) if dmcf_cconv_scatter_forward applies to this call: the outputs are a registered grid_pos lattice
-        with one spacing on all axes, the inputs are not a lattice of that family (then the stencil form applies), few output
-        channels, a 4x4x4 filter with the options that kernel implements, and the default (symmetric) neighbour set -- the
-        transposed list then holds the same pairs as the forward one."""
+    def _scatter_lattice(self, inp_features, out_positions, inp_importance, hash_table, out_channels):
+        """The output lattice if the input-stationary kernels (dmcf_cconv_scatter_forward / _backward) implement this call for a
+        layer with one of ``out_channels`` output channels, else None: the outputs are a registered grid_pos lattice with one
+        spacing on all axes, a 4x4x4 filter with the options those kernels implement, and the default (symmetric) neighbour
+        set -- the transposed list then holds the same pairs as the forward one."""
         from .. import lattice
-        if (os.environ.get("DMCF_SCATTER_CONV", "1") == "0" or not lattice.enabled() or hash_table is not None
+        if (not lattice.enabled() or hash_table is not None
                 or inp_importance is not None or self.symmetric or self.circular or self.normalize
                 or not isinstance(self.window_function, WindowFunction) or self.window_function.name != "poly6"
                 or self.radius_search_ignore_query_points or self.radius_search_metric != "L2" or not inp_features.is_cuda
-                or self.kernel_size != [4, 4, 4] or self.in_channels > 32 or self.filters not in SCATTER_OUT_CHANNELS
+                or self.kernel_size != [4, 4, 4] or self.in_channels > 32 or self.filters not in out_channels
                 or not self.align_corners or self.coordinate_mapping != "ball_to_cube_volume_preserving"
-                or self.interpolation != "linear" or inp_positions.shape[0] < SCATTER_MIN_INPUTS):
+                or self.interpolation != "linear"):
             return None
         info = lattice.lookup(out_positions)
         if info is None or not (info.voxel[0] == info.voxel[1] == info.voxel[2]) or max(info.dims) > SCATTER_MAX_LATTICE_CELLS:
+            return None
+        return info
+
+    def _scatter_form(self, inp_features, inp_positions, out_positions, inp_importance, hash_table, radius):
+        """(voxel, block_cells) if dmcf_cconv_scatter_forward applies to this call (_scatter_lattice) and is the faster forward:
+        few output channels, many inputs, and inputs that are not a lattice of the outputs' family (then the stencil form
+        applies)."""
+        if os.environ.get("DMCF_SCATTER_CONV", "1") == "0" or inp_positions.shape[0] < SCATTER_MIN_INPUTS:
+            return None
+        info = self._scatter_lattice(inp_features, out_positions, inp_importance, hash_table, SCATTER_OUT_CHANNELS)
+        if info is None:
             return None
         reach = ops.scatter_reach(radius, info.voxel[0])
         m = min(ops.SCATTER_BLOCK_CELLS, (13 if self.filters == 4 else 11) - 1 - 2 * reach)
@@ -1090,17 +1085,7 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         """Does dmcf_cconv_scatter_backward apply to this recording call: _scatter_form's conditions with 4 or 8 output channels
         and without those that only decide which FORWARD is faster (the input count, the lattice's fineness, the box fit, the
         channel list, DMCF_SCATTER_CONV)."""
-        from .. import lattice
-        if (not lattice.enabled() or hash_table is not None
-                or inp_importance is not None or self.symmetric or self.circular or self.normalize
-                or not isinstance(self.window_function, WindowFunction) or self.window_function.name != "poly6"
-                or self.radius_search_ignore_query_points or self.radius_search_metric != "L2" or not inp_features.is_cuda
-                or self.kernel_size != [4, 4, 4] or self.in_channels > 32 or self.filters not in (4, 8)
-                or not self.align_corners or self.coordinate_mapping != "ball_to_cube_volume_preserving"
-                or self.interpolation != "linear"):
-            return False
-        info = lattice.lookup(out_positions)
-        return info is not None and info.voxel[0] == info.voxel[1] == info.voxel[2] and max(info.dims) <= SCATTER_MAX_LATTICE_CELLS
+        return self._scatter_lattice(inp_features, out_positions, inp_importance, hash_table, (4, 8)) is not None
 
     def _lattice_form(self, inp_features, inp_positions, out_positions, inp_importance, hash_table, extent):
         """The LatticePair for this call if dmcf_lattice_conv_forward applies: both position tensors registered grid_pos
@@ -1144,6 +1129,10 @@ class PointSampling(PlainAttributes, torch.nn.Module):
     normalisation by the summed window values.  Used by ``dens_norm`` to carry the density to the coarse
     point sets (models/pbf_model.py:177-181, 421-431)."""
 
+    # ml3d.ops.continuous_conv with its defaults (:1038-1052) -- irrelevant for a one-cell filter, every neighbour puts all its
+    # weight on that cell
+    GEOMETRY = dict(align_corners=False, coordinate_mapping="ball_to_cube_radial", interpolation="linear")
+
     def __init__(self, window_function=None, normalize=True, name=None, **kwargs):
         super().__init__()
         self.normalize = normalize
@@ -1165,58 +1154,32 @@ class PointSampling(PlainAttributes, torch.nn.Module):
                 user_neighbors_importance=None):
         if self.kernel is None or self.kernel.shape[-1] != inp_features.shape[-1] or self.kernel.device != inp_features.device:
             self.build(inp_features.shape[-1], inp_features.device)
-        per_point = _rank1_extents(extents, out_positions)
-        if not per_point and isinstance(extents, torch.Tensor) and extents.dim() > 0 and extents.numel() != 1:
-            raise NotImplementedError("extents must be a scalar or of rank 1, [n_out] (convolutions.py:1006-1012)")
-        if per_point and extents.shape[0] != out_positions.shape[0]:
-            raise ValueError(f"extents of rank 1 must hold one value per output point ({out_positions.shape[0]}), "
-                             f"got {extents.shape[0]}")
-        extent = extents if per_point else float(np.float32(float(extents)))
-        window, window_fac, neighbors_value, n_pairs_ref, row_count = None, 1.0, None, None, None
-        if user_neighbors_index is not None and user_neighbors_row_splits is not None:  # :984-993
-            neighbors_index, neighbors_row_splits = user_neighbors_index, user_neighbors_row_splits
-            if user_neighbors_importance is not None and user_neighbors_importance.numel() > 0:
-                window, neighbors_value = "explicit", user_neighbors_importance
-        elif per_point:  # :1006-1010, the reference's defect and its reading as in ContinuousConv._forward_extents
-            named = isinstance(self.window_function, WindowFunction)
-            search = self.radius_search.index_only() if named else self.radius_search
-            self.nns = search(inp_positions, out_positions, 0.5 * extents)
-            neighbors_index, neighbors_row_splits, dist = self.nns
-            if self.window_function is not None:
-                if named:
-                    window, window_fac = self.window_function.name, self.window_function.fac
-                else:
-                    window, neighbors_value = "explicit", self.window_function(dist).to(torch.float32)
+        users = (user_neighbors_index, user_neighbors_row_splits, user_neighbors_importance)
+        n_pairs_ref = None
+        if _rank1_extents(extents, out_positions):  # :1006-1010, the reference's defect and its reading as in ContinuousConv
+            extent = extents
+            lists = _extents_lists(self, inp_positions, out_positions, extents, *users)
         else:
-            radius = float(np.float32(0.5) * np.float32(extent))  # :997
-            if fixed_radius_search_hash_table is not None:
-                self.nns = self.fixed_radius_search(inp_positions, out_positions, radius,
-                                                    hash_table=fixed_radius_search_hash_table)
-            else:
-                self.nns = _CACHE.search(self.fixed_radius_search, inp_positions, out_positions, radius,
-                                         distances=not isinstance(self.window_function, WindowFunction))
-            neighbors_index, neighbors_row_splits, raw_dist = self.nns.raw()
-            row_count = getattr(self.nns, "row_count", None)
-            n_pairs_ref = pairs_ref(self.nns)
-            if self.window_function is not None:  # :1015-1019
-                if isinstance(self.window_function, WindowFunction):
-                    window, window_fac, neighbors_value = self.window_function.name, self.window_function.fac, raw_dist
+            extent = float(np.float32(_scalar_extent(extents, "1006-1012")))
+            lists = _callers_list(*users)
+            if lists is None:
+                radius = _search_radius(extent)
+                if fixed_radius_search_hash_table is not None:
+                    self.nns = self.fixed_radius_search(inp_positions, out_positions, radius,
+                                                        hash_table=fixed_radius_search_hash_table)
                 else:
-                    q = self.nns.neighbors_distance / (np.float32(radius) * np.float32(radius))
-                    neighbors_index = self.nns.neighbors_index
-                    if row_count is not None:
-                        neighbors_row_splits, row_count = self.nns.csr_row_splits, None
-                    window, neighbors_value = "explicit", self.window_function(q).to(torch.float32)
+                    self.nns = _CACHE.search(self.fixed_radius_search, inp_positions, out_positions, radius,
+                                             distances=not isinstance(self.window_function, WindowFunction))
+                n_pairs_ref = pairs_ref(self.nns)
+                lists = _window_operands(self.window_function, self.nns, radius)
+        neighbors_index, neighbors_row_splits, row_count, window, window_fac, neighbors_value = lists
         self._n_out_last = out_positions.shape[0]
         self._pairs_last = n_pairs_ref if n_pairs_ref is not None else (self.nns if user_neighbors_index is None else neighbors_index.shape[0])
-        # ml3d.ops.continuous_conv with its defaults (:1038-1052): align_corners=False, ball_to_cube_radial, linear --
-        # irrelevant for a one-cell filter, every neighbour puts all its weight on that cell
         out = ops.cconv_forward(self.kernel, out_positions, extent, inp_positions, inp_features, neighbors_index,
                                 neighbors_row_splits, neighbors_value=neighbors_value, window=window, window_fac=window_fac,
-                                inp_importance=inp_importance, align_corners=False, coordinate_mapping="ball_to_cube_radial",
-                                interpolation="linear", normalize=self.normalize, n_pairs_ref=n_pairs_ref,
+                                inp_importance=inp_importance, **self.GEOMETRY, normalize=self.normalize, n_pairs_ref=n_pairs_ref,
                                 neighbors_row_count=row_count)
-        self._conv_output = None if _CACHE.depth > 0 else out  # see ContinuousConv.forward
+        self._conv_output = None if _CACHE.depth > 0 else out  # see ContinuousConv._keep_operands
         return out
 
     call = forward
