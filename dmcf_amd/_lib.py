@@ -358,6 +358,9 @@ PROTOTYPES = {
     "dmcf_cconv_backward_extents_kernel_names": (_int, (_P(CconvArgs), _P(CconvBackwardArgs), *_NAME)),
     "dmcf_cconv_scatter_plan_bytes": _BYTES_N,
     "dmcf_cconv_scatter_plan": (_int, (_ptr, _i64, _ptr, _i64, _f32, _f32, _i32, _ptr, _size, _ptr)),
+    # splat S's reach, box limit and instantiation, host only (ABI 2.28)
+    "dmcf_cconv_scatter_reach": (_i32, (_f32, _f32)),
+    "dmcf_cconv_scatter_kernel_name": (_int, (_i32 * 5, _i32, _i32, *_NAME)),
     "dmcf_cconv_scatter_workspace_bytes": (_size, (_P(CconvScatterArgs),)),
     "dmcf_cconv_scatter_forward": (_int, (_P(CconvScatterArgs), _ptr, _size, _ptr)),
     # the backward of the scatter form (ABI 2.19)

@@ -33,13 +33,15 @@
 // VALU active 78 % at 3.75 waves per SIMD (splat F on the same pairs: 4.0 + 2.7 + 0.9 and one matrix instruction per pair, 65 % busy
 // at 1.8 waves).
 //
-// Restrictions (the dispatch in dmcf_amd/utils/convolutions.py checks them, the entry point returns DMCF_EUNSUPPORTED): 4x4x4 filter,
-// Cout 4 or 8, Cin <= 32, linear interpolation, align_corners, volume-preserving map, poly6 or no window (formed from the positions),
-// no per-point importance, no normalisation; output points on a lattice of spacing `voxel` (cell = rint((x - x_0) / voxel)).
+// Restrictions (the entry point returns DMCF_EUNSUPPORTED; the dispatch in dmcf_amd/utils/convolutions.py asks sct_pick below, through
+// dmcf_cconv_scatter_kernel_name, for the filter shape and the box, and checks the layer's options itself): 4x4x4 filter, Cout 4 or 8,
+// Cin <= 32, a box that fits the LDS, linear interpolation, align_corners, volume-preserving map, poly6 or no window (formed from the
+// positions), no per-point importance, no normalisation; output points on a lattice of spacing `voxel` (cell = rint((x - x_0) / voxel)).
 //
 // The backward of this form (dmcf_cconv_scatter_backward) is cconv_sct_bwd.inc, included below: the same order of evaluation run
 // backwards, on the same transposed list, without a plan.
 #include <algorithm>
+#include <cstring>
 
 #include "cconv_common.h"
 
@@ -589,32 +591,69 @@ static size_t sct_lds_bytes(int cout, int D, int waves) {
     return (size_t)cout * NSp * 8 + (size_t)NSp * 4 + (size_t)2 * 2 * waves * 64 * cout * 4 + 16;
 }
 
-// 8 waves while two workgroups fit a CU, else 16 waves in one (cout 4) -- 0: the box does not fit at all
+// 8 waves while two workgroups fit a CU, else one workgroup of 16 waves (cout 4) or 8 (cout 8) -- 0: the box does not fit at all
 static int sct_waves(int cout, int D) {
     if (2 * sct_lds_bytes(cout, D, 8) <= 160 * 1024) return 8;
-    if (cout == 4 && sct_lds_bytes(cout, D, 16) <= 160 * 1024) return 16;
-    if (sct_lds_bytes(cout, D, 8) <= 160 * 1024) return 8;
-    return 0;
+    const int one = cout == 4 ? 16 : 8;
+    return sct_lds_bytes(cout, D, one) <= 160 * 1024 ? one : 0;
 }
 
 #include "cconv_sct_bwd.inc"
+
+// What dmcf_cconv_scatter_forward launches for a filter shape and a box.
+struct SctPick {
+    CconvKernel kernel;  // the instantiation and its printed name
+    int waves;
+    size_t lds;     // sct_lds_bytes of the box
+};
+
+// THE statement of splat S's shape and box limits: sct_check, the launch and dmcf_cconv_scatter_kernel_name all read it.
+static int sct_pick(const int32_t filter_dims[5], int32_t block_cells, int32_t reach, SctPick& k) {
+    if (!filter_dims || filter_dims[3] <= 0 || block_cells <= 0 || reach <= 0) return DMCF_EINVAL;
+    const int cout = filter_dims[4];
+    if (filter_dims[0] != 4 || filter_dims[1] != 4 || filter_dims[2] != 4 || (cout != 4 && cout != 8) || filter_dims[3] > 32)
+        return DMCF_EUNSUPPORTED;
+    const int64_t D = (int64_t)block_cells + 2 * (int64_t)reach + 1;
+    if (D > 64) return DMCF_EUNSUPPORTED;  // (no LDS holds 64^3 sums; and the byte counts below stay in range)
+    k.waves = sct_waves(cout, (int)D);
+    if (k.waves == 0) return DMCF_EUNSUPPORTED;
+    k.lds = sct_lds_bytes(cout, (int)D, k.waves);
+    k.kernel = cout == 4 ? (k.waves == 8 ? CCONV_KERNEL(cconv_sct_kernel<4, 8>) : CCONV_KERNEL(cconv_sct_kernel<4, 16>))
+                         : CCONV_KERNEL(cconv_sct_kernel<8, 8>);
+    return DMCF_OK;
+}
 
 }  // namespace dmcf
 
 using namespace dmcf;
 
-static int sct_check(const dmcf_cconv_scatter_args* a) {
+static int sct_check(const dmcf_cconv_scatter_args* a, SctPick& k) {
     if (!a || !a->filters || !a->out_positions || !a->inp_positions || !a->inp_features || !a->t_index || !a->t_row_begin || !a->plan || !a->out)
         return DMCF_EINVAL;
-    if (a->n_out <= 0 || a->n_inp <= 0 || a->filter_dims[3] <= 0 || a->extent <= 0.0f || a->block_cells <= 0 || a->reach <= 0) return DMCF_EINVAL;
-    if (a->filter_dims[0] != 4 || a->filter_dims[1] != 4 || a->filter_dims[2] != 4 || (a->filter_dims[4] != 4 && a->filter_dims[4] != 8) ||
-        a->filter_dims[3] > 32)
-        return DMCF_EUNSUPPORTED;
+    if (a->n_out <= 0 || a->n_inp <= 0 || a->extent <= 0.0f) return DMCF_EINVAL;
+    const int rc = sct_pick(a->filter_dims, a->block_cells, a->reach, k);
+    if (rc != DMCF_OK) return rc;
     if (a->window != DMCF_WINDOW_NONE && a->window != DMCF_WINDOW_POLY6) return DMCF_EUNSUPPORTED;
     if (a->flags & ~(DMCF_FLAG_ALIGN_CORNERS | DMCF_FLAG_ACCUMULATE)) return DMCF_EUNSUPPORTED;
     if (!(a->flags & DMCF_FLAG_ALIGN_CORNERS)) return DMCF_EUNSUPPORTED;
-    const int D = a->block_cells + 2 * a->reach + 1;
-    if (sct_waves(a->filter_dims[4], D) == 0) return DMCF_EUNSUPPORTED;
+    return DMCF_OK;
+}
+
+extern "C" int32_t dmcf_cconv_scatter_reach(float extent, float voxel) {
+    if (!(extent > 0.0f) || !(voxel > 0.0f)) return 0;
+    const float cells = ceilf(0.5f * extent / voxel - 1e-4f);
+    // (an infinite argument gives an infinite, zero or NaN count: none passes)
+    return cells >= 1.0f && cells < 2147483648.0f ? (int32_t)cells : 0;
+}
+
+extern "C" int dmcf_cconv_scatter_kernel_name(const int32_t filter_dims[5], int32_t block_cells, int32_t reach, char* name,
+                                              size_t name_bytes) {
+    if ((name == nullptr) != (name_bytes == 0)) return DMCF_EINVAL;
+    SctPick k;
+    const int rc = sct_pick(filter_dims, block_cells, reach, k);
+    if (rc != DMCF_OK || !name) return rc;
+    if (strlen(k.kernel.name) + 1 > name_bytes) return DMCF_EINVAL;
+    snprintf(name, name_bytes, "%s", k.kernel.name);
     return DMCF_OK;
 }
 
@@ -633,7 +672,7 @@ extern "C" int dmcf_cconv_scatter_plan(const float* inp_positions, int64_t n_inp
     uint32_t* cell_start = (uint32_t*)(ws + L.off_cell_start);
     uint32_t* cell_fill = (uint32_t*)(ws + L.off_cell_fill);
     int32_t* key = (int32_t*)(ws + L.off_key);
-    const int reach = (int)ceilf(0.5f * extent / voxel - 1e-4f);
+    const int reach = dmcf_cconv_scatter_reach(extent, voxel);
     // (the table is cleared whole: 2 x 8 MB at a few TB/s -- the region's cell count is only known on the device)
     if (hipMemsetAsync(cell_fill, 0, (size_t)(kSTable + 1) * 4, stream) != hipSuccess) { check_launch(); return DMCF_ELAUNCH; }
     hipLaunchKernelGGL(sct_plan_init, dim3(1), dim3(64), 0, stream, h, out_positions, voxel, (int)block_cells, reach);
@@ -661,7 +700,8 @@ extern "C" size_t dmcf_cconv_scatter_workspace_bytes(const dmcf_cconv_scatter_ar
 }
 
 extern "C" int dmcf_cconv_scatter_forward(const dmcf_cconv_scatter_args* a, void* workspace, size_t workspace_bytes, void* stream_) {
-    const int rc = sct_check(a);
+    SctPick k;
+    const int rc = sct_check(a, k);
     if (rc != DMCF_OK) return rc;
     if (!workspace || workspace_bytes < dmcf_cconv_scatter_workspace_bytes(a)) return DMCF_EWORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
@@ -704,17 +744,12 @@ extern "C" int dmcf_cconv_scatter_forward(const dmcf_cconv_scatter_args* a, void
     p.counter = tail + 1;
     hipLaunchKernelGGL(sct_bound_kernel, dim3((unsigned)std::min<int64_t>((a->n_inp + 255) / 256, 1024)), dim3(256), 0, stream, a->inp_features,
                        a->n_inp, cin, a->filters, (int64_t)64 * cin * cout, (uint32_t*)(tail + 2));
-    const int waves = sct_waves(cout, p.D);
-    const size_t lds = sct_lds_bytes(cout, p.D, waves) - 16;
-    const bool two = 2 * (lds + 16) <= 160 * 1024;
+    const size_t lds = k.lds - 16;
+    const bool two = 2 * k.lds <= 160 * 1024;
     const int grid = (int)std::min<int64_t>((int64_t)device_cu_count() * (two ? 2 : 1), a->n_inp);
-    auto launch = [&](auto kernel) {
-        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, stream, p);
-    };
-    if (cout == 4 && waves == 8) launch(cconv_sct_kernel<4, 8>);
-    else if (cout == 4) launch(cconv_sct_kernel<4, 16>);
-    else launch(cconv_sct_kernel<8, 8>);
+    (void)hipFuncSetAttribute(k.kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+    void* kargs[] = {&p};
+    (void)hipLaunchKernel(k.kernel.fn, dim3(grid), dim3(64 * k.waves), kargs, lds, stream);
     int r = check_launch();
     if (r != DMCF_OK) return r;
     const int64_t n = a->n_out * cout;

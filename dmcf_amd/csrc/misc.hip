@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void reduce_subarrays_sum_kernel(const float* 
 
 extern "C" {
 
-int dmcf_version(void) { return 22700; }  // 2.0.0: round 2 removed dmcf_cconv_geometry and the geometry field of dmcf_cconv_args; 2.1.0: filter_tile_mask; 2.2.0: DMCF_FLAG_SKIP_SELF; 2.3.0: row_length_hint (splat F); 2.4.0: dmcf_points_aabb; 2.5.0: DMCF_FLAG_FILTER_PACKED, row_length_hint = 1 (splat H); 2.6.0: dmcf_cconv_scatter_* (splat S), hashed grid_pos table (table_cells < 0); 2.7.0: dmcf_radius_search_count / _write (a radius per query), dmcf_cconv_forward_extents / dmcf_cconv_extents_kernel_name (individual extents); 2.8.0: dmcf_invert_neighbors_list, dmcf_cconv_backward (training); 2.9.0: dmcf_nn_distance, dmcf_approx_match, dmcf_match_cost, dmcf_emd (validation metrics); 2.10.0: dmcf_neighbor_dense_forward / _backward / _kernel_names (PointNet); 2.11.0: dmcf_adam_step (training loop); 2.12.0: dmcf_raster_workspace_bytes / _count / dmcf_raster_discs (renderer); 2.13.0: dmcf_nn_distance_backward, dmcf_match_cost_backward, dmcf_emd_with_levels, dmcf_emd_backward, dmcf_gather_point_backward (metric gradients); 2.14.0: dmcf_frs_window_sum_backward (differentiable density); 2.15.0: dmcf_cconv_backward_extents, dmcf_cconv_backward_extents_kernel_names (training through per-point extents); 2.16.0: dmcf_lattice_conv_backward, dmcf_lattice_conv_backward_workspace_bytes (training through the lattice form); 2.17.0: dmcf_sph1d_rollout (the column datasets' 1-D SPH solver); 2.18.0: DMCF_FRS_METRIC_LINF, dmcf_sparse_conv_forward / _backward / _backward_workspace_bytes / _kernel_names (SparseConv, SparseConvTranspose); 2.19.0: dmcf_cconv_scatter_backward, dmcf_cconv_scatter_backward_workspace_bytes (training through the particles -> lattice layers); 2.20.0: dmcf_frs_workspace_bytes_batched, dmcf_frs_build_batched, dmcf_frs_count_batched / _write_batched, dmcf_radius_search_count_batched / _write_batched (points_row_splits / queries_row_splits in both searches); 2.21.0: dmcf_grid_pos_workspace_bytes_batched, dmcf_grid_pos_bounds_batched / _count_batched / _write_batched, dmcf_points_aabb_batched (grid_pos and the fluid box of a batch of point sets); 2.22.0: dmcf_frs_window_sum_batched, dmcf_frs_window_sum_backward_batched (the window sum and its gradient on a batched structure, with the per-item maximum); 2.23.0: dmcf_nn_distance_ragged_workspace_bytes, dmcf_nn_distance_ragged (nn_distance over a batch of point sets of different sizes); 2.24.0: dmcf_emd_ragged_workspace_bytes, dmcf_emd_ragged (the fused EMD over such a batch, 62 launches whatever the batch); 2.25.0: dmcf_emd_ragged_with_levels, dmcf_emd_ragged_backward_workspace_bytes, dmcf_emd_ragged_backward (the gradient of the ragged EMD, 4 launches whatever the batch); 2.26.0: dmcf_hist_pair_ragged_workspace_bytes, dmcf_hist_pair_ragged (the percentiles and clipped histograms of compare_dist for a ragged batch, 9 launches whatever the batch); 2.27.0: dmcf_camera, dmcf_splat_depth, dmcf_splat_shade (the depth-tested sphere splat of the 3-D renderer)
+int dmcf_version(void) { return 22800; }  // 2.0.0: round 2 removed dmcf_cconv_geometry and the geometry field of dmcf_cconv_args; 2.1.0: filter_tile_mask; 2.2.0: DMCF_FLAG_SKIP_SELF; 2.3.0: row_length_hint (splat F); 2.4.0: dmcf_points_aabb; 2.5.0: DMCF_FLAG_FILTER_PACKED, row_length_hint = 1 (splat H); 2.6.0: dmcf_cconv_scatter_* (splat S), hashed grid_pos table (table_cells < 0); 2.7.0: dmcf_radius_search_count / _write (a radius per query), dmcf_cconv_forward_extents / dmcf_cconv_extents_kernel_name (individual extents); 2.8.0: dmcf_invert_neighbors_list, dmcf_cconv_backward (training); 2.9.0: dmcf_nn_distance, dmcf_approx_match, dmcf_match_cost, dmcf_emd (validation metrics); 2.10.0: dmcf_neighbor_dense_forward / _backward / _kernel_names (PointNet); 2.11.0: dmcf_adam_step (training loop); 2.12.0: dmcf_raster_workspace_bytes / _count / dmcf_raster_discs (renderer); 2.13.0: dmcf_nn_distance_backward, dmcf_match_cost_backward, dmcf_emd_with_levels, dmcf_emd_backward, dmcf_gather_point_backward (metric gradients); 2.14.0: dmcf_frs_window_sum_backward (differentiable density); 2.15.0: dmcf_cconv_backward_extents, dmcf_cconv_backward_extents_kernel_names (training through per-point extents); 2.16.0: dmcf_lattice_conv_backward, dmcf_lattice_conv_backward_workspace_bytes (training through the lattice form); 2.17.0: dmcf_sph1d_rollout (the column datasets' 1-D SPH solver); 2.18.0: DMCF_FRS_METRIC_LINF, dmcf_sparse_conv_forward / _backward / _backward_workspace_bytes / _kernel_names (SparseConv, SparseConvTranspose); 2.19.0: dmcf_cconv_scatter_backward, dmcf_cconv_scatter_backward_workspace_bytes (training through the particles -> lattice layers); 2.20.0: dmcf_frs_workspace_bytes_batched, dmcf_frs_build_batched, dmcf_frs_count_batched / _write_batched, dmcf_radius_search_count_batched / _write_batched (points_row_splits / queries_row_splits in both searches); 2.21.0: dmcf_grid_pos_workspace_bytes_batched, dmcf_grid_pos_bounds_batched / _count_batched / _write_batched, dmcf_points_aabb_batched (grid_pos and the fluid box of a batch of point sets); 2.22.0: dmcf_frs_window_sum_batched, dmcf_frs_window_sum_backward_batched (the window sum and its gradient on a batched structure, with the per-item maximum); 2.23.0: dmcf_nn_distance_ragged_workspace_bytes, dmcf_nn_distance_ragged (nn_distance over a batch of point sets of different sizes); 2.24.0: dmcf_emd_ragged_workspace_bytes, dmcf_emd_ragged (the fused EMD over such a batch, 62 launches whatever the batch); 2.25.0: dmcf_emd_ragged_with_levels, dmcf_emd_ragged_backward_workspace_bytes, dmcf_emd_ragged_backward (the gradient of the ragged EMD, 4 launches whatever the batch); 2.26.0: dmcf_hist_pair_ragged_workspace_bytes, dmcf_hist_pair_ragged (the percentiles and clipped histograms of compare_dist for a ragged batch, 9 launches whatever the batch); 2.27.0: dmcf_camera, dmcf_splat_depth, dmcf_splat_shade (the depth-tested sphere splat of the 3-D renderer); 2.28.0: dmcf_cconv_scatter_reach, dmcf_cconv_scatter_kernel_name (splat S's reach, box limit and instantiation, asked of the library)
 
 const char* dmcf_error_string(int code) {
     switch (code) {

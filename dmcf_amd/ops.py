@@ -14,6 +14,7 @@ All arithmetic happens in libdmcf_hip.so through its C ABI (include/dmcf_hip.h).
 fallback: calling these with CPU tensors or without the built library raises.
 """
 import collections
+import functools
 import os
 import ctypes
 
@@ -1500,8 +1501,14 @@ class ScatterPlan:
 SCATTER_BLOCK_CELLS = 4  # m: blocks of m^3 lattice cells (0.4 units of the 0.1 lattice of Liquid3d: ~500 particles)
 
 
+@functools.lru_cache()
+def _scatter_reach(extent, voxel):
+    return int(_lib.lib().dmcf_cconv_scatter_reach(extent, voxel))
+
+
 def scatter_reach(radius, voxel):
-    return int(np.ceil(np.float32(radius) / np.float32(voxel) - 1e-4))
+    """dmcf_cconv_scatter_reach for the extent scatter_plan passes: the lattice cells a radius covers, as the plan counts them."""
+    return _scatter_reach(2.0 * float(radius), float(voxel))
 
 
 def scatter_plan(inp_positions, out_positions, voxel, radius, block_cells=None):
@@ -1524,22 +1531,29 @@ def scatter_plan(inp_positions, out_positions, voxel, radius, block_cells=None):
     return ScatterPlan(buf, voxel, m, scatter_reach(radius, voxel), n, (inp, out))
 
 
-def scatter_kernel_name(cout, block_cells, reach):
-    """The instantiation dmcf_cconv_scatter_forward launches, as rocprofv3 prints it (csrc/cconv_sct.hip: sct_waves)."""
-    ns = (block_cells + 2 * reach + 1) ** 3
-    ns = (ns + 3) & ~3
+@functools.lru_cache()
+def _scatter_pick(dims, block_cells, reach):
+    """(status, name) of dmcf_cconv_scatter_kernel_name for a filter shape and a box."""
+    name = ctypes.create_string_buffer(64)
+    rc = _lib.lib().dmcf_cconv_scatter_kernel_name((ctypes.c_int32 * 5)(*dims), block_cells, reach, name, len(name))
+    return rc, name.value.decode()
 
-    def lds(waves):
-        return cout * ns * 8 + ns * 4 + 2 * 2 * waves * 64 * cout * 4 + 16
-    waves = 8 if (2 * lds(8) <= 160 * 1024 or cout != 4 or lds(16) > 160 * 1024) else 16
-    return f"cconv_sct_kernel<{cout}, {waves}>"
+
+def scatter_kernel_name(cout, block_cells, reach):
+    """The instantiation dmcf_cconv_scatter_forward launches, as rocprofv3 prints it (DmcfError for a box the library refuses)."""
+    rc, name = _scatter_pick((4, 4, 4, 1, int(cout)), int(block_cells), int(reach))
+    _lib.check(rc, "dmcf_cconv_scatter_kernel_name")
+    return name
 
 
 def cconv_scatter_supported(filters, block_cells, reach):
-    """Does dmcf_cconv_scatter_forward take a layer of this shape (4x4x4 filter, 4 or 8 outputs, a box that fits the LDS)?"""
-    if tuple(filters.shape[:3]) != (4, 4, 4) or filters.shape[3] > 32 or filters.shape[4] not in (4, 8):
-        return False
-    return block_cells + 2 * reach + 1 <= (13 if filters.shape[4] == 4 else 11)
+    """Does dmcf_cconv_scatter_forward take a layer of this filter shape with this box?"""
+    return len(filters.shape) == 5 and _scatter_pick(tuple(int(d) for d in filters.shape), int(block_cells), int(reach))[0] == 0
+
+
+def scatter_block_cells(cout, reach, most=SCATTER_BLOCK_CELLS):
+    """The largest block_cells <= ``most`` whose box the library takes at this reach; 0: none."""
+    return next((m for m in range(int(most), 0, -1) if _scatter_pick((4, 4, 4, 1, int(cout)), m, int(reach))[0] == 0), 0)
 
 
 def _dev_exact_1d(t, name, dtype, device, length=None):
@@ -1603,6 +1617,13 @@ def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_fea
     n_out, n_inp = checked[1].shape[0], checked[2].shape[0]
     if plan.n_inp != n_inp:
         raise ValueError("the plan was made for another input point set")
+    reach = scatter_reach(float(extent) / 2, plan.voxel)
+    if plan.reach != reach:
+        raise ValueError(f"the plan was made for a reach of {plan.reach} lattice cells; extent {float(extent)} over its voxel "
+                         f"{plan.voxel} has a reach of {reach}: make a plan for this radius (scatter_plan)")
+    if not cconv_scatter_supported(checked[0], plan.block_cells, plan.reach):
+        raise ValueError(f"the plan's block_cells {plan.block_cells} and reach {plan.reach} give a box the scatter form does not "
+                         f"take for filters {tuple(checked[0].shape)} (scatter_block_cells)")
     dev = checked[0].device
     if bias is not None:
         _dev_exact_1d(bias, "bias", torch.float32, dev, cout)
@@ -1638,23 +1659,8 @@ def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_fea
         return out
     if plan.buf.numel() == 0:
         raise ValueError("the plan was made for an empty point set: make one for these points (scatter_plan)")
-    a = _lib.CconvScatterArgs()
-    a.filters = _ptr(filters)
-    for k in range(5):
-        a.filter_dims[k] = int(filters.shape[k])
-    a.out_positions, a.n_out = _ptr(out_positions), n_out
-    a.inp_positions, a.n_inp = _ptr(inp_positions), n_inp
-    a.inp_features = _ptr(inp_features)
-    a.t_index, a.t_row_begin = _ptr(t_index), _ptr(t_row_begin)
-    a.t_row_count = _ptr(t_row_count) if t_row_count is not None else None
-    a.t_capacity = int(t_index.shape[0])
-    a.plan = _ptr(plan.buf)
-    a.block_cells, a.reach = plan.block_cells, plan.reach
-    a.extent, a.window_fac, a.window = float(extent), float(window_fac), WINDOWS[window]
-    a.flags = FLAG_ALIGN_CORNERS | (FLAG_ACCUMULATE if accumulate else 0)
-    a.bias = _ptr(bias) if bias is not None else None
-    a.out = _ptr(out)
-    a.error_flag = _ptr(error_flag) if error_flag is not None else None
+    a = _scatter_args(filters, out_positions, extent, inp_positions, inp_features, t_index, t_row_begin, t_row_count, window, window_fac,
+                      plan=plan, bias=bias, out=out, error_flag=error_flag, flags=FLAG_ACCUMULATE if accumulate else 0)
     ws, nbytes = _workspace(filters.device, "dmcf_cconv_scatter_workspace_bytes", ctypes.byref(a), least=0)
     t0 = timer.begin() if timer is not None else None
     _lib.call("dmcf_cconv_scatter_forward", ctypes.byref(a), _ptr(ws), nbytes, _stream())
@@ -1665,7 +1671,9 @@ def cconv_scatter_forward(filters, out_positions, extent, inp_positions, inp_fea
     return out
 
 
-def _scatter_args(filters, out_positions, extent, inp_positions, inp_features, t_index, t_row_begin, t_row_count, window, window_fac):
+def _scatter_args(filters, out_positions, extent, inp_positions, inp_features, t_index, t_row_begin, t_row_count, window, window_fac,
+                  plan=None, bias=None, out=None, error_flag=None, flags=0):
+    """struct dmcf_cconv_scatter_args of a forward call, or of the backward's (which reads no plan, bias, out or error flag)."""
     a = _lib.CconvScatterArgs()
     a.filters = _ptr(filters)
     for k in range(5):
@@ -1676,8 +1684,13 @@ def _scatter_args(filters, out_positions, extent, inp_positions, inp_features, t
     a.t_index, a.t_row_begin = _ptr(t_index), _ptr(t_row_begin)
     a.t_row_count = _ptr(t_row_count) if t_row_count is not None else None
     a.t_capacity = int(t_index.shape[0])
+    if plan is not None:
+        a.plan, a.block_cells, a.reach = _ptr(plan.buf), plan.block_cells, plan.reach
     a.extent, a.window_fac, a.window = float(extent), float(window_fac), WINDOWS[window]
-    a.flags = FLAG_ALIGN_CORNERS
+    a.flags = FLAG_ALIGN_CORNERS | flags
+    a.bias = _ptr(bias) if bias is not None else None
+    a.out = _ptr(out) if out is not None else None
+    a.error_flag = _ptr(error_flag) if error_flag is not None else None
     return a
 
 

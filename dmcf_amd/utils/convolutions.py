@@ -1047,19 +1047,18 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
             out_features = self.activation(out_features)
         return out_features
 
-    def _scatter_lattice(self, inp_features, out_positions, inp_importance, hash_table, out_channels):
-        """The output lattice if the input-stationary kernels (dmcf_cconv_scatter_forward / _backward) implement this call for a
-        layer with one of ``out_channels`` output channels, else None: the outputs are a registered grid_pos lattice with one
-        spacing on all axes, a 4x4x4 filter with the options those kernels implement, and the default (symmetric) neighbour
-        set -- the transposed list then holds the same pairs as the forward one."""
+    def _scatter_lattice(self, inp_features, out_positions, inp_importance, hash_table):
+        """The output lattice if the input-stationary kernels (dmcf_cconv_scatter_forward / _backward) implement this call, else
+        None: the outputs are a registered grid_pos lattice with one spacing on all axes, a filter of a shape the library takes
+        (ops.cconv_scatter_supported, asked with the smallest box) with the options those kernels implement, and the default
+        (symmetric) neighbour set -- the transposed list then holds the same pairs as the forward one."""
         from .. import lattice
         if (not lattice.enabled() or hash_table is not None
                 or inp_importance is not None or self.symmetric or self.circular or self.normalize
                 or not isinstance(self.window_function, WindowFunction) or self.window_function.name != "poly6"
                 or self.radius_search_ignore_query_points or self.radius_search_metric != "L2" or not inp_features.is_cuda
-                or self.kernel_size != [4, 4, 4] or self.in_channels > 32 or self.filters not in out_channels
                 or not self.align_corners or self.coordinate_mapping != "ball_to_cube_volume_preserving"
-                or self.interpolation != "linear"):
+                or self.interpolation != "linear" or not ops.cconv_scatter_supported(self.kernel, 1, 1)):
             return None
         info = lattice.lookup(out_positions)
         if info is None or not (info.voxel[0] == info.voxel[1] == info.voxel[2]) or max(info.dims) > SCATTER_MAX_LATTICE_CELLS:
@@ -1072,20 +1071,21 @@ class ContinuousConv(PlainAttributes, torch.nn.Module):
         applies)."""
         if os.environ.get("DMCF_SCATTER_CONV", "1") == "0" or inp_positions.shape[0] < SCATTER_MIN_INPUTS:
             return None
-        info = self._scatter_lattice(inp_features, out_positions, inp_importance, hash_table, SCATTER_OUT_CHANNELS)
+        if self.filters not in SCATTER_OUT_CHANNELS:
+            return None
+        info = self._scatter_lattice(inp_features, out_positions, inp_importance, hash_table)
         if info is None:
             return None
-        reach = ops.scatter_reach(radius, info.voxel[0])
-        m = min(ops.SCATTER_BLOCK_CELLS, (13 if self.filters == 4 else 11) - 1 - 2 * reach)
+        m = ops.scatter_block_cells(self.filters, ops.scatter_reach(radius, info.voxel[0]))
         if m < 1 or out_positions.shape[0] * 4 > inp_positions.shape[0]:
             return None  # (a fine lattice: few pairs per flushed slot, the gather form is faster -- DESIGN.md section 4.2, splat S)
         return info.voxel[0], m
 
     def _scatter_train_form(self, inp_features, inp_positions, out_positions, inp_importance, hash_table):
-        """Does dmcf_cconv_scatter_backward apply to this recording call: _scatter_form's conditions with 4 or 8 output channels
-        and without those that only decide which FORWARD is faster (the input count, the lattice's fineness, the box fit, the
-        channel list, DMCF_SCATTER_CONV)."""
-        return self._scatter_lattice(inp_features, out_positions, inp_importance, hash_table, (4, 8)) is not None
+        """Does dmcf_cconv_scatter_backward apply to this recording call: _scatter_form's conditions with every output channel
+        count the library takes (4 or 8) and without those that only decide which FORWARD is faster (the input count, the
+        lattice's fineness, the box fit, the channel list, DMCF_SCATTER_CONV)."""
+        return self._scatter_lattice(inp_features, out_positions, inp_importance, hash_table) is not None
 
     def _lattice_form(self, inp_features, inp_positions, out_positions, inp_importance, hash_table, extent):
         """The LatticePair for this call if dmcf_lattice_conv_forward applies: both position tensors registered grid_pos

@@ -503,6 +503,14 @@ int dmcf_cconv_backward_extents_kernel_names(const dmcf_cconv_args* fwd, const d
  * Restrictions (DMCF_EUNSUPPORTED otherwise): 4x4x4 filters, cout 4 or 8, cin <= 32, DMCF_WINDOW_NONE / POLY6 evaluated from the
  * positions, volume-preserving map, linear interpolation; flags: DMCF_FLAG_ALIGN_CORNERS (required) | DMCF_FLAG_ACCUMULATE;
  * block_cells + 2 reach + 1 <= 13 at cout 4 (11 at cout 8): the box must fit the CU's LDS.
+ *
+ * Two host-only queries (ABI 2.28: no device, no HIP call) answer what a caller would otherwise restate:
+ * dmcf_cconv_scatter_reach(extent, voxel): the `reach` the plan made with this extent and voxel holds, and the value of that field
+ *   of dmcf_cconv_scatter_args: ceilf(0.5f * extent / voxel - 1e-4f) in float32; 0 for an argument that is not positive and finite.
+ * dmcf_cconv_scatter_kernel_name(filter_dims, block_cells, reach, name, name_bytes): the instantiation dmcf_cconv_scatter_forward
+ *   launches for this filter shape and box, as a profiler prints it ("cconv_sct_kernel<4, 16>"); DMCF_EUNSUPPORTED where the
+ *   shape or the box is outside the restrictions above, DMCF_EINVAL for block_cells or reach <= 0, a NULL filter_dims or a name
+ *   buffer too short.  name == NULL with name_bytes == 0 asks only whether the form takes the shape.
  * workspace: dmcf_cconv_scatter_workspace_bytes (the 64-bit sums; zeroed by the call).  error_flag (optional device int32, the
  * caller zeroes it): set to 1 when a pair fell outside its block's box, i.e. the plan was not made from these positions,
  * voxel and radius -- the pair is then dropped.
@@ -510,6 +518,8 @@ int dmcf_cconv_backward_extents_kernel_names(const dmcf_cconv_args* fwd, const d
 size_t dmcf_cconv_scatter_plan_bytes(int64_t n_inp);
 int dmcf_cconv_scatter_plan(const float* inp_positions, int64_t n_inp, const float* out_positions, int64_t n_out, float voxel,
                             float extent, int32_t block_cells, void* plan, size_t plan_bytes, dmcf_stream_t stream);
+int32_t dmcf_cconv_scatter_reach(float extent, float voxel);
+int dmcf_cconv_scatter_kernel_name(const int32_t filter_dims[5], int32_t block_cells, int32_t reach, char* name, size_t name_bytes);
 
 typedef struct dmcf_cconv_scatter_args {
     const float* filters;          /* [4][4][4][cin][cout] */
@@ -525,7 +535,7 @@ typedef struct dmcf_cconv_scatter_args {
     int64_t t_capacity;            /* entries t_index holds */
     const void* plan;              /* dmcf_cconv_scatter_plan's output for these positions */
     int32_t block_cells;           /* as passed to the plan */
-    int32_t reach;                 /* ceil(extent / 2 / voxel) */
+    int32_t reach;                 /* dmcf_cconv_scatter_reach(extent, voxel), voxel as passed to the plan */
     float extent;
     float window_fac;
     int32_t window;

@@ -1,7 +1,12 @@
 """The scatter form's error bar of tests/cconv_scatter_ref.py on the CPU: it is sound (the float32 oracle is within its float part
 on every case tests/test_gpu_cconv_scatter_bar.py runs, a numpy emulation of the kernel's fixed-point sum within the whole), its
 conditions hold, the cases hold what they claim, and it has teeth (the 2^30 scale the kernel first had fails the outlier case;
-seeded faults break it).  ops.scatter_reach agrees with the plan's expression."""
+seeded faults break it).  The library's reach (dmcf_cconv_scatter_reach, and ops.scatter_reach over it) agrees with the plan's
+expression as cconv_scatter_ref restates it, and its table of instantiations and box limits (dmcf_cconv_scatter_kernel_name)
+with expected_kernel / two_workgroups."""
+import ctypes
+import os
+
 import numpy as np
 import pytest
 
@@ -11,6 +16,15 @@ import cconv_scatter_ref as sr  # noqa: E402
 
 MATRIX = sr.matrix()
 _CASES = {}
+OK, EINVAL, EUNSUPPORTED = 0, -1, -4  # DMCF_* of include/dmcf_hip.h
+
+
+@pytest.fixture(scope="module")
+def hip_lib():
+    from dmcf_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    return _lib.lib()
 
 
 def _case(spec):
@@ -136,9 +150,9 @@ def test_bias_missing_on_the_rows_without_pairs_breaks_the_bar(oracle):
     assert not sr.within_bar(c.oracle32(bias_rows=c.n_pairs > 0), c)
 
 
-def test_reach_agrees_with_the_plan():
-    """ops.scatter_reach against ceilf(0.5f * extent / voxel - 1e-4f) of dmcf_cconv_scatter_plan, +-400 ulp around the radii at
-    which the ceiling steps."""
+def test_reach_agrees_with_the_plan(hip_lib):
+    """dmcf_cconv_scatter_reach, called directly and through ops.scatter_reach, against ceilf(0.5f * extent / voxel - 1e-4f) of
+    dmcf_cconv_scatter_plan as cconv_scatter_ref restates it, +-400 ulp around the radii at which the ceiling steps."""
     from dmcf_amd import ops
     n = 0
     for voxel in (0.05, 0.1, 0.125, 0.2, 0.3):
@@ -150,8 +164,86 @@ def test_reach_agrees_with_the_plan():
             for _ in range(801):
                 a, b = ops.scatter_reach(float(r), voxel), sr.expected_reach(float(r), voxel)
                 assert a == b, (float(r), voxel, a, b)
+                direct = hip_lib.dmcf_cconv_scatter_reach(2.0 * float(r), voxel)
+                assert direct == b, (float(r), voxel, direct, b)
                 seen.add(a)
                 r = np.nextafter(r, np.float32(np.inf))
                 n += 1
             assert seen == {k, k + 1}, "the sweep does not straddle the step of the ceiling"
     assert n == 5 * 5 * 801
+
+
+def test_reach_refuses_what_is_not_a_length(hip_lib):
+    """0 for an extent or a voxel that is not positive and finite."""
+    from dmcf_amd import ops
+    nan, inf = float("nan"), float("inf")
+    for extent, voxel in ((0.0, 0.1), (-0.8, 0.1), (0.8, 0.0), (0.8, -0.1), (-0.8, -0.1), (nan, 0.1), (0.8, nan), (nan, nan),
+                          (inf, 0.1), (0.8, inf), (inf, inf)):
+        assert hip_lib.dmcf_cconv_scatter_reach(extent, voxel) == 0, (extent, voxel)
+        assert ops.scatter_reach(extent / 2, voxel) == 0, (extent, voxel)
+    assert hip_lib.dmcf_cconv_scatter_reach(0.8, 0.1) == 4 and ops.scatter_reach(0.4, 0.1) == 4
+
+
+def test_reach_where_a_float64_subtraction_steps_early():
+    """The radius at which the wrapper's former expression parted from the plan's when numpy subtracted the 1e-4 in float64 (its
+    scalar arithmetic before 2.0): 0.40001002 / 0.1 - 1e-4 is 4 + 1.4e-7 in float64, which the ceiling takes to 5, and exactly 4
+    in float32, the plan's arithmetic.  A call with the 5 sized its box for a plan whose header said 4."""
+    from dmcf_amd import ops
+    radius, voxel = float(np.float32(0.40001002)), 0.1
+    q = np.float32(radius) / np.float32(voxel)
+    assert int(np.ceil(np.float64(q) - 1e-4)) == 5 and int(np.ceil(np.float32(q - np.float32(1e-4)))) == 4
+    assert ops.scatter_reach(radius, voxel) == sr.expected_reach(radius, voxel) == 4
+
+
+def _kernel_name(hip_lib, dims, block_cells, reach, size=64):
+    name = ctypes.create_string_buffer(size) if size else None
+    rc = hip_lib.dmcf_cconv_scatter_kernel_name((ctypes.c_int32 * 5)(*dims), block_cells, reach, name, size)
+    return rc, (name.value.decode() if size else None)
+
+
+def test_kernel_name_and_box_limits(hip_lib):
+    """dmcf_cconv_scatter_kernel_name over cout 4 / 8, block_cells 1 .. 6, reach 1 .. 5 (D = 4 .. 17, both sides of every limit):
+    the instantiation of expected_kernel where the box fits (D <= 13 at cout 4, 11 at cout 8), DMCF_EUNSUPPORTED beyond; the name
+    buffer is optional; the wrappers say the same; scatter_block_cells is the closed form the dispatch had."""
+    from dmcf_amd import _lib, ops
+    seen_d = set()
+    for cout, limit in ((4, 13), (8, 11)):
+        for reach in range(1, 6):
+            for m in range(1, 7):
+                D = m + 2 * reach + 1
+                seen_d.add(D)
+                dims = (4, 4, 4, 24, cout)
+                rc, name = _kernel_name(hip_lib, dims, m, reach)
+                filt = np.empty(dims, dtype=np.float32)
+                if D <= limit:
+                    assert (rc, name) == (OK, sr.expected_kernel(cout, m, reach)), (cout, m, reach, rc, name)
+                    assert ops.scatter_kernel_name(cout, m, reach) == name and ops.cconv_scatter_supported(filt, m, reach)
+                    if cout == 8:  # 8 waves are chosen first, while two workgroups fit: the instantiation does not tell
+                        assert name == "cconv_sct_kernel<8, 8>" and sr.two_workgroups(8, m, reach) == (D <= 6)
+                    else:
+                        assert sr.two_workgroups(4, m, reach) == (name == "cconv_sct_kernel<4, 8>")
+                else:
+                    assert rc == EUNSUPPORTED, (cout, m, reach, rc, name)
+                    assert not ops.cconv_scatter_supported(filt, m, reach)
+                    with pytest.raises(_lib.DmcfError):
+                        ops.scatter_kernel_name(cout, m, reach)
+                assert _kernel_name(hip_lib, dims, m, reach, size=0) == (rc, None)  # the query without a name
+            assert ops.scatter_block_cells(cout, reach) == max(0, min(4, limit - 1 - 2 * reach))
+            assert ops.scatter_block_cells(cout, reach, most=6) == max(0, min(6, limit - 1 - 2 * reach))
+    assert seen_d == set(range(4, 18))
+
+
+def test_kernel_name_refusals(hip_lib):
+    for dims in ((3, 4, 4, 24, 4), (4, 3, 4, 24, 4), (4, 4, 3, 24, 4), (4, 4, 4, 33, 4), (4, 4, 4, 24, 6), (4, 4, 4, 24, 16)):
+        assert _kernel_name(hip_lib, dims, 2, 2)[0] == EUNSUPPORTED, dims
+        assert _kernel_name(hip_lib, dims, 2, 2, size=0)[0] == EUNSUPPORTED, dims
+    ok = (4, 4, 4, 32, 8)
+    assert _kernel_name(hip_lib, ok, 2, 2) == (OK, "cconv_sct_kernel<8, 8>")
+    for m, reach in ((2, 0), (0, 2), (2, -1), (-3, 2)):
+        assert _kernel_name(hip_lib, ok, m, reach)[0] == EINVAL, (m, reach)
+    assert _kernel_name(hip_lib, ok, 2, 2, size=4)[0] == EINVAL  # a buffer too short for the name
+    assert _kernel_name(hip_lib, (4, 4, 4, 0, 8), 2, 2)[0] == EINVAL
+    # a buffer without a length, a length without a buffer
+    dims = (ctypes.c_int32 * 5)(*ok)
+    assert hip_lib.dmcf_cconv_scatter_kernel_name(dims, 2, 2, ctypes.create_string_buffer(64), 0) == EINVAL
+    assert hip_lib.dmcf_cconv_scatter_kernel_name(dims, 2, 2, None, 64) == EINVAL

@@ -6,8 +6,8 @@ element (tests/cconv_scatter_ref.py):
 on deterministic lattices with controlled transposed row lengths (0, 1, 2, 63 .. 65, 127 .. 129, 257) and block populations
 (1, 8, 9, 15 .. 17, 31 .. 33, 65), an interior origin, strays beyond the plan's region, a scene far from the origin, reach 2 - 4,
 CSR, padded and cut transposed lists, signed features, an outlier 2^10 times the rest, and the three instantiations.  Every case
-first asserts the instantiation's name as ops.scatter_kernel_name gives it -- the Python restatement of the library's choice
-(sct_waves): the C ABI has no entry that names the scatter kernel, so the launch itself is not observed.  The sums are
+first asserts the instantiation's name as ops.scatter_kernel_name gives it -- dmcf_cconv_scatter_kernel_name, which reads the
+function the launch reads (sct_pick) -- against the case's own restatement (cconv_scatter_ref.expected_kernel).  The sums are
 integers: the same call twice, a second plan, the two list forms and the three block sizes return the same bits.  The same cases run on the CPU in tests/test_cconv_scatter_ref_cpu.py, where the bar is
 shown sound.  The worst err / bar per instantiation is printed by test_report_worst_ratio (run with -s)."""
 import numpy as np
@@ -208,6 +208,23 @@ def test_wrapper_rejects_the_plan_of_an_empty_set_in_a_call_that_is_not_empty(de
     assert plan.buf.numel() == 0 and plan.n_inp == a["inp_positions"].shape[0]
     with pytest.raises(ValueError, match="plan"):
         _call(a, plan)
+
+
+def test_wrapper_rejects_a_plan_made_for_another_reach(identity, dev):
+    """A plan for the case's radius and a call whose extent reaches one cell further: ValueError on the host that names both
+    reaches, before anything is launched (a fresh error flag stays 0); with the matching extent the same operands are within
+    the bar."""
+    from dmcf_amd import ops
+    c, call, plan, y = identity
+    extent = 2.0 * (c.radius + c.voxel)
+    assert plan.reach == c.reach and ops.scatter_reach(extent / 2, c.voxel) == c.reach + 1
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    with pytest.raises(ValueError, match=rf"reach of {c.reach} .* reach of {c.reach + 1}\b"):
+        ops.cconv_scatter_forward(call.W, call.Q, extent, call.P, call.F, _t(c.t_idx, dev), _t(c.t_rs, dev), None, plan,
+                                  window=c.window, window_fac=c.window_fac, bias=call.bias, error_flag=flag)
+    torch.cuda.synchronize()
+    assert int(flag.item()) == 0
+    sr.check("identity, matching extent", call.run(plan), c)
 
 
 @pytest.mark.parametrize("accumulate", [False, True])
